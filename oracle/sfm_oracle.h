@@ -8,7 +8,7 @@
  *
  * PARITY UNPINNED: the reference (codebydant/sfM_danPipeline) ships no tests,
  * fixtures or golden vectors, and its arithmetic lives in OpenCV 3.4.1 / Ceres 1.13.0,
- * neither of which is vendored under /root/reference nor installed here.  This file
+ * neither of which is vendored in the reference project nor installed here.  This file
  * restates the published algorithms of those pinned versions at the reference's
  * call sites (cited per function) and is cross-checked against independent
  * numpy / scipy restatements (oracle/np_check.py, tests/golden/).

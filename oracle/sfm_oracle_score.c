@@ -20,7 +20,7 @@
  *   core/mathfuncs.cpp      cv::solvePoly (Durand-Kerner in sequence, start (1+i)^k, 300 iterations or until no root
  *                           moves), cv::RNG (multiply with carry, 4164903690).
  *
- * PARITY UNPINNED: OpenCV is neither under /root/reference nor in this image and the reference holds no vector for this
+ * PARITY UNPINNED: OpenCV is neither in the reference project nor in this image and the reference holds no vector for this
  * call; everything above is restated from the published sources from memory.  What is knowingly NOT reproduced, all of it
  * at the level of the last bit: (1) getCoeffMat and the eleven determinant coefficients are machine-generated sums of
  * products in OpenCV; here the same polynomials are expanded in a fixed order of our own, so individual coefficients

@@ -10,7 +10,7 @@ models in root order.  That file's header lists what is restated and what (at la
 holds the Python-side pieces around it: cv::RNG and getSubset (the sample tables the device code is given), the
 std::map bookkeeping, and the homography path in numpy.
 
-PARITY UNPINNED.  OpenCV 3.4.1 is not in /root/reference and not in this image, and the reference holds no test or
+PARITY UNPINNED.  OpenCV 3.4.1 is not in the reference project and not in this image, and the reference holds no test or
 golden vector for this path.  oracle/np_check.py carries an independent action-matrix five-point solver used by
 tests/test_oracle_score.py to check the restatement's models (same matrices on well-conditioned samples); it is a check
 of the oracle, never an alternative route for a parity test.

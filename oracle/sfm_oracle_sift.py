@@ -2,7 +2,7 @@
 detector / descriptor front end of StructFromMotion::getFeature (reference src/Sfm.cpp:300-330; SURVEY.md section 8f-3).
 
 PARITY UNPINNED.  The algorithm lives in OpenCV 3.4.1 (opencv_contrib xfeatures2d/src/sift.cpp, imgproc's GaussianBlur /
-resize), which is neither under /root/reference nor in this image, and the reference holds no keypoint or descriptor
+resize), which is neither in the reference project nor in this image, and the reference holds no keypoint or descriptor
 fixture.  Restated from the published sources (float pipeline: sift_wt = float, SIFT_FIXPT_SCALE = 1):
 createInitialImage (x2 INTER_LINEAR, blur to sigma 1.6 assuming 0.5 in the input), buildGaussianPyramid (nOctaves =
 round(log2(min side)) - 2 + 1, 6 images per octave, INTER_NEAREST halving), buildDoGPyramid, findScaleSpaceExtrema

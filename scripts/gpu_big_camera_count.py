@@ -1,5 +1,5 @@
 import sys, time, os
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from oracle import orc
 from sfm_danpipeline_amd import synth, bundle, _lib

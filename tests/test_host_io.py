@@ -16,7 +16,8 @@ import pytest
 from sfm_danpipeline_amd import build
 
 PIL = pytest.importorskip("PIL.Image")
-REF_DATA = "/root/reference/data"
+# the reference's data/temple (ten 640 x 480 PNGs + camera_calibration_template.xml), committed byte for byte as test data
+TEMPLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "temple")
 
 
 # ---------------------------------------------------------------- helpers
@@ -341,16 +342,15 @@ def test_load_failures_follow_the_reference(tmp_path):
     assert _run(tmp_path, two, tmp_path / "nok.xml")[1] == 0
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF_DATA, "temple")), reason="the reference's dataset is not on this machine")
 def test_the_references_own_dataset_and_calibration_file(tmp_path):
-    """data/temple (640x480 PNGs: no resize) and its camera_calibration_template.xml, read in place."""
-    ok_img, ok_cal, imgs, K, dist, _ = _run(tmp_path, os.path.join(REF_DATA, "temple"),
-                                           os.path.join(REF_DATA, "temple", "camera_calibration_template.xml"))
+    """data/temple (640x480 PNGs: no resize) and its camera_calibration_template.xml (tests/golden/temple), read in place."""
+    ok_img, ok_cal, imgs, K, dist, _ = _run(tmp_path, TEMPLE,
+                                           os.path.join(TEMPLE, "camera_calibration_template.xml"))
     assert ok_img == 1 and ok_cal == 1
-    names = sorted(f for f in os.listdir(os.path.join(REF_DATA, "temple")) if f.lower().endswith((".png", ".jpg")))
+    names = sorted(f for f in os.listdir(TEMPLE) if f.lower().endswith((".png", ".jpg")))
     assert len(imgs) == len(names) >= 2
     for name, (bgr, gray) in zip(names, imgs):
-        assert np.array_equal(bgr, _pil_bgr(os.path.join(REF_DATA, "temple", name))), name
+        assert np.array_equal(bgr, _pil_bgr(os.path.join(TEMPLE, name))), name
         assert np.array_equal(gray, _cv_gray(bgr))
     assert np.array_equal(K, np.array([[1520.0, 0, 302.2], [0, 1520.0, 246.87], [0, 0, 1.0]]))
     assert np.array_equal(dist, np.zeros(5))
