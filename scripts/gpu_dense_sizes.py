@@ -14,5 +14,5 @@ for nc in [int(a) for a in sys.argv[1:]] or [200, 400, 640]:
     prob.iterate(3)
     n = 10 if nc <= 640 else 4
     t0 = time.time(); s = prob.iterate(n); dt = time.time() - t0
-    print(f"[dense xb={os.environ.get('SFMHIP_BA_DENSE_XB')}] {nc} cameras / {npt} points: {n/dt:.1f} it/s  cost {s.final_cost:.10e}", flush=True)
+    print(f"[dense] {nc} cameras / {npt} points: {n/dt:.1f} it/s  cost {s.final_cost:.10e}", flush=True)
     prob.close()

@@ -14,7 +14,7 @@ buf = np.zeros(4096 * 8 * 16, dtype=np.uint64)
 L = _lib.lib()
 L.sfmhip_dbg_read_stamps.argtypes = [C.c_void_p, C.c_size_t]
 assert L.sfmhip_dbg_read_stamps(buf.ctypes.data, buf.nbytes) == 0
-nwav = int(os.environ.get("SFMHIP_KNN_NW", "8"))
+nwav = 4  # waves per k-NN workgroup
 print('queries redone exactly by the compaction kernel (3 sweeps):', int(buf[-1]), ' of them overflow-flagged:', int(buf[-2]))
 st = buf.reshape(4096, 8, 16).astype(np.int64)[:, :nwav, :]
 st = st[st[:, 0, 5] > 0]          # (persistent workgroups: two per compute unit stamp, each its LAST work item)

@@ -1,5 +1,5 @@
 """Ad-hoc GPU check (run through gpurun): (S + D/r) z = g from the dense and from the dissected factorisation of the
-reduced camera system against numpy, at a given size `n_cam,n_pt,obs_per_pt` (SFMHIP_BA_ND_CUTS / _DEBUG / _VERBOSE
+reduced camera system against numpy, at a given size `n_cam,n_pt,obs_per_pt` (SFMHIP_BA_ND_DEBUG / _ND_VERBOSE
 are read by the library)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

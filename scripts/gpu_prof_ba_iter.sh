@@ -1,5 +1,5 @@
 #!/bin/bash
-# rocprofv3 kernel statistics of scripts/gpu_ba_iter_time.py cfg4 (run through gpurun); env passes through (e.g. SFMHIP_BA_BACKSUB_WPP)
+# rocprofv3 kernel statistics of scripts/gpu_ba_iter_time.py cfg4; env passes through (e.g. SFMHIP_BA_ND)
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_bi
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_bi -o bi --output-format csv -- python3 $GRAFT_REPO_ROOT/scripts/gpu_ba_iter_time.py cfg4 > /tmp/bi.log 2>&1

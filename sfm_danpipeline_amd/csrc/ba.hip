@@ -611,16 +611,12 @@ struct CamLds {  // camera table transposed in LDS: element e of camera slot o a
 #ifndef SFM_ELIM_LB
 #define SFM_ELIM_LB __launch_bounds__(512)
 #endif
-static bool elim_lp10() {
-  static const bool v = !(getenv("SFMHIP_BA_ELIM_LP") && atoi(getenv("SFMHIP_BA_ELIM_LP")) == 16);
-  return v;
-}
-// LP = lanes per point.  16 (rounds 2-5): a point's observations on one 16-lane DPP row, four points per wave and iteration; a
-// ten-camera point leaves six lanes of sixteen with the constant camera slot.  10 (round 6): six points per wave and iteration
-// (lanes 60-63 idle), the same instructions for 1.5 x the points; the twelve sums over a point's lanes, which no longer sit in one
-// DPP row, meet through the wave's panel in LDS (group_sum12), and the Gram panel is 18 rows -- five k-steps -- instead of 12.
-template <int LP>
+// LP = lanes per point: ten (round 6), six points per wave and iteration (lanes 60-63 idle).  Rounds 2-5 had sixteen, a point's
+// observations on one 16-lane DPP row and four points per wave and iteration; ten runs the same instructions for 1.5 x the points.
+// The twelve sums over a point's lanes, which do not sit in one DPP row, meet through the wave's panel in LDS (group10_sum12), and
+// the Gram panel is 18 rows -- five k-steps -- instead of 12.
 struct ElimShape {
+  static constexpr int LP = 10;
   static constexpr int PPW = 64 / LP;               // points per wave and iteration
   static constexpr int KST = (3 * PPW + 3) / 4;     // k-steps of the Gram update (4 panel rows each)
   static constexpr int PROWS = 4 * KST;             // panel rows per wave (rows beyond 3 * PPW stay zero)
@@ -662,17 +658,17 @@ __device__ __forceinline__ void group10_sum12(double (&red)[12], double* R, int 
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int NB, int LP>
+template <int NB>
 __device__ __forceinline__ void elim_chunk(const BaDev& d, const Chunk* __restrict__ chunks, const int chunk_index,
                                                          const int* __restrict__ sig_cams, double inv_radius,
                                                          double lm_lo, double lm_hi, int rank,
                                                          int norms /* 1: unscaled squared column norms of the cameras and the focal into dc, nothing else */,
                                                          double* __restrict__ slab /* non-null: the workgroup's sums go to its slab (ELIM_SLAB doubles per chunk) instead of atomics on S */) {
   constexpr int NT = NB * (NB + 1) / 2;
-  constexpr int PPW = ElimShape<LP>::PPW, KST = ElimShape<LP>::KST, PROWS = ElimShape<LP>::PROWS;
+  constexpr int LP = ElimShape::LP, PPW = ElimShape::PPW, KST = ElimShape::KST, PROWS = ElimShape::PROWS;
   __shared__ __attribute__((aligned(16))) double s_cam[CAMD * 16];
   extern __shared__ __attribute__((aligned(16))) double s_M[];  // nw x PROWS x MP panels; also the cross-wave reduction buffer
-  __shared__ double s_tsc[3 * 16];  // LP = 10: the cameras' translation scales by slot (read per iteration: six registers for F^T F sums)
+  __shared__ double s_tsc[3 * 16];  // the cameras' translation scales by slot (read per iteration: six registers for F^T F sums)
   __shared__ int s_gidx[64];  // local Gram index -> row/column of S; -2: the rhs column u; -1: padding
   __shared__ double s_wv[16];  // per wave: gradient maximum, failed point blocks (slab epilogue)
   const int nw = blockDim.x >> 6;  // 4 waves for long runs, 1 for runs of a few points (unstructured visibility)
@@ -711,16 +707,10 @@ __device__ __forceinline__ void elim_chunk(const BaDev& d, const Chunk* __restri
     else if (tid == 6 * n + 1) gi = -2;
     s_gidx[tid] = gi;
   }
-  const int o = LP == 16 ? (lane & 15) : lane % LP, q = LP == 16 ? (lane >> 4) : lane / LP;
-  const bool lane_ok = q < PPW;  // (LP = 10: lanes 60-63 belong to no point)
+  const int o = lane % LP, q = lane / LP;
+  const bool lane_ok = q < PPW;  // (lanes 60-63 belong to no point)
   const bool valid_o = lane_ok && o < n;
   const int oc = valid_o ? o : 0;  // idle lanes take observation 0's addresses (finite data) and slot 15's camera table (above); masked out below
-  double sc[6];
-  {
-    const int cam = cams[oc];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) sc[j] = norms ? 1.0 : d.scale_c[6 * cam + j];
-  }
   const double sf = norms ? 1.0 : *d.scale_f, focal = *d.focal;
   const int kobs0 = d.optr[ch.p0];
   __syncthreads();
@@ -735,7 +725,7 @@ __device__ __forceinline__ void elim_chunk(const BaDev& d, const Chunk* __restri
   const lds_double* cam_lds = (const lds_double*)s_cam + (valid_o ? o : 15);
   const int frow = lane >> 4, fcol = lane & 15;
   // F^T F part of a camera slot (the 6x6 block (upper, 21), the focal border (6), F^T b (6), Jf^2, Jf r, r^2 --
-  // what ba_cam_blocks formed from a second linearisation) meets in LDS, ds_add_f64 by the slot's four point lanes -- per
+  // what ba_cam_blocks formed from a second linearisation) meets in LDS, ds_add_f64 by the slot's six point lanes -- per
   // iteration for the sums that have no register (below), once behind the loop for those that have
   lds_double* ffw = (lds_double*)s_M + wave * (36 * FP) + oc;
   // point data of the next iteration is loaded one iteration ahead (a lone wave per SIMD otherwise waits a global
@@ -759,16 +749,12 @@ __device__ __forceinline__ void elim_chunk(const BaDev& d, const Chunk* __restri
   // that include iterations past the solve's convergence; 73.9 -> 68.4 us on a solve that still moves).  As many
   // as fit beside the Gram accumulators without spilling: 29 with ten tiles (256 registers, two waves per SIMD either way),
   // all 36 with six tiles or fewer.
-#ifdef SFM_ELIM_FFREG
-  constexpr int FFREG = SFM_ELIM_FFREG;  // (measurement builds)
-#else
-  // (LP = 10: the translation scales come from LDS every iteration, which leaves registers for three more sums; the four that
-  // still have none go to cells of the LANE's own -- [e - FFREG][lane] in the wave's part of the accumulator array, whose cells
-  // for the register sums are idle until the loop is over --, so that their ds_add_f64 hit no cell twice: with six lanes to a
-  // cell they took 2 k cycles that the point sums' LDS round trip, next in the wave's LDS queue, had to wait for)
-  constexpr int FFREG = NB == 4 ? (LP == 10 ? 32 : 29) : 36;
-#endif
-  constexpr bool FF_PRIVATE = LP == 10 && FFREG < 36;
+  // (Round 6: the translation scales come from LDS every iteration, which leaves registers for three more sums, 32 with ten
+  // tiles; the four that still have none go to cells of the LANE's own -- [e - FFREG][lane] in the wave's part of the accumulator
+  // array, whose cells for the register sums are idle until the loop is over --, so that their ds_add_f64 hit no cell twice: with
+  // six lanes to a cell they took 2 k cycles that the point sums' LDS round trip, next in the wave's LDS queue, had to wait for)
+  constexpr int FFREG = NB == 4 ? 32 : 36;
+  constexpr bool FF_PRIVATE = FFREG < 36;
   static_assert(!FF_PRIVATE || (36 - FFREG) * 64 <= FFREG * FP, "the lanes' own cells fit the idle part of the accumulator array");
   lds_double* ffp = (lds_double*)s_M + wave * (36 * FP) + lane;
   double ffr[FFREG > 0 ? FFREG : 1];
@@ -800,7 +786,7 @@ __device__ __forceinline__ void elim_chunk(const BaDev& d, const Chunk* __restri
     const double2 xy = nxy;
     if (PPW * (quad + nw) < ch.cnt) fetch(quad + nw);
     ObsLin ol;
-    if (LP == 10) {
+    {
       const lds_double* tsc = (const lds_double*)s_tsc + (valid_o ? o : 15);
       asm volatile("" : "+v"(tsc));  // (re-read every iteration, not hoisted into six registers)
       struct {
@@ -809,8 +795,6 @@ __device__ __forceinline__ void elim_chunk(const BaDev& d, const Chunk* __restri
         __device__ __forceinline__ double operator[](int j) const { return j >= 3 ? p[(j - 3) * 16] : 1.0; }
       } scl{tsc};
       obs_linearize_g<CamLds, decltype(scl), true>(cd, X, focal, xy.x, xy.y, scl, (const double*)nullptr, sf, ol);
-    } else {
-      obs_linearize_g<CamLds, const double*, true>(cd, X, focal, xy.x, xy.y, sc, (const double*)nullptr, sf, ol);
     }
     EL_STAMP(9, quad == wave + 2 * nw);
     const double live = (pv && valid_o) ? 1.0 : 0.0;
@@ -876,12 +860,7 @@ __device__ __forceinline__ void elim_chunk(const BaDev& d, const Chunk* __restri
       red[6 + a] = ol.Jp[a] * ol.r0 + ol.Jp[3 + a] * ol.r1;
       red[9 + a] = ol.Jp[a] * ol.Jf[0] + ol.Jp[3 + a] * ol.Jf[1];
     }
-    if (LP == 16) {
-#pragma unroll
-      for (int e = 0; e < 12; ++e) red[e] = row16_sum(red[e]);
-    } else {
-      group10_sum12(red, Mw, lane, q, o);
-    }
+    group10_sum12(red, Mw, lane, q, o);
     // LM damping of the point block: D^2 = clamp(diag) / radius
     double C[6] = {red[0], red[1], red[2], red[3], red[4], red[5]};
     C[0] += fmin(fmax(C[0], lm_lo), lm_hi) * inv_radius;
@@ -898,9 +877,9 @@ __device__ __forceinline__ void elim_chunk(const BaDev& d, const Chunk* __restri
     // gradient of the point (unscaled) for the gradient tolerance
     gmax = fmax(gmax, pvf * fmax(fabs(red[6] * isp[0]), fmax(fabs(red[7] * isp[1]), fabs(red[8] * isp[2]))));
     EL_STAMP(12, quad == wave + 2 * nw);
-    // (LP = 10: the sums above went through the panel's rows, so EVERY column of a point's rows is written -- a lane without an
-    // observation writes the zeros that Jp = 0 makes of its products, where LP = 16 leaves the zeros of the set-up alone)
-    if (LP == 16 ? valid_o : lane_ok) {
+    // (the sums above went through the panel's rows, so EVERY column of a point's rows is written -- a lane without an
+    // observation writes the zeros that Jp = 0 makes of its products)
+    if (lane_ok) {
       // T = (Jc^T Jp) Li^T = Jc^T (Jp Li^T): Q = Jp Li^T first (2 x 3, twelve operations), then T[i][k] = Jc[0][i] Q[0][k] +
       // Jc[1][i] Q[1][k] -- 48 operations where forming W = Jc^T Jp and then W Li^T took 72; row k of the panel
       double* row0 = Mw + (3 * q) * MP + 6 * o;
@@ -1164,7 +1143,7 @@ __device__ __forceinline__ void elim_chunk(const BaDev& d, const Chunk* __restri
   EL_STAMP(6, true);
 }
 
-template <int NB, int LP>
+template <int NB>
 __global__ SFM_ELIM_LB void ba_eliminate_mfma(BaDev d, const Chunk* __restrict__ chunks, const int* __restrict__ chunk_ids,
                                               const int* __restrict__ sig_cams, double inv_radius, double lm_lo, double lm_hi,
                                               int rank, int norms, double* __restrict__ slab) {
@@ -1178,7 +1157,7 @@ __global__ SFM_ELIM_LB void ba_eliminate_mfma(BaDev d, const Chunk* __restrict__
     lm_view(d, radius);
     inv_radius = 1.0 / radius;
   }
-  elim_chunk<NB, LP>(d, chunks, chunk_ids[blockIdx.x], sig_cams, inv_radius, lm_lo, lm_hi, rank, norms, slab);
+  elim_chunk<NB>(d, chunks, chunk_ids[blockIdx.x], sig_cams, inv_radius, lm_lo, lm_hi, rank, norms, slab);
 }
 
 // Sums the slabs of ba_eliminate_mfma into the reduced-system buffer: one thread per destination (an entry of S's
@@ -2671,7 +2650,7 @@ __global__ __launch_bounds__(1024) void chol_apply_inverse(const double* __restr
 // Launch K applies z_{K+1} to every tile column left of block K+1 (one workgroup per tile column, sums in a fixed order) and the
 // workgroups of block K's own columns then write their part X(., j) w_j of z_K; the parts are added, in column order, by every
 // workgroup of the next launch (one more launch for z_0): no counters, and the same S and g give the same z bit for bit.
-constexpr int DENSE_XB = 8, DENSE_XB_MIN_NT = 48, DENSE_DEFER4_MIN_NT = 100, DENSE_SWITCH_M2 = 40;
+constexpr int DENSE_XB = 8, DENSE_XB_MIN_NT = 48, DENSE_DEFER4_MIN_NT = 100, DENSE_SWITCH_M2 = 40, DENSE_TPW8_ROUNDS = 4;
 __global__ __launch_bounds__(256) void chol_x_reset(double* __restrict__ X, int ld, int nt, int xb) {
   const int j = blockIdx.x, r0 = j / xb * xb * CB, r1 = min(nt, (j / xb + 1) * xb) * CB;
   for (int e = threadIdx.x; e < CB * (r1 - r0); e += 256) {
@@ -3065,7 +3044,7 @@ __global__ void ba_cand_cams(BaDev d, const unsigned char* __restrict__ cam_used
 //   sum a.r + s.(sum Jp^T r) + (sum |a|^2)/2 + s.(sum Jp^T a) + s^T (sum Jp^T Jp) s / 2,
 // all of them sums the first pass forms next to C_p and e = sum Jp^T (r + a); the second pass only evaluates the
 // candidate's residuals.
-// WPP waves per block of 64 points: a lane is a point, wave `sub` of the block takes the observations sub, sub + WPP,
+// Two waves per block of 64 points: a lane is a point, wave `sub` of the block takes the observations sub, sub + 2,
 // ... -- the lanes of a wave still look at the same observation index, so inside a run they agree on the camera and
 // its table comes through scalar loads (below) -- and the 14 sums meet through LDS, added in wave order by every
 // wave alike.  A thread walks a chain of dependent loads per observation; with one wave per block a SIMD has 1.5
@@ -3232,13 +3211,14 @@ __device__ __forceinline__ void step_skip(const BaDev& d) {
   if (DECIDE && d.step_last && d.decide_here && blockIdx.x == 0 && threadIdx.x == 0) lm_decide_here(d);
 }
 
-template <int WPP>
+constexpr int BS_WPP = 2;  // waves per block of 64 points
 __global__ __launch_bounds__(256) void ba_backsub(BaDev d, double radius, double lm_lo, double lm_hi, const int* __restrict__ plist, int npl,
                                                   int slot0 /* this kernel's first slot of step_part */) {
   if (lm_stopped(d)) return;  // (the decision of a launch of this kernel is ba_decide's: the kernel sits at its register limit)
   lm_view(d, radius);
+  constexpr int WPP = BS_WPP;
   constexpr int BLOCKS = 4 / WPP;  // blocks of 64 points per workgroup
-  __shared__ double s_part[WPP > 1 ? 4 * BS_SUMS * 64 : 1];
+  __shared__ double s_part[4 * BS_SUMS * 64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int wb = wave / WPP, sub = wave % WPP;
   // (plist: the points that ba_backsub_runs does not take -- those of the pair path; null: all of them)
@@ -3301,17 +3281,15 @@ __global__ __launch_bounds__(256) void ba_backsub(BaDev d, double radius, double
       sm[13] += a0 * a0 + a1 * a1;
     }
   }
-  if (WPP > 1) {
 #pragma unroll
-    for (int e = 0; e < BS_SUMS; ++e) s_part[(wave * BS_SUMS + e) * 64 + lane] = sm[e];
-    __syncthreads();
+  for (int e = 0; e < BS_SUMS; ++e) s_part[(wave * BS_SUMS + e) * 64 + lane] = sm[e];
+  __syncthreads();
 #pragma unroll
-    for (int e = 0; e < BS_SUMS; ++e) {
-      double v = 0.0;
+  for (int e = 0; e < BS_SUMS; ++e) {
+    double v = 0.0;
 #pragma unroll
-      for (int w = 0; w < WPP; ++w) v += s_part[((wb * WPP + w) * BS_SUMS + e) * 64 + lane];
-      sm[e] = v;
-    }
+    for (int w = 0; w < WPP; ++w) v += s_part[((wb * WPP + w) * BS_SUMS + e) * 64 + lane];
+    sm[e] = v;
   }
   if (active) {
     double C[6] = {sm[0], sm[1], sm[2], sm[3], sm[4], sm[5]};
@@ -3385,8 +3363,7 @@ __global__ __launch_bounds__(256) void ba_backsub(BaDev d, double radius, double
 constexpr int BSR_PTS = 256;  // points per block of a workgroup (a thread each)
 // bs_desc: 16 ints per run, large runs first: n, p0, cnt, the first observation's index, the n <= 10 cameras -- everything the
 // workgroup's loads depend on in ONE record (chunk id -> chunk -> camera list -> tables was four dependent round trips)
-__global__ __launch_bounds__(256) void ba_backsub_runs(BaDev d, const int4* __restrict__ bs_desc, double radius, double lm_lo, double lm_hi,
-                                                      int split) {
+__global__ __launch_bounds__(256) void ba_backsub_runs(BaDev d, const int4* __restrict__ bs_desc, double radius, double lm_lo, double lm_hi) {
   if (lm_stopped(d)) {
     step_skip<true>(d);
     return;
@@ -3400,13 +3377,11 @@ __global__ __launch_bounds__(256) void ba_backsub_runs(BaDev d, const int4* __re
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int pt = tid;  // (a thread per point: every lane of a wave is at the same observation index, hence the same camera)
   __shared__ int s_cams[12];
-  const int4* const rec = bs_desc + 4 * (size_t)(blockIdx.x / split);
+  const int4* const rec = bs_desc + 4 * (size_t)blockIdx.x;
   const int4 hd = rec[0];  // n, p0, cnt, first observation
   struct { int n, p0, cnt; } ch = {hd.x, hd.y, hd.z};
   const int kobs0 = hd.w;
   if (tid < 12) s_cams[tid] = ((const int*)(rec + 1))[tid];
-  const int part = blockIdx.x % split;
-  const int pt_lo = (int)((long long)ch.cnt * part / split), pt_hi = (int)((long long)ch.cnt * (part + 1) / split);
   const int n = ch.n;
   const double sf = *d.scale_f, focal = *d.focal, focal_c = *d.focal_c, zf = d.z[6 * d.nc];
   __syncthreads();
@@ -3432,8 +3407,8 @@ __global__ __launch_bounds__(256) void ba_backsub_runs(BaDev d, const int4* __re
     s_zs[idx] = v;
   }
   double mcc = 0, cost_c = 0, sn2 = 0, cn2 = 0;
-  for (int blk = pt_lo; blk < pt_hi; blk += BSR_PTS) {
-    const int npts = min(BSR_PTS, pt_hi - blk);
+  for (int blk = 0; blk < ch.cnt; blk += BSR_PTS) {
+    const int npts = min(BSR_PTS, ch.cnt - blk);
     const bool active = pt < npts;
     const int p = ch.p0 + blk + (active ? pt : 0);
     // (the point, its scale and the block's observations are asked for together: one round trip, not three)
@@ -3651,10 +3626,8 @@ struct sfmhip_ba {
   int2* d_pair_cams = nullptr;
   int2* d_pair_ent = nullptr;
   int n_pairs_pp = 0;
-  int tree_xoff = 0;  // which of every `tree_stride` workgroups holds a front: a different one for every problem of the process
   long long tree_dbg_ints = 0, tree_dbg_doubles = 0;  // (sizes of the front tree's tables and pool: diagnostic builds)
   int* d_bs_ids = nullptr;  // ba_backsub_runs' records, 16 ints per chunk, large chunks first
-  int elim_waves = 4;  // waves per workgroup of the long-run class of ba_eliminate_mfma (8, 4 or 2)
   // dissected reduced system (NdPlan below): built at the first solve (with world > 1 the camera graph is the
   // union over the ranks, which needs the all-reduce)
   std::vector<unsigned long long> h_adj;  // camera co-visibility, nc x ceil(nc/64) bit rows (this rank's points)
@@ -3671,7 +3644,7 @@ struct sfmhip_ba {
   bool tree_on = false, tree_attr_set = false, solve_cand = false;
   FrontSet tree_fs{};
   unsigned tree_epoch = 0;
-  int tree_stride = 1, tree_levels = 0, tree_chain_tiles = 0, tree_chain_blocks = 0, tree_max_T = 0;
+  int tree_levels = 0, tree_chain_tiles = 0, tree_chain_blocks = 0, tree_max_T = 0;
   // ba_finalize deferred to the next nd_gather (the LM loop's linearisations, when the dissected solve follows)
   bool fin_pending = false, defer_fin = false;
   double fin_radius = 0, fin_lo = 0, fin_hi = 0;
@@ -3804,7 +3777,7 @@ static int ba_alloc(sfmhip_ba* b, T** p, size_t n) {
     // (a problem of the one-shot entry point: carved from the context's block, given back as a whole when the problem goes)
     void* v = (char*)b->ctx->ba_arena + b->arena_off;
     b->arena_off += bytes;
-    static const bool poison = getenv("SFMHIP_POISON") != nullptr;  // (tests: as sfm_dev_alloc does for fresh allocations)
+    const bool poison = getenv("SFMHIP_POISON") != nullptr;  // (tests: as sfm_dev_alloc does for fresh allocations)
     if (poison) {
       hipMemset(v, 0xFF, bytes);
       hipDeviceSynchronize();
@@ -3894,15 +3867,19 @@ struct BaHostScratch {
   std::vector<uint64_t> sig_hash;
   std::vector<double> h_pts_in;
   // the front tree of the last one-shot problem: the per-view call pattern (src/Sfm.cpp:996) changes the tracks from call to
-  // call and the camera graph hardly ever -- a problem with the same graph (compared bit for bit) and the same planning
-  // switches takes the kept plan instead of dissecting again (2.5 ms of a 23 ms call at cfg4)
+  // call and the camera graph hardly ever -- a problem with the same graph (compared bit for bit) on the same device takes the
+  // kept plan instead of dissecting again (2.5 ms of a 23 ms call at cfg4)
   bool nd_valid = false;
-  int nd_nc = 0, nd_key[5] = {0, 0, 0, 0, 0};
+  int nd_nc = 0, nd_n_cu = 0;
   std::vector<unsigned long long> nd_adj;
   fplan::Plan nd_P;
   fplan::Flat nd_fl;
 };
 static void ba_host_scratch_free(void* p) { delete (BaHostScratch*)p; }
+// SFMHIP_BA_PLAN_CACHE=0: sfmhip_ba_solve keeps neither the last problem nor the last front plan (read at every use)
+static bool ba_plan_cache_on() {
+  return !(getenv("SFMHIP_BA_PLAN_CACHE") && atoi(getenv("SFMHIP_BA_PLAN_CACHE")) == 0);
+}
 static BaHostScratch* ba_host_scratch(sfmhip_ctx* ctx) {
   if (!ctx->ba_host_scratch) {
     ctx->ba_host_scratch = new BaHostScratch();
@@ -3964,6 +3941,12 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   sfmhip_ba* b = new sfmhip_ba();
   b->ctx = ctx;
   b->use_arena = arena;
+  // every error return below hands the half-built problem to sfmhip_ba_destroy: its device memory, and in arena mode the
+  // context's scratch vectors, go back
+  struct DestroyOnError {
+    sfmhip_ba* b;
+    ~DestroyOnError() { sfmhip_ba_destroy(b); }
+  } guard{b};
   b->nc = n_cam;
   b->np_in = n_pt;
   b->no_in = n_obs;
@@ -4069,10 +4052,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
       }
     });
     for (char c : too_many)
-      if (c) {
-        delete b;
-        return SFMHIP_ERR_UNSUPPORTED;  // more than FB_MAXN observations of one point
-      }
+      if (c) return SFMHIP_ERR_UNSUPPORTED;  // more than FB_MAXN observations of one point
     // the blocks' runs, block by block in their local order, into one table: global run ids in the points' order of first appearance
     size_t total = 0;
     for (const auto& r : loc_rep) total += r.size();
@@ -4160,7 +4140,6 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
     for (size_t sp = 0; sp < order1.size(); ++sp) optr1[sp + 1] = optr1[sp] + (cnt[order1[sp] + 1] - cnt[order1[sp]]);
     if (rep1 != run_rep || of1 != run_of || order1 != order || optr1 != optr) {
       fprintf(stderr, "sfmhip_ba_create: the threads' grouping differs from one thread's (SFMHIP_BA_CHECK_SETUP)\n");
-      delete b;
       return SFMHIP_ERR_STATE;
     }
   }
@@ -4202,7 +4181,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   // points per workgroup: 2 workgroups of 4 waves are resident per CU (register-bound), so the launch runs in
   // rounds of 512 workgroups; a wave takes 4 points per iteration (~3.7 us at n = 10) and a fixed ~7 iterations'
   // worth of prologue, reductions and scatter (s_memtime stamps, scripts/elim_stamps.py).  Pick the run length
-  // that minimises rounds x (iterations per wave + fixed).  Measured at cfg4 (scripts/gpu_ba_elim_ab.py, stage
+  // that minimises rounds x (iterations per wave + fixed).  Measured at cfg4 (round 2, stage
   // time per LM iteration): 400 workgroups of 4 waves 100 us; 800 of 2 waves 106 us; 200 of 8 waves 150 us (not a
   // matter of the two waves of a SIMD running in step: starting waves 4..7 up to 8 k cycles late changes nothing,
   // 148-151 us); 800 of 4 waves (2 rounds) 136 us.
@@ -4216,20 +4195,13 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
     for (int t = 32; t <= 1024; t += 4) {
       long long w = 0;
       for (int g : gsz) w += (g + t - 1) / t;
-      // (a workgroup's iteration takes 4 waves x 4 points, or x 6 with ten lanes per point, whose iterations are a third longer:
-      // the fixed part counts for fewer of them)
-      const int ppi = elim_lp10() ? 24 : 16;
-      const double cost = (double)((w + 511) / 512) * ((double)((t + ppi - 1) / ppi) + (elim_lp10() ? 5.5 : 7.0));
+      // (a workgroup's iteration takes 4 waves x 6 points with ten lanes per point; its iterations are a third longer than the
+      // 4 x 4 of sixteen lanes per point, so the fixed part counts for 5.5 of them where it counted for 7)
+      const int ppi = 24;
+      const double cost = (double)((w + 511) / 512) * ((double)((t + ppi - 1) / ppi) + 5.5);
       if (cost < best) {
         best = cost;
         target = t;
-      }
-    }
-    if (const char* e = getenv("SFMHIP_BA_ELIM")) {  // "waves,target" (measurement)
-      int w_ = 0, t_ = 0;
-      if (sscanf(e, "%d,%d", &w_, &t_) == 2 && (w_ == 2 || w_ == 4 || w_ == 8) && t_ >= 8) {
-        b->elim_waves = w_;
-        target = t_;
       }
     }
   }
@@ -4237,9 +4209,8 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   // slots, so 112 CUs hold one workgroup and idle half the launch while 144 hold two), the largest pieces are cut
   // once more until the slots are full, and the launch lists the large pieces first: the dispatcher deals the first
   // n_cu workgroups one per CU, so every CU ends up with a large and a small piece or two small ones.  The busiest
-  // SIMD then has 250 + 167 points instead of 500 (SFMHIP_BA_ELIM_FILL=0: the plain cut).
-  const int slots = (getenv("SFMHIP_BA_ELIM_SLOTS") ? atoi(getenv("SFMHIP_BA_ELIM_SLOTS")) : 2) * std::max(b->ctx->n_cu, 1);  // (resident workgroups per CU: a measurement knob)
-  const bool fill_env = !(getenv("SFMHIP_BA_ELIM_FILL") && atoi(getenv("SFMHIP_BA_ELIM_FILL")) == 0);
+  // SIMD then has 250 + 167 points instead of 500.
+  const int slots = 2 * std::max(b->ctx->n_cu, 1);  // (resident workgroups per CU)
   std::vector<int> parts_of(gstart.size(), 0);
   {
     long long w = 0;
@@ -4247,7 +4218,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
       const int g = gstart[gi + 1] - gstart[gi];
       if (g > SHORT_RUN) w += (parts_of[gi] = (g + target - 1) / target);
     }
-    if (fill_env && w > slots / 2 && w < slots) {
+    if (w > slots / 2 && w < slots) {
       // (a max-heap on the current piece size; a piece of fewer than 64 points is not worth another workgroup)
       std::vector<std::pair<double, size_t>> heap;
       for (size_t gi = 0; gi + 1 < gstart.size(); ++gi)
@@ -4309,9 +4280,8 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
       for (int q = sp; q < e; ++q) fb.push_back(q);
     }
   }
-  if (fill_env)
-    for (auto& l : ids)  // large pieces first (stable: equal sizes keep the point order)
-      std::stable_sort(l.begin(), l.end(), [&](int a, int c) { return chunks[a].cnt > chunks[c].cnt; });
+  for (auto& l : ids)  // large pieces first (stable: equal sizes keep the point order)
+    std::stable_sort(l.begin(), l.end(), [&](int a, int c) { return chunks[a].cnt > chunks[c].cnt; });
   lap_("chunks");
   // ---- the gather lists of the slab epilogue (ba_gather_slabs): for every destination in `red` the slab entries that
   // add to it, in chunk order; list 0 for a full linearisation, list 1 for the norms-only mode (diagonal only)
@@ -4333,8 +4303,6 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
     // a whole row, ld entries zeroed and scanned whatever the row held: at 640 cameras that outweighed what the row-wise reads
     // save, and rows of more than 3072 columns went through the per-destination lists -- scripts/gpu_gather_bits.py: 640 cameras
     // 3305 -> 3619 it/s, 1000: 2805 -> 3267, the same bits as the whole-row form wherever that ran).
-    // SFMHIP_BA_GATHER_ROWS = 0: never (the per-destination lists: measurement, and the check of the row lists)
-    const int rows_env = getenv("SFMHIP_BA_GATHER_ROWS") ? atoi(getenv("SFMHIP_BA_GATHER_ROWS")) : 1;
     // (round 6: a row's accumulator holds only the columns the row can have -- the cameras that share a run with the row's camera,
     // the focal column, g's / the diagonal's / F^T b's entries --, not all ld of them: a wave zeroed and scanned ld entries whatever
     // the row held, which is what kept rows of 640 cameras and more on the per-destination lists)
@@ -4360,7 +4328,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
     }
     size_t accw = 64;  // a wave's accumulator: 6 entries per camera of the longest list + 4, in whole 64s
     for (int c = 0; c < n_cam; ++c) accw = std::max(accw, (6 * (size_t)(tl_off[c + 1] - tl_off[c]) + 4 + 63) / 64 * 64);
-    const bool use_rows = accw * 8 <= 65536 && rows_env != 0;
+    const bool use_rows = accw * 8 <= 65536;
     b->grow_waves = accw * 8 * 4 <= 65536 ? 4 : accw * 8 * 2 <= 65536 ? 2 : 1;
     b->grow_accw = (int)accw;
     if (use_rows) {
@@ -4657,20 +4625,10 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
     if (rc == SFMHIP_OK && hipMemset(b->d_cb_cnt, 0, sizeof(int) * (size_t)n_cam) != hipSuccess) rc = SFMHIP_ERR_HIP;
   }
   {
-    // (measurement: 0 = all of X, DENSE_XB = blocks even below the size that switches them on.  The block width itself is not a
-    // knob: chol_back_block's registers and LDS and the sizes of d_back_part are built for DENSE_XB tile columns)
-    static const int xb_env = [] {
-      const char* e = getenv("SFMHIP_BA_DENSE_XB");
-      if (!e) return -1;
-      const int v = atoi(e);
-      if (v != 0 && v != DENSE_XB) {
-        fprintf(stderr, "[sfmhip-ba] SFMHIP_BA_DENSE_XB=%d ignored: 0 (all of X) or %d (diagonal blocks) are the choices\n", v, DENSE_XB);
-        return -1;
-      }
-      return v;
-    }();
+    // (the block width is not a knob: chol_back_block's registers and LDS and the sizes of d_back_part are built for DENSE_XB
+    // tile columns)
     const int nt = b->ld / CB;
-    b->dense_xb = xb_env == 0 ? 0 : (xb_env > 0 || nt >= DENSE_XB_MIN_NT) ? DENSE_XB : 0;
+    b->dense_xb = nt >= DENSE_XB_MIN_NT ? DENSE_XB : 0;
     if (b->dense_xb) {
       BA_A(b->d_back_part, 2 * DENSE_XB * DENSE_XB * CB);  // (two sets: a launch reads the one the launch before wrote)
       // X outside its diagonal blocks is never written -- but the panel workgroups of a block's first pair of panels read the
@@ -4683,10 +4641,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   BA_A(b->d_pair_cams, pair_cams.size());
   BA_A(b->d_pair_ent, pair_ent.size());
 #undef BA_A
-  if (rc != SFMHIP_OK) {
-    sfmhip_ba_destroy(b);
-    return rc;
-  }
+  if (rc != SFMHIP_OK) return rc;
   d.optr = d_optr;
   d.ocam = d_ocam;
   d.oxy = d_oxy;
@@ -4762,12 +4717,12 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   }
   SFM_HIP_TRY(hipHostGetDevicePointer((void**)&b->h_sc_dev, b->h_sc, 0));
   b->h_sc[SC + 64 + RED2_N] = 0.0;
-  // the trust-region record, the host's ring of copies of it, the step evaluation's slots (runs x split <= 8, blocks of 64
+  // the trust-region record, the host's ring of copies of it, the step evaluation's slots (a workgroup per run, blocks of 64
   // points of ba_backsub, then a pair per front / per wave of ba_cand_cams)
   memset(b->h_ring, 0, sizeof(LmDev) * LM_RING);  // (a shared block: the previous problem's records must not match this one's sequence numbers)
   SFM_HIP_TRY(hipHostGetDevicePointer((void**)&b->h_ring_dev, b->h_ring, 0));
   SFM_TRY(ba_alloc(b, &b->d_lm, 1));
-  b->step_part_n = 4 * ((size_t)b->n_chunks * 8 + ((size_t)b->np + 63) / 64 + 8) + 2 * ((size_t)n_cam + 64);
+  b->step_part_n = 4 * ((size_t)b->n_chunks + ((size_t)b->np + 63) / 64 + 8) + 2 * ((size_t)n_cam + 64);
   SFM_TRY(ba_alloc(b, &b->d_step_part, b->step_part_n));
   {
     std::vector<unsigned long long> pend(b->step_part_n, STEP_PENDING);  // (a slot is a NaN no sum produces until its workgroup has written it)
@@ -4780,6 +4735,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   for (auto& e : b->ev) SFM_HIP_TRY(hipEventCreate(&e));
   b->h_pts_in.assign(3 * (size_t)n_pt, 0.0);
   lap_("pinned + events");
+  guard.b = nullptr;
   *out = b;
   return SFMHIP_OK;
 }
@@ -4975,26 +4931,19 @@ static int ba_launch_eliminate(sfmhip_ba* b, double inv_radius, double lm_lo, do
   // 22.5 us as a thread per destination (1 M scattered 8-byte sources), 10.9 us row by row (ba_gather_rows): the stage
   // 92.2 us against 91.3.
   double* slab = b->elim_deterministic ? b->d_slab : nullptr;
-  // ten lanes per point (six points per wave and iteration) unless SFMHIP_BA_ELIM_LP=16 asks for the sixteen of rounds 2-5 (A/B)
-  const bool lp10 = elim_lp10();
 #define BA_ELIM(NB)                                                                                                   \
   for (int cls = 0; cls < 2; ++cls) {                                                                                 \
-    const int li = 4 * cls + NB - 1, nthreads = cls ? 64 : 64 * b->elim_waves;                                        \
+    const int li = 4 * cls + NB - 1, nthreads = cls ? 64 : 256;                                                       \
     if (!b->n_chunk_ids[li]) continue;                                                                                \
     /* wave panels | the cross-wave Gram reduction (NT x 4 x 64) | the F^T F reduction */                             \
     const size_t nw_ = nthreads / 64, gram_ = (size_t)(NB * (NB + 1) / 2) * 256;                                      \
     /* (four waves: the cross-wave sum takes four buffers of up to five tiles) */                                      \
     const size_t red_ = nw_ == 4 ? (size_t)4 * std::min(NB * (NB + 1) / 2, 5) * 256 : 0;                              \
-    const size_t prows_ = lp10 ? ElimShape<10>::PROWS : ElimShape<16>::PROWS;                                          \
+    const size_t prows_ = ElimShape::PROWS;                                                                           \
     const size_t lds = sizeof(double) * (nw_ * 36 * FP + 3 * FP + std::max(std::max(nw_ * prows_ * MP, gram_), red_)); \
-    if (lp10)                                                                                                         \
-      hipLaunchKernelGGL((ba_eliminate_mfma<NB, 10>), dim3(b->n_chunk_ids[li]), dim3(nthreads), lds, st, b->d,        \
-                         b->d_chunks, b->d_chunk_ids[li],                                                             \
-                         b->d_sig_cams, inv_radius, lm_lo, lm_hi, b->rank, norms, slab);                              \
-    else                                                                                                              \
-      hipLaunchKernelGGL((ba_eliminate_mfma<NB, 16>), dim3(b->n_chunk_ids[li]), dim3(nthreads), lds, st, b->d,        \
-                         b->d_chunks, b->d_chunk_ids[li],                                                             \
-                         b->d_sig_cams, inv_radius, lm_lo, lm_hi, b->rank, norms, slab);                              \
+    hipLaunchKernelGGL((ba_eliminate_mfma<NB>), dim3(b->n_chunk_ids[li]), dim3(nthreads), lds, st, b->d,              \
+                       b->d_chunks, b->d_chunk_ids[li],                                                               \
+                       b->d_sig_cams, inv_radius, lm_lo, lm_hi, b->rank, norms, slab);                                \
     ++nl;                                                                                                             \
   }
   BA_ELIM(1)
@@ -5194,15 +5143,14 @@ static int ba_nd_build(sfmhip_ba* b) {
       for (int j = 0; j < nc; ++j)
         if (h[(size_t)i * nc + j] > 0.5) adj[(size_t)i * wpr + (j >> 6)] |= 1ull << (j & 63);
     // ---- the exchange of a linearisation: only the blocks of camera pairs that some rank's points see together,
-    // when that is less than half of the packed triangle (SFMHIP_BA_XSPARSE=0: the dense exchange always)
+    // when that is less than half of the packed triangle
     std::vector<int2> xb;
     for (int a = 0; a < nc; ++a)
       for (int c = a; c < nc; ++c)
         if (c == a || ((adj[(size_t)a * wpr + (c >> 6)] >> (c & 63)) & 1ull) || ((adj[(size_t)c * wpr + (a >> 6)] >> (a & 63)) & 1ull))
           xb.push_back(make_int2(a, c));
     const size_t tri = (size_t)b->ld * (b->ld + 1) / 2;
-    const char* xs = getenv("SFMHIP_BA_XSPARSE");
-    if (!(xs && xs[0] == '0') && xb.size() * 36 + b->dim < tri / 2) {
+    if (xb.size() * 36 + b->dim < tri / 2) {
       SFM_TRY(ba_alloc(b, &b->d_xblocks, xb.size()));
       SFM_HIP_TRY(hipMemcpy(b->d_xblocks, xb.data(), xb.size() * sizeof(int2), hipMemcpyHostToDevice));
       b->n_xblocks = (int)xb.size();
@@ -5212,15 +5160,7 @@ static int ba_nd_build(sfmhip_ba* b) {
   // ---- the front tree first (SFMHIP_BA_ND=2 or unset): every front on one CU; "1" keeps the chains + separator plan below
   if (!(env && env[0] == '1')) {
     // components up to this many columns become leaves: the largest size whose fronts fit (a leaf of three tiles under a
-    // border of five does not); SFMHIP_BA_TREE_LEAF fixes it (experiments)
-    const char* lc = getenv("SFMHIP_BA_TREE_LEAF");
-    // helper workgroups per front (ba_front_plan.h, Front::nhelp; SFMHIP_BA_TREE_HELPERS = 1 ... 8): built in round 5 and OFF by
-    // default -- measured slower at every setting (cfg4: 0.2146 ms per iteration without, 0.223-0.236 with 2-5 helpers keeping
-    // 4-10 tiles in the front).  A helper's tile reaches the parent three trips through memory behind the front's last solve
-    // (the front's stores acknowledged, its flag seen, its rows of L loaded: ~8 k cycles) where the front folds ALL its tiles
-    // in 10-17 k; DESIGN.md appendix A has the counts.  Never more than leave every workgroup of the up-sweep a compute unit
-    // of its own.
-    const char* he = getenv("SFMHIP_BA_TREE_HELPERS");
+    // border of five does not)
     fplan::Plan P;
     fplan::Flat fl;
     const bool prof_ = getenv("SFMHIP_PROFILE_CREATE") != nullptr;
@@ -5231,29 +5171,21 @@ static int ba_nd_build(sfmhip_ba* b) {
       fprintf(stderr, "[ba_nd_build] %-22s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tp_).count());
       tp_ = now;
     };
-    static const int keep_env = getenv("SFMHIP_BA_TREE_KEEP") ? atoi(getenv("SFMHIP_BA_TREE_KEEP")) : 8;  // (measurement)
-    // (a one-shot problem: the plan of the last one, when the camera graph and the switches are the same -- BaHostScratch)
-    static const bool plan_cache_on = !(getenv("SFMHIP_BA_PLAN_CACHE") && atoi(getenv("SFMHIP_BA_PLAN_CACHE")) == 0);
-    BaHostScratch* const hs = plan_cache_on && b->use_arena && b->world == 1 ? ba_host_scratch(b->ctx) : nullptr;
-    const int key[5] = {lc ? atoi(lc) : -1, he ? atoi(he) : -1, keep_env, b->ctx->n_cu, 1};
-    const bool kept = hs && hs->nd_valid && hs->nd_nc == nc && memcmp(hs->nd_key, key, sizeof key) == 0 && hs->nd_adj == adj;
+    // (a one-shot problem: the plan of the last one, when the camera graph and the device are the same -- BaHostScratch)
+    BaHostScratch* const hs = ba_plan_cache_on() && b->use_arena && b->world == 1 ? ba_host_scratch(b->ctx) : nullptr;
+    const bool kept = hs && hs->nd_valid && hs->nd_nc == nc && hs->nd_n_cu == b->ctx->n_cu && hs->nd_adj == adj;
     b->nd_kept = kept;
     if (kept) {
       P = hs->nd_P;
       fl = hs->nd_fl;
     } else {
-      for (int helpers = he ? std::max(0, std::min(8, atoi(he))) : 0; helpers >= 0; --helpers) {
-        for (int leaf : {96, 64, 32}) {
-          P = fplan::build_plan(nc, adj.data(), wpr, lc ? atoi(lc) : leaf, helpers, keep_env);
-          if (P.ok || lc) break;
-        }
-        if (!P.ok) break;
-        fl = fplan::flatten(P);
-        if ((int)fl.up_roles.size() <= b->ctx->n_cu || he) break;
+      for (int leaf : {96, 64, 32}) {
+        P = fplan::build_plan(nc, adj.data(), wpr, leaf);
+        if (P.ok) break;
       }
+      if (P.ok) fl = fplan::flatten(P);
       if (hs) {  // (a refused plan is kept as well: the next call does not search for it again)
-        hs->nd_valid = true, hs->nd_nc = nc, hs->nd_adj = adj, hs->nd_P = P, hs->nd_fl = fl;
-        memcpy(hs->nd_key, key, sizeof key);
+        hs->nd_valid = true, hs->nd_nc = nc, hs->nd_n_cu = b->ctx->n_cu, hs->nd_adj = adj, hs->nd_P = P, hs->nd_fl = fl;
       }
     }
     lap_(kept ? "front plan (kept)" : "front plan");
@@ -5280,10 +5212,6 @@ static int ba_nd_build(sfmhip_ba* b) {
       b->tree_fs.down_order = d_down;
       b->tree_fs.pool = pool;
       b->tree_dbg_ints = (long long)fl.ints.size(), b->tree_dbg_doubles = (long long)fl.n_doubles;
-      {
-        static std::atomic<int> n_trees{0};
-        b->tree_xoff = n_trees.fetch_add(1) & 7;
-      }
       b->tree_fs.flag_down = d_flags;
       b->tree_fs.tflag = d_flags + fl.n_fronts;
       double* zq = nullptr;
@@ -5296,19 +5224,16 @@ static int ba_nd_build(sfmhip_ba* b) {
       b->tree_fs.zq = zq;
       b->tree_fs.zq_ld = b->ld;
       b->tree_fs.n_fronts = fl.n_fronts;
-      b->tree_fs.n_roles = (int)fl.up_roles.size();
 
       b->tree_levels = fl.levels;
       b->tree_chain_tiles = P.chain_tiles;
       b->tree_chain_blocks = P.chain_blocks;
       b->tree_max_T = P.max_T;
-      const char* se = getenv("SFMHIP_BA_TREE_STRIDE");
-      b->tree_stride = se ? std::max(1, atoi(se)) : 1;
       b->tree_on = true;
       b->nd_on = true;  // (what the two share: the deferred ba_finalize, the pre-zeroed second buffer)
       if (getenv("SFMHIP_BA_ND_VERBOSE"))
-        fprintf(stderr, "[sfmhip] reduced system as a front tree: %d fronts (+ %d helper workgroups), %d levels, %d tile steps (%d block steps) on the chain, fronts of up to %d tiles; dense %d tiles\n",
-                fl.n_fronts, (int)fl.up_roles.size() - fl.n_fronts, fl.levels, P.chain_tiles, P.chain_blocks, P.max_T, b->ld / CB);
+        fprintf(stderr, "[sfmhip] reduced system as a front tree: %d fronts, %d levels, %d tile steps (%d block steps) on the chain, fronts of up to %d tiles; dense %d tiles\n",
+                fl.n_fronts, fl.levels, P.chain_tiles, P.chain_blocks, P.max_T, b->ld / CB);
       return SFMHIP_OK;
     }
     if (getenv("SFMHIP_BA_ND_VERBOSE")) fprintf(stderr, "[sfmhip] no front tree: %s\n", P.why);
@@ -5419,15 +5344,13 @@ static int ba_nd_build(sfmhip_ba* b) {
     std::vector<int> grid;
     for (int k = 1; k < G; ++k) grid.push_back((int)((long long)nc * k / G));
     Eval e;
-    const char* ce = getenv("SFMHIP_BA_ND_CUTS");  // at most this many cuts (experiments)
-    const int max_cuts = ce ? atoi(ce) : 3;
-    for (size_t i = 0; i < grid.size(); ++i) {
+    for (size_t i = 0; i < grid.size(); ++i) {  // at most three cuts
       evaluate({grid[i]}, e);
       if (e.cost < best.cost) best = e;
-      for (size_t j = i + 1; j < grid.size() && max_cuts >= 2; ++j) {
+      for (size_t j = i + 1; j < grid.size(); ++j) {
         evaluate({grid[i], grid[j]}, e);
         if (e.cost < best.cost) best = e;
-        if (nc <= 1024 && max_cuts >= 3)
+        if (nc <= 1024)
           for (size_t k = j + 1; k < grid.size(); k += 2) {
             evaluate({grid[i], grid[j], grid[k]}, e);
             if (e.cost < best.cost) best = e;
@@ -5583,23 +5506,20 @@ static int ba_reduced_solve_tree(sfmhip_ba* b) {
   const size_t nz = b->red_count - b->ssz;
   if (prezero && !b->red_alt && nz % 2 == 0) SFM_TRY(ba_alloc(b, &b->red_alt, nz));
   const int zwg = prezero && b->red_alt ? (int)((nz + ND_ZERO_SLICE - 1) / ND_ZERO_SLICE) : 0;
-  const int nF = b->tree_fs.n_roles, stride = b->tree_stride;  // (fronts and their helper workgroups)
-  // grid: the fronts at multiples of `stride`; the zeroing workgroups fill the gaps and follow; one more for the bookkeeping
-  const int gaps = (stride - 1) * nF;
-  const int grid = stride * nF + std::max(0, zwg + 1 - gaps);
+  const int nF = b->tree_fs.n_fronts;
+  // grid: the fronts, then the zeroing workgroups, then one more for the bookkeeping
+  const int grid = nF + zwg + 1;
   const unsigned epoch = ++b->tree_epoch;
-  static const bool by_level_env = getenv("SFMHIP_BA_TREE_BY_LEVEL") != nullptr;  // (diagnostic: one launch per tree level)
-  const bool by_level = by_level_env || b->tree_by_level;  // (... and what a solve falls back to once a hand-off between fronts has timed out)
   int nl = 0;
-  if (by_level) {
+  if (b->tree_by_level) {  // (one launch per tree level: what a solve falls back to once a hand-off between fronts has timed out)
     for (int l = b->tree_levels - 1; l >= 0; --l, ++nl)
-      hipLaunchKernelGGL(front_up, dim3(l == b->tree_levels - 1 ? grid : stride * nF), dim3(FR_WAVES * 64), FR_LDS_BYTES, st, b->tree_fs, d.red,
-                         d.red + b->ssz, d.ld, d, b->fin_pending ? 1 : 0, b->fin_radius, b->fin_lo, b->fin_hi, b->world, epoch, stride, l, l,
-                         b->red_alt, (long long)nz, l == b->tree_levels - 1 ? zwg : 0, b->tree_xoff % stride);
+      hipLaunchKernelGGL(front_up, dim3(l == b->tree_levels - 1 ? grid : nF), dim3(FR_WAVES * 64), FR_LDS_BYTES, st, b->tree_fs, d.red,
+                         d.red + b->ssz, d.ld, d, b->fin_pending ? 1 : 0, b->fin_radius, b->fin_lo, b->fin_hi, b->world, epoch, l, l,
+                         b->red_alt, (long long)nz, l == b->tree_levels - 1 ? zwg : 0);
   } else {
     hipLaunchKernelGGL(front_up, dim3(grid), dim3(FR_WAVES * 64), FR_LDS_BYTES, st, b->tree_fs, d.red, d.red + b->ssz, d.ld, d,
-                       b->fin_pending ? 1 : 0, b->fin_radius, b->fin_lo, b->fin_hi, b->world, epoch, stride, 0, 1 << 30, b->red_alt,
-                       (long long)nz, zwg, b->tree_xoff % stride);
+                       b->fin_pending ? 1 : 0, b->fin_radius, b->fin_lo, b->fin_hi, b->world, epoch, 0, 1 << 30, b->red_alt,
+                       (long long)nz, zwg);
     nl = 1;
   }
   if (zwg) b->alt_clean = true;
@@ -5702,12 +5622,10 @@ static int ba_reduced_solve(sfmhip_ba* b) {
       SFM_HIP_TRY(hipFuncSetAttribute((const void*)chol_step2, hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS_BYTES));
       b->chol_attr_set = true;
     }
-    static const int dfr_env = getenv("SFMHIP_BA_DENSE_DEFER") ? atoi(getenv("SFMHIP_BA_DENSE_DEFER")) : 0;  // (measurement)
-    const int xb = b->dense_xb, dfr0 = !xb ? 1 : dfr_env > 0 ? dfr_env : nt >= DENSE_DEFER4_MIN_NT ? 4 : 2;
-    static const int sw_env = getenv("SFMHIP_BA_DENSE_SWITCH") ? atoi(getenv("SFMHIP_BA_DENSE_SWITCH")) : -1;  // (measurement)
+    const int xb = b->dense_xb, dfr0 = !xb ? 1 : nt >= DENSE_DEFER4_MIN_NT ? 4 : 2;
     // (measured, scripts/gpu_dense_sizes.py: worth it only behind visits of four pairs -- 640 cameras 624 -> 643 it/s at 40 tile
     // rows, 618 at 72; behind visits of two pairs the undeferred tail is slower: 400 cameras 1433 -> 1407)
-    const int sw_m2 = sw_env >= 0 ? sw_env : dfr0 >= 4 ? DENSE_SWITCH_M2 : 0;
+    const int sw_m2 = dfr0 >= 4 ? DENSE_SWITCH_M2 : 0;
     bool deferred = false;  // some earlier launch of this factorisation left columns behind
     for (int k2 = 0; 2 * k2 < nt; ++k2, ++nchol) {
       const int m2 = nt - 2 * k2 - 2;
@@ -5727,8 +5645,7 @@ static int ba_reduced_solve(sfmhip_ba* b) {
       if (dfr >= 4 || catchup >= 4) tpw = 4;
       // (... unless that makes many rounds of workgroups: then two visits per SIMD, one's loads under the other's MFMAs -- 1400
       // cameras 118.7 -> 125 it/s; at 640 cameras, under two rounds, the same choice loses 1-2 %)
-      static const int rounds_env = getenv("SFMHIP_BA_DENSE_TPW8_ROUNDS") ? atoi(getenv("SFMHIP_BA_DENSE_TPW8_ROUNDS")) : 4;  // (measurement)
-      if (dfr >= 4 && (ntrail + 3) / 4 > rounds_env * b->ctx->n_cu) tpw = 8;
+      if (dfr >= 4 && (ntrail + 3) / 4 > DENSE_TPW8_ROUNDS * b->ctx->n_cu) tpw = 8;
       hipLaunchKernelGGL(chol_step2, dim3(npan + (ntrail + tpw - 1) / tpw), dim3(C2_WAVES * 64), C2_LDS_BYTES, st, A, y, d.xinv, d.ld, nt, k2,
                          tpw, d.info, xb, dfr, catchup);
     }
@@ -5766,23 +5683,19 @@ __global__ __launch_bounds__(256) void ba_step_nopoints(BaDev d) {
 struct StepLayout {
   bool runs;
   bool fits;  // the slots fit step_part (checked BEFORE the reduced solve, whose down-sweep writes the camera parts behind them)
-  int n_runs_wg, npl, n_bs_wg, split, wpp;
+  int n_runs_wg, npl, n_bs_wg;
   const int* plist;
 };
 static StepLayout ba_step_layout(sfmhip_ba* b) {
-  static const bool runs_env = !(getenv("SFMHIP_BA_BACKSUB_RUNS") && atoi(getenv("SFMHIP_BA_BACKSUB_RUNS")) == 0);
-  static const int wpp_env = getenv("SFMHIP_BA_BACKSUB_WPP") ? atoi(getenv("SFMHIP_BA_BACKSUB_WPP")) : 2;  // (measurement)
-  static const int split_env = getenv("SFMHIP_BA_BACKSUB_SPLIT") ? std::min(8, std::max(1, atoi(getenv("SFMHIP_BA_BACKSUB_SPLIT")))) : 1;  // (measured at cfg4: 21.0 us / 33 / 53 for 1 / 2 / 4 workgroups per run)
   StepLayout L;
-  // the points in runs: a thread per point, the run's cameras in LDS (ba_backsub_runs); the pair path's points (or,
-  // SFMHIP_BA_BACKSUB_RUNS=0, all of them): ba_backsub
-  L.runs = runs_env && b->n_chunks > 0 && b->d_bs_ids && b->np > 0;
-  L.split = split_env, L.wpp = wpp_env;
-  L.n_runs_wg = L.runs ? b->n_chunks * split_env : 0;
+  // the points in runs: a thread per point, the run's cameras in LDS (ba_backsub_runs), a workgroup per run (two or four per
+  // run were measured slower at cfg4: 21.0 us / 33 / 53); the pair path's points (or all of them when there is no run): ba_backsub
+  L.runs = b->n_chunks > 0 && b->d_bs_ids && b->np > 0;
+  L.n_runs_wg = L.runs ? b->n_chunks : 0;
   L.plist = L.runs ? b->d_fb_points : nullptr;
   L.npl = b->np ? (L.runs ? b->n_fb : b->np) : 0;
   const size_t nblk = ((size_t)L.npl + 63) / 64;  // blocks of 64 points
-  L.n_bs_wg = L.npl <= 0 ? 0 : wpp_env == 1 ? (int)((nblk + 3) / 4) : wpp_env == 2 ? (int)((nblk + 1) / 2) : (int)nblk;
+  L.n_bs_wg = L.npl <= 0 ? 0 : (int)((nblk + 4 / BS_WPP - 1) / (4 / BS_WPP));
   b->d.step_total = std::max(1, L.n_runs_wg + L.n_bs_wg);
   b->d.cam_parts = b->tree_on ? b->tree_fs.n_fronts : (b->nc + 1 + 63) / 64;
   L.fits = 4 * (size_t)b->d.step_total + 2 * (size_t)b->d.cam_parts <= b->step_part_n;
@@ -5794,7 +5707,7 @@ static int ba_step_eval(sfmhip_ba* b, double radius, const sfmhip_ba_opts* o) {
   BaDev& d = b->d;
   const StepLayout L = ba_step_layout(b);
   const bool runs = L.runs;
-  const int n_runs_wg = L.n_runs_wg, npl = L.npl, n_bs_wg = L.n_bs_wg, split_env = L.split, wpp_env = L.wpp;
+  const int n_runs_wg = L.n_runs_wg, npl = L.npl, n_bs_wg = L.n_bs_wg;
   const int* plist = L.plist;
   // (the decision: by the finisher of ba_backsub_runs when that is the step evaluation's last kernel and there is one
   // rank; else by ba_decide behind the all-reduce)
@@ -5805,17 +5718,12 @@ static int ba_step_eval(sfmhip_ba* b, double radius, const sfmhip_ba_opts* o) {
   if (runs) {
     d.step_last = npl > 0 ? 0 : 1;
     hipLaunchKernelGGL(ba_backsub_runs, dim3(n_runs_wg), dim3(256), 0, st, d, (const int4*)b->d_bs_ids, radius, o->min_lm_diagonal,
-                       o->max_lm_diagonal, split_env);
+                       o->max_lm_diagonal);
     ++nbs;
   }
   d.step_last = 1;
   if (npl > 0) {
-    if (wpp_env == 1)
-      hipLaunchKernelGGL(ba_backsub<1>, dim3(n_bs_wg), dim3(256), 0, st, d, radius, o->min_lm_diagonal, o->max_lm_diagonal, plist, npl, n_runs_wg);
-    else if (wpp_env == 2)
-      hipLaunchKernelGGL(ba_backsub<2>, dim3(n_bs_wg), dim3(256), 0, st, d, radius, o->min_lm_diagonal, o->max_lm_diagonal, plist, npl, n_runs_wg);
-    else
-      hipLaunchKernelGGL(ba_backsub<4>, dim3(n_bs_wg), dim3(256), 0, st, d, radius, o->min_lm_diagonal, o->max_lm_diagonal, plist, npl, n_runs_wg);
+    hipLaunchKernelGGL(ba_backsub, dim3(n_bs_wg), dim3(256), 0, st, d, radius, o->min_lm_diagonal, o->max_lm_diagonal, plist, npl, n_runs_wg);
     ++nbs;
   }
   if (!nbs) {
@@ -5956,7 +5864,7 @@ static void lm_log(const sfmhip_ba* b, const LmDev& r) {
   else
     fprintf(stderr, "[sfmhip-ba] it %d cost %.9e -> %.9e rho %.3e radius %.3e |step| %.3e%s\n", r.iter, r.log_cost0, r.log_cost_c, r.log_rho,
             r.radius, r.log_step_norm, r.log_kind == LM_KIND_ACCEPTED ? "" : r.log_kind == LM_KIND_REJECTED ? " (rejected)" : " (stop)");
-  static const bool bits = getenv("SFMHIP_BA_VERBOSE_BITS") != nullptr;  // (diagnostics: the decision's inputs to the last bit)
+  const bool bits = getenv("SFMHIP_BA_VERBOSE_BITS") != nullptr;  // (diagnostics: the decision's inputs to the last bit)
   if (bits) fprintf(stderr, "[sfmhip-ba-bits] it %d cost %a cost_c %a mcc %a rho %a radius %a |step| %a\n", r.iter, r.log_cost0, r.log_cost_c, r.log_mcc, r.log_rho, r.radius, r.log_step_norm);
   (void)b;
 }
@@ -6099,7 +6007,7 @@ static int ba_lm_loop(sfmhip_ba* b, const sfmhip_ba_opts* o, int iters, const st
     return SFMHIP_OK;
   }
   // ---- the loop on the device: iterations are enqueued a batch ahead, the records are read behind the GPU
-  static const int batch_env = getenv("SFMHIP_BA_LM_BATCH") ? std::max(1, std::min(LM_RING / 2, atoi(getenv("SFMHIP_BA_LM_BATCH")))) : 0;
+  const int batch_env = getenv("SFMHIP_BA_LM_BATCH") ? std::max(1, std::min(LM_RING / 2, atoi(getenv("SFMHIP_BA_LM_BATCH")))) : 0;
   int rc = SFMHIP_OK;
   s.seq = b->lm_seq;
   s.parity = 0;
@@ -6229,7 +6137,7 @@ extern "C" int sfmhip_ba_iterate(sfmhip_ba* b, int iters, sfmhip_ba_summary* sum
   auto elapsed = [&]() { return std::chrono::duration<double>(clk::now() - t0).count(); };
   sfmhip_ba_opts o;
   sfmhip_ba_default_opts(&o);
-  static const bool verbose_env = getenv("SFMHIP_BA_VERBOSE") != nullptr;  // (diagnostics: a line per iteration on stderr)
+  const bool verbose_env = getenv("SFMHIP_BA_VERBOSE") != nullptr;  // (diagnostics: a line per iteration on stderr)
   if (verbose_env) o.verbose = 1;
   sfmhip_ba_summary sm;
   memset(&sm, 0, sizeof sm);
@@ -6494,7 +6402,7 @@ extern "C" int sfmhip_ba_solve(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, 
   };
   sfmhip_ba_solve_profile& pr = ctx->ba_profile;
   pr = sfmhip_ba_solve_profile{};
-  static const bool cache_on = !(getenv("SFMHIP_BA_PLAN_CACHE") && atoi(getenv("SFMHIP_BA_PLAN_CACHE")) == 0);
+  const bool cache_on = ba_plan_cache_on();
   BaPlanCache* cache = (BaPlanCache*)ctx->ba_cache;
   sfmhip_ba* b = nullptr;
   int rc = SFMHIP_OK;
@@ -6512,7 +6420,7 @@ extern "C" int sfmhip_ba_solve(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, 
     }
     // the block: as large as the last problem turned out to need, and a quarter more (a problem whose needs exceed it takes
     // the rest by hipMalloc, and the next call's block is larger)
-    static const bool arena_on = !(getenv("SFMHIP_BA_ARENA") && atoi(getenv("SFMHIP_BA_ARENA")) == 0);
+    const bool arena_on = !(getenv("SFMHIP_BA_ARENA") && atoi(getenv("SFMHIP_BA_ARENA")) == 0);
     if (arena_on && ctx->ba_arena_need > ctx->ba_arena_bytes) {
       hipSetDevice(ctx->device);
       if (ctx->ba_arena) hipFree(ctx->ba_arena);

@@ -81,12 +81,11 @@ struct FrontSet {
                           // FR_Z_PENDING until its front has solved it; a front resets its entries of the OTHER generation
   int zq_ld;
   int n_fronts;
-  int n_roles;            // workgroups of the up-sweep with a front's or a helper's role (up_order: front | helper << 16)
 };
 
 struct FrDesc {
   int no, ns, T, nb_last, parent, nchild, child_off, inv_off, ptinv_off, sched_off, ncam, cam_off, has_focal, offL, offy, own_cols, off_pbuf, live,
-      focal_pos, tflag_off, nhelp, help_off, pflag_off;
+      focal_pos, tflag_off;
 };
 __device__ __forceinline__ FrDesc fr_desc(const int* __restrict__ ints, int f) {
   const int* p = ints + (size_t)fplan::FD_INTS * f;
@@ -97,7 +96,6 @@ __device__ __forceinline__ FrDesc fr_desc(const int* __restrict__ ints, int f) {
   D.ncam = p[fplan::FD_NCAM], D.cam_off = p[fplan::FD_CAM_OFF], D.has_focal = p[fplan::FD_HAS_FOCAL];
   D.offL = p[fplan::FD_OFF_L], D.offy = p[fplan::FD_OFF_Y], D.own_cols = p[fplan::FD_OWN_COLS];
   D.off_pbuf = p[fplan::FD_OFF_PBUF], D.live = p[fplan::FD_LIVE], D.focal_pos = p[fplan::FD_FOCAL_POS], D.tflag_off = p[fplan::FD_TFLAG_OFF];
-  D.nhelp = p[fplan::FD_NHELP], D.help_off = p[fplan::FD_HELP_OFF], D.pflag_off = p[fplan::FD_PFLAG_OFF];
   return D;
 }
 
@@ -326,8 +324,7 @@ __device__ __forceinline__ void fr_potrf(v4d (&acc)[3], double* sD, double* sdi,
 // tile's LDS home (scratch for the layout changes, X when done, row-major); *oflag = base + finished blocks; out_bytes:
 // the lane's row of the copy in memory, as an offset into the pool (its columns of this block column are contiguous).
 __device__ __forceinline__ void fr_trsm(v4d (&acc)[4], double* sT, const double* sL, const double* sdi, const int* prog, int* oflag,
-                                        int base, int nb, __amdgpu_buffer_rsrc_t pool, int out_bytes, int lane,
-                                        bool through /* helper workgroups of this launch read the rows: write-through */) {
+                                        int base, int nb, __amdgpu_buffer_rsrc_t pool, int out_bytes, int lane) {
   const int i = lane & 31, j16 = lane & 15, q = lane >> 4;
   double* const rowp = sT + i * CBP;
   double* const op0 = sT + j16 * CBP + q;
@@ -360,13 +357,8 @@ __device__ __forceinline__ void fr_trsm(v4d (&acc)[4], double* sT, const double*
       *(v2d*)(rowp + c + 2) = v2d{x2, x3};
       lds_flag_set(oflag, base + b + 1);
       if (lane < CB) {
-        if (through) {
-          __builtin_amdgcn_raw_buffer_store_b128(fr_pack2(x0, x1), pool, out_bytes + c * 8, 0, 16 /* sc1 */);
-          __builtin_amdgcn_raw_buffer_store_b128(fr_pack2(x2, x3), pool, out_bytes + (c + 2) * 8, 0, 16);
-        } else {
-          __builtin_amdgcn_raw_buffer_store_b128(fr_pack2(x0, x1), pool, out_bytes + c * 8, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b128(fr_pack2(x2, x3), pool, out_bytes + (c + 2) * 8, 0, 0);
-        }
+        __builtin_amdgcn_raw_buffer_store_b128(fr_pack2(x0, x1), pool, out_bytes + c * 8, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(fr_pack2(x2, x3), pool, out_bytes + (c + 2) * 8, 0, 0);
       }
       if (b + 1 < nb) {
         const double X0 = op0[c], X1 = op1[c];
@@ -465,7 +457,7 @@ __device__ __forceinline__ void fr_fold(v4d (&acc)[4], const double* Xr, const d
 
 __device__ __forceinline__ void fr_report_timeout(const int* s_flag, int* __restrict__ info);
 
-// the children's contributions to tile (R, C) of front D (a flag per tile; the front and its helpers alike).  Two children at
+// the children's contributions to tile (R, C) of front D (a flag per tile).  Two children at
 // a time: their two flags are polled TOGETHER (one round trip through memory when both are up, which they usually are by the time
 // a tile is wanted -- polled one after the other, each in front of its own loads, a tile with two contributions cost four round
 // trips, ~10 k cycles: profiles/round4_front_stamps.txt, "children done" and every "fetch<"), and a wave with registers to spare
@@ -518,60 +510,6 @@ __device__ __forceinline__ void fr_recv_children(const FrontSet& fs, const FrDes
   }
 }
 
-// A helper workgroup of front D (ba_front_plan.h, Front::nhelp): some of the front's border x border tiles are this
-// workgroup's -- zero, plus the children's contributions, minus the front's panels -- folded on this compute unit's four
-// matrix pipes while the front folds its own share.  The panels are the border rows of L that the front stores for the
-// down-sweep anyway (write-through when it has helpers), a flag per solved tile; they are copied into LDS in the layout the
-// front's own fold reads, every wave of the workgroup taking some, and folded from there.  The tiles go to the parent as the
-// front's do: a contribution tile has a flag of its own, whoever computed it.
-__device__ __forceinline__ void fr_helper(const FrontSet& fs, const FrDesc& D, int hlp, unsigned epoch, double* sAll, int* __restrict__ info) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int no = D.no, ns = D.ns, ldk = CB * no;
-  double* const sPanel = sAll + FR_OFF_PANEL;
-  int* const s_flag = (int*)(sAll + FR_OFF_FLAG);
-  const __amdgpu_buffer_rsrc_t pool_rs = __builtin_amdgcn_make_buffer_rsrc((void*)fs.pool, 0, 0x7FFFFFFF, 0x00020000);
-  const unsigned live = (unsigned)D.live;
-  if (threadIdx.x < 32) s_flag[threadIdx.x] = 0;
-  __syncthreads();
-  // (one tile per wave -- ba_front_plan.h deals a helper at most FP_WAVES tiles: three register tiles per wave, as the front's
-  // own waves hold them, cost this path 28 bytes of scratch per lane at front_up's 168-register limit)
-  const int hv = __builtin_amdgcn_readfirstlane(fs.ints[D.help_off + (hlp - 1) * (FR_WAVES * FR_SLOTS) + wave * FR_SLOTS]);
-  const int hr = hv < 0 ? -1 : (hv & 255), hc = hv < 0 ? -1 : ((hv >> 8) & 255);
-  // the children's parts of this wave's tile (they may be there long before the front's panels)
-  v4d t[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) t[i] = v4d{0.0, 0.0, 0.0, 0.0};
-  if (hr >= 0) fr_recv_children<false>(fs, D, t, hr, hc, epoch, pool_rs, s_flag + FRC_MARK1, lane);
-  // the front's panels: tile (r, j) of L, r a border row, as its solve finishes it
-  auto panel_tile = [&](int gen, int r) -> double* { return sPanel + (size_t)(gen * (FR_TMAX - 1) + (r - 1)) * FR_TILE; };
-#pragma unroll 1
-  for (int idx = wave; idx < no * ns; idx += FR_WAVES) {
-    const int j = idx / ns, i = idx - j * ns, r = no + i;
-    fr_poll_flag(fs.tflag + D.pflag_off + j * ns + i, epoch, s_flag + FRC_MARK1);
-    const int row = lane >> 1, half = lane & 1;
-    const int src = (D.offL + (CB * r + row) * ldk + CB * j + 16 * half) * 8;
-    v4u v[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = __builtin_amdgcn_raw_buffer_load_b128(pool_rs, src + 16 * k, 0, 16 /* sc1 */);
-    double* const dst = panel_tile(j, r) + row * CBP + 16 * half;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      *(v2d*)(dst + 2 * k) = v2d{__hiloint2double((int)v[k].y, (int)v[k].x), __hiloint2double((int)v[k].w, (int)v[k].z)};
-  }
-  __syncthreads();
-  if (hr >= 0) {
-    const unsigned subs = fr_live_subs(live, hr, hc);
-#pragma unroll 1
-    for (int j = 0; j < no; ++j) fr_fold(t, panel_tile(j, hr), panel_tile(j, hc), j == no - 1 ? D.nb_last : 8, subs, lane);
-    const int i = hr - no, j = hc - no;
-    fr_send(t, pool_rs, (D.off_pbuf + (i * (i + 1) / 2 + j) * (CB * CB)) * 8, subs, lane);
-    fr_raise_flag(fs.tflag + D.tflag_off + i * (i + 1) / 2 + j, epoch, lane);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  fr_report_timeout(s_flag, info);
-}
-
 __device__ __forceinline__ void fr_report_timeout(const int* s_flag, int* __restrict__ info) {
   if ((*(volatile const lds_int*)(s_flag + FRC_MARK0) != 0 || *(volatile const lds_int*)(s_flag + FRC_MARK1) != 0) && (threadIdx.x & 63) == 0)
     atomicExch(info, -1);
@@ -579,21 +517,17 @@ __device__ __forceinline__ void fr_report_timeout(const int* s_flag, int* __rest
 
 __global__ __launch_bounds__(FR_WAVES * 64) void front_up(FrontSet fs, const double* __restrict__ S, const double* __restrict__ g, int ldS,
                                                           BaDev d, int fin, double radius, double lm_lo, double lm_hi, int world,
-                                                          unsigned epoch, int stride, int lvl_lo, int lvl_hi, double* __restrict__ zero_ptr,
-                                                          long long zero_n, int n_zero, int xoff /* the fronts' place in every `stride` workgroups */) {
+                                                          unsigned epoch, int lvl_lo, int lvl_hi, double* __restrict__ zero_ptr,
+                                                          long long zero_n, int n_zero) {
   extern __shared__ __attribute__((aligned(16))) double sAll[];
-  const int nF = fs.n_roles;  // (fronts and their helper workgroups)
+  const int nF = fs.n_fronts;
   if (lm_stopped(d)) return;  // (an iteration enqueued behind a stop of the device's LM loop: every role of the launch returns)
   {
-    // ---- which role: the fronts sit at multiples of `stride` (stride 8: one XCD's L2 under round-robin placement,
-    // speed only), the workgroups between and behind them zero the other reduced-system buffer slice by slice (the next
-    // linearisation starts on it without a memset of its own), one more does ba_finalize's bookkeeping
-    // (xoff: problems that run side by side -- one per stream -- put their fronts on different XCDs)
+    // ---- which role: the fronts come first, the workgroups behind them zero the other reduced-system buffer slice by slice
+    // (the next linearisation starts on it without a memset of its own), one more does ba_finalize's bookkeeping
     const int b = (int)blockIdx.x;
-    const bool is_front = b < stride * nF && b % stride == xoff;
-    if (!is_front) {
-      const int before = b > xoff ? (b - xoff - 1) / stride + 1 : 0;  // fronts among the workgroups before this one
-      const int zi = b < stride * nF ? b - before : b - nF;
+    if (b >= nF) {
+      const int zi = b - nF;
       if (zi < n_zero) {
         const long long lo = (long long)zi * ND_ZERO_SLICE;
         double2* p2 = (double2*)(zero_ptr + lo);
@@ -623,16 +557,11 @@ __global__ __launch_bounds__(FR_WAVES * 64) void front_up(FrontSet fs, const dou
       return;
     }
   }
-  const int role = fs.up_order[blockIdx.x / stride];
-  const int f = role & 0xFFFF;
+  const int f = fs.up_order[blockIdx.x];
   const FrDesc D = fr_desc(fs.ints, f);
   {
     const int lvl = fs.ints[(size_t)fplan::FD_INTS * f + fplan::FD_LEVEL];
     if (lvl < lvl_lo || lvl > lvl_hi) return;  // (level-by-level launches: the fallback behind a timed-out hand-off, and a diagnostic mode)
-  }
-  if (role >> 16) {  // a helper workgroup of front f
-    fr_helper(fs, D, role >> 16, epoch, sAll, d.info);
-    return;
   }
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int no = D.no, T = D.T, nrow = CB * T, ldk = CB * no;
@@ -816,7 +745,7 @@ __global__ __launch_bounds__(FR_WAVES * 64) void front_up(FrontSet fs, const dou
     // diagnostic build only (tests/test_gpu_geometry.py::test_a_timed_out_hand_off_...): in the one-launch form the first front of
     // the up-sweep never raises its right-hand side's flag -- what a child that got no compute unit in time looks like to its
     // parent; launched level by level the hand-off is whole
-    if (!(lvl_lo == 0 && lvl_hi == (1 << 30) && (int)blockIdx.x / stride == 0))
+    if (!(lvl_lo == 0 && lvl_hi == (1 << 30) && blockIdx.x == 0))
 #endif
     fr_raise_flag(fs.tflag + D.tflag_off + D.ns * (D.ns + 1) / 2, epoch, lane);
   } else {
@@ -847,7 +776,7 @@ __global__ __launch_bounds__(FR_WAVES * 64) void front_up(FrontSet fs, const dou
         if (sc[s] == j && sr[s] > j) {
           need(s);
           fr_trsm(t[s], panel_tile(gen, sr[s]), sD + gen * FR_TILE, sdi + gen * CB, progL_of(gen), prog_of(gen, sr[s]), base, nbj,
-                  pool_rs, (D.offL + (CB * sr[s] + (lane & 31)) * ldk + CB * j) * 8, lane, D.nhelp > 0 && sr[s] >= no);
+                  pool_rs, (D.offL + (CB * sr[s] + (lane & 31)) * ldk + CB * j) * 8, lane);
         }
 #pragma unroll
       for (int s = 0; s < FR_SLOTS; ++s)
@@ -859,20 +788,6 @@ __global__ __launch_bounds__(FR_WAVES * 64) void front_up(FrontSet fs, const dou
         }
       lds_flag_add(s_flag + FRC_CONS + gen, lane);
     }
-    // helper workgroups fold some of the border tiles: the border rows of L this wave has solved are in memory (write-through),
-    // a flag per tile tells them.  A flag may only follow the wave's stores, and waiting for stores that have just been issued
-    // costs ~2 us -- on every level, when it sat here between the steps and the wave's first border tile (measured: 11 us per
-    // solve, more than the helpers gave back).  So the flags go out where the wait is free: while the wave waits for its turn
-    // anyway, or behind the wait its first tile's own flag needs, or -- a wave with no border tile -- here.
-    bool panels_told = D.nhelp <= 0;
-    auto tell_panels = [&]() {
-      if (!panels_told) {
-#pragma unroll
-        for (int s = 0; s < FR_SLOTS; ++s)
-          if (sc[s] >= 0 && sc[s] < no && sr[s] >= no) fr_raise_flag(fs.tflag + D.pflag_off + sc[s] * D.ns + (sr[s] - no), epoch, lane);
-        panels_told = true;
-      }
-    };
     // the border tiles.  A front that folded them as it went sends them; a front of one or two own tiles folds both panels into
     // them now that nothing solves beside them, a tile at a time per SIMD in the plan's order (ba_front_plan.h: the order in
     // which the ancestors need them), sends each and raises its flag
@@ -891,7 +806,6 @@ __global__ __launch_bounds__(FR_WAVES * 64) void front_up(FrontSet fs, const dou
           lds_wait_ge(progL_of((no - 1) & 1), D.nb_last);
           if ((wave & 3) >= 2)
             for (int r = no; r < T; ++r) lds_wait_ge(prog_of((no - 1) & 1, r), D.nb_last);
-          if (sturn[s] > 0) tell_panels();
           lds_wait_ge(turn, sturn[s]);
           FR_STAMP(32 + 8 * wave + 2 * s);
           for (int j = 0; j < no; ++j) {
@@ -906,10 +820,8 @@ __global__ __launch_bounds__(FR_WAVES * 64) void front_up(FrontSet fs, const dou
         const int i = sr[s] - no, j = sc[s] - no;
         fr_send(t[s], pool_rs, (D.off_pbuf + (i * (i + 1) / 2 + j) * (CB * CB)) * 8, subs, lane);
         fr_raise_flag(fs.tflag + D.tflag_off + i * (i + 1) / 2 + j, epoch, lane);
-        tell_panels();
         if (wave == 8 && sturn[s] == 0) FR_STAMP(29);
       }
-    tell_panels();
   }
   // ---- every store of this workgroup has left before the flag does
   if (wave == 1) FR_STAMP(19);

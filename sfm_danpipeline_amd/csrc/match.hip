@@ -51,6 +51,7 @@ constexpr int FIX_GRID = 1024;       // workgroups of knn_fixup_kernel
 constexpr int FIX_CAP = 1 << 20;     // flagged queries that are also LISTED, for a one-wave-per-query fix-up kernel;
                                      // beyond it they stay flagged in-band and the compaction kernel redoes them
 constexpr int DIST_EMPTY = 0x7FFFFFFF;
+constexpr int KNN_WAVES = 4;  // waves per k-NN workgroup: two workgroups per CU, which drift half a sweep apart
 constexpr int HCHUNK = 1024;  // Hamming kernel: rows per tie-break chunk (10 index bits in the key: the query's bytes are scaled to +-64)
 #ifndef SFM_RESOLVE_V2
 #define SFM_RESOLVE_V2 1  // 0: the lanes with two slots at the threshold recompute all four rows (the form of rounds 2-5; A/B builds)
@@ -376,16 +377,17 @@ __device__ __forceinline__ void epi_range(const v16i& D0, const v16i& D1, int (&
 // MFMAs into two accumulator blocks); between its MFMAs ride the 38 epilogue ops of the
 // previously filled accumulator blocks, so a SIMD's matrix and vector pipes run side by side
 // (4.75 VALU ops per MFMA: scripts/ubench/epi_mix.hip, the gap stays MFMA-paced).
-template <int KS, int MODE, int NU, int SR, int NW>
-__global__ __launch_bounds__(NW * 64, 2) void knn_kernel(const ImgDev* __restrict__ imgs,
+template <int KS, int MODE, int NU, int SR>
+__global__ __launch_bounds__(KNN_WAVES * 64, 2) void knn_kernel(const ImgDev* __restrict__ imgs,
                                                          const WorkItem* __restrict__ items,
                                                          const int* __restrict__ nonintegral, int gen, int dim,
-                                                         int4* __restrict__ knn, int maxq, int late_start,
+                                                         int4* __restrict__ knn, int maxq,
                                                          int* __restrict__ fix_count, int2* __restrict__ fix_items) {
   constexpr int NC = 2 * KS;
   constexpr int RB = 32 * KS;
   constexpr int TILE_BYTES = TILE_ROWS * RB;
   constexpr int STAGE_ROW_BYTES = SR * RB;
+  constexpr int NW = KNN_WAVES;
   constexpr int NT = NW * 64;                            // threads
   constexpr int CIN_COPIES = (SR + NT - 1) / NT;           // every thread copies CIN_COPIES C inputs: no divergent copy code
   constexpr int STAGE_BYTES = STAGE_ROW_BYTES + CIN_COPIES * NT * 4;
@@ -424,11 +426,6 @@ __global__ __launch_bounds__(NW * 64, 2) void knn_kernel(const ImgDev* __restric
   }
   SFM_STAMP(0);
   int dbg_trips = 0;
-  // Two workgroups share a CU (NW = 4).  Launched together they would stay in step -- both in the
-  // MFMA-bound sweep, then both in the memory-bound resolve.  The second set of resident workgroups
-  // starts late_start * 8 k cycles late, and every later workgroup inherits the phase of the one it replaces.
-  if (late_start > 0 && blockIdx.x >= 256 && blockIdx.x < 512)
-    for (int i = 0; i < late_start; ++i) __builtin_amdgcn_s_sleep(127);
 
   // query fragments (B operand): lane (r,h) holds bytes [32ks+16h, +16) of query row r
   v4i bq[NU][KS];
@@ -1691,8 +1688,6 @@ struct sfmhip_imageset {
   sfmhip_ctx* ctx;
   int n_images, dim, dtype, norm;
   int kind, ks, sr, nu;  // ks==0: no MFMA instantiation -> exact kernel only; nu = query tiles per wave
-  int nw = 4;            // waves per k-NN workgroup: 4 (two workgroups per CU, which drift half a sweep apart) or 8
-  int late_start = 0;    // nw == 4: start delay of the second set of resident workgroups, in 8 k cycles
   std::vector<int> n_rows, n_pad;
   std::vector<ImgDev> h_imgs;
   std::vector<void*> owned_raw;
@@ -1734,21 +1729,19 @@ struct sfmhip_matchplan {
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_k = nullptr;  // end of the k-NN kernel proper (ev[0] .. ev_k = that one launch)
   bool timed = false;
-  // pipelined fetch (sfmhip_matchplan_pipeline): after every run a second stream packs the lists straight into one of
+  // pipelined fetch (sfmhip_matchplan_pipeline): after every run a second stream packs the lists and copies them into one of
   // two pinned host buffers while the first stream goes on with the next sweep
   bool pipe_on = false;
   hipStream_t pipe_st = nullptr;
   hipEvent_t ev_ready = nullptr, ev_host[2] = {nullptr, nullptr};
   void* h_pipe[2] = {nullptr, nullptr};   // [int64 total | int64 capacity | int32 counts[cap_pairs] | int32 q[], t[], d[]]
-  int* dh_pipe[2] = {nullptr, nullptr};   // the same buffers as the device sees them
-  // round 5: the lists are packed into a DEVICE buffer of the same layout by a short many-workgroup launch and leave over the
-  // DMA engine (hipMemcpyAsync on the copy stream): eight workgroups writing 3 MB through the PCIe link held their compute units
-  // for a sixth of a sweep (host-visible 0.86 of the device-only rate).  The copy carries the matches the last runs had, plus a
+  // The lists are packed into a DEVICE buffer of the same layout by a short many-workgroup launch and leave over the
+  // DMA engine (hipMemcpyAsync on the copy stream): packing straight into host memory (round 3), eight workgroups writing
+  // 3 MB through the PCIe link held their compute units for a sixth of a sweep (host-visible 0.86 of the device-only rate).  The copy carries the matches the last runs had, plus a
   // quarter (the count is only known on the device); a run that has more gets the rest in fetch_wait.
   int* d_pipe[2] = {nullptr, nullptr};
   long long pipe_copied[2] = {0, 0};      // matches the slot's copy carried
   long long pipe_est = -1;                // matches to copy (< 0: not known yet, the whole capacity)
-  bool pipe_zero_copy = false;            // SFMHIP_PIPE_ZEROCOPY=1: the round-3 path (measurement)
   long long pipe_capacity = 0;            // matches per slot
   long long runs = 0;                     // runs enqueued since the pipeline was switched on
 };
@@ -1784,9 +1777,6 @@ extern "C" int sfmhip_imageset_create(sfmhip_ctx* ctx, int n_images, const int32
   s->sr = s->ks == 8 ? 128 : 256;
   s->nu = s->ks == 8 ? 1 : 2;
   if (s->kind == KIND_U8_HAMMING) s->nu = 2;  // (knn_keyed_kernel: 4 waves x 2 query tiles)
-  if (const char* e = getenv("SFMHIP_KNN_NW")) s->nw = atoi(e) == 8 ? 8 : 4;          // (tuning knobs, not API)
-  if (const char* e = getenv("SFMHIP_KNN_LATE")) s->late_start = std::max(0, atoi(e));
-  if (s->kind == KIND_U8_HAMMING) s->nw = 4;
   const int rb = 32 * (s->ks ? s->ks : 1);
   size_t tot_pad = 0;
   std::vector<int> tile_img, tile_first(n_images + 1, 0);
@@ -1950,7 +1940,7 @@ extern "C" void sfmhip_imageset_destroy(sfmhip_imageset* s) {
   delete s;
 }
 
-// work list: one workgroup per (pair, block of nw*nu query tiles: nu per wave).  Ordered so that the blocks a
+// work list: one workgroup per (pair, block of KNN_WAVES*nu query tiles: nu per wave).  Ordered so that the blocks a
 // round-robin dispatcher puts on one XCD (equal index mod 8) walk the same train image
 // together: train images are dealt to the 8 groups, each group sorted by train image.
 static void build_work_items(const sfmhip_imageset* s, const int32_t* pairs, int n_pairs, std::vector<WorkItem>& items) {
@@ -1970,7 +1960,7 @@ static void build_work_items(const sfmhip_imageset* s, const int32_t* pairs, int
     // query tiles cover the positions: the rows plus the padding of the odd class (L2 kinds)
     const int npos = s->n_rows[qi] + (s->kind == KIND_U8_HAMMING ? 0 : TILE_ROWS - 1);
     const int nqt = std::min((npos + TILE_ROWS - 1) / TILE_ROWS, s->n_pad[qi] / TILE_ROWS);
-    for (int t0 = 0; t0 < nqt; t0 += s->nw * s->nu) {
+    for (int t0 = 0; t0 < nqt; t0 += KNN_WAVES * s->nu) {
       lanes[cur_lane].push_back(WorkItem{p, t0, qi, ti});
       load[cur_lane] += (size_t)s->n_pad[ti];
     }
@@ -2006,7 +1996,7 @@ extern "C" int sfmhip_matchplan_create(sfmhip_imageset* s, const int32_t* pairs,
   build_work_items(s, pairs, n_pairs, items);
   pl->n_items = (int)items.size();
   // room for any pair list of up to cap_pairs pairs (sfmhip_matchplan_set_pairs)
-  pl->cap_items = (size_t)pl->cap_pairs * (size_t)(((pl->maxq + 2 * TILE_ROWS - 2) / TILE_ROWS + s->nw * s->nu - 1) / (s->nw * s->nu));
+  pl->cap_items = (size_t)pl->cap_pairs * (size_t)(((pl->maxq + 2 * TILE_ROWS - 2) / TILE_ROWS + KNN_WAVES * s->nu - 1) / (KNN_WAVES * s->nu));
   int rc = SFMHIP_OK;
   const size_t slots = (size_t)pl->cap_pairs * pl->maxq;
   if ((rc = sfm_dev_alloc(&pl->d_pairs, (size_t)pl->cap_pairs)) || (rc = sfm_dev_alloc(&pl->d_items, pl->cap_items)) ||
@@ -2059,13 +2049,8 @@ extern "C" int sfmhip_matchplan_set_pairs(sfmhip_matchplan* pl, const int32_t* p
 template <int KS, int MODE, int NU, int SR>
 static int launch_knn(sfmhip_matchplan* pl) {
   sfmhip_imageset* s = pl->set;
-  if (s->nw == 4)
-    hipLaunchKernelGGL((knn_kernel<KS, MODE, NU, SR, 4>), dim3(pl->n_items), dim3(256), 0, s->ctx->stream, s->d_imgs,
-                       pl->d_items, s->d_nonintegral, s->gen, s->dim, pl->d_knn, pl->maxq, s->late_start, pl->d_fix_count,
-                       pl->d_fix_items);
-  else
-    hipLaunchKernelGGL((knn_kernel<KS, MODE, NU, SR, 8>), dim3(pl->n_items), dim3(512), 0, s->ctx->stream, s->d_imgs,
-                       pl->d_items, s->d_nonintegral, s->gen, s->dim, pl->d_knn, pl->maxq, 0, pl->d_fix_count, pl->d_fix_items);
+  hipLaunchKernelGGL((knn_kernel<KS, MODE, NU, SR>), dim3(pl->n_items), dim3(KNN_WAVES * 64), 0, s->ctx->stream, s->d_imgs,
+                     pl->d_items, s->d_nonintegral, s->gen, s->dim, pl->d_knn, pl->maxq, pl->d_fix_count, pl->d_fix_items);
   SFM_HIP_TRY(hipGetLastError());
   return SFMHIP_OK;
 }
@@ -2141,32 +2126,26 @@ extern "C" int sfmhip_matchplan_run_async(sfmhip_matchplan* pl, float ratio) {
     const int slot = (int)(pl->runs & 1);
     SFM_HIP_TRY(hipEventRecord(pl->ev_ready, st));
     SFM_HIP_TRY(hipStreamWaitEvent(pl->pipe_st, pl->ev_ready, 0));
-    const bool zc = pl->pipe_zero_copy;
-    int* base = zc ? pl->dh_pipe[slot] : pl->d_pipe[slot];
-    long long* h_hdr = (long long*)base;
-    int* h_counts = base + 4;
-    int* h_rec = h_counts + pl->cap_pairs;
+    int* base = pl->d_pipe[slot];
+    long long* hdr = (long long*)base;
+    int* counts = base + 4;
+    int* rec = counts + pl->cap_pairs;
     if (pl->n_pairs > 0) {
-      hipLaunchKernelGGL(pack_offsets_kernel, dim3(1), dim3(1024), 0, pl->pipe_st, pl->d_counts, pl->n_pairs, pl->d_offsets, h_counts, h_hdr);
-      static const int pipe_wgs_env = getenv("SFMHIP_PIPE_WGS") ? atoi(getenv("SFMHIP_PIPE_WGS")) : 0;
-      // (zero copy: 8 workgroups, 0.977 of the device-only sweep rate on one stream, 64 or more 0.91 -- scripts/gpu_hostvisible_ab.py;
-      // into device memory the launch is over in microseconds whatever its size)
-      const int pipe_wgs = pipe_wgs_env > 0 ? pipe_wgs_env : zc ? 8 : 128;
-      hipLaunchKernelGGL(pack_lists_kernel, dim3(std::max(1, std::min(pl->n_pairs, pipe_wgs))), dim3(256), 0, pl->pipe_st, pl->d_counts,
-                         pl->d_offsets, pl->n_pairs, pl->maxq, pl->d_out_q, pl->d_out_t, pl->d_out_d, h_rec, pl->pipe_capacity);
+      hipLaunchKernelGGL(pack_offsets_kernel, dim3(1), dim3(1024), 0, pl->pipe_st, pl->d_counts, pl->n_pairs, pl->d_offsets, counts, hdr);
+      // (into device memory the launch is over in microseconds whatever its size)
+      hipLaunchKernelGGL(pack_lists_kernel, dim3(std::max(1, std::min(pl->n_pairs, 128))), dim3(256), 0, pl->pipe_st, pl->d_counts,
+                         pl->d_offsets, pl->n_pairs, pl->maxq, pl->d_out_q, pl->d_out_t, pl->d_out_d, rec, pl->pipe_capacity);
       SFM_HIP_TRY(hipGetLastError());
-      if (!zc) {
-        // how much to copy: what the finished runs had, plus a quarter (their totals are in the host buffers already)
-        for (int k = 0; k < 2; ++k)
-          if (pl->runs > k && hipEventQuery(pl->ev_host[(pl->runs - 1 - k) & 1]) == hipSuccess) {
-            const long long seen = ((const long long*)pl->h_pipe[(pl->runs - 1 - k) & 1])[0];
-            if (seen <= pl->pipe_capacity) pl->pipe_est = std::max(pl->pipe_est, seen + seen / 4 + 1024);
-          }
-        const long long n_copy = pl->pipe_est < 0 ? pl->pipe_capacity : std::min(pl->pipe_capacity, pl->pipe_est);
-        pl->pipe_copied[slot] = n_copy;
-        SFM_HIP_TRY(hipMemcpyAsync(pl->h_pipe[slot], pl->d_pipe[slot], 16 + sizeof(int) * ((size_t)pl->cap_pairs + 3 * (size_t)n_copy),
-                                   hipMemcpyDeviceToHost, pl->pipe_st));
-      }
+      // how much to copy: what the finished runs had, plus a quarter (their totals are in the host buffers already)
+      for (int k = 0; k < 2; ++k)
+        if (pl->runs > k && hipEventQuery(pl->ev_host[(pl->runs - 1 - k) & 1]) == hipSuccess) {
+          const long long seen = ((const long long*)pl->h_pipe[(pl->runs - 1 - k) & 1])[0];
+          if (seen <= pl->pipe_capacity) pl->pipe_est = std::max(pl->pipe_est, seen + seen / 4 + 1024);
+        }
+      const long long n_copy = pl->pipe_est < 0 ? pl->pipe_capacity : std::min(pl->pipe_capacity, pl->pipe_est);
+      pl->pipe_copied[slot] = n_copy;
+      SFM_HIP_TRY(hipMemcpyAsync(pl->h_pipe[slot], pl->d_pipe[slot], 16 + sizeof(int) * ((size_t)pl->cap_pairs + 3 * (size_t)n_copy),
+                                 hipMemcpyDeviceToHost, pl->pipe_st));
     } else {
       ((long long*)pl->h_pipe[slot])[0] = 0;
     }
@@ -2192,7 +2171,6 @@ extern "C" int sfmhip_matchplan_pipeline(sfmhip_matchplan* pl, int64_t capacity)
     // (highest priority: the packing launch gets the first compute units a sweep's workgroups give back, not the last)
     int prio_lo = 0, prio_hi = 0;
     if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_lo = prio_hi = 0;
-    if (getenv("SFMHIP_PIPE_PRIORITY") && atoi(getenv("SFMHIP_PIPE_PRIORITY")) == 0) prio_hi = prio_lo;  // (measurement)
     SFM_HIP_TRY(hipStreamCreateWithPriority(&pl->pipe_st, hipStreamNonBlocking, prio_hi));
     SFM_HIP_TRY(hipEventCreateWithFlags(&pl->ev_ready, hipEventDisableTiming));
     for (auto& e : pl->ev_host) SFM_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -2206,9 +2184,6 @@ extern "C" int sfmhip_matchplan_pipeline(sfmhip_matchplan* pl, int64_t capacity)
       pl->h_pipe[k] = nullptr;
       const size_t bytes = 16 + sizeof(int) * ((size_t)pl->cap_pairs + 3 * (size_t)capacity);
       SFM_HIP_TRY(hipHostMalloc(&pl->h_pipe[k], bytes, hipHostMallocMapped));
-      void* dp = nullptr;
-      SFM_HIP_TRY(hipHostGetDevicePointer(&dp, pl->h_pipe[k], 0));
-      pl->dh_pipe[k] = (int*)dp;
       memset(pl->h_pipe[k], 0, 16);
       if (pl->d_pipe[k]) hipFree(pl->d_pipe[k]);
       pl->d_pipe[k] = nullptr;
@@ -2219,7 +2194,6 @@ extern "C" int sfmhip_matchplan_pipeline(sfmhip_matchplan* pl, int64_t capacity)
   }
   pl->pipe_on = true;
   pl->runs = 0;
-  pl->pipe_zero_copy = getenv("SFMHIP_PIPE_ZEROCOPY") && atoi(getenv("SFMHIP_PIPE_ZEROCOPY")) != 0;
   return SFMHIP_OK;
 }
 
@@ -2234,7 +2208,7 @@ extern "C" int sfmhip_matchplan_fetch_wait(sfmhip_matchplan* pl, int back, const
   if (total) *total = tot;
   if (counts) *counts = c;
   if (tot > pl->pipe_capacity) return SFMHIP_ERR_ALLOC;  // (total is set: switch the pipeline on again with that much room)
-  if (!pl->pipe_zero_copy && tot > pl->pipe_copied[slot]) {
+  if (tot > pl->pipe_copied[slot]) {
     // the run found more matches than the copy was sized for: the rest of the three arrays, now (the device buffer of the slot
     // is untouched until the slot's next run)
     const size_t lo = (size_t)pl->cap_pairs + 3 * (size_t)pl->pipe_copied[slot], hi = (size_t)pl->cap_pairs + 3 * (size_t)tot;
