@@ -34,6 +34,7 @@
 // every rank then solves the same reduced system and back-substitutes its own points.
 #include "common.h"
 #include "ba_front_plan.h"
+#include "ba_setup.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -51,7 +52,7 @@
 namespace {
 
 constexpr int CAMD = 40;     // doubles per camera table: R[9] t[3] dR/dw[27] pad
-constexpr int SC = 16;       // scalar slots at the tail of the all-reduce buffer (+ world)
+using bsetup::SC;            // scalar slots at the tail of the all-reduce buffer (+ world)
 // red2, the step evaluation's scalars at the tail of the reduced-system buffer: [0..4) the four totals (candidate cost, model cost
 // change, |step|^2, |candidate|^2) that step_finish leaves -- the sums of the workgroups' slots in BaDev::step_part, added in a
 // fixed order; [0, 8) is what several ranks all-reduce -- | (RED2_SLOTS x 4: the slots round 4's atomics landed in, unused since
@@ -65,14 +66,7 @@ constexpr int RED2_TIMEOUT = 4;
 // the reduced solve's status word (RED2_INFO): > 0 a pivot was not positive; -1 a hand-off of the reduced solve never arrived
 // (the front tree then runs level by level); -2 a slot of the step evaluation's sums never arrived (no fallback: SFMHIP_ERR_TIMEOUT)
 constexpr int INFO_FINISHER_TIMEOUT = -2;
-constexpr int FB_MAXN = 4096;  // sanity cap on the observations of one point (the pair path has no structural limit)
-
-struct Chunk {
-  int sig_off;  // offset into sig_cams
-  int n;        // observations per point in this signature
-  int p0;       // first sorted point
-  int cnt;      // points in the chunk
-};
+using bsetup::Chunk;  // a piece of a run of ba_eliminate_mfma (the set-up's, ba_setup.h)
 
 struct BaDev {
   // problem (sorted order)
@@ -594,9 +588,9 @@ __device__ unsigned long long g_elim_wg[2048 * 5];
 #define EL_STAMPW(slot)
 #define EL_WG(slot)
 #endif
-// a chunk's slab: [Gram block, MFMA layout, NT x 256 <= 2560 | F^T F sums 36 x FP | Jf^2, Jf r, r^2 | gmax | nfail]
-constexpr int ELIM_SLAB_FF = 2560, ELIM_SLAB = 2944;
-constexpr int FP = 10;  // slots per row of the F^T F accumulators in LDS (the MFMA path takes signatures of n <= 10 cameras)
+using bsetup::ELIM_SLAB_FF;  // a chunk's slab (ba_setup.h lays it out for the gather lists)
+using bsetup::ELIM_SLAB;
+using bsetup::FP;  // slots per row of the F^T F accumulators in LDS
 constexpr int MP = 80;  // LDS row pitch (doubles) of a wave's M panel: the 4 k-rows of one
                         // fragment read sit 160 dwords apart -> disjoint banks
 
@@ -3680,94 +3674,14 @@ struct sfmhip_ba {
   int launches = 0;
 };
 
-// fn(lo, hi) over [0, n) on up to 8 host threads (problem set-up only)
-static int host_threads(int n) {
-  const unsigned hw = std::thread::hardware_concurrency();
-  const int nth = (int)std::max(1u, std::min(16u, hw ? hw : 1u));
-  return n < 20000 ? 1 : nth;
-}
-// The host threads of the set-up's passes: a pool that lives as long as the process (starting and joining sixteen threads is
-// 0.4-0.5 ms, and a set-up has five such passes).  One job at a time; a caller that finds the pool busy (another host thread is
-// setting a problem up) starts threads of its own, as every pass did before.
-class HostPool {
- public:
-  static HostPool& get() {
-    static HostPool* p = new HostPool();  // (never destroyed: its threads wait on a condition variable until the process ends)
-    return *p;
-  }
-  // f(t) for t in [0, nth): the caller is t = 0.  Returns false when the pool is taken (nothing has run).
-  bool run(int nth, const std::function<void(int)>& f) {
-    if (getpid() != pid_) return false;  // (a forked child has this object but none of its threads: it starts its own)
-    std::unique_lock<std::mutex> job_lock(job_m_, std::try_to_lock);
-    if (!job_lock.owns_lock()) return false;
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      while ((int)workers_.size() < nth - 1) {
-        const int id = (int)workers_.size() + 1;
-        workers_.emplace_back([this, id]() { work(id); });
-        workers_.back().detach();
-      }
-      f_ = &f;
-      nth_ = nth;
-      pending_ = nth - 1;
-      ++gen_;
-    }
-    cv_.notify_all();
-    f(0);
-    std::unique_lock<std::mutex> lk(m_);
-    done_.wait(lk, [this]() { return pending_ == 0; });
-    f_ = nullptr;
-    return true;
-  }
-
- private:
-  void work(int id) {
-    unsigned seen = 0;
-    for (;;) {
-      const std::function<void(int)>* f = nullptr;
-      {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [&]() { return gen_ != seen; });
-        seen = gen_;
-        if (id < nth_) f = f_;
-      }
-      if (!f) continue;
-      (*f)(id);
-      {
-        std::lock_guard<std::mutex> lk(m_);
-        if (--pending_ == 0) done_.notify_all();
-      }
-    }
-  }
-  const pid_t pid_ = getpid();
-  std::mutex job_m_, m_;
-  std::condition_variable cv_, done_;
-  std::vector<std::thread> workers_;
-  const std::function<void(int)>* f_ = nullptr;
-  int nth_ = 0, pending_ = 0;
-  unsigned gen_ = 0;
-};
-
-// fn(t, lo, hi): thread t of host_threads(n) takes [lo, hi)
-template <typename F>
-static void host_parallel_for_t(int n, int nth, F fn) {
-  if (nth <= 1) {
-    fn(0, 0, n);
-    return;
-  }
-  const std::function<void(int)> job = [&](int t) {
-    const int lo = (int)((long long)n * t / nth), hi = (int)((long long)n * (t + 1) / nth);
-    fn(t, lo, hi);
-  };
-  if (HostPool::get().run(nth, job)) return;
-  std::vector<std::thread> th;
-  for (int t = 0; t < nth; ++t) th.emplace_back([&job, t]() { job(t); });
-  for (auto& x : th) x.join();
-}
-template <typename F>
-static void host_parallel_for(int n, F fn) {
-  host_parallel_for_t(n, host_threads(n), [&](int, int lo, int hi) { fn(lo, hi); });
-}
+using bsetup::host_parallel_for;
+using bsetup::host_parallel_for_t;
+using bsetup::host_threads;
+// the set-up's lists go to the device in one copy each
+static_assert(sizeof(bsetup::I2) == sizeof(int2) && offsetof(bsetup::I2, y) == offsetof(int2, y), "I2 is not int2");
+static_assert(sizeof(bsetup::I4) == sizeof(int4) && offsetof(bsetup::I4, y) == offsetof(int4, y) &&
+                  offsetof(bsetup::I4, z) == offsetof(int4, z) && offsetof(bsetup::I4, w) == offsetof(int4, w),
+              "I4 is not int4");
 
 template <typename T>
 static int ba_alloc(sfmhip_ba* b, T** p, size_t n) {
@@ -3863,8 +3777,7 @@ extern "C" void sfmhip_ba_default_opts(sfmhip_ba_opts* o) {
 // vectors at cfg4, and fresh ones cost their page faults on the way in (3-4 ms) and their unmapping on the way out (3.9 ms of a
 // 33 ms call) -- the allocator of the host process decides which, the library should not depend on it.
 struct BaHostScratch {
-  std::vector<int> cnt, slot, scam, run_of, order, optr, ocam, table, obs_src, cxy_src;
-  std::vector<uint64_t> sig_hash;
+  bsetup::Scratch setup;
   std::vector<double> h_pts_in;
   // the front tree of the last one-shot problem: the per-view call pattern (src/Sfm.cpp:996) changes the tracks from call to
   // call and the camera graph hardly ever -- a problem with the same graph (compared bit for bit) on the same device takes the
@@ -3918,17 +3831,6 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
                           const double* obs_xy, bool arena, sfmhip_ba** out) {
   if (!ctx || !out || n_cam <= 0 || n_pt < 0 || n_obs < 0) return SFMHIP_ERR_ARG;
   if (n_obs && (!obs_cam || !obs_pt || !obs_xy)) return SFMHIP_ERR_ARG;
-  // (one pass: the range check, and whether the observations already come grouped by point -- the order the reference adds
-  // residual blocks in, src/BundleAdjustment.cpp:83-110 -- in which case the counting sort's scatter below is the identity)
-  bool grouped = true;
-  {
-    int bad = 0;
-    for (int o = 0; o < n_obs; ++o) {
-      bad |= (obs_cam[o] < 0) | (obs_cam[o] >= n_cam) | (obs_pt[o] < 0) | (obs_pt[o] >= n_pt);
-      grouped &= o == 0 || obs_pt[o - 1] <= obs_pt[o];
-    }
-    if (bad) return SFMHIP_ERR_ARG;
-  }
   SFM_HIP_TRY(hipSetDevice(ctx->device));
   const bool prof_ = getenv("SFMHIP_PROFILE_CREATE") != nullptr;
   auto tp_ = std::chrono::steady_clock::now();
@@ -3953,603 +3855,42 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   b->dim = 6 * n_cam + 1;
   b->ld = (b->dim + 2 * CB - 1) / (2 * CB) * (2 * CB);  // chol_step2 takes two 32-column panels per launch
   b->ssz = (size_t)b->ld * b->ld;
-  // ---- group observations by point, ascending camera inside a point (std::map order of
-  //      Point3D::idxImage, reference src/BundleAdjustment.cpp:87)
-  // (a one-shot problem takes the context's vectors -- their capacity survives the call -- and gives its own back when it goes)
-  BaHostScratch own_scratch, *hs = arena ? ba_host_scratch(ctx) : &own_scratch;
-  if (arena) {
-    b->obs_src.swap(hs->obs_src);
-    b->cxy_src.swap(hs->cxy_src);
-    b->h_pts_in.swap(hs->h_pts_in);
-  }
-  std::vector<int>& cnt = hs->cnt;
-  cnt.assign((size_t)n_pt + 1, 0);
-  for (int o = 0; o < n_obs; ++o) cnt[obs_pt[o] + 1]++;
-  for (int p = 0; p < n_pt; ++p) cnt[p + 1] += cnt[p];
-  std::vector<int>& slot = hs->slot;
-  slot.resize(n_obs);
-  if (grouped) {
-    host_parallel_for(n_obs, [&](int lo, int hi) {
-      for (int o = lo; o < hi; ++o) slot[o] = o;
-    });
-  } else {
-    std::vector<int> fill(n_pt, 0);
-    for (int o = 0; o < n_obs; ++o) slot[cnt[obs_pt[o]] + fill[obs_pt[o]]++] = o;
-  }
-  // per point (a few host threads: every pass over a million observations is a cache-miss chain on
-  // one core): stable insertion sort -- a point has a handful of observations --, then the point's
-  // ascending camera list, flat, and a hash of it: the signature grouping below compares
-  // (length, hash) first and walks the lists only on equal hashes
-  std::vector<int>& scam = hs->scam;
-  scam.resize(n_obs);
-  std::vector<uint64_t>& sig_hash = hs->sig_hash;
-  sig_hash.assign(n_pt, 0);
-  host_parallel_for(n_pt, [&](int plo, int phi) {
-    for (int p = plo; p < phi; ++p) {
-      for (int i = cnt[p] + 1; i < cnt[p + 1]; ++i) {
-        const int v = slot[i], cv = obs_cam[v];
-        int j = i - 1;
-        for (; j >= cnt[p] && obs_cam[slot[j]] > cv; --j) slot[j + 1] = slot[j];
-        slot[j + 1] = v;
-      }
-      uint64_t h = 1469598103934665603ull;
-      for (int k = cnt[p]; k < cnt[p + 1]; ++k) {
-        scam[k] = obs_cam[slot[k]];
-        h = (h ^ (uint64_t)(uint32_t)scam[k]) * 1099511628211ull;
-      }
-      sig_hash[p] = h;
+  // ---- the set-up on the host (ba_setup.h).  A one-shot problem borrows the context's vectors for its five large arrays --
+  // their capacity survives the call -- and gives them back below (the observation maps stay with the problem until it goes)
+  BaHostScratch* const hs = arena ? ba_host_scratch(ctx) : nullptr;
+  if (arena) b->h_pts_in.swap(hs->h_pts_in);
+  bsetup::Setup S;
+  struct GiveBack {
+    bsetup::Scratch* scr;
+    bsetup::Setup& S;
+    ~GiveBack() {
+      if (scr) scr->swap_kept(S);
     }
-  });
-  lap_("group by point");
-  // ---- group the points that have observations by signature (their ascending camera list): a
-  //      hash table assigns run ids in order of first appearance, a counting sort makes the runs
-  //      contiguous (stable: ascending point index inside a run)
-  auto sig_equal = [&](int x, int y) {  // x, y: input point indices
-    const int nx = cnt[x + 1] - cnt[x];
-    if (nx != cnt[y + 1] - cnt[y] || sig_hash[x] != sig_hash[y]) return false;
-    for (int k = 0; k < nx; ++k)
-      if (scam[cnt[x] + k] != scam[cnt[y] + k]) return false;
-    return true;
-  };
-  // (round 6: the three passes run on the host threads.  Every thread groups the points of ITS block with a table of its own --
-  // local run ids in the block's order of first appearance --, the blocks' runs then meet one table in block order, which IS the
-  // points' order of first appearance, and the counting sort scatters block by block from per-block start positions: the same
-  // run ids, the same order as one thread produces, whatever the number of threads)
-  std::vector<int>& run_of = hs->run_of;
-  run_of.resize(n_pt);
-  std::vector<int> run_rep, run_cnt;
-  const int sig_threads = host_threads(n_pt);
-  std::vector<std::vector<int>> loc_rep((size_t)sig_threads), loc_cnt((size_t)sig_threads);
-  auto probe = [&](int* table, size_t cap, std::vector<int>& rep, int p) -> int {  // the run of point p among `rep`, entered when new
-    size_t slot_i = (size_t)(sig_hash[p] ^ (sig_hash[p] >> 29)) & (cap - 1);
-    for (;; slot_i = (slot_i + 1) & (cap - 1)) {
-      const int r = table[slot_i];
-      if (r < 0) {
-        table[slot_i] = (int)rep.size();
-        rep.push_back(p);
-        return (int)rep.size() - 1;
-      }
-      if (sig_equal(rep[r], p)) return r;
-    }
-  };
+  } give_back{arena ? &hs->setup : nullptr, S};
+  if (arena) hs->setup.swap_kept(S);
   {
-    const size_t blk = ((size_t)n_pt + sig_threads - 1) / sig_threads;
-    size_t cap = 64;
-    while (cap < 2 * blk + 16) cap <<= 1;
-    std::vector<int>& table = hs->table;  // open addressing: run id, keyed by the signature hash; a slice per thread
-    table.resize(cap * (size_t)sig_threads);
-    std::vector<char> too_many((size_t)sig_threads, 0);
-    host_parallel_for_t(n_pt, sig_threads, [&](int t, int lo, int hi) {
-      int* tab = table.data() + cap * (size_t)t;
-      std::fill(tab, tab + cap, -1);
-      for (int p = lo; p < hi; ++p) {
-        const int n = cnt[p + 1] - cnt[p];
-        if (n > FB_MAXN) {
-          too_many[t] = 1;
-          return;
-        }
-        run_of[p] = n == 0 ? -1 : probe(tab, cap, loc_rep[t], p);
-      }
-    });
-    for (char c : too_many)
-      if (c) return SFMHIP_ERR_UNSUPPORTED;  // more than FB_MAXN observations of one point
-    // the blocks' runs, block by block in their local order, into one table: global run ids in the points' order of first appearance
-    size_t total = 0;
-    for (const auto& r : loc_rep) total += r.size();
-    size_t gcap = 64;
-    while (gcap < 2 * total + 16) gcap <<= 1;
-    std::vector<int> gtab(gcap, -1);
-    for (int t = 0; t < sig_threads; ++t)
-      for (int& lp : loc_rep[t]) lp = probe(gtab.data(), gcap, run_rep, lp);  // (the block's representative -> the global run)
-    // global ids for the points, and every block's count per run
-    const size_t R = run_rep.size();
-    host_parallel_for_t(n_pt, sig_threads, [&](int t, int lo, int hi) {
-      std::vector<int>& c = loc_cnt[t];
-      c.assign(R, 0);
-      const int* l2g = loc_rep[t].data();
-      for (int p = lo; p < hi; ++p)
-        if (run_of[p] >= 0) ++c[run_of[p] = l2g[run_of[p]]];
-    });
-    run_cnt.assign(R, 0);
-    for (int t = 0; t < sig_threads; ++t)
-      for (size_t r = 0; r < R; ++r) run_cnt[r] += loc_cnt[t][r];
+    bsetup::Input in;
+    in.n_cam = n_cam, in.n_pt = n_pt, in.n_obs = n_obs;
+    in.obs_cam = obs_cam, in.obs_pt = obs_pt, in.obs_xy = obs_xy;
+    in.ld = b->ld;
+    in.n_cu = ctx->n_cu;
+    in.deterministic = b->elim_deterministic;
+    in.short_pieces = getenv("SFMHIP_BA_SHORT_PIECES") ? atoi(getenv("SFMHIP_BA_SHORT_PIECES")) : 512;  // (read per problem)
+    if (prof_) in.lap = lap_;
+    bsetup::Scratch own_scratch;
+    SFM_TRY(bsetup::build(in, arena ? hs->setup : own_scratch, S));
   }
-  lap_("  sig: hash table");
-  std::vector<int> run_start(run_rep.size() + 1, 0);
-  for (size_t r = 0; r < run_rep.size(); ++r) run_start[r + 1] = run_start[r] + run_cnt[r];
-  std::vector<int>& order = hs->order;
-  order.resize(run_start.back());
-  {
-    // block t starts run r behind the points of the blocks before it (loc_cnt becomes the blocks' write positions)
-    for (size_t r = 0; r < run_rep.size(); ++r) {
-      int at = run_start[r];
-      for (int t = 0; t < sig_threads; ++t) {
-        const int c = loc_cnt[t][r];
-        loc_cnt[t][r] = at;
-        at += c;
-      }
-    }
-    host_parallel_for_t(n_pt, sig_threads, [&](int t, int lo, int hi) {
-      int* at = loc_cnt[t].data();
-      for (int p = lo; p < hi; ++p)
-        if (run_of[p] >= 0) order[at[run_of[p]]++] = p;
-    });
-  }
-  lap_("  sig: counting sort");
-  b->np = (int)order.size();
-  b->perm = order;
-  std::vector<int>& optr = hs->optr;
-  optr.resize((size_t)b->np + 1);
-  {
-    // prefix sums of the sorted points' observation counts: block sums first, then every block from its own start
-    const int nth = host_threads(b->np);
-    std::vector<long long> bsum((size_t)nth + 1, 0);
-    host_parallel_for_t(b->np, nth, [&](int t, int lo, int hi) {
-      long long sacc = 0;
-      for (int sp = lo; sp < hi; ++sp) sacc += cnt[order[sp] + 1] - cnt[order[sp]];
-      bsum[t + 1] = sacc;
-    });
-    for (int t = 0; t < nth; ++t) bsum[t + 1] += bsum[t];
-    host_parallel_for_t(b->np, nth, [&](int t, int lo, int hi) {
-      int at = (int)bsum[t];
-      for (int sp = lo; sp < hi; ++sp) {
-        optr[sp] = at;
-        at += cnt[order[sp] + 1] - cnt[order[sp]];
-      }
-    });
-    optr[b->np] = (int)bsum[nth];
-  }
-  if (getenv("SFMHIP_BA_CHECK_SETUP")) {
-    // (tests: the grouping of one thread, pass by pass as it was written before round 6, must be what the threads produced)
-    std::vector<int> rep1, of1(n_pt, -1), cnt1;
-    size_t cap1 = 64;
-    while (cap1 < 2 * (size_t)n_pt + 16) cap1 <<= 1;
-    std::vector<int> tab1(cap1, -1);
-    for (int p = 0; p < n_pt; ++p) {
-      if (cnt[p + 1] == cnt[p]) continue;
-      const size_t before = rep1.size();
-      of1[p] = probe(tab1.data(), cap1, rep1, p);
-      if (rep1.size() != before) cnt1.push_back(0);
-      ++cnt1[of1[p]];
-    }
-    std::vector<int> start1(rep1.size() + 1, 0);
-    for (size_t r = 0; r < rep1.size(); ++r) start1[r + 1] = start1[r] + cnt1[r];
-    std::vector<int> order1((size_t)start1.back()), optr1((size_t)start1.back() + 1, 0);
-    for (int p = 0; p < n_pt; ++p)
-      if (of1[p] >= 0) order1[start1[of1[p]]++] = p;
-    for (size_t sp = 0; sp < order1.size(); ++sp) optr1[sp + 1] = optr1[sp] + (cnt[order1[sp] + 1] - cnt[order1[sp]]);
-    if (rep1 != run_rep || of1 != run_of || order1 != order || optr1 != optr) {
-      fprintf(stderr, "sfmhip_ba_create: the threads' grouping differs from one thread's (SFMHIP_BA_CHECK_SETUP)\n");
-      return SFMHIP_ERR_STATE;
-    }
-  }
-  b->no = optr[b->np];
-  std::vector<int>& ocam = hs->ocam;
-  ocam.resize(b->no);
-  b->obs_src.resize(b->no);
-  b->h_cam_used.assign(n_cam, 0);
-  lap_("  sig: optr + resizes");
-  // the gather of a million observations is a cache-miss chain on one core: split it over a few (each marks the cameras it
-  // meets in a list of its own; the lists are merged behind the threads)
-  {
-    const int nth = host_threads(b->np);
-    std::vector<std::vector<unsigned char>> used((size_t)nth, std::vector<unsigned char>(n_cam, 0));
-    host_parallel_for_t(b->np, nth, [&](int t, int lo, int hi) {
-      unsigned char* mine = used[t].data();
-      for (int sp = lo; sp < hi; ++sp) {
-        const int p = order[sp];
-        int w = optr[sp];
-        for (int k = cnt[p]; k < cnt[p + 1]; ++k, ++w) {
-          const int o = slot[k];
-          b->obs_src[w] = o;
-          ocam[w] = obs_cam[o];
-          if (!mine[ocam[w]]) mine[ocam[w]] = 1;  // (written once: the threads' lists are neighbours in memory, and a store per
-                                                  //  observation to a line another thread's list shares kept that line travelling)
-          // (the coordinates are put in this order on the device: ba_permute_xy)
-        }
-      }
-    });
-    for (const auto& u : used)
-      for (int c = 0; c < n_cam; ++c) b->h_cam_used[c] |= u[c];
-  }
-  lap_("signature sort + csr");
-  // ---- chunks: runs of equal signature with strictly ascending cameras, n <= 10 -> MFMA path,
-  //      classed by the width of the local Gram matrix: NB = ceil((6n+2)/16) column blocks
-  std::vector<Chunk> chunks;
-  std::vector<int> ids[8], sig_cams, fb;
-  constexpr int SHORT_RUN = 12;  // runs of at most this many points go to the pair path
-  // points per workgroup: 2 workgroups of 4 waves are resident per CU (register-bound), so the launch runs in
-  // rounds of 512 workgroups; a wave takes 4 points per iteration (~3.7 us at n = 10) and a fixed ~7 iterations'
-  // worth of prologue, reductions and scatter (s_memtime stamps, scripts/elim_stamps.py).  Pick the run length
-  // that minimises rounds x (iterations per wave + fixed).  Measured at cfg4 (round 2, stage
-  // time per LM iteration): 400 workgroups of 4 waves 100 us; 800 of 2 waves 106 us; 200 of 8 waves 150 us (not a
-  // matter of the two waves of a SIMD running in step: starting waves 4..7 up to 8 k cycles late changes nothing,
-  // 148-151 us); 800 of 4 waves (2 rounds) 136 us.
-  int target = 64;
-  const std::vector<int>& gstart = run_start;  // first sorted point of every run, + np
-  {
-    std::vector<int> gsz;
-    for (size_t gi = 0; gi + 1 < gstart.size(); ++gi)
-      if (gstart[gi + 1] - gstart[gi] > SHORT_RUN) gsz.push_back(gstart[gi + 1] - gstart[gi]);
-    double best = 1e300;
-    for (int t = 32; t <= 1024; t += 4) {
-      long long w = 0;
-      for (int g : gsz) w += (g + t - 1) / t;
-      // (a workgroup's iteration takes 4 waves x 6 points with ten lanes per point; its iterations are a third longer than the
-      // 4 x 4 of sixteen lanes per point, so the fixed part counts for 5.5 of them where it counted for 7)
-      const int ppi = 24;
-      const double cost = (double)((w + 511) / 512) * ((double)((t + ppi - 1) / ppi) + 5.5);
-      if (cost < best) {
-        best = cost;
-        target = t;
-      }
-    }
-  }
-  // One round of workgroups: when the runs cut at `target` leave resident slots empty (cfg4: 400 workgroups on 512
-  // slots, so 112 CUs hold one workgroup and idle half the launch while 144 hold two), the largest pieces are cut
-  // once more until the slots are full, and the launch lists the large pieces first: the dispatcher deals the first
-  // n_cu workgroups one per CU, so every CU ends up with a large and a small piece or two small ones.  The busiest
-  // SIMD then has 250 + 167 points instead of 500.
-  const int slots = 2 * std::max(b->ctx->n_cu, 1);  // (resident workgroups per CU)
-  std::vector<int> parts_of(gstart.size(), 0);
-  {
-    long long w = 0;
-    for (size_t gi = 0; gi + 1 < gstart.size(); ++gi) {
-      const int g = gstart[gi + 1] - gstart[gi];
-      if (g > SHORT_RUN) w += (parts_of[gi] = (g + target - 1) / target);
-    }
-    if (w > slots / 2 && w < slots) {
-      // (a max-heap on the current piece size; a piece of fewer than 64 points is not worth another workgroup)
-      std::vector<std::pair<double, size_t>> heap;
-      for (size_t gi = 0; gi + 1 < gstart.size(); ++gi)
-        if (parts_of[gi]) heap.push_back({(double)(gstart[gi + 1] - gstart[gi]) / parts_of[gi], gi});
-      std::make_heap(heap.begin(), heap.end());
-      while (w < slots && !heap.empty()) {
-        std::pop_heap(heap.begin(), heap.end());
-        const size_t gi = heap.back().second;
-        heap.pop_back();
-        const int g = gstart[gi + 1] - gstart[gi];
-        if (g / (parts_of[gi] + 1) < 64) continue;
-        ++parts_of[gi];
-        ++w;
-        heap.push_back({(double)g / parts_of[gi], gi});
-        std::push_heap(heap.begin(), heap.end());
-      }
-    }
-  }
-  // Short runs: the pair path sums per camera pair instead of per run, which is what a camera list shared by a dozen points
-  // wants -- when there are thousands of such lists.  The path itself costs four launches behind the elimination (33 us of a
-  // 220 us iteration at cfg4, measured with ONE such point), so while nothing else needs it (no ragged, unsorted or > 10-camera
-  // point) and the short runs are few, each becomes a small piece of the elimination: a workgroup among 512
-  // (SFMHIP_BA_SHORT_PIECES = the most short runs that are turned into pieces, 0: none; scripts/gpu_short_runs_ab.py)
-  bool short_as_pieces = false;
-  {
-    const int max_pieces = getenv("SFMHIP_BA_SHORT_PIECES") ? atoi(getenv("SFMHIP_BA_SHORT_PIECES")) : 512;  // (read per problem)
-    int n_short = 0;
-    bool pair_path_needed = false;
-    for (size_t gi = 0; gi + 1 < gstart.size() && !pair_path_needed; ++gi) {
-      const int sp = gstart[gi], n = optr[sp + 1] - optr[sp];
-      bool strict = true;
-      for (int k = 1; k < n; ++k) strict = strict && ocam[optr[sp] + k - 1] < ocam[optr[sp] + k];
-      if (!(n <= 10 && strict)) pair_path_needed = true;
-      else if (gstart[gi + 1] - sp <= SHORT_RUN) ++n_short;
-    }
-    short_as_pieces = !pair_path_needed && n_short > 0 && n_short <= max_pieces;
-  }
-  for (size_t gi = 0; gi + 1 < gstart.size(); ++gi) {
-    const int sp = gstart[gi], e = gstart[gi + 1];
-    const int n = optr[sp + 1] - optr[sp];
-    bool strict = true;
-    for (int k = 1; k < n; ++k) strict = strict && ocam[optr[sp] + k - 1] < ocam[optr[sp] + k];
-    if (n <= 10 && strict) {
-      const int so = (int)sig_cams.size();
-      for (int k = 0; k < n; ++k) sig_cams.push_back(ocam[optr[sp] + k]);
-      const int nb = (6 * n + 2 + 15) / 16;
-      if (e - sp <= SHORT_RUN && !short_as_pieces) {
-        sig_cams.resize(so);  // (a camera list shared by few points: the pair path, per-pair instead of per-run sums)
-        for (int q = sp; q < e; ++q) fb.push_back(q);
-      } else {
-        const int parts = std::max(parts_of[gi], 1);
-        for (int q = 0; q < parts; ++q) {
-          const int lo = sp + (int)((long long)(e - sp) * q / parts), hi = sp + (int)((long long)(e - sp) * (q + 1) / parts);
-          ids[nb - 1].push_back((int)chunks.size());
-          chunks.push_back(Chunk{so, n, lo, hi - lo});
-        }
-      }
-    } else {
-      for (int q = sp; q < e; ++q) fb.push_back(q);
-    }
-  }
-  for (auto& l : ids)  // large pieces first (stable: equal sizes keep the point order)
-    std::stable_sort(l.begin(), l.end(), [&](int a, int c) { return chunks[a].cnt > chunks[c].cnt; });
-  lap_("chunks");
-  // ---- the gather lists of the slab epilogue (ba_gather_slabs): for every destination in `red` the slab entries that
-  // add to it, in chunk order; list 0 for a full linearisation, list 1 for the norms-only mode (diagonal only)
-  std::vector<int> gth_ptr[2], gth_dest[2], grow_ptr, grow_id, grow_colmap;
-  std::vector<unsigned> gth_src[2];
-  std::vector<int4> grow_src, grow_hdr, grow_head, grow_over;
-  if (b->elim_deterministic && chunks.size() * (size_t)ELIM_SLAB >= ((size_t)1 << 31)) {
-    // the gather lists address a slab entry with 31 bits (bit 31 carries the sign): past ~740 000 chunks the elimination goes
-    // back to the atomic epilogue -- said out loud, because the sums are then no longer the same bit patterns run after run
-    fprintf(stderr, "sfmhip_ba: %zu chunks exceed the slab epilogue's 31-bit offsets; atomic epilogue (not run-to-run identical)\n",
-            chunks.size());
-    b->elim_deterministic = false;
-  }
-  if (b->elim_deterministic && !chunks.empty()) {
-    const int ld = b->ld, fo = 6 * n_cam;
-    const long long ssz = (long long)b->ssz, o_g = ssz, o_gF = ssz + ld, o_dc = ssz + 2LL * ld, o_sc = ssz + 3LL * ld;
-    std::vector<std::pair<long long, unsigned>> ent[2];  // (destination, source | sign)
-    // rows of S by their own kernel role while a wave's accumulator fits the default LDS limit (until round 6 the accumulator was
-    // a whole row, ld entries zeroed and scanned whatever the row held: at 640 cameras that outweighed what the row-wise reads
-    // save, and rows of more than 3072 columns went through the per-destination lists -- scripts/gpu_gather_bits.py: 640 cameras
-    // 3305 -> 3619 it/s, 1000: 2805 -> 3267, the same bits as the whole-row form wherever that ran).
-    // (round 6: a row's accumulator holds only the columns the row can have -- the cameras that share a run with the row's camera,
-    // the focal column, g's / the diagonal's / F^T b's entries --, not all ld of them: a wave zeroed and scanned ld entries whatever
-    // the row held, which is what kept rows of 640 cameras and more on the per-destination lists)
-    // per camera: the cameras of the runs it is in, ascending (tl_flat[tl_off[c] .. tl_off[c + 1])): a bit row per camera first
-    std::vector<int> tl_off(n_cam + 1, 0), tl_flat;
-    {
-      const int wpr_ = (n_cam + 63) / 64;
-      std::vector<unsigned long long> bits((size_t)n_cam * wpr_, 0ull);
-      std::vector<char> seen_sig(sig_cams.size() + 1, 0);
-      for (const Chunk& ch : chunks) {
-        if (seen_sig[ch.sig_off]) continue;
-        seen_sig[ch.sig_off] = 1;
-        for (int a = 0; a < ch.n; ++a) {
-          unsigned long long* row = bits.data() + (size_t)sig_cams[ch.sig_off + a] * wpr_;
-          for (int c2 = 0; c2 < ch.n; ++c2) row[sig_cams[ch.sig_off + c2] >> 6] |= 1ull << (sig_cams[ch.sig_off + c2] & 63);
-        }
-      }
-      for (int c = 0; c < n_cam; ++c) {
-        for (int w = 0; w < wpr_; ++w)
-          for (unsigned long long m = bits[(size_t)c * wpr_ + w]; m; m &= m - 1) tl_flat.push_back(64 * w + __builtin_ctzll(m));
-        tl_off[c + 1] = (int)tl_flat.size();
-      }
-    }
-    size_t accw = 64;  // a wave's accumulator: 6 entries per camera of the longest list + 4, in whole 64s
-    for (int c = 0; c < n_cam; ++c) accw = std::max(accw, (6 * (size_t)(tl_off[c + 1] - tl_off[c]) + 4 + 63) / 64 * 64);
-    const bool use_rows = accw * 8 <= 65536;
-    b->grow_waves = accw * 8 * 4 <= 65536 ? 4 : accw * 8 * 2 <= 65536 ? 2 : 1;
-    b->grow_accw = (int)accw;
-    if (use_rows) {
-      std::vector<int> cntr((size_t)fo + 1, 0);
-      for (const Chunk& ch : chunks)
-        for (int sl = 0; sl < ch.n; ++sl)
-          for (int i = 0; i < 6; ++i) ++cntr[(size_t)6 * sig_cams[ch.sig_off + sl] + i + 1];
-      for (int r = 0; r < fo; ++r) cntr[r + 1] += cntr[r];
-      grow_src.resize((size_t)cntr[fo]);
-      std::vector<int> pos(cntr.begin(), cntr.end() - 1);
-      // the cameras' lists, each behind its length: a row's header points at its camera's
-      std::vector<int> clist_of(n_cam, 0);
-      for (int c = 0; c < n_cam; ++c) {
-        if (tl_off[c + 1] == tl_off[c]) continue;
-        grow_colmap.push_back(tl_off[c + 1] - tl_off[c]);
-        clist_of[c] = (int)grow_colmap.size();
-        grow_colmap.insert(grow_colmap.end(), tl_flat.begin() + tl_off[c], tl_flat.begin() + tl_off[c + 1]);
-      }
-      // (signature = offset of its camera list, the row's camera's place in it) -> offset of the column map (64 ints)
-      std::vector<int> cmap_of(sig_cams.size() + 1, -1);
-      for (size_t c = 0; c < chunks.size(); ++c) {  // chunk order inside every row
-        const Chunk& ch = chunks[c];
-        const int n = ch.n, NBc = (6 * n + 2 + 15) / 16;
-        for (int sl = 0; sl < n; ++sl) {
-          int& cm = cmap_of[ch.sig_off + sl];
-          if (cm < 0) {
-            // local column lc < 6 n of the signature -> its place in the accumulator of a row of camera sig[sl]: 6 * (the rank of
-            // camera sig[lc / 6] in that camera's list) + lc % 6; behind the nT = 6 * |list| columns of S: the focal column, g's
-            // entry, the diagonal's and F^T b's (ba_gather_rows)
-            cm = (int)grow_colmap.size();
-            const int row_cam = sig_cams[ch.sig_off + sl];
-            const int* tl = tl_flat.data() + tl_off[row_cam];
-            const int nT = 6 * (tl_off[row_cam + 1] - tl_off[row_cam]);
-            grow_colmap.resize((size_t)cm + 64);
-            int* out = grow_colmap.data() + cm;
-            for (int a = 0, t = 0; a < n; ++a) {  // (both lists ascend: one walk gives every camera's rank)
-              while (tl[t] != sig_cams[ch.sig_off + a]) ++t;
-              for (int i = 0; i < 6; ++i) out[6 * a + i] = 6 * t + i;
-            }
-            for (int lc = 6 * n; lc < 62; ++lc) out[lc] = lc == 6 * n ? nT : nT + 1;
-            out[62] = nT + 2, out[63] = nT + 3;
-          }
-          for (int i = 0; i < 6; ++i) {
-            const int lr = 6 * sl + i, ti = lr >> 4;
-            const int t0 = ti * NBc - ti * (ti - 1) / 2;  // tile (ti, ti)
-            const int roff = (t0 * 4 + ((lr & 15) >> 2)) * 64 + (lr & 3) * 16 - 256 * ti;
-            const int dcr = (i * 6 - i * (i - 1) / 2) * FP + sl, gfr = (27 + i) * FP + sl;
-            grow_src[(size_t)pos[(size_t)6 * sig_cams[ch.sig_off + sl] + i]++] =
-                make_int4((int)(unsigned)(c * (size_t)ELIM_SLAB), lr | (n << 8) | (roff << 16), cm, dcr | (gfr << 16));
-          }
-        }
-      }
-      for (int r = 0; r < fo; ++r)
-        if (cntr[r + 1] > cntr[r]) {
-          grow_ptr.push_back(cntr[r]);
-          grow_id.push_back(r);
-        }
-      grow_ptr.push_back(cntr[fo]);
-      // a row's first 32 records in a table of their own (fixed stride), the rest in one overflow list
-      for (size_t r = 0; r < grow_id.size(); ++r) {
-        const int k0 = grow_ptr[r], cnt = grow_ptr[r + 1] - k0;
-        grow_hdr.push_back(make_int4(grow_id[r], cnt, (int)grow_over.size(), clist_of[grow_id[r] / 6]));
-        for (int k = 0; k < 32; ++k) grow_head.push_back(k < cnt ? grow_src[(size_t)k0 + k] : make_int4(0, 0, 0, 0));
-        for (int k = 32; k < cnt; ++k) grow_over.push_back(grow_src[(size_t)k0 + k]);
-      }
-      if (grow_over.empty()) grow_over.push_back(make_int4(0, 0, 0, 0));
-    }
-    const long long GMAX = -1;                            // (sorts first; the kernel takes the rank's slot as an argument)
-    for (size_t c = 0; c < chunks.size(); ++c) {
-      const Chunk& ch = chunks[c];
-      const int n = ch.n, NBc = (6 * n + 2 + 15) / 16, NTc = NBc * (NBc + 1) / 2;
-      const int* cams = sig_cams.data() + ch.sig_off;
-      const unsigned base = (unsigned)(c * (size_t)ELIM_SLAB);
-      auto gidx = [&](int l) { return l < 6 * n ? 6 * cams[l / 6] + l % 6 : l == 6 * n ? fo : l == 6 * n + 1 ? -2 : -1; };
-      // (ba_gather_rows: the cameras' rows from the row lists above, the focal row chunk by chunk -- nothing of the Gram block
-      // goes through the destination lists then, and walking its NTc * 256 entries per chunk was half of this stage's time)
-      for (int idx = 0; !use_rows && idx < NTc * 256; ++idx) {  // the Gram block, as the kernel lays it out
-        int t = idx >> 8, ti = 0;
-        while (t >= NBc - ti) {
-          t -= NBc - ti;
-          ++ti;
-        }
-        const int tj = ti + t, gg = (idx >> 6) & 3, ln = idx & 63;
-        const int lr = 16 * ti + (ln >> 4) + 4 * gg, lc = 16 * tj + (ln & 15);
-        const int gr = gidx(lr), gc = gidx(lc);
-        if (gr < 0 || lr > lc || gc == -1) continue;
-        ent[0].push_back({gc >= 0 ? (long long)gr * ld + gc : o_g + gr, (base + idx) | 0x80000000u});  // S -= Gram (F^T F folded in)
-      }
-      for (int e = 0; e < 33; ++e)
-        for (int slot = 0; slot < n; ++slot) {
-          const unsigned sidx = base + ELIM_SLAB_FF + e * FP + slot;
-          const int r0 = 6 * cams[slot];
-          if (e < 21) {
-            int i = 0, rem = e;
-            while (rem >= 6 - i) {
-              rem -= 6 - i;
-              ++i;
-            }
-            if (rem == 0) {
-              if (!use_rows) ent[0].push_back({o_dc + r0 + i, sidx});
-              ent[1].push_back({o_dc + r0 + i, sidx});
-            }
-          } else if (e >= 27) {
-            if (!use_rows) ent[0].push_back({o_gF + r0 + e - 27, sidx});
-          }
-        }
-      const unsigned tail = base + ELIM_SLAB_FF + 36 * FP;
-      ent[1].push_back({o_dc + fo, tail});
-      if (!use_rows) {
-        ent[0].push_back({o_dc + fo, tail});
-        ent[0].push_back({o_gF + fo, tail + 1});
-        ent[0].push_back({o_sc + 0, tail + 2});
-        ent[0].push_back({GMAX, tail + 3});
-        ent[0].push_back({o_sc + 2, tail + 4});
-      }
-    }
-    for (int m = 0; m < 2; ++m) {
-      const size_t range = (size_t)(o_sc + SC + 64) + 2;   // destinations + the GMAX key shifted to 0
-      if (ent[m].size() * 16 < range) {
-        // few entries for the range (the row lists carry S: what is left are the diagonal's entries): a stable sort of the
-        // entries instead of three passes over ld^2 counters (cfg4: 31 k entries, 1.5 M destinations)
-        std::stable_sort(ent[m].begin(), ent[m].end(), [](const std::pair<long long, unsigned>& a, const std::pair<long long, unsigned>& c) { return a.first < c.first; });
-        gth_src[m].resize(ent[m].size());
-        for (size_t k = 0; k < ent[m].size(); ++k) {
-          gth_src[m][k] = ent[m][k].second;
-          if (k == 0 || ent[m][k].first != ent[m][k - 1].first) {
-            gth_ptr[m].push_back((int)k);
-            gth_dest[m].push_back((int)ent[m][k].first);
-          }
-        }
-        gth_ptr[m].push_back((int)ent[m].size());
-        continue;
-      }
-      // counting sort by destination (stable: a destination's sources stay in chunk order)
-      std::vector<int> cnt(range + 1, 0);
-      for (const auto& e : ent[m]) ++cnt[(size_t)(e.first + 1) + 1];
-      for (size_t k = 0; k < range; ++k) cnt[k + 1] += cnt[k];
-      gth_src[m].resize(ent[m].size());
-      {
-        std::vector<int> pos(cnt.begin(), cnt.end() - 1);
-        for (const auto& e : ent[m]) gth_src[m][(size_t)pos[(size_t)(e.first + 1)]++] = e.second;
-      }
-      for (size_t k = 0; k < range; ++k)
-        if (cnt[k + 1] > cnt[k]) {
-          gth_ptr[m].push_back(cnt[k]);
-          gth_dest[m].push_back((int)((long long)k - 1));
-        }
-      gth_ptr[m].push_back((int)ent[m].size());
-    }
-  }
-  lap_("gather lists");
-  // ---- camera co-visibility (one bit row per camera) for the dissection of the reduced system
-  if (n_cam <= 4096) {  // (from one camera on: a small system is one front)
-    const int wpr = (n_cam + 63) / 64;
-    b->h_adj.assign((size_t)n_cam * wpr, 0ull);
-    auto add_clique = [&](const int* cs, int n) {
-      for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) b->h_adj[(size_t)cs[i] * wpr + (cs[j] >> 6)] |= 1ull << (cs[j] & 63);
-    };
-    std::vector<char> is_fb(b->np, 0);
-    for (int q : fb) is_fb[q] = 1;
-    for (size_t gi = 0; gi + 1 < gstart.size(); ++gi) {
-      const int sp = gstart[gi];
-      if (!is_fb[sp]) add_clique(&ocam[optr[sp]], optr[sp + 1] - optr[sp]);  // one signature per run
-    }
-    for (int q : fb) add_clique(&ocam[optr[q]], optr[q + 1] - optr[q]);
-    lap_("camera graph");
-  }
-  // ---- the pair path's lists (ba_pp_points / ba_pp_pairs / ba_cam_blocks): its points in ascending sorted order, a
-  //      row of T per observation, the camera-major list of those observations, and per camera pair that a point
-  //      sees together the (row of a, row of b) entries
-  std::sort(fb.begin(), fb.end());
-  std::vector<int> cptr(n_cam + 1, 0), cpt, pp_obase(fb.size() + 1, 0), pair_ptr(1, 0);
-  std::vector<int2> cslot, pair_cams, pair_ent;
-  std::vector<double> cxy;
-  {
-    for (size_t i = 0; i < fb.size(); ++i) pp_obase[i + 1] = pp_obase[i] + (optr[fb[i] + 1] - optr[fb[i]]);
-    const size_t nfo = (size_t)pp_obase[fb.size()];
-    cpt.resize(nfo);
-    cslot.resize(nfo);
-    cxy.resize(2 * nfo);
-    b->cxy_src.resize(nfo);
-    for (int sp : fb)
-      for (int k = optr[sp]; k < optr[sp + 1]; ++k) cptr[ocam[k] + 1]++;
-    for (int c = 0; c < n_cam; ++c) cptr[c + 1] += cptr[c];
-    std::vector<int> fill(cptr.begin(), cptr.end() - 1);
-    struct PE {
-      long long key;
-      int a, b;
-    };
-    std::vector<PE> pes;
-    for (size_t i = 0; i < fb.size(); ++i) {  // ascending sorted point index: the order inside a camera is the stable one
-      const int sp = fb[i], k0 = optr[sp], n = optr[sp + 1] - k0;
-      for (int o = 0; o < n; ++o) {
-        const int dst = fill[ocam[k0 + o]]++;
-        cpt[dst] = sp;
-        cslot[dst] = make_int2(pp_obase[i] + o, (int)i);
-        b->cxy_src[dst] = k0 + o;
-        cxy[2 * (size_t)dst] = obs_xy[2 * (size_t)b->obs_src[k0 + o]];
-        cxy[2 * (size_t)dst + 1] = obs_xy[2 * (size_t)b->obs_src[k0 + o] + 1];
-        for (int o2 = o + 1; o2 < n; ++o2) {
-          int ca = ocam[k0 + o], cb = ocam[k0 + o2], ra = pp_obase[i] + o, rb = pp_obase[i] + o2;
-          if (ca > cb) std::swap(ca, cb), std::swap(ra, rb);
-          pes.push_back(PE{(long long)ca * n_cam + cb, ra, rb});
-        }
-      }
-    }
-    std::sort(pes.begin(), pes.end(), [](const PE& x, const PE& y) { return x.key != y.key ? x.key < y.key : (x.a != y.a ? x.a < y.a : x.b < y.b); });
-    for (size_t e = 0; e < pes.size(); ++e) {
-      if (e == 0 || pes[e].key != pes[e - 1].key) {
-        if (e) pair_ptr.push_back((int)e);
-        pair_cams.push_back(make_int2((int)(pes[e].key / n_cam), (int)(pes[e].key % n_cam)));
-      }
-      pair_ent.push_back(make_int2(pes[e].a, pes[e].b));
-    }
-    if (!pes.empty()) pair_ptr.push_back((int)pes.size());
-    // (a workgroup per (camera, slice): ~1024 entries each, so that the 69-value block reduction is paid once per four
-    // entries of a thread: 57 -> 25 us at 200 cameras x 1000 observations)
-    b->cam_split = (int)std::max<size_t>(1, std::min<size_t>(64, nfo / (size_t)std::max(n_cam, 1) / 1024));
-  }
-  lap_("camera-major copy");
+  b->np = S.np;
+  b->no = S.no;
+  b->perm = S.order;
+  b->obs_src.swap(S.obs_src);
+  b->cxy_src.swap(S.cxy_src);
+  b->h_cam_used.swap(S.cam_used);
+  b->h_adj.swap(S.adj);
+  b->elim_deterministic = S.elim_deterministic;
+  b->grow_waves = S.grow_waves;
+  b->grow_accw = S.grow_accw;
+  b->cam_split = S.cam_split;
   // ---- device storage
   BaDev& d = b->d;
   d.nc = n_cam;
@@ -4592,32 +3933,32 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   }
   BA_A(b->d_cam_used, n_cam);
   BA_A(b->d_flag, 2);
-  BA_A(b->d_chunks, chunks.size());
-  if (!gth_dest[0].empty() || !gth_dest[1].empty() || !grow_id.empty()) {
-    BA_A(b->d_slab, chunks.size() * (size_t)ELIM_SLAB);
+  BA_A(b->d_chunks, S.chunks.size());
+  if (!S.gth_dest[0].empty() || !S.gth_dest[1].empty() || !S.grow_hdr.empty()) {
+    BA_A(b->d_slab, S.chunks.size() * (size_t)ELIM_SLAB);
     for (int m = 0; m < 2; ++m) {
-      BA_A(b->d_gth_ptr[m], gth_ptr[m].size());
-      BA_A(b->d_gth_src[m], gth_src[m].size());
-      BA_A(b->d_gth_dest[m], gth_dest[m].size());
+      BA_A(b->d_gth_ptr[m], S.gth_ptr[m].size());
+      BA_A(b->d_gth_src[m], S.gth_src[m].size());
+      BA_A(b->d_gth_dest[m], S.gth_dest[m].size());
     }
-    if (!grow_id.empty()) {
-      BA_A(b->d_grow_hdr, grow_hdr.size());
-      BA_A(b->d_grow_head, grow_head.size());
-      BA_A(b->d_grow_src, grow_over.size());
-      BA_A(b->d_grow_colmap, grow_colmap.size());
+    if (!S.grow_hdr.empty()) {
+      BA_A(b->d_grow_hdr, S.grow_hdr.size());
+      BA_A(b->d_grow_head, S.grow_head.size());
+      BA_A(b->d_grow_src, S.grow_over.size());
+      BA_A(b->d_grow_colmap, S.grow_colmap.size());
     }
   }
-  for (int c = 0; c < 8; ++c) BA_A(b->d_chunk_ids[c], ids[c].size());
-  BA_A(b->d_sig_cams, sig_cams.size());
-  BA_A(b->d_cptr, cptr.size());
-  BA_A(b->d_cpt, cpt.size());
-  BA_A(b->d_cxy, cpt.size());
-  BA_A(b->d_fb_points, fb.size());
-  BA_A(b->d_pp_obase, pp_obase.size());
-  BA_A(b->d_cslot, cslot.size());
-  BA_A(b->d_ppT, 18 * cslot.size());
-  BA_A(b->d_tfu, 6 * fb.size());
-  b->n_pp_part = (int)((fb.size() * PP_LANES + 255) / 256);
+  for (int c = 0; c < 8; ++c) BA_A(b->d_chunk_ids[c], S.ids[c].size());
+  BA_A(b->d_sig_cams, S.sig_cams.size());
+  BA_A(b->d_cptr, S.cptr.size());
+  BA_A(b->d_cpt, S.cpt.size());
+  BA_A(b->d_cxy, S.cpt.size());
+  BA_A(b->d_fb_points, S.fb.size());
+  BA_A(b->d_pp_obase, S.pp_obase.size());
+  BA_A(b->d_cslot, S.cslot.size());
+  BA_A(b->d_ppT, 18 * S.cslot.size());
+  BA_A(b->d_tfu, 6 * S.fb.size());
+  b->n_pp_part = (int)((S.fb.size() * PP_LANES + 255) / 256);
   BA_A(b->d_pp_part, 8 * (size_t)b->n_pp_part);
   if (b->cam_split > 1) {
     BA_A(b->d_cb_part, 66 * (size_t)n_cam * b->cam_split);
@@ -4637,67 +3978,57 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
       if (rc == SFMHIP_OK && hipMemset(d.xinv, 0, sizeof(double) * b->ssz) != hipSuccess) rc = SFMHIP_ERR_HIP;
     }
   }
-  BA_A(b->d_pair_ptr, pair_ptr.size());
-  BA_A(b->d_pair_cams, pair_cams.size());
-  BA_A(b->d_pair_ent, pair_ent.size());
+  BA_A(b->d_pair_ptr, S.pair_ptr.size());
+  BA_A(b->d_pair_cams, S.pair_cams.size());
+  BA_A(b->d_pair_ent, S.pair_ent.size());
 #undef BA_A
   if (rc != SFMHIP_OK) return rc;
   d.optr = d_optr;
   d.ocam = d_ocam;
   d.oxy = d_oxy;
   b->d_oxy_w = d_oxy;
-  for (int c = 0; c < 8; ++c) b->n_chunk_ids[c] = (int)ids[c].size();
-  b->n_fb = (int)fb.size();
+  for (int c = 0; c < 8; ++c) b->n_chunk_ids[c] = (int)S.ids[c].size();
+  b->n_fb = (int)S.fb.size();
   auto up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
     return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
   };
   lap_("hipMalloc x27");
-  SFM_HIP_TRY(up(d_optr, optr.data(), optr.size() * 4));
-  SFM_HIP_TRY(up(d_ocam, ocam.data(), ocam.size() * 4));
+  SFM_HIP_TRY(up(d_optr, S.optr.data(), S.optr.size() * 4));
+  SFM_HIP_TRY(up(d_ocam, S.ocam.data(), S.ocam.size() * 4));
   SFM_HIP_TRY(up(b->d_obs_src, b->obs_src.data(), b->obs_src.size() * 4));
   SFM_TRY(ba_upload_xy(b, obs_xy, n_obs));
   SFM_HIP_TRY(up(b->d_cam_used, b->h_cam_used.data(), n_cam));
-  SFM_HIP_TRY(up(b->d_chunks, chunks.data(), chunks.size() * sizeof(Chunk)));
-  b->n_chunks = (int)chunks.size();
-  if (!chunks.empty()) {
-    std::vector<int> all(chunks.size());
-    for (size_t i = 0; i < all.size(); ++i) all[i] = (int)i;
-    std::stable_sort(all.begin(), all.end(), [&](int a, int c) { return chunks[a].cnt > chunks[c].cnt; });
-    std::vector<int> desc(16 * all.size(), 0);
-    for (size_t i = 0; i < all.size(); ++i) {
-      const Chunk& c = chunks[all[i]];
-      int* r = &desc[16 * i];
-      r[0] = c.n, r[1] = c.p0, r[2] = c.cnt, r[3] = optr[c.p0];
-      for (int k = 0; k < c.n && k < 10; ++k) r[4 + k] = sig_cams[c.sig_off + k];
-    }
-    SFM_TRY(ba_alloc(b, &b->d_bs_ids, desc.size()));
-    SFM_HIP_TRY(hipMemcpy(b->d_bs_ids, desc.data(), desc.size() * sizeof(int), hipMemcpyHostToDevice));
+  SFM_HIP_TRY(up(b->d_chunks, S.chunks.data(), S.chunks.size() * sizeof(Chunk)));
+  b->n_chunks = (int)S.chunks.size();
+  if (!S.bs_desc.empty()) {
+    SFM_TRY(ba_alloc(b, &b->d_bs_ids, S.bs_desc.size()));
+    SFM_HIP_TRY(hipMemcpy(b->d_bs_ids, S.bs_desc.data(), S.bs_desc.size() * sizeof(int), hipMemcpyHostToDevice));
   }
   for (int m = 0; m < 2 && b->d_slab; ++m) {
-    SFM_HIP_TRY(up(b->d_gth_ptr[m], gth_ptr[m].data(), gth_ptr[m].size() * 4));
-    SFM_HIP_TRY(up(b->d_gth_src[m], gth_src[m].data(), gth_src[m].size() * 4));
-    SFM_HIP_TRY(up(b->d_gth_dest[m], gth_dest[m].data(), gth_dest[m].size() * 4));
-    b->n_gth[m] = (int)gth_dest[m].size();
+    SFM_HIP_TRY(up(b->d_gth_ptr[m], S.gth_ptr[m].data(), S.gth_ptr[m].size() * 4));
+    SFM_HIP_TRY(up(b->d_gth_src[m], S.gth_src[m].data(), S.gth_src[m].size() * 4));
+    SFM_HIP_TRY(up(b->d_gth_dest[m], S.gth_dest[m].data(), S.gth_dest[m].size() * 4));
+    b->n_gth[m] = (int)S.gth_dest[m].size();
   }
-  if (b->d_slab && !grow_id.empty()) {
-    SFM_HIP_TRY(up(b->d_grow_hdr, grow_hdr.data(), grow_hdr.size() * sizeof(int4)));
-    SFM_HIP_TRY(up(b->d_grow_head, grow_head.data(), grow_head.size() * sizeof(int4)));
-    SFM_HIP_TRY(up(b->d_grow_src, grow_over.data(), grow_over.size() * sizeof(int4)));
-    SFM_HIP_TRY(up(b->d_grow_colmap, grow_colmap.data(), grow_colmap.size() * 4));
-    b->n_grow = (int)grow_id.size();
+  if (b->d_slab && !S.grow_hdr.empty()) {
+    SFM_HIP_TRY(up(b->d_grow_hdr, S.grow_hdr.data(), S.grow_hdr.size() * sizeof(int4)));
+    SFM_HIP_TRY(up(b->d_grow_head, S.grow_head.data(), S.grow_head.size() * sizeof(int4)));
+    SFM_HIP_TRY(up(b->d_grow_src, S.grow_over.data(), S.grow_over.size() * sizeof(int4)));
+    SFM_HIP_TRY(up(b->d_grow_colmap, S.grow_colmap.data(), S.grow_colmap.size() * 4));
+    b->n_grow = (int)S.grow_hdr.size();
   }
-  for (int c = 0; c < 8; ++c) SFM_HIP_TRY(up(b->d_chunk_ids[c], ids[c].data(), ids[c].size() * 4));
-  SFM_HIP_TRY(up(b->d_sig_cams, sig_cams.data(), sig_cams.size() * 4));
-  SFM_HIP_TRY(up(b->d_cptr, cptr.data(), cptr.size() * 4));
-  SFM_HIP_TRY(up(b->d_cpt, cpt.data(), cpt.size() * 4));
-  SFM_HIP_TRY(up(b->d_cxy, cxy.data(), cxy.size() * 8));
-  SFM_HIP_TRY(up(b->d_fb_points, fb.data(), fb.size() * 4));
-  SFM_HIP_TRY(up(b->d_pp_obase, pp_obase.data(), pp_obase.size() * 4));
-  SFM_HIP_TRY(up(b->d_cslot, cslot.data(), cslot.size() * sizeof(int2)));
-  SFM_HIP_TRY(up(b->d_pair_ptr, pair_ptr.data(), pair_ptr.size() * 4));
-  SFM_HIP_TRY(up(b->d_pair_cams, pair_cams.data(), pair_cams.size() * sizeof(int2)));
-  SFM_HIP_TRY(up(b->d_pair_ent, pair_ent.data(), pair_ent.size() * sizeof(int2)));
-  b->n_pairs_pp = (int)pair_cams.size();
+  for (int c = 0; c < 8; ++c) SFM_HIP_TRY(up(b->d_chunk_ids[c], S.ids[c].data(), S.ids[c].size() * 4));
+  SFM_HIP_TRY(up(b->d_sig_cams, S.sig_cams.data(), S.sig_cams.size() * 4));
+  SFM_HIP_TRY(up(b->d_cptr, S.cptr.data(), S.cptr.size() * 4));
+  SFM_HIP_TRY(up(b->d_cpt, S.cpt.data(), S.cpt.size() * 4));
+  SFM_HIP_TRY(up(b->d_cxy, S.cxy.data(), S.cxy.size() * 8));
+  SFM_HIP_TRY(up(b->d_fb_points, S.fb.data(), S.fb.size() * 4));
+  SFM_HIP_TRY(up(b->d_pp_obase, S.pp_obase.data(), S.pp_obase.size() * 4));
+  SFM_HIP_TRY(up(b->d_cslot, S.cslot.data(), S.cslot.size() * sizeof(int2)));
+  SFM_HIP_TRY(up(b->d_pair_ptr, S.pair_ptr.data(), S.pair_ptr.size() * 4));
+  SFM_HIP_TRY(up(b->d_pair_cams, S.pair_cams.data(), S.pair_cams.size() * sizeof(int2)));
+  SFM_HIP_TRY(up(b->d_pair_ent, S.pair_ent.data(), S.pair_ent.size() * sizeof(int2)));
+  b->n_pairs_pp = (int)S.pair_cams.size();
   lap_("uploads");
   const size_t sc_bytes = (sizeof(double) * (SC + 64 + RED2_N + 1) + 255) & ~(size_t)255, ring_bytes = sizeof(LmDev) * LM_RING;
   if (arena) {
@@ -6333,8 +5664,8 @@ extern "C" void sfmhip_ba_destroy(sfmhip_ba* b) {
   lap_("events");
   if (b->use_arena && b->ctx->ba_host_scratch) {  // (a one-shot problem: its large vectors go back to the context's)
     BaHostScratch* hs = (BaHostScratch*)b->ctx->ba_host_scratch;
-    hs->obs_src.swap(b->obs_src);
-    hs->cxy_src.swap(b->cxy_src);
+    hs->setup.obs_src.swap(b->obs_src);
+    hs->setup.cxy_src.swap(b->cxy_src);
     hs->h_pts_in.swap(b->h_pts_in);
   }
   delete b;
