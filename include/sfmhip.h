@@ -247,6 +247,41 @@ int sfmhip_score_homography(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets
                             const double* right_xy, const double* thresholds, double confidence, int max_iters,
                             int32_t* inliers, uint8_t* mask, int32_t* iterations);
 
+/* ---- the pose step of baseReconstruction: getCameraPose (reference src/Sfm.cpp:713-789) ----
+ * cv::recoverPose(E, p1, p2, R, t, focal, pp, mask) as OpenCV 3.4.1 (calib3d/five-point.cpp) runs it, with
+ * K = [f 0 ppx; 0 f ppy; 0 0 1] (the focal / principal-point overload: ONE focal for both axes):
+ *   1. x' = x * (1 / f) + (-ppx * (1 / f)), y' likewise with ppy and the same f (findEssentialMat's MatExpr route);
+ *   2. decomposeEssentialMat(E): SVD::compute (JacobiSVDImpl_<double> on E^T: the rotation rule, convergence test,
+ *      descending selection sort and 1 / sd scaling of U of the five-point and triangulation code), U and Vt negated
+ *      when their determinant is negative, W = [0 1 0; -1 0 0; 0 0 1], R1 = U W Vt, R2 = U W^T Vt, t = U.col(2).  A
+ *      singular value <= DBL_MIN sends the library to a random-vector branch (RNG(0x12345678)) that is NOT restated:
+ *      sfmhip_pose_last_flags reports it (bit 0) and that column of U is left zero;
+ *   3. per candidate P1 = [R1|t], P2 = [R2|t], P3 = [R1|-t], P4 = [R2|-t] and per point: Q = triangulatePoints([I|0], Pi,
+ *      x1', x2') (the 4 x 4 DLT of sfmhip_triangulate), ok = Q2 Q3 > 0, Q /= Q3 (row 3: Q3 / Q3), ok &= Q2 < dist,
+ *      z = Pi.row(2) Q summed in k order, ok &= z > 0 && z < dist (a comparison with a NaN is false);
+ *   4. mask_in (nullable) ANDed into all four masks (bitwise_and: the output byte is the input byte where the chosen
+ *      candidate passes, 255 where it passes without an input mask, 0 elsewhere);
+ *   5. good_i = countNonZero(mask_i); the first of good1, good2, good3 that is >= every other count picks (R1, t),
+ *      (R2, t), (R1, -t), else (R2, -t); n_good = its count, mask_out = its mask.
+ * distance_thresh: the library's default is 50.  Offsets / points as sfmhip_score_essential; E: 9 doubles per pair,
+ * row-major; R: 9 per pair, t: 3 per pair.  Parity UNPINNED like the score entries (OpenCV is not in the image). */
+int sfmhip_recover_pose(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, const double* left_xy,
+                        const double* right_xy, const double* E, double focal, double ppx, double ppy,
+                        double distance_thresh, const uint8_t* mask_in /* nullable */, double* R /* 9/pair */,
+                        double* t /* 3/pair */, int32_t* n_good, uint8_t* mask_out /* nullable */);
+/* getCameraPose's numerics for a batch: findEssentialMat(K, RANSAC, prob, threshold) exactly as sfmhip_score_essential
+ * (same inliers, same mask), then recoverPose(E, ..., fx, (cx, cy), mask) with the RANSAC mask as input and
+ * distance_thresh 50, E never leaving the device.  fy serves the RANSAC's normalisation only.  Pairs without a model
+ * (fewer than five matches, or no sample gave one): inliers 0, n_good -1, E / R / t zero, mask zero.  A pair of exactly
+ * five matches poses with the first model of its one sample.  CheckCoherentRotation is the caller's. */
+int sfmhip_essential_pose(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, const double* left_xy,
+                          const double* right_xy, double fx, double fy, double cx, double cy, double prob,
+                          double threshold, double* E, int32_t* inliers, double* R, double* t, int32_t* n_good,
+                          uint8_t* mask /* nullable: recoverPose's output mask */);
+/* OR over the decompositions of the last sfmhip_recover_pose / sfmhip_essential_pose call: bit 0 = a singular value of
+ * E was <= DBL_MIN (OpenCV's random-vector branch, not restated).  0 = every pair went the documented way. */
+int sfmhip_pose_last_flags(sfmhip_ctx* ctx);
+
 /* ---- adjustBundle solver core (reference src/BundleAdjustment.cpp:46-175) ---- */
 typedef struct {
   int max_iterations;           /* 500   src/BundleAdjustment.cpp:118 */

@@ -10,12 +10,12 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libsfmhip.so")
-# per-source floating-point contraction: the matcher's exact kernel and the triangulation restate
+# per-source floating-point contraction: the matcher's exact kernel, the triangulation and the pose step restate
 # OpenCV's operation order (no compiler-chosen FMAs); the BA kernels are tolerance-level f64
 # and want v_fma_f64 -- "fast-honor-pragmas", not "fast": the one function that must NOT contract, the trust-region decision
 # lm_decide (the same bits on the host and on the device), says so with a pragma, which plain "fast" ignores
 SOURCES = {"context.hip": "off", "match.hip": "off", "triangulate.hip": "off", "incremental.hip": "off",
-           "score.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
+           "score.hip": "off", "pose.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -108,14 +108,22 @@ def build_io_demo(force=False):
     return _build_host_exe(os.path.join(HERE, "sfm_io_selftest"), ("Sfm.cpp", "SfmIO.cpp", "BundleAdjustment.cpp", "io_selftest.cpp"), force)
 
 
-def _build_host_exe(exe, files, force):
+def build_pose_demo(force=False):
+    """The base reconstruction of the host mirror (baseReconstruction: findBestPair, getCameraPose over the map in one
+    sfmhip_essential_pose call, triangulateViews) followed by adjustCurrentBundle, on a directory of frames (needs the GPU)."""
+    return _build_host_exe(os.path.join(HERE, "sfm_pose_selftest"),
+                           ("Sfm.cpp", "SfmIO.cpp", "SfmPose.cpp", "BundleAdjustment.cpp", "pose_selftest.cpp"), force,
+                           std="c++17")  # (SfmPose.cpp includes ../pose.h, whose hypot restatement has hex float literals)
+
+
+def _build_host_exe(exe, files, force, std="c++14"):
     host = os.path.join(CSRC, "host")
     srcs = [os.path.join(host, f) for f in files]
-    deps = srcs + [os.path.join(host, f) for f in os.listdir(host) if f.endswith(".h")]
+    deps = srcs + [os.path.join(host, f) for f in os.listdir(host) if f.endswith(".h")] + [os.path.join(CSRC, "pose.h")]
     if not force and os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(s) for s in deps):
         return exe
     build()
-    cmd = ["g++", "-O2", "-std=c++14", "-pthread", "-I", os.path.join(HERE, "..", "include"), "-I", host, "-o", exe] + srcs + \
+    cmd = ["g++", "-O2", f"-std={std}", "-pthread", "-I", os.path.join(HERE, "..", "include"), "-I", host, "-o", exe] + srcs + \
           ["-L", HERE, "-lsfmhip", "-Wl,-rpath,$ORIGIN"]
     subprocess.check_call(cmd)
     return exe

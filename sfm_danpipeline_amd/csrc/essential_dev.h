@@ -1,0 +1,37 @@
+// essential_dev.h -- the RANSAC of sfmhip_score_essential (score.hip) as an internal routine whose results stay on the
+// device, so that the pose step (pose.hip, sfmhip_essential_pose) reads E and the inlier mask where they are.
+#pragma once
+#include <vector>
+#include "common.h"
+
+struct EssentialDev {
+  // every buffer below is freed with the object
+  std::vector<void*> bufs;
+  double* d_left = nullptr;   // the pixel coordinates as given: 2 doubles per match
+  double* d_right = nullptr;
+  double* d_p1 = nullptr;     // normalised with (fx, fy, cx, cy): findEssentialMat's points
+  double* d_p2 = nullptr;
+  double* d_bestE = nullptr;  // 9 per pair, row-major; zero where has[pair] == 0
+  int* d_off = nullptr;       // offsets (n_pairs + 1)
+  unsigned char* d_has = nullptr;   // per pair: 0 no model, 1 a RANSAC model, 2 exactly five matches
+  unsigned char* d_mask = nullptr;  // the RANSAC mask, 1 byte per match (want_mask only)
+  std::vector<unsigned char> has;
+  EssentialDev() = default;
+  EssentialDev(const EssentialDev&) = delete;
+  EssentialDev& operator=(const EssentialDev&) = delete;
+  ~EssentialDev() {
+    for (void* p : bufs) hipFree(p);
+  }
+  int alloc(void** p, size_t bytes) {
+    if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) return SFMHIP_ERR_ALLOC;
+    bufs.push_back(*p);
+    return SFMHIP_OK;
+  }
+};
+
+// findEssentialMat(left, right, K, RANSAC, prob, threshold) for a batch of pairs (arguments checked by the caller).
+// Fills inliers (and iterations when non-null) on the host, ctx->score_flags, and dev; the work is ordered on
+// ctx->stream and is complete when the call returns.
+int sfm_essential_ransac(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, const double* left_xy, const double* right_xy,
+                         double fx, double fy, double cx, double cy, double prob, double threshold, int32_t* inliers,
+                         int32_t* iterations, bool want_mask, EssentialDev& dev);

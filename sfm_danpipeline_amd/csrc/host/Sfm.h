@@ -1,7 +1,6 @@
 // Sfm.h -- the hot-path part of the reference's StructFromMotion (include/Sfm.h:15-35,89,
-// 107-117): same member names, same method signatures.  Everything above the hot path
-// (image loading, feature extraction, RANSAC pose, PMVS/PCL post-processing) is out of scope
-//  and is replaced by the loader methods at the bottom.
+// 107-117): same member names, same method signatures.  The PnP step (addMoreViews) and the
+// PMVS/PCL post-processing are out of scope.
 #pragma once
 #include <map>
 #include <set>
@@ -40,6 +39,15 @@ class StructFromMotion {
   std::vector<void*> devDescriptors;
   void releaseDeviceDescriptors();
   int uploadOrAdopt(sfmhip_imageset* set, int image);
+  // the pose step: one pair's sfmhip_essential_pose outcome, and the part of getCameraPose after it
+  struct PoseOutcome {
+    double E[9], R[9], T[3];
+    int32_t inliers, n_good;
+    std::vector<uint8_t> mask;
+  };
+  bool essentialPoses(const std::vector<Points2d>& left, const std::vector<Points2d>& right, std::vector<PoseOutcome>& out);
+  bool cameraPoseFrom(const int& idx_query, const int& idx_train, const Matching& matches, const Points2d& alignedLeft,
+                      const Points2d& alignedRight, const PoseOutcome* outcome, cv::Matx34d& Pleft, cv::Matx34d& Pright);
 
  public:
   std::vector<Point3D> nReconstructionCloud;
@@ -83,6 +91,44 @@ class StructFromMotion {
   // reference src/Sfm.cpp:883-888 is a stub whose call names a member that no longer exists;
   // wired here with imagesPts2D, the member of the required type
   void adjustCurrentBundle();
+
+  // ---- the pose step of baseReconstruction (csrc/host/SfmPose.cpp; sfmhip_essential_pose)
+  // reference include/Sfm.h:121, src/Sfm.cpp:408-492: findBestPair, then ONE sfmhip_essential_pose call over every entry
+  // of its map (each pair's outcome is independent of the others), then the map in ascending key order: the first pair
+  // whose pose passes is triangulated and seeds nReconstructionCloud, nCameraPoses, nDoneViews and nGoodViews.  Prints
+  // the reference's lines for the pairs it would have tried (not mirrored: the drawMatches / imshow / waitKey).
+  // DEVIATION: where RANSAC returns no model the reference throws inside decomposeEssentialMat; the mirror writes a line
+  // to stderr and goes on with the next pair.  Returns true, like the reference, once findBestPair's map is non-empty
+  // and the batched pose call ran; false when the map is empty or that call failed (a device error).
+  bool baseReconstruction();
+  // reference include/Sfm.h:168, src/Sfm.cpp:713-789: prunedMatchingWithHomography (printed only, SURVEY.md appendix B
+  // quirk 7), findEssentialMat(K, RANSAC, 0.999, 1.0) -> recoverPose(E, ..., fx, (cx, cy), mask) on the unpruned
+  // matches (sfmhip_essential_pose), CheckCoherentRotation; false when K is empty, 7 or fewer points are aligned, RANSAC
+  // finds no model (the deviation above) or the rotation check fails.  Pleft = [I|0], Pright = [R|T].  The pose comes
+  // from AlignedPointsFromMatch(left, right, matches); the pruning reads the member imagesPts2D, as the reference's reads
+  // imagesKeypoints.
+  bool getCameraPose(const Intrinsics& intrinsics, const int& idx_query, const int& idx_train, const Matching& matches,
+                     const Points2d& left, const Points2d& right, cv::Matx34d& Pleft, cv::Matx34d& Pright);
+  // reference include/Sfm.h:103, src/Sfm.cpp:791-799: fabsf(determinante(R)) - 1.0 > 1e-07 fails (fabsf narrows to float)
+  bool CheckCoherentRotation(cv::Mat& R);
+  // reference include/Sfm.h:133, src/Sfm.cpp:1119-1131: Eigen::FullPivLU(R).determinant() of a 3 x 3 CV_64F
+  double determinante(cv::Mat& relativeRotationCam);
+  // reference include/Sfm.h:90, src/Sfm.cpp:610-662: the inliers of cv::findHomography(RANSAC, 2.5) on the keypoints
+  // (sfmhip_score_homography, confidence 0.995, 2000 iterations); fewer than 4 matches: none
+  void prunedMatchingWithHomography(const int& idx_query, const int& idx_train, const Matching& goodMatches,
+                                    Matching* prunedMatch);
+  // what the last baseReconstruction chose (pose_selftest): the pair, E, R, T, recoverPose's count and mask
+  struct BasePose {
+    int query = -1, train = -1, n_good = 0;
+    double E[9] = {0}, R[9] = {0}, T[3] = {0};
+    std::vector<uint8_t> mask;
+  };
+  const BasePose& basePose() const { return lastBasePose; }
+
+ private:
+  BasePose lastBasePose;
+
+ public:
 
   // ---- detector / descriptor front end (csrc/host/SfmIO.cpp)
   // reference include/Sfm.h:85, src/Sfm.cpp:257-296: every gray image through getFeature (the imshow / waitKey(100) per

@@ -10,6 +10,7 @@
 
 #define CV_8U 0
 #define CV_32F 5
+#define CV_64F 6
 #define CV_8UC1 0
 #define CV_8UC3 16  /* CV_MAKETYPE(CV_8U, 3) */
 
@@ -64,7 +65,8 @@ struct Mat_ {
 };
 
 // descriptor matrix: rows = features, row-major contiguous, CV_32F (SIFT) or CV_8U (ORB/AKAZE);
-// also the 8-bit images of the loader (CV_8UC1 gray, CV_8UC3 BGR: interleaved channels)
+// also the 8-bit images of the loader (CV_8UC1 gray, CV_8UC3 BGR: interleaved channels) and the pose step's 3 x 3
+// CV_64F rotation (CheckCoherentRotation / determinante)
 struct Mat {
   int rows, cols, depth, ch;
   std::vector<unsigned char> bytes;
@@ -73,7 +75,8 @@ struct Mat {
     bytes.resize((size_t)r * c * elemSize());
     if (src && !bytes.empty()) std::memcpy(bytes.data(), src, bytes.size());
   }
-  size_t elemSize() const { return (depth == CV_32F ? 4 : 1) * (size_t)ch; }
+  size_t elemSize() const { return (depth == CV_64F ? 8 : depth == CV_32F ? 4 : 1) * (size_t)ch; }
+  template <typename T> T& at(int r, int c) { return ((T*)bytes.data())[(size_t)r * cols + c]; }
   int type() const { return depth | ((ch - 1) << 3); }
   int channels() const { return ch; }
   bool empty() const { return bytes.empty(); }

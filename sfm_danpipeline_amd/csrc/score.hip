@@ -18,6 +18,7 @@
 // checker (the CPU restatement of the same route: test infrastructure, never linked here); parity is unpinned (OpenCV is not in
 // the image).  sfmhip_score_last_flags reports samples that reached a corner of solvePoly that is not restated.
 #include "common.h"
+#include "essential_dev.h"
 #include "hypot_glibc.h"
 #include <algorithm>
 #include <cfloat>
@@ -886,15 +887,10 @@ __global__ void score_keep_best(const int2* __restrict__ upd, int n, const doubl
 
 }  // namespace
 
-extern "C" int sfmhip_score_essential(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, const double* left_xy,
-                                      const double* right_xy, double fx, double fy, double cx, double cy, double prob,
-                                      double threshold, int32_t* inliers, uint8_t* mask, int32_t* iterations) {
-  if (!ctx || n_pairs < 0 || !offsets || !inliers || !(prob > 0 && prob < 1)) return SFMHIP_ERR_ARG;
-  if (n_pairs == 0) return SFMHIP_OK;
+int sfm_essential_ransac(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, const double* left_xy, const double* right_xy,
+                         double fx, double fy, double cx, double cy, double prob, double threshold, int32_t* inliers,
+                         int32_t* iterations, bool want_mask, EssentialDev& dev) {
   const long long total = offsets[n_pairs];
-  if (total < 0 || (total > 0 && (!left_xy || !right_xy))) return SFMHIP_ERR_ARG;
-  for (int p = 0; p < n_pairs; ++p)
-    if (offsets[p + 1] < offsets[p]) return SFMHIP_ERR_ARG;
   SFM_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   constexpr int MAX_ITERS = 1000, MODEL_POINTS = 5;
@@ -904,7 +900,7 @@ extern "C" int sfmhip_score_essential(sfmhip_ctx* ctx, int n_pairs, const int32_
   int flags_any = 0;
   ctx->score_flags = 0;
 
-  struct Bufs {
+  struct Bufs {  // the loop's scratch (what the caller reads lives in dev)
     std::vector<void*> v;
     ~Bufs() {
       for (void* p : v) hipFree(p);
@@ -915,17 +911,18 @@ extern "C" int sfmhip_score_essential(sfmhip_ctx* ctx, int n_pairs, const int32_
     bufs.v.push_back(*p);
     return SFMHIP_OK;
   };
-  double *d_raw = nullptr, *d_p1 = nullptr, *d_p2 = nullptr;
-  SFM_TRY(dalloc((void**)&d_raw, sizeof(double) * 2 * (size_t)std::max<long long>(total, 1)));
-  SFM_TRY(dalloc((void**)&d_p1, sizeof(double) * 2 * (size_t)std::max<long long>(total, 1)));
-  SFM_TRY(dalloc((void**)&d_p2, sizeof(double) * 2 * (size_t)std::max<long long>(total, 1)));
+  const size_t pts_bytes = sizeof(double) * 2 * (size_t)std::max<long long>(total, 1);
+  SFM_TRY(dev.alloc((void**)&dev.d_left, pts_bytes));
+  SFM_TRY(dev.alloc((void**)&dev.d_right, pts_bytes));
+  SFM_TRY(dev.alloc((void**)&dev.d_p1, pts_bytes));
+  SFM_TRY(dev.alloc((void**)&dev.d_p2, pts_bytes));
+  double *d_p1 = dev.d_p1, *d_p2 = dev.d_p2;
   if (total > 0) {
     const int nb = (int)((2 * total + 255) / 256);
-    SFM_HIP_TRY(hipMemcpyAsync(d_raw, left_xy, sizeof(double) * 2 * total, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(score_normalize, dim3(nb), dim3(256), 0, st, d_raw, d_p1, 2 * total, ax, bx, ay, by);
-    SFM_HIP_TRY(hipStreamSynchronize(st));  // (d_raw is reused)
-    SFM_HIP_TRY(hipMemcpyAsync(d_raw, right_xy, sizeof(double) * 2 * total, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(score_normalize, dim3(nb), dim3(256), 0, st, d_raw, d_p2, 2 * total, ax, bx, ay, by);
+    SFM_HIP_TRY(hipMemcpyAsync(dev.d_left, left_xy, sizeof(double) * 2 * total, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(score_normalize, dim3(nb), dim3(256), 0, st, dev.d_left, d_p1, 2 * total, ax, bx, ay, by);
+    SFM_HIP_TRY(hipMemcpyAsync(dev.d_right, right_xy, sizeof(double) * 2 * total, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(score_normalize, dim3(nb), dim3(256), 0, st, dev.d_right, d_p2, 2 * total, ax, bx, ay, by);
   }
   // per pair: the state of ptsetreg's loop
   struct PairState {
@@ -938,7 +935,8 @@ extern "C" int sfmhip_score_essential(sfmhip_ctx* ctx, int n_pairs, const int32_
   double* d_bestE = nullptr;
   int2* d_upd = nullptr;
   std::vector<int2> upd;
-  SFM_TRY(dalloc((void**)&d_bestE, sizeof(double) * 9 * n_pairs));
+  SFM_TRY(dev.alloc((void**)&d_bestE, sizeof(double) * 9 * n_pairs));
+  dev.d_bestE = d_bestE;
   SFM_TRY(dalloc((void**)&d_upd, sizeof(int2) * n_pairs));
   SFM_HIP_TRY(hipMemsetAsync(d_bestE, 0, sizeof(double) * 9 * n_pairs, st));
   for (int p = 0; p < n_pairs; ++p) {
@@ -1054,19 +1052,39 @@ extern "C" int sfmhip_score_essential(sfmhip_ctx* ctx, int n_pairs, const int32_
     if (iterations) iterations[p] = ps[p].iter;
   }
   ctx->score_flags = flags_any;
-  if (mask && total > 0) {
-    int* d_off = nullptr;
-    unsigned char *d_has = nullptr, *d_mask = nullptr;
-    SFM_TRY(dalloc((void**)&d_off, sizeof(int) * (n_pairs + 1)));
-    SFM_TRY(dalloc((void**)&d_has, n_pairs));
-    SFM_TRY(dalloc((void**)&d_mask, (size_t)total));
-    SFM_HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int) * (n_pairs + 1), hipMemcpyHostToDevice, st));
-    SFM_HIP_TRY(hipMemcpyAsync(d_has, has.data(), n_pairs, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(score_mask, dim3(n_pairs), dim3(256), 0, st, d_off, d_p1, d_p2, d_bestE, d_has, t, d_mask);
-    SFM_HIP_TRY(hipGetLastError());
-    SFM_HIP_TRY(hipMemcpyAsync(mask, d_mask, (size_t)total, hipMemcpyDeviceToHost, st));
+  dev.has = has;
+  if (want_mask) {
+    SFM_TRY(dev.alloc((void**)&dev.d_off, sizeof(int) * (n_pairs + 1)));
+    SFM_TRY(dev.alloc((void**)&dev.d_has, n_pairs));
+    SFM_TRY(dev.alloc((void**)&dev.d_mask, (size_t)std::max<long long>(total, 1)));
+    SFM_HIP_TRY(hipMemcpyAsync(dev.d_off, offsets, sizeof(int) * (n_pairs + 1), hipMemcpyHostToDevice, st));
+    SFM_HIP_TRY(hipMemcpyAsync(dev.d_has, has.data(), n_pairs, hipMemcpyHostToDevice, st));
+    if (total > 0) {
+      hipLaunchKernelGGL(score_mask, dim3(n_pairs), dim3(256), 0, st, dev.d_off, d_p1, d_p2, d_bestE, dev.d_has, t, dev.d_mask);
+      SFM_HIP_TRY(hipGetLastError());
+    }
   }
   SFM_HIP_TRY(hipStreamSynchronize(st));
+  return SFMHIP_OK;
+}
+
+extern "C" int sfmhip_score_essential(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, const double* left_xy,
+                                      const double* right_xy, double fx, double fy, double cx, double cy, double prob,
+                                      double threshold, int32_t* inliers, uint8_t* mask, int32_t* iterations) {
+  if (!ctx || n_pairs < 0 || !offsets || !inliers || !(prob > 0 && prob < 1)) return SFMHIP_ERR_ARG;
+  if (n_pairs == 0) return SFMHIP_OK;
+  const long long total = offsets[n_pairs];
+  if (total < 0 || (total > 0 && (!left_xy || !right_xy))) return SFMHIP_ERR_ARG;
+  for (int p = 0; p < n_pairs; ++p)
+    if (offsets[p + 1] < offsets[p]) return SFMHIP_ERR_ARG;
+  EssentialDev dev;
+  const bool want_mask = mask && total > 0;
+  SFM_TRY(sfm_essential_ransac(ctx, n_pairs, offsets, left_xy, right_xy, fx, fy, cx, cy, prob, threshold, inliers, iterations,
+                               want_mask, dev));
+  if (want_mask) {
+    SFM_HIP_TRY(hipMemcpyAsync(mask, dev.d_mask, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    SFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
   return SFMHIP_OK;
 }
 

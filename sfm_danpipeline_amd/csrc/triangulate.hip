@@ -8,10 +8,12 @@
 // HBM-bound by construction (2 x 16 B in, 24 B + 1 B (+8 B) out per match); the track /
 // visibility bookkeeping (Point3D::idxImage, src/Sfm.cpp:862-873) is the host mirror's job.
 #include "common.h"
-#include "hypot_glibc.h"
+#include "pose.h"
 #include <float.h>
 
 namespace {
+
+using sfmpose::dlt_null_vector;  // (pose.h: shared with the pose kernels and the CPU test stub)
 
 struct TriParams {
   double P1[12], P2[12], K[9], dist[5];
@@ -52,99 +54,6 @@ __device__ __forceinline__ void project_point(const double* P, const TriParams& 
   const double yd = y * cdist + p1 * a3 + p2 * a1;
   u = xd * p.K[0] + p.K[2];
   v = yd * p.K[4] + p.K[5];
-}
-
-// One-sided Jacobi on At (rows = columns of A), as OpenCV's JacobiSVDImpl_<double> runs it for a
-// 4x4: rotations until every row pair is orthogonal to 10*eps, singular values = row norms,
-// selection sort descending; returns Vt row 3.  All indices are compile-time so the 32 doubles
-// stay in registers.
-__device__ __forceinline__ void dlt_null_vector(double At[4][4], double out[4]) {
-  const double eps = DBL_EPSILON * 10;
-  double W[4], Vt[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    double sd = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sd += At[i][k] * At[i][k];
-    W[i] = sd;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) Vt[i][k] = (i == k) ? 1.0 : 0.0;
-  }
-#pragma unroll 1
-  for (int iter = 0; iter < 30; ++iter) {
-    bool changed = false;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = i + 1; j < 4; ++j) {
-        double a = W[i], p = 0, b = W[j];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) p += At[i][k] * At[j][k];
-        if (fabs(p) <= eps * sqrt(a * b)) continue;
-        p *= 2;
-        const double beta = a - b, gamma = sfm_hypot(p, beta);  // (the host libm's hypot, bit for bit: hypot_glibc.h)
-        double c, s;
-        if (beta < 0) {
-          const double delta = (gamma - beta) * 0.5;
-          s = sqrt(delta / gamma);
-          c = p / (gamma * s * 2);
-        } else {
-          c = sqrt((gamma + beta) / (gamma * 2));
-          s = p / (gamma * c * 2);
-        }
-        a = b = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const double t0 = c * At[i][k] + s * At[j][k];
-          const double t1 = -s * At[i][k] + c * At[j][k];
-          At[i][k] = t0;
-          At[j][k] = t1;
-          a += t0 * t0;
-          b += t1 * t1;
-        }
-        W[i] = a;
-        W[j] = b;
-        changed = true;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const double t0 = c * Vt[i][k] + s * Vt[j][k];
-          const double t1 = -s * Vt[i][k] + c * Vt[j][k];
-          Vt[i][k] = t0;
-          Vt[j][k] = t1;
-        }
-      }
-    if (!__any(changed)) break;  // wave-uniform exit; converged lanes see no further rotation
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    double sd = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sd += At[i][k] * At[i][k];
-    W[i] = sqrt(sd);
-  }
-  // row of the smallest singular value under OpenCV's descending selection sort = the LAST
-  // position; among equal values the sort keeps the earlier row earlier, so take the last
-  // index attaining the minimum... except that selection sort swaps can reorder equal values;
-  // replay the sort on (W, row id) to land on exactly the row OpenCV leaves in position 3.
-  int id[4] = {0, 1, 2, 3};
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    int j = i;
-#pragma unroll
-    for (int k = i + 1; k < 4; ++k)
-      if (W[j] < W[k]) j = k;
-    if (i != j) {
-      const double tw = W[i];
-      W[i] = W[j];
-      W[j] = tw;
-      const int ti = id[i];
-      id[i] = id[j];
-      id[j] = ti;
-    }
-  }
-  const int sel = id[3];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) out[k] = sel == 0 ? Vt[0][k] : sel == 1 ? Vt[1][k] : sel == 2 ? Vt[2][k] : Vt[3][k];
 }
 
 __global__ __launch_bounds__(256) void triangulate_kernel(TriParams p, const double2* __restrict__ xy1,

@@ -1,0 +1,290 @@
+"""GPU: the pose step of baseReconstruction (getCameraPose, reference src/Sfm.cpp:713-789) -- sfmhip_recover_pose bit for
+bit against the CPU build of the same header (tests/stub/pose_capi.cpp over csrc/pose.h), sfmhip_essential_pose against
+the oracle's findEssentialMat and that stub, the RANSAC it shares with sfmhip_score_essential, batch independence, and
+the host mirror's baseReconstruction on the temple sequence (BASELINE.json configs[0]).  PARITY UNPINNED: OpenCV is not
+in the image (include/sfmhip.h)."""
+import ctypes as C
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from sfm_danpipeline_amd import build, pose, scoring, synth
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+STUB = os.path.join(HERE, "stub", "pose_capi.cpp")
+TEMPLE = os.path.join(HERE, "golden", "temple")
+XML = os.path.join(TEMPLE, "camera_calibration_template.xml")
+K = np.array([[1520.0, 0, 302.2], [0, 1490.0, 246.87], [0, 0, 1]])   # fx != fy: recoverPose takes fx for both axes
+
+
+@pytest.fixture(scope="module")
+def pc(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("pose") / "libposecapi.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, STUB])
+    lib = C.CDLL(so)
+    vp = C.c_void_p
+    lib.pose_recover.argtypes = [C.c_int, vp, vp, vp] + [C.c_double] * 4 + [vp] * 6
+    lib.pose_check_rotation.argtypes = [vp]
+    return lib
+
+
+def stub_recover(pc, a, b, E, f, ppx, ppy, mask=None, dist=50.0):
+    a = np.ascontiguousarray(a, np.float64).reshape(-1, 2)
+    b = np.ascontiguousarray(b, np.float64).reshape(-1, 2)
+    E = np.ascontiguousarray(E, np.float64)
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+    R, t, out = np.zeros(9), np.zeros(3), np.zeros(max(len(a), 1), np.uint8)
+    ng, cnt, fl = C.c_int32(0), np.zeros(4, np.int32), C.c_int32(0)
+    pc.pose_recover(len(a), a.ctypes.data, b.ctypes.data, E.ctypes.data, f, ppx, ppy, dist, m.ctypes.data if m is not None else None,
+                    R.ctypes.data, t.ctypes.data, C.byref(ng), out.ctypes.data, cnt.ctypes.data, C.byref(fl))
+    return R.reshape(3, 3), t, ng.value, out[:len(a)]
+
+
+def _essential(R, t):
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    E = tx @ R
+    return E / np.linalg.norm(E)
+
+
+def _scene(m, seed, outliers=0.1, noise=0.3):
+    sc = synth.two_view_scene(m=max(m, 1), seed=seed, K=K, noise_px=noise, outlier_frac=outliers)
+    return sc["xy1"][:m], sc["xy2"][:m], _essential(sc["P2"][:, :3], sc["P2"][:, 3])
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, np.float64).view(np.uint64)
+
+
+@pytest.mark.parametrize("with_mask", [False, True])
+def test_recover_pose_equals_the_stub_bit_for_bit(ctx, pc, with_mask):
+    sizes = [0, 1, 7, 300, 2000, 5000, 257]                     # (several tiles of 256 matches; an empty pair)
+    pairs, Es, masks = [], [], []
+    rng = np.random.default_rng(4)
+    for i, m in enumerate(sizes):
+        a, b, E = _scene(m, 31 + i)
+        E = E + rng.normal(0, 1e-4, (3, 3)) * (i % 2)          # (odd pairs: a noisy E)
+        pairs.append((a, b))
+        Es.append(E)
+        masks.append((rng.random(m) < 0.85).astype(np.uint8))
+    R, t, ng, out = pose.recover_pose(pairs, np.array(Es), K[0, 0], (K[0, 2], K[1, 2]), masks=masks if with_mask else None, ctx=ctx)
+    assert pose.last_flags(ctx) == 0
+    for i, (a, b) in enumerate(pairs):
+        sR, st, sng, sout = stub_recover(pc, a, b, Es[i], K[0, 0], K[0, 2], K[1, 2], mask=masks[i] if with_mask else None)
+        assert np.array_equal(_bits(R[i]), _bits(sR)) and np.array_equal(_bits(t[i]), _bits(st)), i
+        assert int(ng[i]) == sng and np.array_equal(out[i], sout), (i, int(ng[i]), sng)
+        if sizes[i] >= 300:
+            assert sng > 0.5 * sizes[i]
+
+
+def test_recover_pose_argument_checks(ctx):
+    from sfm_danpipeline_amd._lib import lib
+    L = lib()
+    off = np.array([0, 3, 2], np.int32)
+    xy = np.zeros((3, 2))
+    E = np.zeros((2, 9))
+    R, t, ng = np.zeros(18), np.zeros(6), np.zeros(2, np.int32)
+    assert L.sfmhip_recover_pose(ctx.h, 2, off.ctypes.data, xy.ctypes.data, xy.ctypes.data, E.ctypes.data, 1.0, 0.0, 0.0, 50.0, None,
+                                 R.ctypes.data, t.ctypes.data, ng.ctypes.data, None) == -3          # decreasing offsets
+    assert L.sfmhip_recover_pose(ctx.h, 0, off.ctypes.data, None, None, E.ctypes.data, 1.0, 0.0, 0.0, 50.0, None, R.ctypes.data,
+                                 t.ctypes.data, ng.ctypes.data, None) == 0                          # no pairs: a no-op
+    off = np.array([0, 3], np.int32)
+    for prob in (0.0, 1.0):
+        assert L.sfmhip_essential_pose(ctx.h, 1, off.ctypes.data, xy.ctypes.data, xy.ctypes.data, 1.0, 1.0, 0.0, 0.0, prob, 1.0,
+                                       E.ctypes.data, ng.ctypes.data, R.ctypes.data, t.ctypes.data, ng.ctypes.data, None) == -3
+    assert L.sfmhip_essential_pose(ctx.h, 1, off.ctypes.data, None, None, 1.0, 1.0, 0.0, 0.0, 0.999, 1.0, E.ctypes.data,
+                                   ng.ctypes.data, R.ctypes.data, t.ctypes.data, ng.ctypes.data, None) == -3
+
+
+def _pairs_for_essential():
+    return [_scene(500, 99), _scene(150, 3, outliers=0.3), _scene(2000, 7, outliers=0.5, noise=0.5), _scene(121, 11, outliers=0.0),
+            _scene(40, 5), _scene(777, 21, outliers=0.7), _scene(4, 8), _scene(0, 9), _scene(5, 12), _scene(1200, 17)]
+
+
+def test_essential_pose_against_the_oracle_and_the_stub(ctx, pc, orc):
+    pairs = [(a, b) for a, b, _ in _pairs_for_essential()]
+    r = pose.essential_pose(pairs, K, ctx=ctx)
+    assert pose.last_flags(ctx) == 0
+    for i, (a, b) in enumerate(pairs):
+        cnt, mask, E, it, fl = orc.find_essential_mat(a, b, K)
+        assert fl == 0 and int(r["inliers"][i]) == cnt, i
+        if len(a) < 5 or E is None:
+            assert r["n_good"][i] == -1 and not r["E"][i].any() and not r["R"][i].any() and not r["t"][i].any(), i
+            assert not r["masks"][i].any()
+            continue
+        assert np.array_equal(_bits(r["E"][i]), _bits(E)), i                    # findEssentialMat's E, bit for bit
+        sR, st, sng, sout = stub_recover(pc, a, b, E, K[0, 0], K[0, 2], K[1, 2], mask=mask)
+        assert np.array_equal(_bits(r["R"][i]), _bits(sR)) and np.array_equal(_bits(r["t"][i]), _bits(st)), i
+        assert int(r["n_good"][i]) == sng and np.array_equal(r["masks"][i], sout), i
+        assert not (r["masks"][i] & ~mask).any()                                # (a subset of the RANSAC inliers)
+
+
+def test_shared_ransac_with_score_essential(ctx):
+    """essential_pose's RANSAC half is score_essential's: the same inliers, and its mask -- fed with essential_pose's E to
+    the explicit-E entry -- gives essential_pose's R, t, count and mask bit for bit.  The mask bytes show the RANSAC mask
+    itself wherever the chosen candidate passes (bitwise_and: the input byte there); where no candidate passes, the
+    RANSAC masks are compared through the oracle in test_essential_pose_against_the_oracle_and_the_stub."""
+    pairs = [(a, b) for a, b, _ in _pairs_for_essential()]
+    inl, masks, _ = scoring.score_essential(pairs, K, want_mask=True, ctx=ctx)
+    r = pose.essential_pose(pairs, K, ctx=ctx)
+    assert np.array_equal(inl, r["inliers"])
+    live = [i for i in range(len(pairs)) if r["n_good"][i] >= 0]
+    R, t, ng, out = pose.recover_pose([pairs[i] for i in live], r["E"][live], K[0, 0], (K[0, 2], K[1, 2]),
+                                      masks=[masks[i] for i in live], ctx=ctx)
+    R1, t1, ng1, out1 = pose.recover_pose([pairs[i] for i in live], r["E"][live], K[0, 0], (K[0, 2], K[1, 2]), ctx=ctx)
+    for k, i in enumerate(live):
+        assert np.array_equal(_bits(R[k]), _bits(r["R"][i])) and np.array_equal(_bits(t[k]), _bits(r["t"][i])), i
+        assert int(ng[k]) == int(r["n_good"][i]) and np.array_equal(out[k], r["masks"][i]), i
+        if np.array_equal(_bits(R1[k]), _bits(R[k])) and np.array_equal(_bits(t1[k]), _bits(t[k])):
+            passes = out1[k] != 0                                      # the same candidate, unmasked: where it passes,
+            assert np.array_equal(r["masks"][i][passes], masks[i][passes]), i   # the output byte IS the RANSAC mask's
+    for i in range(len(pairs)):
+        if r["n_good"][i] < 0:
+            assert not masks[i].any() and not r["masks"][i].any(), i
+
+
+def test_get_camera_pose_uses_its_own_points(ctx, pc, orc, tmp_path):
+    """getCameraPose(K, q, t, matches, left, right) poses AlignedPointsFromMatch(left, right, matches), not the member
+    imagesPts2D (which only the homography pruning reads): the C++ mirror and pose.get_camera_pose against the stub's
+    recoverPose on the oracle's E and mask of the caller's points"""
+    a, b, _ = _scene(600, 55)
+    qa, qb, _ = _scene(600, 56, outliers=0.3)                    # what the members hold: another scene
+    Kc = np.array([[1520.0, 0, 302.2], [0, 1520.0, 246.87], [0, 0, 1]])   # (the calibration file's K)
+    cnt, mask, E, _, fl = orc.find_essential_mat(a, b, Kc)
+    assert fl == 0 and E is not None
+    sR, st, sng, sout = stub_recover(pc, a, b, E, Kc[0, 0], Kc[0, 2], Kc[1, 2], mask=mask)
+    assert pc.pose_check_rotation(np.ascontiguousarray(sR).ctypes.data)
+    with open(tmp_path / "in.bin", "wb") as f:
+        f.write(np.array([600], np.int32).tobytes())
+        for x in (a, b, qa, qb):
+            f.write(np.ascontiguousarray(x, np.float64).tobytes())
+    exe = build.build_pose_demo()
+    r = subprocess.run([exe, "--get-camera-pose", XML, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    raw = open(tmp_path / "out.bin", "rb").read()
+    ok = struct.unpack_from("<i", raw)[0]
+    Pl, Pr = np.frombuffer(raw, "<f8", 12, 4).reshape(3, 4), np.frombuffer(raw, "<f8", 12, 100).reshape(3, 4)
+    assert ok == 1 and len(raw) == 4 + 192
+    want = np.hstack([sR, st[:, None]])
+    assert np.array_equal(_bits(Pr), _bits(want)) and np.array_equal(Pl, np.hstack([np.eye(3), np.zeros((3, 1))]))
+    assert "aligned: 600 and 600" in r.stdout and "Pright:" in r.stdout
+    g = pose.get_camera_pose(Kc, a, b, ctx=ctx)
+    assert g is not None and np.array_equal(_bits(g["Pright"]), _bits(want)) and g["n_good"] == sng
+    assert np.array_equal(_bits(g["E"]), _bits(E)) and g["inliers"] == cnt and np.array_equal(g["mask"], sout)
+
+
+def test_batch_independence(ctx):
+    rng = np.random.default_rng(77)
+    pairs = []
+    for p in range(1225):
+        m = int(rng.integers(1800, 2200))
+        a, b, _ = _scene(m, 1000 + p, outliers=float(rng.uniform(0.05, 0.5)))
+        pairs.append((a, b))
+    r = pose.essential_pose(pairs, K, ctx=ctx)
+    assert (r["n_good"] > 0).all()
+    for p in list(range(0, 1225, 7)) + [1224]:
+        s = pose.essential_pose([pairs[p]], K, ctx=ctx)
+        assert int(s["inliers"][0]) == int(r["inliers"][p]) and int(s["n_good"][0]) == int(r["n_good"][p]), p
+        for k in ("E", "R", "t"):
+            assert np.array_equal(_bits(s[k][0]), _bits(r[k][p])), (p, k)
+        assert np.array_equal(s["masks"][0], r["masks"][p]), p
+
+
+# ---------------------------------------------------------------- cfg1: the temple sequence through baseReconstruction
+class _Reader:
+    def __init__(self, raw):
+        self.raw, self.pos = raw, 0
+
+    def i32(self, n=1):
+        v = struct.unpack_from("<%di" % n, self.raw, self.pos)
+        self.pos += 4 * n
+        return v[0] if n == 1 else v
+
+    def arr(self, dtype, count):
+        dt = np.dtype(dtype)
+        a = np.frombuffer(self.raw, dt, count, self.pos)
+        self.pos += dt.itemsize * count
+        return a
+
+
+def _cfg1_front(tmp_path):
+    """features, matches and findBestPair's map of the temple run (io_selftest --cfg1)"""
+    exe = build.build_io_demo()
+    r = subprocess.run([exe, "--cfg1", TEMPLE, XML, str(tmp_path / "front.bin")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rd = _Reader(open(tmp_path / "front.bin", "rb").read())
+    n = rd.i32()
+    pts = []
+    for _ in range(n):
+        nk = rd.i32()
+        pts.append(rd.arr("<f4", 6 * nk).reshape(nk, 6)[:, :2].astype(np.float64))
+        rd.arr("<f4", 128 * nk)
+    Kf = rd.arr("<f8", 9).reshape(3, 3)
+    rd.arr("<f8", 5)
+    matches = {}
+    for _ in range(rd.i32()):
+        q, t, nm = rd.i32(3)
+        matches[(q, t)] = rd.arr(np.dtype([("q", "<i4"), ("t", "<i4"), ("d", "<f4")]), nm)
+    nmap = rd.i32()
+    mp = [(float(k), (int(q), int(t))) for k, q, t in rd.arr(np.dtype([("k", "<f4"), ("q", "<i4"), ("t", "<i4")]), nmap)]
+    return pts, Kf, matches, mp
+
+
+def test_cfg1_temple_base_reconstruction(tmp_path, pc, orc):
+    pts, Kf, matches, mp = _cfg1_front(tmp_path)
+    exe = build.build_pose_demo()
+    r = subprocess.run([exe, TEMPLE, XML, str(tmp_path / "pose.bin")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rd = _Reader(open(tmp_path / "pose.bin", "rb").read())
+    q, t = rd.i32(2)
+    # the pair the reference settles on: the first map entry whose pose (stub recoverPose on the oracle's E and mask,
+    # fx for both axes) passes CheckCoherentRotation
+    want, tried = None, 0
+    for _, (pq, pt) in mp:
+        tried += 1
+        m = matches[(pq, pt)]
+        a, b = pts[pq][m["q"]], pts[pt][m["t"]]
+        cnt, mask, E, _, fl = orc.find_essential_mat(a, b, Kf)
+        assert fl == 0
+        if E is None or len(a) <= 7:
+            continue
+        sR, st, sng, sout = stub_recover(pc, a, b, E, Kf[0, 0], Kf[0, 2], Kf[1, 2], mask=mask)
+        if pc.pose_check_rotation(np.ascontiguousarray(sR).ctypes.data):
+            want = dict(pair=(pq, pt), E=E, R=sR, t=st, n_good=sng, mask=sout, a=a, b=b, m=m)
+            break
+    assert want is not None and (q, t) == want["pair"], ((q, t), mp[:3])
+    n_good = rd.i32()
+    E, R, T = rd.arr("<f8", 9).reshape(3, 3), rd.arr("<f8", 9).reshape(3, 3), rd.arr("<f8", 3)
+    mask = rd.arr(np.uint8, rd.i32())
+    Pq, Pt = rd.arr("<f8", 12).reshape(3, 4), rd.arr("<f8", 12).reshape(3, 4)
+    assert np.array_equal(_bits(E), _bits(want["E"])) and np.array_equal(_bits(R), _bits(want["R"]))
+    assert np.array_equal(_bits(T), _bits(want["t"])) and n_good == want["n_good"] and np.array_equal(mask, want["mask"])
+    Pright = np.hstack([want["R"], want["t"][:, None]])
+    Pleft = np.hstack([np.eye(3), np.zeros((3, 1))])
+    assert np.array_equal(_bits(Pt), _bits(Pright)) and np.array_equal(Pq, Pleft)
+    nc = rd.i32()
+    cloud = rd.arr(np.dtype([("X", "<f8", 3), ("q", "<i4"), ("t", "<i4")]), nc)
+    Xo, _, keepo = orc.triangulate(Pleft, Pright, Kf, np.zeros(5), want["a"], want["b"])
+    kept = np.nonzero(keepo)[0]
+    assert nc == len(kept) >= 50
+    assert np.array_equal(cloud["q"], want["m"]["q"][kept]) and np.array_equal(cloud["t"], want["m"]["t"][kept])
+    assert np.array_equal(cloud["X"].view(np.uint64), np.ascontiguousarray(Xo[kept]).view(np.uint64))
+    rd.arr("<f8", 9 + 24 + 3 * nc)                                  # (after adjustCurrentBundle: K, the two poses, the cloud)
+    assert rd.pos == len(rd.raw)
+    # the reference's lines, for the pairs it would have tried
+    out = r.stdout
+    assert out.count("Best pair:") == tried and out.count("Estimating camera pose with Essential Matrix...") == tried
+    assert out.count("pruned matches:") == tried and out.count("Essential matrix:") == tried
+    assert out.count("\nR:\n") == tried and out.count("\nT:\n") == tried and out.count("Pright:") == 1
+    assert f"Best pair:[{q},{t}] has:{len(want['m'])} matches" in out
+    assert out.count(f"Showing matches between image:{q} and image:{t}") == 1
+    # the Python mirror on the same front end settles on the same pair, pose and cloud
+    pyr = pose.base_reconstruction(mp, pts, {k: (v["q"], v["t"]) for k, v in matches.items()}, Kf)
+    assert pyr is not None and pyr["pair"] == (q, t)
+    assert np.array_equal(_bits(pyr["pose"]["Pright"]), _bits(Pright)) and pyr["pose"]["n_good"] == want["n_good"]
+    assert len(pyr["cloud"]) == nc
+    assert np.array_equal(np.array([p["pt"] for p in pyr["cloud"]]).view(np.uint64), cloud["X"].view(np.uint64))
