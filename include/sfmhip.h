@@ -282,6 +282,37 @@ int sfmhip_essential_pose(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, 
  * E was <= DBL_MIN (OpenCV's random-vector branch, not restated).  0 = every pair went the documented way. */
 int sfmhip_pose_last_flags(sfmhip_ctx* ctx);
 
+/* ---- map3D step 10: the dense cloud's filters and normals (reference src/Sfm.cpp:94-102, bodies :1323-1383) ----
+ * PCL 1.8.1's PassThrough, RadiusOutlierRemoval and NormalEstimation (k nearest) on a device-resident cloud: the points
+ * are uploaded once by sfmhip_cloud_create and every call below reuses them and the spatial grid built for them (one
+ * grid per radius last used, one k-NN grid).  The rules (parity UNPINNED, PCL is not in the image):
+ *   - a point with a non-finite coordinate is dropped by both filters, is nobody's neighbour, and has -1 / +inf k-NN
+ *     entries and a NaN normal and curvature;
+ *   - d2 = ((dx*dx) + dy*dy) + dz*dz in float (FLANN L2_Simple); the radius test is d2 < (float)(r * r), r squared in
+ *     double; the count includes the point itself and its duplicates;
+ *   - k-NN lists are sorted by (d2, index) and include the point itself; k > the finite count pads with -1 / +inf;
+ *   - normals: PCL's float covariance of the k nearest (9 sums in list order, divided by the count), pcl::eigen33 (its
+ *     trigonometric roots, with atan2 / cos / sin restated from + - * / sqrt), curvature |lambda0 / trace| (0 for a zero
+ *     trace), then flipped iff (vp - p) . n < 0; fewer than 3 neighbours: NaN.  Every NaN written is 0x7FC00000.
+ * Index outputs are input indices in input order; idx_out holds up to n entries.  A handle belongs to its context and
+ * is not thread-safe; several handles may live on one context. */
+typedef struct sfmhip_cloud sfmhip_cloud;
+int sfmhip_cloud_create(sfmhip_ctx* ctx, int n, const float* xyz /* 3 n */, sfmhip_cloud** out);
+void sfmhip_cloud_destroy(sfmhip_cloud* cloud);
+/* PassThrough on field `axis` (0 x, 1 y, 2 z) with float limits, inclusive: kept iff lo <= v <= hi (negative != 0: iff
+ * not); non-finite points are never kept.  *n_out = the kept count. */
+int sfmhip_cloud_passthrough(sfmhip_cloud* cloud, int axis, float lo, float hi, int negative, int32_t* idx_out,
+                             int32_t* n_out);
+/* per point: the number of finite points with d2 < (float)(radius * radius), itself included; cap > 0 reports
+ * min(count, cap) (and lets the kernel stop early), cap <= 0 the exact count.  Non-finite points: 0. */
+int sfmhip_cloud_radius_count(sfmhip_cloud* cloud, double radius, int cap, int32_t* counts /* n */);
+/* RadiusOutlierRemoval: kept iff the count above is > min_pts (a count <= min_pts is an outlier). */
+int sfmhip_cloud_radius_outlier(sfmhip_cloud* cloud, double radius, int min_pts, int32_t* idx_out, int32_t* n_out);
+/* the k (1..32) nearest finite points of every point, (d2, index) order: idx / d2 are n x k, row-major. */
+int sfmhip_cloud_knn(sfmhip_cloud* cloud, int k, int32_t* idx, float* d2);
+/* NormalEstimation with setKSearch(k), k in 1..32, viewpoint vp[3]: out4 = n x (nx, ny, nz, curvature). */
+int sfmhip_cloud_normals(sfmhip_cloud* cloud, int k, const float* vp /* 3 */, float* out4);
+
 /* ---- adjustBundle solver core (reference src/BundleAdjustment.cpp:46-175) ---- */
 typedef struct {
   int max_iterations;           /* 500   src/BundleAdjustment.cpp:118 */

@@ -11,11 +11,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libsfmhip.so")
 # per-source floating-point contraction: the matcher's exact kernel, the triangulation and the pose step restate
-# OpenCV's operation order (no compiler-chosen FMAs); the BA kernels are tolerance-level f64
+# OpenCV's operation order, the dense-cloud step PCL's (no compiler-chosen FMAs); the BA kernels are tolerance-level f64
 # and want v_fma_f64 -- "fast-honor-pragmas", not "fast": the one function that must NOT contract, the trust-region decision
 # lm_decide (the same bits on the host and on the device), says so with a pragma, which plain "fast" ignores
 SOURCES = {"context.hip": "off", "match.hip": "off", "triangulate.hip": "off", "incremental.hip": "off",
-           "score.hip": "off", "pose.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
+           "score.hip": "off", "pose.hip": "off", "cloud.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -114,6 +114,13 @@ def build_pose_demo(force=False):
     return _build_host_exe(os.path.join(HERE, "sfm_pose_selftest"),
                            ("Sfm.cpp", "SfmIO.cpp", "SfmPose.cpp", "BundleAdjustment.cpp", "pose_selftest.cpp"), force,
                            std="c++17")  # (SfmPose.cpp includes ../pose.h, whose hypot restatement has hex float literals)
+
+
+def build_cloud_demo(force=False):
+    """map3D's steps 8-10 in the host mirror (convertPLYtoPCD, loadPCDFile, cloudPointFilter, removePoints and create_mesh's
+    normals, all on the unfiltered cloud as the reference calls them) on a PLY file (needs the GPU)."""
+    return _build_host_exe(os.path.join(HERE, "sfm_cloud_selftest"),
+                           ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "cloud_selftest.cpp"), force)
 
 
 def _build_host_exe(exe, files, force, std="c++14"):

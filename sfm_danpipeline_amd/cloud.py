@@ -1,0 +1,106 @@
+"""map3D's step 10 (reference src/Sfm.cpp:94-102, bodies :1323-1383) on the GPU: PCL 1.8.1's PassThrough,
+RadiusOutlierRemoval and k-nearest NormalEstimation over a device-resident cloud (include/sfmhip.h, sfmhip_cloud_*).
+
+`Cloud(xyz)` uploads the points once; its methods share that upload and the grids built for it.  `map3d_step10(xyz)`
+runs the three calls with the reference's constants, including its quirk: all three read the unfiltered cloud, so
+the normals are those of every input point (then negated, as create_mesh does).  Parity with PCL is UNPINNED
+(DESIGN.md f-6)."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+PASS_AXIS, PASS_LO, PASS_HI = 0, 0.003, 0.83     # cloudPointFilter: setFilterFieldName("x"), setFilterLimits(0.003, 0.83)
+RADIUS, MIN_PTS = 0.07, 150                      # removePoints: setRadiusSearch(0.07), setMinNeighborsInRadius(150)
+K_NORMALS = 10                                   # create_mesh: setKSearch(10)
+KMAX = 32
+AXES = {"x": 0, "y": 1, "z": 2}
+
+
+def _p(a):
+    return a.ctypes.data
+
+
+class Cloud:
+    """A cloud of n points (float32 [n, 3]) resident on the device of `ctx`."""
+
+    def __init__(self, xyz, ctx=None):
+        self.ctx = ctx or _lib.default_context()
+        self.xyz = np.ascontiguousarray(np.asarray(xyz, np.float32).reshape(-1, 3))
+        self.n = len(self.xyz)
+        self.h = C.c_void_p()
+        _lib.check(_lib.lib().sfmhip_cloud_create(self.ctx.h, self.n, _p(self.xyz), C.byref(self.h)), "sfmhip_cloud_create")
+
+    def passthrough(self, axis="x", lo=PASS_LO, hi=PASS_HI, negative=False):
+        """Indices (input order) PassThrough keeps: finite points with lo <= v <= hi in float (outside, if negative)."""
+        ax = AXES[axis] if isinstance(axis, str) else int(axis)
+        if ax not in (0, 1, 2):
+            raise ValueError("axis must be x, y or z")
+        out, m = np.empty(max(self.n, 1), np.int32), C.c_int32(0)
+        _lib.check(_lib.lib().sfmhip_cloud_passthrough(self.h, ax, float(np.float32(lo)), float(np.float32(hi)), int(bool(negative)),
+                                                       _p(out), C.byref(m)), "sfmhip_cloud_passthrough")
+        return out[:m.value].copy()
+
+    def radius_count(self, radius, cap=0):
+        """Per point: finite points with d2 < (float)(r * r), itself included (min(count, cap) when cap > 0)."""
+        if not radius > 0:
+            raise ValueError("radius must be > 0")
+        out = np.empty(max(self.n, 1), np.int32)
+        _lib.check(_lib.lib().sfmhip_cloud_radius_count(self.h, float(radius), int(cap), _p(out)), "sfmhip_cloud_radius_count")
+        return out[:self.n].copy()
+
+    def radius_outlier(self, radius=RADIUS, min_pts=MIN_PTS):
+        """Indices RadiusOutlierRemoval keeps: count (above) > min_pts."""
+        if not radius > 0 or min_pts < 0:
+            raise ValueError("radius must be > 0 and min_pts >= 0")
+        out, m = np.empty(max(self.n, 1), np.int32), C.c_int32(0)
+        _lib.check(_lib.lib().sfmhip_cloud_radius_outlier(self.h, float(radius), int(min_pts), _p(out), C.byref(m)),
+                   "sfmhip_cloud_radius_outlier")
+        return out[:m.value].copy()
+
+    def knn(self, k):
+        """(idx [n, k] int32, d2 [n, k] float32): the k nearest finite points in (d2, index) order, -1 / inf padded."""
+        if not 1 <= k <= KMAX:
+            raise ValueError(f"k must be in 1..{KMAX}")
+        idx, d2 = np.empty((max(self.n, 1), k), np.int32), np.empty((max(self.n, 1), k), np.float32)
+        _lib.check(_lib.lib().sfmhip_cloud_knn(self.h, int(k), _p(idx), _p(d2)), "sfmhip_cloud_knn")
+        return idx[:self.n].copy(), d2[:self.n].copy()
+
+    def normals(self, k=K_NORMALS, viewpoint=(0.0, 0.0, 0.0)):
+        """[n, 4] float32 (nx, ny, nz, curvature) of NormalEstimation with setKSearch(k), flipped towards viewpoint."""
+        if not 1 <= k <= KMAX:
+            raise ValueError(f"k must be in 1..{KMAX}")
+        vp = np.ascontiguousarray(np.asarray(viewpoint, np.float32).reshape(3))
+        out = np.empty((max(self.n, 1), 4), np.float32)
+        _lib.check(_lib.lib().sfmhip_cloud_normals(self.h, int(k), _p(vp), _p(out)), "sfmhip_cloud_normals")
+        return out[:self.n].copy()
+
+    def close(self):
+        if self.h:
+            _lib.lib().sfmhip_cloud_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def map3d_step10(xyz, viewpoint=(0.0, 0.0, 0.0), ctx=None):
+    """The reference's step 10 on a loaded MAP3D.pcd cloud: cloudPointFilter, removePoints and create_mesh's normals,
+    each on the UNFILTERED cloud as map3D passes it.  Returns (passthrough indices, radius-outlier indices, normals
+    [n, 4] with the normal negated)."""
+    with Cloud(xyz, ctx=ctx) as c:
+        keep_pass = c.passthrough(PASS_AXIS, PASS_LO, PASS_HI)
+        keep_radius = c.radius_outlier(RADIUS, MIN_PTS)
+        nrm = c.normals(K_NORMALS, viewpoint)
+    nrm[:, :3] = -nrm[:, :3]
+    return keep_pass, keep_radius, nrm

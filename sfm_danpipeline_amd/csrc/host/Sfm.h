@@ -1,11 +1,12 @@
 // Sfm.h -- the hot-path part of the reference's StructFromMotion (include/Sfm.h:15-35,89,
-// 107-117): same member names, same method signatures.  The PnP step (addMoreViews) and the
-// PMVS/PCL post-processing are out of scope.
+// 107-117): same member names, same method signatures.  The PnP step (addMoreViews), the Poisson mesh and the
+// viewers are out of scope; map3D's step 10 filters and normals are in SfmCloud.cpp.
 #pragma once
 #include <map>
 #include <set>
 #include <string>
 #include "BundleAdjustment.h"
+#include "pcllite.h"
 #include "sfmhip.h"
 
 class StructFromMotion {
@@ -168,6 +169,22 @@ class StructFromMotion {
   // 1.8 documents (FIELDS x y z rgb, rgb = the packed 0x00RRGGBB word printed as a float).  Returns the point count
   // (0 = "ply file is empty", the reference's failure case).  Not pinned against PCL: it is absent from the image.
   static size_t convertPLYtoPCD(const std::string& plyPath, const std::string& pcdPath);
+  // ---- map3D step 10 on the dense cloud (csrc/host/SfmCloud.cpp; sfmhip_cloud_*, PCL parity UNPINNED: DESIGN.md f-6)
+  // The three calls share one device upload and its grids while the cloud's points are unchanged (SfmCloud.cpp keeps
+  // one handle, keyed by the points' count and a hash of their bytes).  The reference's step 10 passes the UNFILTERED
+  // cloud to all three (src/Sfm.cpp:98-100); cloud_selftest.cpp reproduces that order.
+  // reference include/Sfm.h:182, src/Sfm.cpp:1323-1332: PassThrough on x, limits (float) 0.003 and 0.83, inclusive;
+  // non-finite points dropped; input order kept.  filterCloud takes the kept points, is_dense and the sensor origin of
+  // `cloud`.
+  void cloudPointFilter(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PointCloud<pcl::PointXYZ>::Ptr& filterCloud);
+  // reference include/Sfm.h:184, src/Sfm.cpp:1334-1344: RadiusOutlierRemoval, radius 0.07, 150 neighbours: a point is
+  // kept iff more than 150 finite points (itself included) lie at d2 < (float)(0.07 * 0.07); input order kept.
+  void removePoints(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PointCloud<pcl::PointXYZ>::Ptr& filterCloud);
+  // the first half of create_mesh (reference include/Sfm.h:186, src/Sfm.cpp:1346-1366): NormalEstimation with
+  // setKSearch(10) towards the cloud's sensor origin, then every normal multiplied by -1.  normals has one entry per
+  // point of `cloud` (NaN where PCL writes NaN).  The Poisson half is not built.
+  void computeNormals(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PointCloud<pcl::Normal>::Ptr& normals);
+
   const std::vector<cv::Mat>& colorImages() const { return mColorImages; }
   const std::vector<cv::Mat>& grayImages() const { return mGrayImages; }
   const std::vector<std::string>& imagePaths() const { return nImagesPath; }

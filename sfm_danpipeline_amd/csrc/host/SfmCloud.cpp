@@ -1,0 +1,105 @@
+// SfmCloud.cpp -- map3D's step 10 on the dense cloud (reference src/Sfm.cpp:94-102, bodies :1323-1383) in the host
+// mirror: cloudPointFilter, removePoints and the normal half of create_mesh over sfmhip_cloud_* (cloud.hip).  Kept out
+// of Sfm.cpp / SfmIO.cpp, which the oracle's sanitizer builds link against a CPU stub of the C ABI.
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+#include "Sfm.h"
+#include "hip_backend.h"
+
+namespace {
+
+// the one device cloud the three calls share: the handle of the last cloud asked for, keyed by its point count and an
+// FNV-1a hash of its bytes (so a cloud edited in place gets a fresh upload).  Replaced, never freed at exit.
+struct DeviceCloud {
+  sfmhip_cloud* h = nullptr;
+  size_t n = 0;
+  uint64_t hash = 0;
+};
+
+uint64_t hash_points(const std::vector<pcl::PointXYZ>& p) {
+  const unsigned char* b = reinterpret_cast<const unsigned char*>(p.data());
+  uint64_t h = 1469598103934665603ull;
+  for (size_t i = 0; i < p.size() * sizeof(pcl::PointXYZ); ++i) h = (h ^ b[i]) * 1099511628211ull;
+  return h;
+}
+
+sfmhip_cloud* device_cloud(const pcl::PointCloud<pcl::PointXYZ>& c) {
+  static DeviceCloud cache;
+  const uint64_t h = hash_points(c.points);
+  if (cache.h && cache.n == c.size() && cache.hash == h) return cache.h;
+  if (cache.h) sfmhip_cloud_destroy(cache.h);
+  cache = DeviceCloud();
+  static_assert(sizeof(pcl::PointXYZ) == 12, "PointXYZ is three packed floats");
+  const int rc = sfmhip_cloud_create(sfm_hip_context(), (int)c.size(), c.size() ? &c.points[0].x : nullptr, &cache.h);
+  if (rc != SFMHIP_OK) {
+    std::fprintf(stderr, "[sfm] sfmhip_cloud_create: %s\n", sfmhip_error_string(rc));
+    std::abort();
+  }
+  cache.n = c.size();
+  cache.hash = h;
+  return cache.h;
+}
+
+void check(int rc, const char* what) {
+  if (rc != SFMHIP_OK) {
+    std::fprintf(stderr, "[sfm] %s: %s\n", what, sfmhip_error_string(rc));
+    std::abort();  // (no CPU fallback behind the drop-in)
+  }
+}
+
+void take(const pcl::PointCloud<pcl::PointXYZ>& in, const std::vector<int32_t>& idx, int32_t m,
+          pcl::PointCloud<pcl::PointXYZ>& out) {
+  pcl::PointCloud<pcl::PointXYZ> r;
+  r.points.resize((size_t)m);
+  for (int32_t i = 0; i < m; ++i) r.points[i] = in.points[idx[i]];
+  r.width = (uint32_t)m;
+  r.height = 1;
+  r.is_dense = in.is_dense;
+  for (int a = 0; a < 4; ++a) r.sensor_origin_[a] = in.sensor_origin_[a];
+  out = r;
+}
+
+}  // namespace
+
+void StructFromMotion::cloudPointFilter(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud,
+                                        pcl::PointCloud<pcl::PointXYZ>::Ptr& filterCloud) {
+  std::vector<int32_t> idx(cloud->size() + 1);
+  int32_t m = 0;
+  check(sfmhip_cloud_passthrough(device_cloud(*cloud), 0, 0.003f, 0.83f, 0, idx.data(), &m), "sfmhip_cloud_passthrough");
+  if (!filterCloud) filterCloud.reset(new pcl::PointCloud<pcl::PointXYZ>);
+  take(*cloud, idx, m, *filterCloud);
+}
+
+void StructFromMotion::removePoints(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud,
+                                    pcl::PointCloud<pcl::PointXYZ>::Ptr& filterCloud) {
+  std::vector<int32_t> idx(cloud->size() + 1);
+  int32_t m = 0;
+  check(sfmhip_cloud_radius_outlier(device_cloud(*cloud), 0.07, 150, idx.data(), &m), "sfmhip_cloud_radius_outlier");
+  if (!filterCloud) filterCloud.reset(new pcl::PointCloud<pcl::PointXYZ>);
+  take(*cloud, idx, m, *filterCloud);
+}
+
+void StructFromMotion::computeNormals(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PointCloud<pcl::Normal>::Ptr& normals) {
+  const size_t n = cloud->size();
+  std::vector<float> out(4 * n + 4);
+  const float vp[3] = {cloud->sensor_origin_[0], cloud->sensor_origin_[1], cloud->sensor_origin_[2]};  // (use_sensor_origin_)
+  check(sfmhip_cloud_normals(device_cloud(*cloud), 10, vp, out.data()), "sfmhip_cloud_normals");
+  if (!normals) normals.reset(new pcl::PointCloud<pcl::Normal>);
+  pcl::PointCloud<pcl::Normal> r;
+  r.points.resize(n);
+  bool dense = true;
+  for (size_t i = 0; i < n; ++i) {
+    pcl::Normal& q = r.points[i];
+    q.normal_x = -out[4 * i];  // create_mesh: every normal times -1 (src/Sfm.cpp:1358-1362)
+    q.normal_y = -out[4 * i + 1];
+    q.normal_z = -out[4 * i + 2];
+    q.curvature = out[4 * i + 3];
+    dense = dense && q.normal_x == q.normal_x;
+  }
+  r.width = (uint32_t)n;
+  r.height = 1;
+  r.is_dense = dense;
+  for (int a = 0; a < 4; ++a) r.sensor_origin_[a] = cloud->sensor_origin_[a];
+  *normals = r;
+}

@@ -1,0 +1,207 @@
+// pcllite.h -- the few PCL 1.8.1 types map3D's step 10 passes around (reference src/Sfm.cpp:94-102, include/Sfm.h:182-186),
+// as plain stand-ins next to cvlite.h (PCL is not a dependency of this build), and the PCD reader that loads MAP3D.pcd
+// into them (pcl::io::loadPCDFile for PointXYZ).  Header-only and C++14: the host mirror and the CPU tests include it.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <sstream>
+#include <string>
+#include <vector>
+
+namespace pcl {
+
+struct PointXYZ {
+  float x, y, z;
+  PointXYZ() : x(0), y(0), z(0) {}
+  PointXYZ(float x_, float y_, float z_) : x(x_), y(y_), z(z_) {}
+};
+
+struct Normal {
+  float normal_x, normal_y, normal_z, curvature;
+  Normal() : normal_x(0), normal_y(0), normal_z(0), curvature(0) {}
+};
+
+template <typename T>
+struct PointCloud {
+  std::vector<T> points;
+  uint32_t width = 0, height = 0;  // an unorganised cloud: width = size, height = 1
+  bool is_dense = true;            // false when a point may hold a non-finite value
+  float sensor_origin_[4] = {0, 0, 0, 0};  // the PCD's VIEWPOINT translation (Eigen::Vector4f in PCL)
+  typedef std::shared_ptr<PointCloud<T>> Ptr;
+  size_t size() const { return points.size(); }
+  bool empty() const { return points.empty(); }
+  void push_back(const T& p) {
+    points.push_back(p);
+    width = (uint32_t)points.size();
+    height = 1;
+  }
+};
+
+namespace io {
+
+// pcl::io::loadPCDFile(path, cloud) for PointXYZ: PCD v0.5-0.7, DATA ascii or binary (little-endian records), fields x,
+// y, z of TYPE F and SIZE 4 or 8 (other fields skipped); binary_compressed is refused with a message.  Returns 0, or
+// -1 when the file is missing, malformed or truncated (the cloud is then left empty).  is_dense = every point finite.
+inline int loadPCDFile(const std::string& path, PointCloud<PointXYZ>& cloud) {
+  cloud = PointCloud<PointXYZ>();
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) {
+    std::fprintf(stderr, "[pcd] cannot open %s\n", path.c_str());
+    return -1;
+  }
+  std::vector<char> buf;
+  char tmp[65536];
+  size_t got;
+  while ((got = std::fread(tmp, 1, sizeof tmp, f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
+  std::fclose(f);
+  size_t pos = 0;
+  std::vector<std::string> names, types;
+  std::vector<int> sizes, counts;
+  long long width = -1, height = 1, points = -1;
+  float vp[7] = {0, 0, 0, 1, 0, 0, 0};
+  std::string data;
+  while (pos < buf.size()) {
+    size_t e = pos;
+    while (e < buf.size() && buf[e] != '\n') ++e;
+    std::string l(&buf[pos], e - pos);
+    pos = e + 1;
+    if (!l.empty() && l.back() == '\r') l.pop_back();
+    if (l.empty() || l[0] == '#') continue;
+    std::istringstream is(l);
+    std::string w, v;
+    is >> w;
+    if (w == "VERSION") continue;
+    if (w == "FIELDS" || w == "COLUMNS") {
+      while (is >> v) names.push_back(v);
+    } else if (w == "SIZE") {
+      int s;
+      while (is >> s) sizes.push_back(s);
+    } else if (w == "TYPE") {
+      while (is >> v) types.push_back(v);
+    } else if (w == "COUNT") {
+      int s;
+      while (is >> s) counts.push_back(s);
+    } else if (w == "WIDTH") {
+      is >> width;
+    } else if (w == "HEIGHT") {
+      is >> height;
+    } else if (w == "VIEWPOINT") {
+      for (int k = 0; k < 7; ++k) is >> vp[k];
+    } else if (w == "POINTS") {
+      is >> points;
+    } else if (w == "DATA") {
+      is >> data;
+      break;
+    } else {
+      std::fprintf(stderr, "[pcd] %s: unknown header line '%s'\n", path.c_str(), l.c_str());
+      return -1;
+    }
+  }
+  if (counts.empty()) counts.assign(names.size(), 1);
+  if (points < 0 && width >= 0) points = width * height;
+  if (names.empty() || sizes.size() != names.size() || types.size() != names.size() || counts.size() != names.size() ||
+      points < 0 || width < 0 || height < 0 || width * height != points || points > (1ll << 31) - 1) {
+    std::fprintf(stderr, "[pcd] %s: malformed header\n", path.c_str());
+    return -1;
+  }
+  if (data == "binary_compressed") {
+    std::fprintf(stderr, "[pcd] %s: DATA binary_compressed is not supported (save the cloud as ascii or binary)\n",
+                 path.c_str());
+    return -1;
+  }
+  if (data != "ascii" && data != "binary") {
+    std::fprintf(stderr, "[pcd] %s: unknown DATA '%s'\n", path.c_str(), data.c_str());
+    return -1;
+  }
+  int col[3] = {-1, -1, -1}, off[3] = {0, 0, 0}, fsz[3] = {0, 0, 0};
+  int ncol = 0, rec = 0;
+  for (size_t i = 0; i < names.size(); ++i) {
+    const int a = names[i] == "x" ? 0 : names[i] == "y" ? 1 : names[i] == "z" ? 2 : -1;
+    if (a >= 0) {
+      if (types[i] != "F" || (sizes[i] != 4 && sizes[i] != 8) || counts[i] != 1) {
+        std::fprintf(stderr, "[pcd] %s: field %s must be one float\n", path.c_str(), names[i].c_str());
+        return -1;
+      }
+      col[a] = ncol;
+      off[a] = rec;
+      fsz[a] = sizes[i];
+    }
+    if (sizes[i] <= 0 || counts[i] <= 0) {
+      std::fprintf(stderr, "[pcd] %s: malformed header\n", path.c_str());
+      return -1;
+    }
+    ncol += counts[i];
+    rec += sizes[i] * counts[i];
+  }
+  if (col[0] < 0 || col[1] < 0 || col[2] < 0) {
+    std::fprintf(stderr, "[pcd] %s: no x y z fields\n", path.c_str());
+    return -1;
+  }
+  PointCloud<PointXYZ> out;
+  out.points.resize((size_t)points);
+  bool dense = true;
+  if (data == "binary") {
+    if (buf.size() < pos || (unsigned long long)(buf.size() - pos) < (unsigned long long)points * rec) {
+      std::fprintf(stderr, "[pcd] %s: truncated binary data\n", path.c_str());
+      return -1;
+    }
+    for (long long k = 0; k < points; ++k) {
+      const char* r = &buf[pos] + (size_t)k * rec;
+      float v[3];
+      for (int a = 0; a < 3; ++a) {
+        if (fsz[a] == 4) {
+          std::memcpy(&v[a], r + off[a], 4);
+        } else {
+          double d;
+          std::memcpy(&d, r + off[a], 8);
+          v[a] = (float)d;
+        }
+      }
+      out.points[(size_t)k] = PointXYZ(v[0], v[1], v[2]);
+    }
+  } else {
+    const char* p = buf.empty() ? "" : &buf[0];
+    const char* end = p + buf.size();
+    p += std::min(pos, buf.size());
+    std::string tok;
+    for (long long k = 0; k < points; ++k) {
+      float v[3] = {0, 0, 0};
+      for (int c = 0; c < ncol; ++c) {
+        while (p < end && (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n')) ++p;
+        const char* s = p;
+        while (p < end && !(*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n')) ++p;
+        if (s == p) {
+          std::fprintf(stderr, "[pcd] %s: truncated ascii data (point %lld)\n", path.c_str(), k);
+          return -1;
+        }
+        for (int a = 0; a < 3; ++a)
+          if (c == col[a]) {
+            tok.assign(s, p - s);
+            char* q = nullptr;
+            v[a] = std::strtof(tok.c_str(), &q);
+            if (q == tok.c_str()) {
+              std::fprintf(stderr, "[pcd] %s: bad number '%s'\n", path.c_str(), tok.c_str());
+              return -1;
+            }
+          }
+      }
+      out.points[(size_t)k] = PointXYZ(v[0], v[1], v[2]);
+    }
+  }
+  for (const PointXYZ& q : out.points) dense = dense && std::isfinite(q.x) && std::isfinite(q.y) && std::isfinite(q.z);
+  out.width = (uint32_t)width;
+  out.height = (uint32_t)height;
+  out.is_dense = dense;
+  for (int k = 0; k < 3; ++k) out.sensor_origin_[k] = vp[k];
+  out.sensor_origin_[3] = 0;
+  cloud = out;
+  return 0;
+}
+
+}  // namespace io
+}  // namespace pcl
