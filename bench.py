@@ -23,9 +23,12 @@ N > 1 (launched by torch.distributed.run, one rank per GPU, RCCL):
     system summed by one all-reduce per LM iteration (strong scaling; `ba_amdahl` splits the iteration
     into what shards, what is replicated and the exchange).
 
-Extra fields: `sustained` (the same step looped for >= 2 s: past DVFS settling), `value_host_visible`
-(every sweep followed by the packed device-to-host fetch of counts + match lists), the dominant kernel's own
-duration behind `roofline` (`launch_ms`, HIP events on the library's stream around that one launch).
+A plain run does only what the headline needs: set-up, warm-up, the two timed regions, `--dump-outputs`, the line.
+Everything else is measured with `--full` (its fields are null otherwise), which `--lean` and the `--no-*` switches
+narrow: `sustained` (the same step looped for >= 2 s: past DVFS settling), `value_host_visible` (every sweep followed
+by the packed device-to-host fetch of counts + match lists), the dominant kernel's own duration behind `roofline`
+(`launch_ms`, HIP events on the library's stream around that one launch), the BA stage times (`roofline_ba`,
+`ba_amdahl`), `ba_batch`, `cfg5_strong`, the scoring / SIFT / adjustBundle legs and the CPU baseline.
 """
 import argparse
 import json
@@ -89,6 +92,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too (sustained and host-visible rates, per-kernel samples and "
+                         "rooflines, BA stage times and shards, ba_batch, cfg5, scoring, SIFT, adjustBundle, CPU baseline); --lean "
+                         "and the --no-* switches narrow it and change nothing without it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-pairs", type=int, default=256, help="pairs of cfg2 timed on the host cores")
     ap.add_argument("--cpu-ba-iters", type=int, default=8)
@@ -99,10 +106,10 @@ def main():
     ap.add_argument("--no-ba-batch", action="store_true")
     ap.add_argument("--no-score", action="store_true", help="skip the findBestPair scoring leg (E-matrix RANSAC of 1225 pairs)")
     ap.add_argument("--lean", action="store_true",
-                    help="timed regions and per-kernel samples only (no sustained / host-visible loops, no cfg5, no CPU "
+                    help="with --full: timed regions and per-kernel samples only (no sustained / host-visible loops, no cfg5, no CPU "
                          "baseline): the command to run under rocprofv3, whose traces grow with every dispatch")
     ap.add_argument("--cfg5-sample", type=int, default=0,
-                    help="with --lean: also sweep this many pairs of BASELINE cfg5 (evenly spaced over the 124 750, checksums asserted "
+                    help="with --full --lean: also sweep this many pairs of BASELINE cfg5 (evenly spaced over the 124 750, checksums asserted "
                          "against tests/golden/cfg5_checksums.npz) so that a profile of the command holds knn_keyed_kernel rows")
     ap.add_argument("--no-adjust-bundle", action="store_true", help="skip the whole-call leg (BundleAdjustment::adjustBundle through "
                                                                      "the C++ mirror, a subprocess)")
@@ -118,7 +125,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    if args.lean:
+    # `lean`: no sustained / host-visible loops, shards or batch BA below; what --lean keeps of --full (the clock probes,
+    # per-kernel samples, BA stage times and the rooflines built on them) is gated by args.full alone
+    lean = args.lean or not args.full
+    if lean:
         args.no_cfg5 = args.no_cpu_baseline = args.no_score = args.no_adjust_bundle = True
 
     # `python bench.py --gpus N` on its own (no WORLD_SIZE in the environment): this process becomes the launcher -- before
@@ -221,15 +231,19 @@ def main():
     barrier()
     # the measured ceiling of THIS box, right before the timed region: bare i8 MFMAs on random operands for 50 ms (the chip
     # lowers its clock under matrix load; the nominal 5 POP/s assumes 2.4 GHz), and the shader clock while the sweep itself
-    # runs (a one-wave sampler on the second stream beside 30 single-stream sweeps)
-    sustained_peak_ops, sustained_peak_ghz = ctx.probe_i8_mfma_peak(0.05)
+    # runs (a one-wave sampler on the second stream beside 30 single-stream sweeps).  Both probes are --full's; a plain run
+    # takes the same sweeps, so that the timed region starts from the load it has always started from
+    if args.full:
+        sustained_peak_ops, sustained_peak_ghz = ctx.probe_i8_mfma_peak(0.05)
     for _ in range(10):
         match_step(one_stream=True)
     torch.cuda.synchronize(dev)
-    ctxs[1].probe_clock_start(0.012)
+    if args.full:
+        ctxs[1].probe_clock_start(0.012)
     for _ in range(30):
         match_step(one_stream=True)
-    sweep_clock_ghz = ctxs[1].probe_clock_read()
+    if args.full:
+        sweep_clock_ghz = ctxs[1].probe_clock_read()
     for _ in range(max(args.warmup, 1)):
         match_step()
     barrier()
@@ -250,18 +264,19 @@ def main():
     # per-kernel device time of the dominant kernel: HIP events recorded by the library on the
     # stream the kernels run on, one extra step outside the timed region per sample
     # (stage timing is opt-in in the library: the events cost stream bubbles the timed region does not pay)
-    samples = []
-    ctx.set_timing(True)
-    barrier()
-    # (rounds of back-to-back steps, the events of the last step of a round read back: a step timed on
-    # its own, with the GPU idle before it, holds a higher clock than the sustained loop does)
-    for _ in range(4):
-        for _ in range(min(args.steps, 5)):
-            match_step(one_stream=True)
-        tm = plan.last_timing()          # synchronises on the recorded events
-        samples.append((tm["prepare_s"], tm["knn_kernel_s"], tm["compact_s"], tm["knn_s"]))
-    ctx.set_timing(False)
-    prep_s, knn_s, comp_s, knn_stage_s = [float(np.mean([s[i] for s in samples])) for i in range(4)]
+    if args.full:
+        samples = []
+        ctx.set_timing(True)
+        barrier()
+        # (rounds of back-to-back steps, the events of the last step of a round read back: a step timed on
+        # its own, with the GPU idle before it, holds a higher clock than the sustained loop does)
+        for _ in range(4):
+            for _ in range(min(args.steps, 5)):
+                match_step(one_stream=True)
+            tm = plan.last_timing()          # synchronises on the recorded events
+            samples.append((tm["prepare_s"], tm["knn_kernel_s"], tm["compact_s"], tm["knn_s"]))
+        ctx.set_timing(False)
+        prep_s, knn_s, comp_s, knn_stage_s = [float(np.mean([s[i] for s in samples])) for i in range(4)]
     counts = plan.counts()
 
     # ------------------------------------------------------------------ sustained (>= 2 s) and host-visible rates
@@ -277,7 +292,7 @@ def main():
                 break
         barrier()
         return n, time.perf_counter() - t0
-    n_sus, t_sus = (0, 1.0) if args.lean else loop_for(args.sustain_s, match_step, 50)
+    n_sus, t_sus = (0, 1.0) if lean else loop_for(args.sustain_s, match_step, 50)
     sustained_pairs_s = n_sus * len(pairs) / t_sus
 
     # host-visible rate: every sweep's counts + {queryIdx, trainIdx, distance} lists in host memory -- what getMatching's
@@ -296,7 +311,7 @@ def main():
             hv_seen[1] += int(c_.sum()) == len(q_) == len(t_) == len(d_)
         match_step()
         hv_seen[0] += 1
-    if args.lean:
+    if lean:
         n_hv, t_hv = 0, 1.0
     else:
         for pl_ in plans:
@@ -316,7 +331,7 @@ def main():
     def match_and_copy():
         match_step(one_stream=True)
         plan.fetch()
-    n_hc, t_hc = (0, 1.0) if args.lean else loop_for(0.5, match_and_copy, 5)
+    n_hc, t_hc = (0, 1.0) if lean else loop_for(0.5, match_and_copy, 5)
     host_copy_pairs_s = n_hc * len(pairs) / t_hc
 
     # ------------------------------------------------------------------ timed: BA, K iterations
@@ -346,25 +361,26 @@ def main():
     ba_accepted_timed = int(ba_sum.successful_steps - ba_pre.successful_steps)   # (on the line: the timed iterations moved the solve)
     # per-stage device time: the same iterations once more with stage timing on, outside the
     # timed region (the library accumulates since the run began, hence the difference)
-    ba_restart()
-    ctx.set_timing(True)
-    ba_t0 = ba.last_timing()
-    ba.iterate(args.steps)
-    ba_t = {k: v - ba_t0[k] for k, v in ba.last_timing().items()}
-    ba_layout = dict(ba.reduced_layout(), front_tree=ba.reduced_tree())
-    ctx.set_timing(False)
-    barrier()
+    if args.full:
+        ba_restart()
+        ctx.set_timing(True)
+        ba_t0 = ba.last_timing()
+        ba.iterate(args.steps)
+        ba_t = {k: v - ba_t0[k] for k, v in ba.last_timing().items()}
+        ba_layout = dict(ba.reduced_layout(), front_tree=ba.reduced_tree())
+        ctx.set_timing(False)
+        barrier()
     # sustained BA rate: every ba.iterate issues all-reduces, so the number of batches must be THE SAME on every rank --
     # it is derived from the timed region's duration agreed over the ranks (MAX), not from each rank's own clock
     t_ba_agreed = t_ba
-    if world > 1:
+    if world > 1 and not lean:
         tt = torch.tensor([t_ba], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         t_ba_agreed = float(tt[0])
     # (a batch = restart + the K timed iterations; the restarts keep the device as busy as the timed part does, only the K
     # iterations behind each count)
     t_batch = (2 * args.steps + BA_PRE) * t_ba_agreed / args.steps
-    n_batches = 0 if args.lean else max(1, int(np.ceil(args.sustain_s / max(t_batch, 1e-6))))
+    n_batches = 0 if lean else max(1, int(np.ceil(args.sustain_s / max(t_batch, 1e-6))))
     t_sus_ba = 0.0
     for _ in range(n_batches):
         ba_restart()
@@ -380,7 +396,7 @@ def main():
     # same reduced system's size and front tree): its eliminate + back-substitute stage times over the same iterations -- what
     # `sharded_ms / N` only extrapolates (does ba_eliminate_mfma still fill 256 CUs with an eighth of the pieces?)
     shard_ms = {}
-    if world == 1 and not args.lean:
+    if world == 1 and not lean:
         for w_ in (2, 4, 8):
             loc_ = sharding.local_ba_problem(pb["obs_cam"], pb["obs_pt"], pb["obs_xy"], pb["pts0"], 0, w_)
             p_ = bundle.BaProblem(200, len(loc_["pts"]), loc_["obs_cam"], loc_["obs_pt"], loc_["obs_xy"], ctx=ctx)
@@ -402,7 +418,7 @@ def main():
     # node of N GPUs does scale is N independent problems -- one whole cfg4 problem per rank, no collective: the rate a
     # reconstruction service sees.  Reported next to the strong-scaled figure, never instead of it.
     ba_batch = None
-    if not args.no_ba_batch and not args.lean:
+    if not args.no_ba_batch and not lean:
         import threading
         ba.close()
         # several problems in flight per GPU (a context + stream + host thread each): the reduced solve of an LM
@@ -451,7 +467,7 @@ def main():
     # ------------------------------------------------------------------ cfg5, strong scaling over the ranks
     cfg5 = None
     cfg5_sample = None
-    if args.lean and args.cfg5_sample > 0:
+    if args.full and args.lean and args.cfg5_sample > 0:
         # the profiled sample of cfg5 (K2, knn_keyed_kernel): pairs evenly spaced over the 124 750, every one checked against the golden file
         o_imgs = synth.orb_image_set()
         o_all = synth.all_pairs(len(o_imgs))
@@ -639,56 +655,58 @@ def main():
     traffic_source = ("profiles/traffic.json: rocprofv3 PMC passes of `bench.py --lean` on the builder's box (" +
                       str(traffic.get("_source", "round-tagged files under profiles/")) + "), not measured in this run") if traffic else None
 
-    ops_per_pair = 2.0 * n_feat * n_feat * dim                     # 1.024 GOP per cfg2 pair
-    knn_tops = ops_per_pair * len(pairs) / knn_s / 1e12
-    # secondary limiter: the epilogue, 19 VALU lane-ops per 16 distances
-    # (v_max3_i32 slot maxima over tile pairs + a max3 tree per tile) against 256 CU x 128 lanes x 2.4 GHz
-    valu_tlops = (19.0 / 16.0) * n_feat * n_feat * len(pairs) / knn_s / 1e12
-    roofline = {"kernel": "knn_kernel<KS=4,L2,NU=2,SR=256,NW=4> (i8 MFMA 32x32x32, train norm through the C operand, "
-                          "value-only slot / tile-maximum epilogue, exact resolve of the candidates)", "bound": "mfma",
-                "achieved": round(knn_tops, 2), "peak": I8_DENSE_PEAK_TOPS, "unit": "TFLOP/s",
-                "frac": round(knn_tops / I8_DENSE_PEAK_TOPS, 4), "traffic": hbm_bytes("knn_kernel"), "traffic_source": traffic_source,
-                "sustained_peak": round(sustained_peak_ops / 1e12, 1), "sustained_peak_clock_ghz": round(sustained_peak_ghz, 3),
-                "frac_of_sustained": round(knn_tops / max(sustained_peak_ops / 1e12, 1e-9), 4),
-                "sweep_clock_ghz": round(sweep_clock_ghz, 3),
-                "sustained_note": "sustained_peak = what this box held for bare v_mfma_i32_32x32x32_i8 on random operands, every "
-                                  "SIMD busy, 50 ms, measured right before the timed region (csrc/probe.hip); sweep_clock_ghz = the "
-                                  "shader clock while the sweep ran (s_memtime / s_memrealtime of a one-wave sampler on the "
-                                  "second stream); frac stays against the nominal 5 POP/s",
-                "f32_equivalent_frac": round(knn_tops / F32_MFMA_PEAK_TFLOPS, 3),
-                "valu_epilogue": {"achieved": round(valu_tlops, 2), "peak": VALU_PEAK_TLANEOPS, "unit": "Tlane-op/s",
-                                  "frac": round(valu_tlops / VALU_PEAK_TLANEOPS, 4),
-                                  "note": "19 VALU ops per 32x32 tile = 1.19 per distance (v_max3_i32 / v_med3_i32 issue "
-                                          "at ~4 cycles per wave64 op on gfx950: scripts/ubench/epi_mix.hip); the MFMA "
-                                          "pipe bounds the sweep, the per-sweep resolve the rest (DESIGN.md K1)"},
-                "launch_ms": round(knn_s * 1e3, 4), "knn_stage_ms": round(knn_stage_s * 1e3, 4),
-                "prepare_ms": round(prep_s * 1e3, 4), "compact_ms": round(comp_s * 1e3, 4),
-                "note": "launch_ms = that one kernel (hipEvents on the library's stream around its launch, mean of the last "
-                        "step of 4 rounds of back-to-back steps); knn_stage_ms adds the exact / fix-up kernels behind it"}
     n_obs_l, n_pt_l, n_cam = len(loc["obs_cam"]), len(loc["pts"]), 200
-    red_dim = 6 * n_cam + 1
-    ba_bytes = 3 * n_obs_l * 24 + 2 * n_pt_l * 24 + 2 * red_dim * red_dim * 8 + n_cam * 48   # section 8d
-    ba_stream_s = (ba_t["eliminate_s"] + ba_t["backsub_s"]) / max(args.steps, 1)
-    ba_gbs = ba_bytes / ba_stream_s / 1e9
-    tr_ba = [hbm_bytes("ba_eliminate_mfma"), hbm_bytes("ba_backsub_runs") if hbm_bytes("ba_backsub_runs") is not None else hbm_bytes("ba_backsub")]
-    if hbm_bytes("ba_gather_rows") is not None:      # (the default slab epilogue's second kernel; absent from older profiles)
-        tr_ba.append(hbm_bytes("ba_gather_rows"))
-    roofline_ba = {"kernels": "ba_eliminate_mfma + ba_gather_rows (one linearisation: F^T F + Schur correction, per-workgroup slabs "
-                              "summed in a fixed order: S, g and the cost are bitwise reproducible) + ba_backsub_runs (per LM iteration, "
-                              "this rank's shard)",
-                   "bound": "hbm", "achieved": round(ba_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                   "frac": round(ba_gbs / HBM_PEAK_GBS, 4),
-                   "traffic": sum(tr_ba) if all(t is not None for t in tr_ba) else None, "traffic_source": traffic_source,
-                   "eliminate_ms": round(1e3 * ba_t["eliminate_s"] / args.steps, 4),
-                   "allreduce_ms": round(1e3 * ba_t["allreduce_s"] / args.steps, 4),
-                   "reduced_solve_ms": round(1e3 * ba_t["solve_s"] / args.steps, 4),
-                   "backsub_cost_ms": round(1e3 * ba_t["backsub_s"] / args.steps, 4),
-                   "launches_per_iter": round(ba_t["launches"] / max(args.steps, 1), 1),
-                   "reduced_layout": ba_layout,
-                   "note": "instruction-issue / latency-bound in the per-point linearisation; the reduced system is factored "
-                           "as a tree of fronts of the recursively dissected camera graph, one workgroup per front "
-                           "(reduced_layout.front_tree: the dependency chain is chain_tiles tile steps of 32 columns instead "
-                           "of dense_tiles), or, where no such tree exists, as chains + separator / dense; DESIGN.md section 3"}
+    roofline = roofline_ba = None
+    if args.full:
+        ops_per_pair = 2.0 * n_feat * n_feat * dim                     # 1.024 GOP per cfg2 pair
+        knn_tops = ops_per_pair * len(pairs) / knn_s / 1e12
+        # secondary limiter: the epilogue, 19 VALU lane-ops per 16 distances
+        # (v_max3_i32 slot maxima over tile pairs + a max3 tree per tile) against 256 CU x 128 lanes x 2.4 GHz
+        valu_tlops = (19.0 / 16.0) * n_feat * n_feat * len(pairs) / knn_s / 1e12
+        roofline = {"kernel": "knn_kernel<KS=4,L2,NU=2,SR=256,NW=4> (i8 MFMA 32x32x32, train norm through the C operand, "
+                              "value-only slot / tile-maximum epilogue, exact resolve of the candidates)", "bound": "mfma",
+                    "achieved": round(knn_tops, 2), "peak": I8_DENSE_PEAK_TOPS, "unit": "TFLOP/s",
+                    "frac": round(knn_tops / I8_DENSE_PEAK_TOPS, 4), "traffic": hbm_bytes("knn_kernel"), "traffic_source": traffic_source,
+                    "sustained_peak": round(sustained_peak_ops / 1e12, 1), "sustained_peak_clock_ghz": round(sustained_peak_ghz, 3),
+                    "frac_of_sustained": round(knn_tops / max(sustained_peak_ops / 1e12, 1e-9), 4),
+                    "sweep_clock_ghz": round(sweep_clock_ghz, 3),
+                    "sustained_note": "sustained_peak = what this box held for bare v_mfma_i32_32x32x32_i8 on random operands, every "
+                                      "SIMD busy, 50 ms, measured right before the timed region (csrc/probe.hip); sweep_clock_ghz = the "
+                                      "shader clock while the sweep ran (s_memtime / s_memrealtime of a one-wave sampler on the "
+                                      "second stream); frac stays against the nominal 5 POP/s",
+                    "f32_equivalent_frac": round(knn_tops / F32_MFMA_PEAK_TFLOPS, 3),
+                    "valu_epilogue": {"achieved": round(valu_tlops, 2), "peak": VALU_PEAK_TLANEOPS, "unit": "Tlane-op/s",
+                                      "frac": round(valu_tlops / VALU_PEAK_TLANEOPS, 4),
+                                      "note": "19 VALU ops per 32x32 tile = 1.19 per distance (v_max3_i32 / v_med3_i32 issue "
+                                              "at ~4 cycles per wave64 op on gfx950: scripts/ubench/epi_mix.hip); the MFMA "
+                                              "pipe bounds the sweep, the per-sweep resolve the rest (DESIGN.md K1)"},
+                    "launch_ms": round(knn_s * 1e3, 4), "knn_stage_ms": round(knn_stage_s * 1e3, 4),
+                    "prepare_ms": round(prep_s * 1e3, 4), "compact_ms": round(comp_s * 1e3, 4),
+                    "note": "launch_ms = that one kernel (hipEvents on the library's stream around its launch, mean of the last "
+                            "step of 4 rounds of back-to-back steps); knn_stage_ms adds the exact / fix-up kernels behind it"}
+        red_dim = 6 * n_cam + 1
+        ba_bytes = 3 * n_obs_l * 24 + 2 * n_pt_l * 24 + 2 * red_dim * red_dim * 8 + n_cam * 48   # section 8d
+        ba_stream_s = (ba_t["eliminate_s"] + ba_t["backsub_s"]) / max(args.steps, 1)
+        ba_gbs = ba_bytes / ba_stream_s / 1e9
+        tr_ba = [hbm_bytes("ba_eliminate_mfma"), hbm_bytes("ba_backsub_runs") if hbm_bytes("ba_backsub_runs") is not None else hbm_bytes("ba_backsub")]
+        if hbm_bytes("ba_gather_rows") is not None:      # (the default slab epilogue's second kernel; absent from older profiles)
+            tr_ba.append(hbm_bytes("ba_gather_rows"))
+        roofline_ba = {"kernels": "ba_eliminate_mfma + ba_gather_rows (one linearisation: F^T F + Schur correction, per-workgroup slabs "
+                                  "summed in a fixed order: S, g and the cost are bitwise reproducible) + ba_backsub_runs (per LM iteration, "
+                                  "this rank's shard)",
+                       "bound": "hbm", "achieved": round(ba_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(ba_gbs / HBM_PEAK_GBS, 4),
+                       "traffic": sum(tr_ba) if all(t is not None for t in tr_ba) else None, "traffic_source": traffic_source,
+                       "eliminate_ms": round(1e3 * ba_t["eliminate_s"] / args.steps, 4),
+                       "allreduce_ms": round(1e3 * ba_t["allreduce_s"] / args.steps, 4),
+                       "reduced_solve_ms": round(1e3 * ba_t["solve_s"] / args.steps, 4),
+                       "backsub_cost_ms": round(1e3 * ba_t["backsub_s"] / args.steps, 4),
+                       "launches_per_iter": round(ba_t["launches"] / max(args.steps, 1), 1),
+                       "reduced_layout": ba_layout,
+                       "note": "instruction-issue / latency-bound in the per-point linearisation; the reduced system is factored "
+                               "as a tree of fronts of the recursively dissected camera graph, one workgroup per front "
+                               "(reduced_layout.front_tree: the dependency chain is chain_tiles tile steps of 32 columns instead "
+                               "of dense_tiles), or, where no such tree exists, as chains + separator / dense; DESIGN.md section 3"}
 
     # K2 (knn_keyed_kernel, cfg5): times from this run (the full sweep of this rank, or the profiled sample), the counters from the
     # committed PMC passes of `bench.py --lean --cfg5-sample N`
@@ -890,7 +908,7 @@ def main():
                        "parallelism": f"pairs x{world} (weak" + (f"; consecutive batches alternate between {N_STREAMS} HIP "
                                       "streams per GPU" if N_STREAMS > 1 else "") + f"), BA points/{world} + all-reduce"},
             "sustained": {"seconds": args.sustain_s, "pairs_per_s": round(sustained_pairs_s, 1),
-                          "ba_iterations_per_s": round(sustained_ba_its, 2)},
+                          "ba_iterations_per_s": round(sustained_ba_its, 2)} if args.full else None,
             "value_host_visible": {"pairs_per_s": round(host_visible_pairs_s, 1),
                                    "frac_of_value": round(host_visible_pairs_s / max(pairs_per_s, 1e-9), 3),
                                    "stop_and_copy_pairs_per_s": round(host_copy_pairs_s, 1),
@@ -898,7 +916,7 @@ def main():
                                            "second stream packs sweep n into a device buffer and copies it (DMA) into one of two "
                                            "pinned buffers while the next sweeps run (sfmhip_matchplan_pipeline / _fetch_wait); the host "
                                            "takes a plan's lists two of its runs behind the one it enqueues; stop_and_copy = "
-                                           "sfmhip_matchplan_fetch after every sweep"},
+                                           "sfmhip_matchplan_fetch after every sweep"} if args.full else None,
             "cfg5_strong": cfg5, "find_best_pair_scoring": score_leg, "sift_front_end": sift_leg, "ba_batch": ba_batch,
             "adjust_bundle_call": adjust_call, "roofline_k2": roofline_k2, "cfg5_sample": cfg5_sample,
             "ba_amdahl": (lambda sh, rep, ar: {
@@ -919,7 +937,7 @@ def main():
                         "bound_8gpu_speedup = (sharded + replicated) / (sharded / 8 + replicated + allreduce): BA iterations/s "
                         "do not scale with N, independent BA problems do (ba_batch; DESIGN.md section 5)"})(
                 1e3 * (ba_t["eliminate_s"] + ba_t["backsub_s"]) / args.steps, 1e3 * ba_t["solve_s"] / args.steps,
-                1e3 * ba_t["allreduce_s"] / args.steps),
+                1e3 * ba_t["allreduce_s"] / args.steps) if args.full else None,
             "roofline": roofline, "roofline_ba": roofline_ba, "cpu_baseline": cpu_baseline,
         }
         if dumps:

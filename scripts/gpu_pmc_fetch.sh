@@ -7,7 +7,7 @@ O=$R/gpurun_out/$1
 mkdir -p $O
 FILES=""
 for P in FETCH_SIZE WRITE_SIZE; do
-  timeout 400 rocprofv3 --pmc $P --kernel-trace -d $O/$P -o $P --output-format csv -- python3 $R/bench.py --lean --steps 4 --warmup 1 > $O/$P.log 2>&1
+  timeout 400 rocprofv3 --pmc $P --kernel-trace -d $O/$P -o $P --output-format csv -- python3 $R/bench.py --full --lean --steps 4 --warmup 1 > $O/$P.log 2>&1
   F=$(find $O/$P -name "*counter_collection.csv" | head -1)
   [ -n "$F" ] && cp $F $O/${P}_counters.csv && FILES="$FILES $O/${P}_counters.csv"
   rm -rf $O/$P

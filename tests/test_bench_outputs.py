@@ -49,3 +49,18 @@ def test_dumped_outputs_are_the_timed_steps_results(tmp_path, orc):
     assert got["ba_cameras"].shape == (200, 6) and got["ba_points"].shape == (100000, 3) and got["ba_focal"].shape == (1,)
     assert np.all(np.isfinite(got["ba_points"])) and got["ba_focal"][0] > 0
     assert got["ba_cost"].tolist() == line["config"]["ba_cost"]
+
+
+@pytest.mark.gpu
+def test_a_plain_run_measures_the_headline_only():
+    """Without --full the line carries the two timed regions and leaves every other leg out (null)."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["value"] > 0 and line["ba_iterations_per_s"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "pairs/s" and line["higher_is_better"] is True and line["dtype"] == "i8"
+    assert line["config"]["ba_timed_iterations"] == [16, 17] and line["config"]["matches_found"] > 0
+    full_only = ("sustained", "value_host_visible", "roofline", "roofline_ba", "ba_amdahl", "ba_batch", "cfg5_strong",
+                 "find_best_pair_scoring", "sift_front_end", "adjust_bundle_call", "cpu_baseline")
+    assert all(line[k] is None for k in full_only), {k: line[k] is None for k in full_only}
