@@ -282,6 +282,66 @@ int sfmhip_essential_pose(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, 
  * E was <= DBL_MIN (OpenCV's random-vector branch, not restated).  0 = every pair went the documented way. */
 int sfmhip_pose_last_flags(sfmhip_ctx* ctx);
 
+/* ---- camera registration: findCameraPosePNP (reference src/Sfm.cpp:1137-1210) ----
+ * cv::solvePnPRansac(pts3D, pts2D, K, dist, rvec, T, useExtrinsicGuess, max_iters, threshold, confidence, inliers, CV_EPNP)
+ * for a batch of views.  THE CONTRACT IS THE RULE LIST BELOW, not "what OpenCV does": OpenCV is not in the image, so
+ * parity is UNPINNED; the rules are written as 3.4.1 (calib3d/solvepnp.cpp, epnp.cpp, ptsetreg.cpp) is understood to run
+ * them, and a rule marked † is a reading from memory that nothing here can check.
+ *  RANSAC shape
+ *   1. object and image points are converted to float32 first †; a view of fewer than 5 correspondences has status -1
+ *      (exactly 4, the library's P3P branch, is not built and reports -1 too);
+ *   2. 5 model points; cv::RNG restarts at (uint64)-1 in every call, so a view's samples depend on its correspondence count
+ *      alone; the subset draw is getSubset's (an index drawn before is drawn again); the default checkSubset accepts every
+ *      sample; a view of exactly 5 correspondences is its one sample, every point an inlier, 0 iterations;
+ *  one model per sample
+ *   3. undistortPoints (five fixed-point iterations) on the 5 float pixels, its output stored as float32 †, then EPnP
+ *      with an identity camera matrix † on the float points read as f64:
+ *      control points = centroid + sqrt(d_i / n) * principal axis i of the 3 x 3 covariance (cvSVD, U^T rows);
+ *      barycentric alphas through cvInvert(CC, CV_SVD) (SVD::backSubst: singular values <= 2 eps sum(w) skipped);
+ *      M (2n x 12), M^T M, its SVD by the library's one-sided Jacobi (JacobiSVDImpl_<double>, glibc's hypot), rows
+ *      11, 10, 9, 8 of U^T as the four smallest eigenvectors; L_6x10 and rho; betas for N = 1, 2, 3 by cvSolve(CV_SVD);
+ *      five Gauss-Newton steps each with the file's own Householder QR (its column maximum looks at rows k .. nr - 2 †);
+ *      R and t from the 3 x 3 SVD of the Procrustes sum with the determinant fix, after solve_for_sign by the first
+ *      point's depth; the N with the smallest mean reprojection error wins (ties: the smaller N); Rodrigues(R) = rvec;
+ *   4. NOT the library's: (a) every sum over the points of a problem is taken in one fixed order (slot i mod 256, each 64
+ *      slots folded by strides 32..1, the four groups as (g0 + g1) + (g2 + g3)), so that one thread, one workgroup and the
+ *      CPU build give the same bits; (b) sin, cos and acos in Rodrigues are plain-f64 restatements (measured: at most 1 ulp from libm; the test allows 2), not
+ *      libm's; (c) a point set whose covariance has a third singular value <= 1e-12 of its first (planar, collinear) is
+ *      not solved: the hypothesis is skipped and bit 0 of sfmhip_pnp_last_flags is set;
+ *  error and inliers
+ *   5. projectPoints(float point, Rodrigues(rvec), tvec, K, dist) in f64, stored as float32; err = dx * dx + dy * dy in
+ *      float; inlier iff err <= (float)(thr * thr);
+ *  best model and stopping
+ *   6. a model replaces the best when its count > max(best, 4); the limit becomes RANSACUpdateNumIters(confidence,
+ *      (n - count) / n, 5, limit) with the host's libm; status 0 when no model ever did;
+ *  refit and the returned pose
+ *   7. on success EPnP runs once more on all inliers (the float points back as f64, undistortPoints in f64);
+ *   8. which pose 3.4.1 returns †: the RANSAC model; the refit only decides success (EPnP always succeeds).  rvec / tvec
+ *      follow that reading; rvec_ransac / tvec_ransac and rvec_refit / tvec_refit hand out both.
+ * offsets: n_views + 1, offsets[0] = 0; xyz: 3 doubles, xy: 2 doubles (pixels) per correspondence; thresholds: pixels, one
+ * per view; status / inliers / iterations: per view; rvec / tvec (and the nullable _ransac, _refit pairs): 3 doubles per
+ * view, zero without a model; mask (nullable): 1 byte per correspondence, the best model's inliers.  Views are
+ * independent of each other. */
+int sfmhip_pnp_ransac(sfmhip_ctx* ctx, int n_views, const int32_t* offsets, const double* xyz, const double* xy,
+                      const double K[9], const double dist[5], const double* thresholds, double confidence,
+                      int max_iters, int32_t* status, double* rvec, double* tvec, double* rvec_ransac /* nullable */,
+                      double* tvec_ransac /* nullable */, double* rvec_refit /* nullable */,
+                      double* tvec_refit /* nullable */, int32_t* inliers, uint8_t* mask /* nullable */,
+                      int32_t* iterations /* nullable */);
+/* The EPnP solve of rule 3 alone for explicit point sets of any size >= 5 (xy_normalised: 2 doubles per point, already
+ * undistorted and normalised): R 9 doubles (row-major), t 3 doubles per problem, zero for a set rule 4c refuses.  What
+ * the RANSAC runs per sample and the refit per view, exposed for sample-level checks. */
+int sfmhip_pnp_epnp(sfmhip_ctx* ctx, int n_problems, const int32_t* offsets, const double* xyz,
+                    const double* xy_normalised, double* R, double* t);
+/* OR over the solves of the last sfmhip_pnp_ransac / sfmhip_pnp_epnp call: bit 0 = a rank-deficient control-point
+ * covariance (rule 4c), bit 1 = a 3 x 3 singular value <= DBL_MIN (the library's random-vector branch, not restated),
+ * bit 2 = qr_solve met a zero column (the library then uses an uninitialised step; here the step is 0).  0 = every solve
+ * went the documented way. */
+int sfmhip_pnp_last_flags(sfmhip_ctx* ctx);
+/* With sfmhip_set_timing on: the kernel time (ms, by events on the context's stream) of the last sfmhip_pnp_ransac call:
+ * ms3 = solver, scoring, mask + refit. */
+int sfmhip_pnp_last_timing(sfmhip_ctx* ctx, double* ms3);
+
 /* ---- map3D step 10: the dense cloud's filters and normals (reference src/Sfm.cpp:94-102, bodies :1323-1383) ----
  * PCL 1.8.1's PassThrough, RadiusOutlierRemoval and NormalEstimation (k nearest) on a device-resident cloud: the points
  * are uploaded once by sfmhip_cloud_create and every call below reuses them and the spatial grid built for them (one

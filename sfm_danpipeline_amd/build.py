@@ -15,7 +15,7 @@ SO = os.path.join(HERE, "libsfmhip.so")
 # and want v_fma_f64 -- "fast-honor-pragmas", not "fast": the one function that must NOT contract, the trust-region decision
 # lm_decide (the same bits on the host and on the device), says so with a pragma, which plain "fast" ignores
 SOURCES = {"context.hip": "off", "match.hip": "off", "triangulate.hip": "off", "incremental.hip": "off",
-           "score.hip": "off", "pose.hip": "off", "cloud.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
+           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -116,6 +116,15 @@ def build_pose_demo(force=False):
                            std="c++17")  # (SfmPose.cpp includes ../pose.h, whose hypot restatement has hex float literals)
 
 
+def build_incr_demo(force=False):
+    """The incremental reconstruction of the host mirror: baseReconstruction, then addMoreViews (findCameraPosePNP over
+    sfmhip_pnp_ransac, triangulateViews, mergeNewPoints, adjustCurrentBundle per added view) on a scene file of points and
+    matches or on a directory of frames (needs the GPU)."""
+    return _build_host_exe(os.path.join(HERE, "sfm_incr_selftest"),
+                           ("Sfm.cpp", "SfmIO.cpp", "SfmPose.cpp", "SfmIncremental.cpp", "BundleAdjustment.cpp", "incr_selftest.cpp"),
+                           force, std="c++17")
+
+
 def build_cloud_demo(force=False):
     """map3D's steps 8-10 in the host mirror (convertPLYtoPCD, loadPCDFile, cloudPointFilter, removePoints and create_mesh's
     normals, all on the unfiltered cloud as the reference calls them) on a PLY file (needs the GPU)."""
@@ -126,7 +135,7 @@ def build_cloud_demo(force=False):
 def _build_host_exe(exe, files, force, std="c++14"):
     host = os.path.join(CSRC, "host")
     srcs = [os.path.join(host, f) for f in files]
-    deps = srcs + [os.path.join(host, f) for f in os.listdir(host) if f.endswith(".h")] + [os.path.join(CSRC, "pose.h")]
+    deps = srcs + [os.path.join(host, f) for f in os.listdir(host) if f.endswith(".h")] + [os.path.join(CSRC, h) for h in ("pose.h", "pnp.h", "camera.h", "jacobi.h", "ransac_host.h")]
     if not force and os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(s) for s in deps):
         return exe
     build()

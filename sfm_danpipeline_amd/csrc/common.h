@@ -43,6 +43,8 @@ struct sfmhip_ctx {
   std::vector<sfmhip_ctx*> workers;
   int score_flags = 0;  // OR of the five-point samples' flags of the last sfmhip_score_essential call (score.hip)
   int pose_flags = 0;   // OR of the decompositions' flags of the last pose call (pose.hip, sfmhip_pose_last_flags)
+  int pnp_flags = 0;    // OR of the EPnP solves' flags of the last PnP call (pnp.hip, sfmhip_pnp_last_flags)
+  double pnp_ms[3] = {0, 0, 0};  // solver / scoring / refit kernel time of the last sfmhip_pnp_ransac call (timing on)
   // sfmhip_ba_solve (ba.hip): where the last call's time went, and the problem it keeps for a next call of the same structure
   sfmhip_ba_solve_profile ba_profile = {};
   void* ba_cache = nullptr;

@@ -1,6 +1,7 @@
 // Sfm.h -- the hot-path part of the reference's StructFromMotion (include/Sfm.h:15-35,89,
-// 107-117): same member names, same method signatures.  The PnP step (addMoreViews), the Poisson mesh and the
-// viewers are out of scope; map3D's step 10 filters and normals are in SfmCloud.cpp.
+// 107-117): same member names, same method signatures.  The incremental loop (addMoreViews, findCameraPosePNP over
+// sfmhip_pnp_ransac) is in SfmIncremental.cpp; the Poisson mesh and the viewers are out of scope;
+// map3D's step 10 filters and normals are in SfmCloud.cpp.
 #pragma once
 #include <map>
 #include <set>
@@ -118,6 +119,32 @@ class StructFromMotion {
   // (sfmhip_score_homography, confidence 0.995, 2000 iterations); fewer than 4 matches: none
   void prunedMatchingWithHomography(const int& idx_query, const int& idx_train, const Matching& goodMatches,
                                     Matching* prunedMatch);
+  // ---- the incremental loop (csrc/host/SfmIncremental.cpp; sfmhip_pnp_ransac)
+  // reference include/Sfm.h:141-142, src/Sfm.cpp:1137-1210: refuses 7 or fewer points or lists of different length;
+  // solvePnPRansac(K, dist, 1000 iterations, 0.006 * the largest 2-D coordinate, 0.99, CV_EPNP) = one sfmhip_pnp_ransac view
+  // (its rules: include/sfmhip.h); when RANSAC returns no inliers (no model: rvec and T stay zero, as the
+  // reference's freshly assigned outputs do) the points that project within 8 pixels form the inlier list; refuses
+  // norm(T) > 200 and a rotation that fails CheckCoherentRotation; P = [R|T].
+  // DEVIATION: the reference passes useExtrinsicGuess = true with an empty rvec; that is treated as no guess.
+  bool findCameraPosePNP(const Intrinsics& intrinsics, const std::vector<cv::Point3d>& pts3D,
+                         const std::vector<cv::Point2d>& pts2D, cv::Matx34d& P);
+  // reference include/Sfm.h:125, src/Sfm.cpp:893-1006, line by line: each round proposes the neighbours i - 1 / i + 1 of the
+  // done views (with the reference's quirks: |i - 1| for view 0 never arises, view nImages.size() is compared but cannot
+  // exist, so the last view proposes one past the end), every proposed view is
+  // marked done BEFORE its pose is tried, a posed view is triangulated against every good view (getMatching ->
+  // triangulateViews -> mergeNewPoints), becomes good, and adjustCurrentBundle() runs.
+  // DEVIATIONS: a proposed view outside [0, nImages.size()) is dropped (the reference would throw in .at()); the loop also
+  // ends when a round proposes no new view (the reference would spin when a view can never be reached).
+  bool addMoreViews();
+  // the inlier list of the last findCameraPosePNP (the reference computes it and reads it nowhere)
+  const std::vector<int>& lastPnpInliers() const { return pnpInliers; }
+  const std::set<int>& doneViews() const { return nDoneViews; }
+  const std::set<int>& goodViews() const { return nGoodViews; }
+
+ private:
+  std::vector<int> pnpInliers;
+
+ public:
   // what the last baseReconstruction chose (pose_selftest): the pair, E, R, T, recoverPose's count and mask
   struct BasePose {
     int query = -1, train = -1, n_good = 0;
@@ -205,5 +232,16 @@ class StructFromMotion {
   void setDoneViews(const std::set<int>& v) { nDoneViews = v; }
   void setGoodViews(const std::set<int>& v) { nGoodViews = v; }
   void clearPairCache() { pairCache.clear(); pairCacheOn = false; }
+  // n images without pixels or descriptors: what the loops that count images (nImages, mGrayImages, imagesDescriptors) see
+  void setImageCount(int n) {
+    nImages.resize((size_t)n);
+    mGrayImages.resize((size_t)n);
+    if (imagesDescriptors.size() < (size_t)n) imagesDescriptors.resize((size_t)n);
+  }
+  // precomputed matches of pair (q, t), q < t: getMatching serves them from the pair cache
+  void setPairMatches(int q, int t, const Matching& m) {
+    pairCache[std::make_pair(q, t)] = m;
+    pairCacheOn = true;
+  }
   size_t pairCacheSize() const { return pairCache.size(); }
 };

@@ -1,0 +1,111 @@
+// incr_selftest.cpp -- drives the incremental reconstruction of the C++ host mirror (needs the GPU): baseReconstruction()
+// then addMoreViews().
+//   incr_selftest --scene <scene.bin> <out.bin>
+// scene.bin: i32 n_img, f64 K[9], f64 dist[5]; per image: i32 n, n x f64 xy[2] (imagesPts2D); i32 n_pairs; per pair:
+// i32 q, i32 t (q < t), i32 m, m x (i32 queryIdx, i32 trainIdx): precomputed matches, served through the pair cache.
+//   incr_selftest --images <image dir> <calibration.xml> <out.bin>
+// imagesLOAD -> getCameraMatrix -> extractFeature, then the same two steps.
+// out.bin: i32 n_img, i32 base_q, i32 base_t (-1: no base pair; nothing follows), i32 cloud size after the base pair,
+//   n_img x f64 P[12] (zero: not registered), f64 K[9] (after the last bundle adjustment),
+//   i32 n_done, n_done x i32, i32 n_good, n_good x i32,
+//   i32 n_cloud, per point: f64 xyz[3], i32 n_track, n_track x (i32 view, i32 feature).
+// Exit 5 when baseReconstruction fails, 6 when addMoreViews does.
+#include <cstdio>
+#include <string>
+#include <vector>
+#include "Sfm.h"
+
+namespace {
+bool rd(FILE* f, void* p, size_t bytes) { return bytes == 0 || fread(p, bytes, 1, f) == 1; }
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc < 4) return 2;
+  StructFromMotion sfm;
+  std::string out;
+  int n_img = 0;
+  if (std::string(argv[1]) == "--scene") {
+    FILE* fi = fopen(argv[2], "rb");
+    if (!fi) return 2;
+    Intrinsics in;
+    in.K = cv::Mat_<double>(3, 3);
+    in.distCoef = cv::Mat_<double>(1, 5);
+    if (!rd(fi, &n_img, 4) || n_img < 2 || !rd(fi, in.K.data.data(), 72) || !rd(fi, in.distCoef.data.data(), 40)) return 2;
+    std::vector<Points2d> pts((size_t)n_img);
+    for (Points2d& p : pts) {
+      int n = 0;
+      if (!rd(fi, &n, 4) || n < 0) return 2;
+      p.resize((size_t)n);
+      if (!rd(fi, p.data(), 16 * (size_t)n)) return 2;
+    }
+    sfm.setDescriptors(std::vector<cv::Mat>((size_t)n_img));
+    sfm.setImageCount(n_img);
+    sfm.setPoints2D(pts);
+    sfm.setCameraMatrix(in);
+    int n_pairs = 0;
+    if (!rd(fi, &n_pairs, 4) || n_pairs < 0) return 2;
+    for (int p = 0; p < n_pairs; ++p) {
+      int hdr[3];
+      if (!rd(fi, hdr, 12) || hdr[0] < 0 || hdr[1] <= hdr[0] || hdr[1] >= n_img || hdr[2] < 0) return 2;
+      std::vector<int> qt(2 * (size_t)hdr[2]);
+      if (!rd(fi, qt.data(), 8 * (size_t)hdr[2])) return 2;
+      Matching m;
+      for (int i = 0; i < hdr[2]; ++i) {
+        if (qt[2 * i] < 0 || qt[2 * i] >= (int)pts[hdr[0]].size() || qt[2 * i + 1] < 0 || qt[2 * i + 1] >= (int)pts[hdr[1]].size()) return 2;
+        m.push_back(cv::DMatch(qt[2 * i], qt[2 * i + 1], 0.f));
+      }
+      sfm.setPairMatches(hdr[0], hdr[1], m);
+    }
+    fclose(fi);
+    out = argv[3];
+  } else if (std::string(argv[1]) == "--images") {
+    if (argc < 5) return 2;
+    if (!sfm.imagesLOAD(argv[2])) return 3;
+    if (!sfm.getCameraMatrix(argv[3])) return 4;
+    sfm.extractFeature();
+    n_img = (int)sfm.grayImages().size();
+    out = argv[4];
+  } else {
+    return 2;
+  }
+  if (!sfm.baseReconstruction()) return 5;
+  FILE* o = fopen(out.c_str(), "wb");
+  if (!o) return 2;
+  const StructFromMotion::BasePose& b = sfm.basePose();
+  fwrite(&n_img, 4, 1, o);
+  fwrite(&b.query, 4, 1, o);
+  fwrite(&b.train, 4, 1, o);
+  if (b.query < 0) {
+    fclose(o);
+    return 0;
+  }
+  const int base_cloud = (int)sfm.nReconstructionCloud.size();
+  fwrite(&base_cloud, 4, 1, o);
+  if (!sfm.addMoreViews()) {
+    fclose(o);
+    return 6;
+  }
+  for (int i = 0; i < n_img; ++i) {
+    const cv::Matx34d P = (size_t)i < sfm.cameraPoses().size() ? sfm.cameraPoses()[i] : cv::Matx34d();
+    fwrite(P.val, 8, 12, o);
+  }
+  fwrite(sfm.intrinsics().K.data.data(), 8, 9, o);
+  for (const std::set<int>* s : {&sfm.doneViews(), &sfm.goodViews()}) {
+    const int n = (int)s->size();
+    fwrite(&n, 4, 1, o);
+    for (int v : *s) fwrite(&v, 4, 1, o);
+  }
+  const int nc = (int)sfm.nReconstructionCloud.size();
+  fwrite(&nc, 4, 1, o);
+  for (const Point3D& p : sfm.nReconstructionCloud) {
+    fwrite(&p.pt.x, 8, 3, o);
+    const int nt = (int)p.idxImage.size();
+    fwrite(&nt, 4, 1, o);
+    for (const auto& kv : p.idxImage) {
+      const int vf[2] = {kv.first, kv.second};
+      fwrite(vf, 4, 2, o);
+    }
+  }
+  fclose(o);
+  return 0;
+}

@@ -20,6 +20,8 @@
 #include "common.h"
 #include "essential_dev.h"
 #include "hypot_glibc.h"
+#include "jacobi.h"
+#include "ransac_host.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -28,6 +30,9 @@
 #include <vector>
 
 namespace {
+
+using sfmjacobi::DevRng;  // (jacobi.h)
+using sfmjacobi::jacobi_svd;
 
 constexpr int MAX_MODELS = 10;
 
@@ -46,132 +51,8 @@ __device__ void mul21(const double* a /*10*/, const double* b /*4*/, double* out
   for (int i = 0; i < 10; ++i)
     for (int j = 0; j < 4; ++j) out[T21[i][j]] += s * a[i] * b[j];
 }
-// ---- cv::RNG (multiply with carry), as JacobiSVDImpl_ seeds it
-struct DevRng {
-  unsigned long long state;
-  __device__ unsigned next() {
-    state = (unsigned long long)(unsigned)state * 4164903690U + (unsigned)(state >> 32);
-    return (unsigned)state;
-  }
-};
-
-// ---- core/lapack.cpp JacobiSVDImpl_<double>: one-sided Jacobi on the N rows (length M, stride LDA) of At; rows N..N1-1
-// (and rows whose singular value is <= DBL_MIN) filled from RNG(0x12345678) sign vectors, orthogonalised twice against
-// the rows before them.  Vt (N x N) accumulates the rotations.  Operation for operation the restatement in
-// the CPU restatement used as checker (test infrastructure), which cites the library.
-template <int M, int N, int N1, int LDA>
-__device__ void jacobi_svd(double* At, double* W, double* Vt) {
-  const double minval = DBL_MIN, eps = DBL_EPSILON * 10;
-  const int max_iter = M > 30 ? M : 30;
-  for (int i = 0; i < N; ++i) {
-    double sd = 0;
-    for (int k = 0; k < M; ++k) {
-      const double t = At[i * LDA + k];
-      sd += t * t;
-    }
-    W[i] = sd;
-    for (int k = 0; k < N; ++k) Vt[i * N + k] = 0;
-    Vt[i * N + i] = 1;
-  }
-  for (int iter = 0; iter < max_iter; ++iter) {
-    bool changed = false;
-    for (int i = 0; i < N - 1; ++i)
-      for (int j = i + 1; j < N; ++j) {
-        double *Ai = At + i * LDA, *Aj = At + j * LDA;
-        double a = W[i], p = 0, b = W[j];
-        for (int k = 0; k < M; ++k) p += Ai[k] * Aj[k];
-        if (fabs(p) <= eps * sqrt(a * b)) continue;
-        p *= 2;
-        const double beta = a - b, gamma = sfm_hypot(p, beta);  // (the host libm's hypot, bit for bit: hypot_glibc.h)
-        double c, sn;
-        if (beta < 0) {
-          const double delta = (gamma - beta) * 0.5;
-          sn = sqrt(delta / gamma);
-          c = p / (gamma * sn * 2);
-        } else {
-          c = sqrt((gamma + beta) / (gamma * 2));
-          sn = p / (gamma * c * 2);
-        }
-        a = b = 0;
-        for (int k = 0; k < M; ++k) {
-          const double t0 = c * Ai[k] + sn * Aj[k];
-          const double t1 = -sn * Ai[k] + c * Aj[k];
-          Ai[k] = t0;
-          Aj[k] = t1;
-          a += t0 * t0;
-          b += t1 * t1;
-        }
-        W[i] = a;
-        W[j] = b;
-        changed = true;
-        double *Vi = Vt + i * N, *Vj = Vt + j * N;
-        for (int k = 0; k < N; ++k) {
-          const double t0 = c * Vi[k] + sn * Vj[k];
-          const double t1 = -sn * Vi[k] + c * Vj[k];
-          Vi[k] = t0;
-          Vj[k] = t1;
-        }
-      }
-    if (!changed) break;
-  }
-  for (int i = 0; i < N; ++i) {
-    double sd = 0;
-    for (int k = 0; k < M; ++k) {
-      const double t = At[i * LDA + k];
-      sd += t * t;
-    }
-    W[i] = sqrt(sd);
-  }
-  for (int i = 0; i < N - 1; ++i) {
-    int j = i;
-    for (int k = i + 1; k < N; ++k)
-      if (W[j] < W[k]) j = k;
-    if (i != j) {
-      double t = W[i];
-      W[i] = W[j];
-      W[j] = t;
-      for (int k = 0; k < M; ++k) {
-        t = At[i * LDA + k];
-        At[i * LDA + k] = At[j * LDA + k];
-        At[j * LDA + k] = t;
-      }
-      for (int k = 0; k < N; ++k) {
-        t = Vt[i * N + k];
-        Vt[i * N + k] = Vt[j * N + k];
-        Vt[j * N + k] = t;
-      }
-    }
-  }
-  DevRng rng{0x12345678ull};
-  for (int i = 0; i < N1; ++i) {
-    double sd = i < N ? W[i] : 0;
-    for (int ii = 0; ii < 100 && sd <= minval; ++ii) {
-      const double val0 = 1. / M;
-      for (int k = 0; k < M; ++k) At[i * LDA + k] = (rng.next() & 256) != 0 ? val0 : -val0;
-      for (int it2 = 0; it2 < 2; ++it2)
-        for (int j = 0; j < i; ++j) {
-          sd = 0;
-          for (int k = 0; k < M; ++k) sd += At[i * LDA + k] * At[j * LDA + k];
-          double asum = 0;
-          for (int k = 0; k < M; ++k) {
-            const double t = At[i * LDA + k] - sd * At[j * LDA + k];
-            At[i * LDA + k] = t;
-            asum += fabs(t);
-          }
-          asum = asum > eps * 100 ? 1 / asum : 0;
-          for (int k = 0; k < M; ++k) At[i * LDA + k] *= asum;
-        }
-      sd = 0;
-      for (int k = 0; k < M; ++k) {
-        const double t = At[i * LDA + k];
-        sd += t * t;
-      }
-      sd = sqrt(sd);
-    }
-    const double sc = sd > minval ? 1 / sd : 0.;
-    for (int k = 0; k < M; ++k) At[i * LDA + k] *= sc;
-  }
-}
+// (cv::RNG as JacobiSVDImpl_ seeds it, and JacobiSVDImpl_<double> itself -- jacobi_svd<M, N, N1, LDA> -- are in jacobi.h,
+// shared with the EPnP code and the CPU test stubs)
 
 // ---- hal::LU64f: A (10 x 10) against 10 right-hand sides b; false when a pivot is below 100 DBL_EPSILON
 __device__ bool lu_solve10(double* A, double* b) {
@@ -546,44 +427,8 @@ __global__ __launch_bounds__(256) void score_mask(const int* __restrict__ offset
 }
 
 // ---------------------------------------------------------------- host: cv::RNG, the sample tables, the update rule
-struct CvRng {
-  unsigned long long state = 0xFFFFFFFFFFFFFFFFull;  // RNG rng((uint64)-1)
-  unsigned next() {
-    state = (unsigned long long)(unsigned)state * 4164903690U + (unsigned)(state >> 32);
-    return (unsigned)state;
-  }
-  int uniform(int a, int b) { return a == b ? a : (int)(next() % (unsigned)(b - a) + a); }
-};
-struct SampleStream {  // the samples of one match count, generated on demand
-  CvRng rng;
-  std::vector<int> idx;  // 5 per iteration
-  void extend(int count, int n_iters) {
-    while ((int)idx.size() < 5 * n_iters) {
-      int s[5];
-      for (int i = 0; i < 5;) {
-        const int v = rng.uniform(0, count);
-        int j = 0;
-        for (; j < i; ++j)
-          if (s[j] == v) break;
-        if (j < i) continue;  // drawn before: again
-        s[i++] = v;
-      }
-      idx.insert(idx.end(), s, s + 5);
-    }
-  }
-};
-int ransac_update_num_iters(double p, double ep, int model_points, int max_iters) {
-  p = std::max(p, 0.0);
-  p = std::min(p, 1.0);
-  ep = std::max(ep, 0.0);
-  ep = std::min(ep, 1.0);
-  double num = std::max(1.0 - p, DBL_MIN);
-  double denom = 1.0 - std::pow(1.0 - ep, model_points);
-  if (denom < DBL_MIN) return 0;
-  num = std::log(num);
-  denom = std::log(denom);
-  return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)std::nearbyint(num / denom);  // cvRound
-}
+// (cv::RNG, the distinct-index subset draw and RANSACUpdateNumIters are in ransac_host.h, shared with the PnP RANSAC)
+using namespace sfmransac;
 
 
 // ================================================================ homography (findHomographyInliers, src/Sfm.cpp:667-689)

@@ -8,53 +8,20 @@
 // HBM-bound by construction (2 x 16 B in, 24 B + 1 B (+8 B) out per match); the track /
 // visibility bookkeeping (Point3D::idxImage, src/Sfm.cpp:862-873) is the host mirror's job.
 #include "common.h"
+#include "camera.h"
 #include "pose.h"
 #include <float.h>
 
 namespace {
 
 using sfmpose::dlt_null_vector;  // (pose.h: shared with the pose kernels and the CPU test stub)
+using sfmcam::project_point;     // (camera.h: shared with the PnP kernels and their CPU test stub)
+using sfmcam::undistort_point;
 
 struct TriParams {
   double P1[12], P2[12], K[9], dist[5];
   float max_err;
 };
-
-__device__ __forceinline__ void undistort_point(const TriParams& p, double u, double v, double& xo, double& yo) {
-  const double ifx = 1. / p.K[0], ify = 1. / p.K[4];
-  double x = (u - p.K[2]) * ifx, y = (v - p.K[5]) * ify;
-  const double x0 = x, y0 = y;
-  const double k1 = p.dist[0], k2 = p.dist[1], p1 = p.dist[2], p2 = p.dist[3], k3 = p.dist[4];
-#pragma unroll 1
-  for (int j = 0; j < 5; ++j) {
-    const double r2 = x * x + y * y;
-    const double icdist = 1. / (1 + ((k3 * r2 + k2) * r2 + k1) * r2);
-    const double deltaX = 2 * p1 * x * y + p2 * (r2 + 2 * x * x);
-    const double deltaY = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
-    x = (x0 - deltaX) * icdist;
-    y = (y0 - deltaY) * icdist;
-  }
-  xo = x;
-  yo = y;
-}
-
-__device__ __forceinline__ void project_point(const double* P, const TriParams& p, const double X[3], double& u,
-                                              double& v) {
-  double x = P[0] * X[0] + P[1] * X[1] + P[2] * X[2] + P[3];
-  double y = P[4] * X[0] + P[5] * X[1] + P[6] * X[2] + P[7];
-  double z = P[8] * X[0] + P[9] * X[1] + P[10] * X[2] + P[11];
-  z = z ? 1. / z : 1;
-  x *= z;
-  y *= z;
-  const double k1 = p.dist[0], k2 = p.dist[1], p1 = p.dist[2], p2 = p.dist[3], k3 = p.dist[4];
-  const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-  const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
-  const double cdist = 1 + k1 * r2 + k2 * r4 + k3 * r6;
-  const double xd = x * cdist + p1 * a1 + p2 * a2;
-  const double yd = y * cdist + p1 * a3 + p2 * a1;
-  u = xd * p.K[0] + p.K[2];
-  v = yd * p.K[4] + p.K[5];
-}
 
 __global__ __launch_bounds__(256) void triangulate_kernel(TriParams p, const double2* __restrict__ xy1,
                                                           const double2* __restrict__ xy2, int m,
@@ -65,8 +32,8 @@ __global__ __launch_bounds__(256) void triangulate_kernel(TriParams p, const dou
   const double2 a = live ? xy1[i] : make_double2(0, 0);
   const double2 b = live ? xy2[i] : make_double2(0, 0);
   double x1, y1, x2, y2;
-  undistort_point(p, a.x, a.y, x1, y1);
-  undistort_point(p, b.x, b.y, x2, y2);
+  undistort_point(p.K, p.dist, a.x, a.y, x1, y1);
+  undistort_point(p.K, p.dist, b.x, b.y, x2, y2);
   double At[4][4];  // At[c][r] = A[r][c]
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -80,8 +47,8 @@ __global__ __launch_bounds__(256) void triangulate_kernel(TriParams p, const dou
   const double scale = v[3] != 0 ? 1. / v[3] : 1.;
   const double Xi[3] = {v[0] * scale, v[1] * scale, v[2] * scale};
   double u1, v1, u2, v2;
-  project_point(p.P1, p, Xi, u1, v1);
-  project_point(p.P2, p, Xi, u2, v2);
+  project_point(p.P1, p.K, p.dist, Xi, u1, v1);
+  project_point(p.P2, p.K, p.dist, Xi, u2, v2);
   const double dx1 = u1 - a.x, dy1 = v1 - a.y, dx2 = u2 - b.x, dy2 = v2 - b.y;
   const float e1 = (float)sqrt(dx1 * dx1 + dy1 * dy1);
   const float e2 = (float)sqrt(dx2 * dx2 + dy2 * dy2);
