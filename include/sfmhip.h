@@ -373,6 +373,62 @@ int sfmhip_cloud_knn(sfmhip_cloud* cloud, int k, int32_t* idx, float* d2);
 /* NormalEstimation with setKSearch(k), k in 1..32, viewpoint vp[3]: out4 = n x (nx, ny, nz, curvature). */
 int sfmhip_cloud_normals(sfmhip_cloud* cloud, int k, const float* vp /* 3 */, float* out4);
 
+/* ---- colour region growing and the dendrometry bounds (reference src/Segmentation.cpp:3-66, src/DendrometryE.cpp:3-29) ----
+ * pcl::RegionGrowingRGB over the index list of a PassThrough, on the same device-resident cloud.  The rules (DESIGN.md
+ * f-8 has them in full; parity UNPINNED, PCL is not in the image; + marks what is our reading):
+ *   1. the options below; the three thresholds are stored squared, in float;
+ *   2. every indexed point gets its min(region_neighbour_number, n_idx) nearest INDEXED points, itself included, in
+ *      (d2, index) order +, d2 as above; a point outside the list (or non-finite +) has no list and is nobody's neighbour;
+ *   3. colour difference: the integer sum of the squared differences of the 8-bit channels of 0x00RRGGBB;
+ *   4. growth: seeds in list order; a flood (FIFO) from each unlabelled seed looks at the first neighbour_number
+ *      entries of the current point u and takes an unlabelled v iff colour_diff(u, v) <= point threshold^2;
+ *   5. segment neighbours: the minimum d2 over all entries of a segment's points to each other segment, the
+ *      region_neighbour_number nearest kept, stored in descending (d2, segment) order; segment colour per channel
+ *      unsigned(float(sum) / float(count));
+ *   6. homogeneous merging in segment order over the stored lists (d2 > distance^2 skipped; an unlabelled neighbour
+ *      joins iff its colour difference to THIS segment is < region threshold^2), then every region under
+ *      min_cluster_size moves into the region of the nearest entry of its list (sorted by (d2, segment) +);
+ *   7. clusters in region order after PCL's swap-with-last compaction of emptied regions +, then those outside
+ *      [min_cluster_size, max_cluster_size] erased.
+ * The index list must be strictly ascending (what sfmhip_cloud_passthrough writes); an empty or malformed list is
+ * SFMHIP_ERR_ARG.  rgb: n packed colours as a PCD's rgb field holds them (the top byte is ignored). */
+typedef struct {
+  int32_t region_neighbour_number; /* 100 (1..128) */
+  int32_t neighbour_number;        /* 30 */
+  int32_t min_cluster_size;        /* 600 */
+  int32_t max_cluster_size;        /* INT_MAX */
+  float distance_threshold;        /* 10 */
+  float point_color_threshold;     /* 6 */
+  float region_color_threshold;    /* 5 */
+} sfmhip_segment_opts;
+typedef struct {
+  int32_t n_idx;      /* indexed points that took part (the finite ones) */
+  int32_t n_segments; /* segments the growth made */
+  int32_t n_regions;  /* regions the homogeneous merging opened */
+  int32_t rounds;     /* label-propagation rounds */
+} sfmhip_segment_stats;
+/* the reference's values (setDistanceThreshold(10), setPointColorThreshold(6), setRegionColorThreshold(5),
+ * setMinClusterSize(600); PCL's defaults for the rest) */
+void sfmhip_segment_default_opts(sfmhip_segment_opts* opts);
+/* labels: n entries, the final cluster of every point of the cloud, -1 = in no cluster; cluster c lists its points in
+ * ascending index.  *n_clusters = 0 is not an error here (the reference exits on it).  stats may be NULL. */
+int sfmhip_cloud_segment_rgb(sfmhip_cloud* cloud, const uint32_t* rgb /* n */, const int32_t* indices, int n_idx,
+                             const sfmhip_segment_opts* opts, int32_t* labels /* n */, int32_t* n_clusters,
+                             sfmhip_segment_stats* stats);
+/* staged: rule 2 alone.  idx / d2 are n_idx x k (k in 1..128), row r for indices[r]; idx holds cloud indices, -1 / +inf
+ * where the list is shorter than k. */
+int sfmhip_cloud_subset_knn(sfmhip_cloud* cloud, const int32_t* indices, int n_idx, int k, int32_t* idx, float* d2);
+/* staged: rules 2-4.  segment: n entries, the growth's segment of every point (-1 outside the list). */
+int sfmhip_cloud_segment_grow(sfmhip_cloud* cloud, const uint32_t* rgb, const int32_t* indices, int n_idx,
+                              const sfmhip_segment_opts* opts, int32_t* segment /* n */, int32_t* n_segments,
+                              int32_t* rounds);
+/* host-clock ms of the last sfmhip_cloud_segment_rgb call on this handle: subset k-NN, growth, segment statistics,
+ * the host's region step, the whole call. */
+int sfmhip_cloud_segment_last_timing(sfmhip_cloud* cloud, double* ms5);
+/* pcl::getMinMax3D over the finite points + (FLT_MAX / -FLT_MAX for none) and, if height is not NULL,
+ * Dendrometry::estimate's "Total Height": the sqrt of the double sum of squares of the float differences. */
+int sfmhip_cloud_minmax(sfmhip_cloud* cloud, float* mn /* 3 */, float* mx /* 3 */, double* height);
+
 /* ---- adjustBundle solver core (reference src/BundleAdjustment.cpp:46-175) ---- */
 typedef struct {
   int max_iterations;           /* 500   src/BundleAdjustment.cpp:118 */

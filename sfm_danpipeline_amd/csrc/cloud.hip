@@ -21,89 +21,23 @@
 // The arithmetic is cloud.h's, which the CPU test stub compiles too.
 #include "common.h"
 #include "cloud.h"
+#include "cloud_grid.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+using namespace sfmgrid;
+
 namespace {
 
-constexpr int CHUNK = 64;                 // points per radius_count workgroup (one wave)
 constexpr int KNN_BLOCK = 256;
-constexpr long long AXIS_CAP = 1 << 12;   // cells per axis
-constexpr long long CELL_CAP = 1 << 22;   // cells in all
 constexpr double KNN_OCCUPANCY = 16.0;    // points per occupied cell the k-NN grid aims at
-
-struct GridDev {
-  double o[3], cell;
-  int D[3];
-  int n_valid;
-  const int* start;
-  const int* end;
-  const int* keys;    // sorted cell ids (n_valid)
-  const float4* pts;  // sorted points, w = the input index's bits
-};
-
-struct Grid {
-  bool built = false;
-  double param = 0;  // the radius it was built for (radius grid)
-  double o[3] = {0, 0, 0}, cell = 1;
-  int D[3] = {1, 1, 1};
-  long long ncell = 1;
-  int nonempty = 0;
-  int* start = nullptr;
-  int* end = nullptr;
-  int* keys = nullptr;
-  float4* pts = nullptr;
-  int4* chunks = nullptr;
-  int n_chunks = 0;
-  void release() {
-    hipFree(start);
-    hipFree(end);
-    hipFree(keys);
-    hipFree(pts);
-    hipFree(chunks);
-    start = end = keys = nullptr;
-    pts = nullptr;
-    chunks = nullptr;
-    built = false;
-    n_chunks = nonempty = 0;
-  }
-  GridDev dev(int n_valid) const {
-    GridDev g;
-    for (int a = 0; a < 3; ++a) {
-      g.o[a] = o[a];
-      g.D[a] = D[a];
-    }
-    g.cell = cell;
-    g.n_valid = n_valid;
-    g.start = start;
-    g.end = end;
-    g.keys = keys;
-    g.pts = pts;
-    return g;
-  }
-};
 
 }  // namespace
 
-struct sfmhip_cloud {
-  sfmhip_ctx* ctx = nullptr;
-  int n = 0, n_valid = 0;
-  float* xyz = nullptr;          // 3 n, as given
-  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // box of the finite points
-  Grid rg, kg;                   // radius grid, k-NN grid
-  void* tmp = nullptr;           // rocPRIM temporary storage (grow-only)
-  size_t tmp_bytes = 0;
-  int* ibuf[4] = {nullptr, nullptr, nullptr, nullptr};  // 4 int scratch arrays of max(n, 1) (keys / values in, flags, scan)
-  int* cbuf[2] = {nullptr, nullptr};                    // 2 int scratch arrays of ncell (chunk counts and offsets)
-  long long cbuf_n = 0;
-};
-
-namespace {
-
-int grow_tmp(sfmhip_cloud* c, size_t bytes) {
+int sfmgrid::grow_tmp(sfmhip_cloud* c, size_t bytes) {
   if (bytes <= c->tmp_bytes) return SFMHIP_OK;
   hipFree(c->tmp);
   c->tmp = nullptr;
@@ -113,12 +47,7 @@ int grow_tmp(sfmhip_cloud* c, size_t bytes) {
   return SFMHIP_OK;
 }
 
-__device__ __forceinline__ int cell_of(double v, double o, double cell, int D) {
-  double f = floor((v - o) / cell);
-  f = f < 0.0 ? 0.0 : f;
-  f = f > (double)(D - 1) ? (double)(D - 1) : f;
-  return (int)f;
-}
+namespace {
 
 __global__ void cloud_keys(const float* xyz, int n, GridDev g, int invalid, int* keys, int* vals) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -197,17 +126,6 @@ __global__ __launch_bounds__(CHUNK) void cloud_radius_count(GridDev g, const int
     }
 done:
   if (live) counts[__float_as_int(p.w)] = cap > 0 ? min(cnt, cap) : cnt;
-}
-
-// distance from p to the nearest face of the block of cells [c - R, c + R] that has cells beyond it (+inf if none)
-__device__ __forceinline__ double block_bound(const GridDev& g, const float4& p, const int c[3], int R) {
-  const double pv[3] = {(double)p.x, (double)p.y, (double)p.z};
-  double b = INFINITY;
-  for (int a = 0; a < 3; ++a) {
-    if (c[a] - R > 0) b = fmin(b, fmax(0.0, pv[a] - (g.o[a] + (double)(c[a] - R) * g.cell)));
-    if (c[a] + R < g.D[a] - 1) b = fmin(b, fmax(0.0, (g.o[a] + (double)(c[a] + R + 1) * g.cell) - pv[a]));
-  }
-  return b;
 }
 
 template <int N>
@@ -310,23 +228,34 @@ __global__ void cloud_scatter(const int* flags, const int* off, int n, int* out,
   if (i == n - 1) *n_out = off[i] + flags[i];
 }
 
-unsigned blocks(long long n, int b) { return (unsigned)((n + b - 1) / b); }
+}  // namespace
 
-int ensure_ibuf(sfmhip_cloud* c) {
+int sfmgrid::ensure_ibuf(sfmhip_cloud* c) {
   if (c->ibuf[0]) return SFMHIP_OK;
   for (int b = 0; b < 4; ++b) SFM_TRY(sfm_dev_alloc(&c->ibuf[b], (size_t)std::max(c->n, 1)));
   return SFMHIP_OK;
 }
 
-// build `g` with cells of `cell` (grown by 2 until the grid fits CELL_CAP); chunk list for the radius kernel if asked
-int grid_build(sfmhip_cloud* c, Grid& g, double cell, bool chunks) {
+GridSrc sfmgrid::whole_cloud(const sfmhip_cloud* c) {
+  GridSrc s;
+  s.xyz = c->xyz;
+  s.n = c->n;
+  s.n_valid = c->n_valid;
+  for (int a = 0; a < 3; ++a) {
+    s.lo[a] = c->lo[a];
+    s.hi[a] = c->hi[a];
+  }
+  return s;
+}
+
+int sfmgrid::grid_build(sfmhip_cloud* c, const GridSrc& src, Grid& g, double cell, bool chunks) {
   g.release();
   SFM_TRY(ensure_ibuf(c));
   hipStream_t st = c->ctx->stream;
   for (;;) {
     long long tot = 1;
     for (int a = 0; a < 3; ++a) {
-      const double ext = c->n_valid ? c->hi[a] - c->lo[a] : 0.0;
+      const double ext = src.n_valid ? src.hi[a] - src.lo[a] : 0.0;
       const double d = std::floor(ext / cell) + 1.0;
       g.D[a] = (int)std::min((double)AXIS_CAP, d);
       tot *= g.D[a];
@@ -337,35 +266,35 @@ int grid_build(sfmhip_cloud* c, Grid& g, double cell, bool chunks) {
     }
     cell *= 2;
   }
-  for (int a = 0; a < 3; ++a) g.o[a] = c->lo[a];
+  for (int a = 0; a < 3; ++a) g.o[a] = src.lo[a];
   g.cell = cell;
   SFM_TRY(sfm_dev_alloc(&g.start, (size_t)g.ncell));
   SFM_TRY(sfm_dev_alloc(&g.end, (size_t)g.ncell));
-  SFM_TRY(sfm_dev_alloc(&g.keys, (size_t)std::max(c->n, 1)));
-  SFM_TRY(sfm_dev_alloc(&g.pts, (size_t)std::max(c->n_valid, 1)));
+  SFM_TRY(sfm_dev_alloc(&g.keys, (size_t)std::max(src.n, 1)));
+  SFM_TRY(sfm_dev_alloc(&g.pts, (size_t)std::max(src.n_valid, 1)));
   SFM_HIP_TRY(hipMemsetAsync(g.start, 0, sizeof(int) * g.ncell, st));
   SFM_HIP_TRY(hipMemsetAsync(g.end, 0, sizeof(int) * g.ncell, st));
   int* nonempty = c->ibuf[3];
   SFM_HIP_TRY(hipMemsetAsync(nonempty, 0, sizeof(int), st));
-  if (c->n > 0) {
+  if (src.n > 0) {
     int *kin = c->ibuf[0], *vin = c->ibuf[1], *vout = c->ibuf[2];
-    GridDev gd = g.dev(c->n_valid);
-    hipLaunchKernelGGL(cloud_keys, dim3(blocks(c->n, 256)), dim3(256), 0, st, c->xyz, c->n, gd, (int)g.ncell, kin, vin);
+    GridDev gd = g.dev(src.n_valid);
+    hipLaunchKernelGGL(cloud_keys, dim3(blocks(src.n, 256)), dim3(256), 0, st, src.xyz, src.n, gd, (int)g.ncell, kin, vin);
     SFM_HIP_TRY(hipGetLastError());
     unsigned bits = 1;
     while (bits < 31 && (1ll << bits) <= g.ncell) ++bits;  // (the invalid key is ncell)
     size_t need = 0;
-    SFM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, kin, g.keys, vin, vout, (unsigned)c->n, 0u, bits, st));
+    SFM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, kin, g.keys, vin, vout, (unsigned)src.n, 0u, bits, st));
     SFM_TRY(grow_tmp(c, need));
     need = c->tmp_bytes;
-    SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp, need, kin, g.keys, vin, vout, (unsigned)c->n, 0u, bits, st));
-    if (c->n_valid > 0)
-      hipLaunchKernelGGL(cloud_ranges, dim3(blocks(c->n_valid, 256)), dim3(256), 0, st, c->xyz, g.keys, vout, c->n_valid, g.start,
+    SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp, need, kin, g.keys, vin, vout, (unsigned)src.n, 0u, bits, st));
+    if (src.n_valid > 0)
+      hipLaunchKernelGGL(cloud_ranges, dim3(blocks(src.n_valid, 256)), dim3(256), 0, st, src.xyz, g.keys, vout, src.n_valid, g.start,
                          g.end, g.pts, nonempty);
     SFM_HIP_TRY(hipGetLastError());
   }
   SFM_HIP_TRY(hipMemcpyAsync(&g.nonempty, nonempty, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (chunks && c->n_valid > 0) {
+  if (chunks && src.n_valid > 0) {
     if (c->cbuf_n < g.ncell) {
       hipFree(c->cbuf[0]);
       hipFree(c->cbuf[1]);
@@ -397,29 +326,34 @@ int grid_build(sfmhip_cloud* c, Grid& g, double cell, bool chunks) {
   return SFMHIP_OK;
 }
 
+int sfmgrid::density_grid(sfmhip_cloud* c, const GridSrc& src, Grid& g, double occupancy) {
+  double ext = 0, vol = 1;
+  for (int a = 0; a < 3; ++a) ext = std::max(ext, src.hi[a] - src.lo[a]);
+  if (!(ext > 0)) ext = 1;
+  for (int a = 0; a < 3; ++a) vol *= std::max(src.hi[a] - src.lo[a], ext * 1e-3);
+  double cell = std::cbrt(vol * occupancy / std::max(src.n_valid, 1));
+  SFM_TRY(grid_build(c, src, g, cell, false));
+  for (int it = 0; it < 6 && g.nonempty > 0; ++it) {  // (a far outlier stretches the box: several rounds)
+    const double occ = (double)src.n_valid / g.nonempty;
+    if (occ <= 2 * occupancy) break;
+    SFM_TRY(grid_build(c, src, g, g.cell * std::max(1e-3, std::sqrt(occupancy / occ)), false));
+  }
+  return SFMHIP_OK;
+}
+
+namespace {
+
 int radius_grid(sfmhip_cloud* c, double radius) {
   if (c->rg.built && c->rg.param == radius) return SFMHIP_OK;
-  SFM_TRY(grid_build(c, c->rg, radius * (1.0 + 1.0 / 1024.0), true));
+  SFM_TRY(grid_build(c, whole_cloud(c), c->rg, radius * (1.0 + 1.0 / 1024.0), true));
   c->rg.param = radius;
   return SFMHIP_OK;
 }
 
-// the k-NN grid: a first guess from the box volume, then rebuilds while the occupied cells hold far more points than
-// aimed at (a surface fills few of the cells a volume estimate makes: cells shrink by the square root of the excess)
+// the k-NN grid: about KNN_OCCUPANCY points per occupied cell
 int knn_grid(sfmhip_cloud* c) {
   if (c->kg.built) return SFMHIP_OK;
-  double ext = 0, vol = 1;
-  for (int a = 0; a < 3; ++a) ext = std::max(ext, c->hi[a] - c->lo[a]);
-  if (!(ext > 0)) ext = 1;
-  for (int a = 0; a < 3; ++a) vol *= std::max(c->hi[a] - c->lo[a], ext * 1e-3);
-  double cell = std::cbrt(vol * KNN_OCCUPANCY / std::max(c->n_valid, 1));
-  SFM_TRY(grid_build(c, c->kg, cell, false));
-  for (int it = 0; it < 6 && c->kg.nonempty > 0; ++it) {  // (a far outlier stretches the box: several rounds)
-    const double occ = (double)c->n_valid / c->kg.nonempty;
-    if (occ <= 2 * KNN_OCCUPANCY) break;
-    SFM_TRY(grid_build(c, c->kg, c->kg.cell * std::max(1e-3, std::sqrt(KNN_OCCUPANCY / occ)), false));
-  }
-  return SFMHIP_OK;
+  return density_grid(c, whole_cloud(c), c->kg, KNN_OCCUPANCY);
 }
 
 int compact(sfmhip_cloud* c, int32_t* idx_out, int32_t* n_out) {
@@ -520,6 +454,7 @@ extern "C" void sfmhip_cloud_destroy(sfmhip_cloud* c) {
   hipStreamSynchronize(c->ctx->stream);
   c->rg.release();
   c->kg.release();
+  if (c->seg && c->seg_free) c->seg_free(c->seg);
   hipFree(c->xyz);
   hipFree(c->tmp);
   for (int b = 0; b < 4; ++b) hipFree(c->ibuf[b]);

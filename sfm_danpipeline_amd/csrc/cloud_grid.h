@@ -1,0 +1,129 @@
+// cloud_grid.h -- the device-resident cloud (sfmhip_cloud) and its uniform grids, shared by cloud.hip (map3D's step 10)
+// and segment.hip (the colour region growing after it).  The bodies of the host functions declared here live in
+// cloud.hip; the two device helpers are inline.
+//
+// Spatial index: cell coordinates floor((x - lo) / cell) in double, clamped to the grid (a far outlier lands in a
+// border cell instead of stretching the grid: clamping keeps two points whose true cells are adjacent in adjacent
+// cells, so no neighbour is lost), the linear cell id x-fastest, then rocPRIM's radix sort of (cell, point) pairs and
+// a pass that records each cell's [start, end) in sorted order.  Non-finite points get the key one past the last cell
+// and are in no cell.
+#pragma once
+#include "common.h"
+#include <cmath>
+
+namespace sfmgrid {
+
+constexpr int CHUNK = 64;                 // points per radius_count workgroup (one wave)
+constexpr long long AXIS_CAP = 1 << 12;   // cells per axis
+constexpr long long CELL_CAP = 1 << 22;   // cells in all
+
+struct GridDev {
+  double o[3], cell;
+  int D[3];
+  int n_valid;
+  const int* start;
+  const int* end;
+  const int* keys;    // sorted cell ids (n_valid)
+  const float4* pts;  // sorted points, w = the input index's bits
+};
+
+struct Grid {
+  bool built = false;
+  double param = 0;  // the radius it was built for (radius grid)
+  double o[3] = {0, 0, 0}, cell = 1;
+  int D[3] = {1, 1, 1};
+  long long ncell = 1;
+  int nonempty = 0;
+  int* start = nullptr;
+  int* end = nullptr;
+  int* keys = nullptr;
+  float4* pts = nullptr;
+  int4* chunks = nullptr;
+  int n_chunks = 0;
+  void release() {
+    hipFree(start);
+    hipFree(end);
+    hipFree(keys);
+    hipFree(pts);
+    hipFree(chunks);
+    start = end = keys = nullptr;
+    pts = nullptr;
+    chunks = nullptr;
+    built = false;
+    n_chunks = nonempty = 0;
+  }
+  GridDev dev(int n_valid) const {
+    GridDev g;
+    for (int a = 0; a < 3; ++a) {
+      g.o[a] = o[a];
+      g.D[a] = D[a];
+    }
+    g.cell = cell;
+    g.n_valid = n_valid;
+    g.start = start;
+    g.end = end;
+    g.keys = keys;
+    g.pts = pts;
+    return g;
+  }
+};
+
+// the points a grid is built over: the handle's own cloud, or a subset gathered into an array of its own (at most as
+// many points as the handle's cloud: the scratch arrays are sized by it)
+struct GridSrc {
+  const float* xyz;  // 3 n, on the device
+  int n, n_valid;
+  double lo[3], hi[3];  // box of the finite points
+};
+
+}  // namespace sfmgrid
+
+struct sfmhip_cloud {
+  sfmhip_ctx* ctx = nullptr;
+  int n = 0, n_valid = 0;
+  float* xyz = nullptr;          // 3 n, as given
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // box of the finite points
+  sfmgrid::Grid rg, kg;          // radius grid, k-NN grid
+  void* tmp = nullptr;           // rocPRIM temporary storage (grow-only)
+  size_t tmp_bytes = 0;
+  int* ibuf[4] = {nullptr, nullptr, nullptr, nullptr};  // 4 int scratch arrays of max(n, 1) (keys / values in, flags, scan)
+  int* cbuf[2] = {nullptr, nullptr};                    // 2 int scratch arrays of ncell (chunk counts and offsets)
+  long long cbuf_n = 0;
+  void* seg = nullptr;           // segment.hip's state on this handle (the subset grid and its buffers), freed with it
+  void (*seg_free)(void*) = nullptr;
+};
+
+namespace sfmgrid {
+
+inline unsigned blocks(long long n, int b) { return (unsigned)((n + b - 1) / b); }
+int grow_tmp(sfmhip_cloud* c, size_t bytes);
+int ensure_ibuf(sfmhip_cloud* c);
+GridSrc whole_cloud(const sfmhip_cloud* c);
+// build `g` over `src` with cells of `cell` (grown by 2 until the grid fits CELL_CAP); chunk list for the radius kernel if asked
+int grid_build(sfmhip_cloud* c, const GridSrc& src, Grid& g, double cell, bool chunks);
+// a grid sized by density: a first guess from the box volume, then rebuilds while the occupied cells hold far more
+// points than `occupancy` (a surface fills few of the cells a volume estimate makes: cells shrink by the square root of
+// the excess)
+int density_grid(sfmhip_cloud* c, const GridSrc& src, Grid& g, double occupancy);
+
+#ifdef __HIPCC__
+__device__ __forceinline__ int cell_of(double v, double o, double cell, int D) {
+  double f = floor((v - o) / cell);
+  f = f < 0.0 ? 0.0 : f;
+  f = f > (double)(D - 1) ? (double)(D - 1) : f;
+  return (int)f;
+}
+
+// distance from p to the nearest face of the block of cells [c - R, c + R] that has cells beyond it (+inf if none)
+__device__ __forceinline__ double block_bound(const GridDev& g, const float4& p, const int c[3], int R) {
+  const double pv[3] = {(double)p.x, (double)p.y, (double)p.z};
+  double b = INFINITY;
+  for (int a = 0; a < 3; ++a) {
+    if (c[a] - R > 0) b = fmin(b, fmax(0.0, pv[a] - (g.o[a] + (double)(c[a] - R) * g.cell)));
+    if (c[a] + R < g.D[a] - 1) b = fmin(b, fmax(0.0, (g.o[a] + (double)(c[a] + R + 1) * g.cell) - pv[a]));
+  }
+  return b;
+}
+#endif
+
+}  // namespace sfmgrid

@@ -1,0 +1,45 @@
+// DendrometryE.cpp -- Dendrometry::estimate (reference src/DendrometryE.cpp:3-29) in the host mirror: the bounds of the
+// cloud on the device (sfmhip_cloud_minmax) and the reference's printed lines, the empty ones included.
+#include "DendrometryE.h"
+#include <cstdio>
+#include <cstdlib>
+#include <iostream>
+#include <vector>
+#include "hip_backend.h"
+
+void Dendrometry::estimate(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL) {
+  std::cout << "************************************************" << std::endl;
+  std::cout << "              DENDROMETRY ESTIMATION            " << std::endl;
+  std::cout << "************************************************" << std::endl;
+
+  const int n = (int)cloudPCL->size();
+  std::vector<float> xyz((size_t)3 * n + 3);
+  for (int i = 0; i < n; ++i) {
+    xyz[3 * (size_t)i] = cloudPCL->points[i].x;
+    xyz[3 * (size_t)i + 1] = cloudPCL->points[i].y;
+    xyz[3 * (size_t)i + 2] = cloudPCL->points[i].z;
+  }
+  sfmhip_cloud* dev = nullptr;
+  int rc = sfmhip_cloud_create(sfm_hip_context(), n, xyz.data(), &dev);
+  if (rc == SFMHIP_OK) rc = sfmhip_cloud_minmax(dev, min_, max_, &height_);
+  if (rc != SFMHIP_OK) {
+    std::fprintf(stderr, "[sfm] sfmhip_cloud_minmax: %s\n", sfmhip_error_string(rc));
+    std::abort();  // (no CPU fallback behind the drop-in)
+  }
+  sfmhip_cloud_destroy(dev);
+
+  std::cout << "Max: [" << max_[0] << ", " << max_[1] << ", " << max_[2] << "]" << std::endl;  // (cv::Point3f's operator<<)
+  std::cout << "Min: [" << min_[0] << ", " << min_[1] << ", " << min_[2] << "]" << std::endl;
+
+  std::cout << "*** Measurements ***" << std::endl;
+  std::cout << "Total Height =" << height_ << std::endl;
+  std::cout << "Altura copa viva=" << std::endl;
+  std::cout << "Altura base de copa=" << std::endl;
+  std::cout << "Altura DAP=" << 1.3 << std::endl;
+  std::cout << "DAP=" << std::endl;
+  std::cout << "Amplitud N-S=" << std::endl;
+  std::cout << "Amplitud E-W=" << std::endl;
+
+  std::cout << "************************************************" << std::endl;
+  std::cout << "************************************************" << std::endl;
+}

@@ -1,6 +1,6 @@
 // pcllite.h -- the few PCL 1.8.1 types map3D's step 10 passes around (reference src/Sfm.cpp:94-102, include/Sfm.h:182-186),
 // as plain stand-ins next to cvlite.h (PCL is not a dependency of this build), and the PCD reader that loads MAP3D.pcd
-// into them (pcl::io::loadPCDFile for PointXYZ).  Header-only and C++14: the host mirror and the CPU tests include it.
+// into them (pcl::io::loadPCDFile for PointXYZ and PointXYZRGB).  Header-only and C++14: the host mirror and the CPU tests include it.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -19,6 +19,22 @@ struct PointXYZ {
   float x, y, z;
   PointXYZ() : x(0), y(0), z(0) {}
   PointXYZ(float x_, float y_, float z_) : x(x_), y(y_), z(z_) {}
+};
+
+// x, y, z and the packed colour 0x00RRGGBB (PCL's rgba member; its float view `rgb` is what a PCD's rgb field of TYPE F holds)
+struct PointXYZRGB {
+  float x, y, z;
+  uint32_t rgba;
+  PointXYZRGB() : x(0), y(0), z(0), rgba(0) {}
+  PointXYZRGB(float x_, float y_, float z_, uint32_t c) : x(x_), y(y_), z(z_), rgba(c) {}
+  uint8_t r() const { return (uint8_t)(rgba >> 16); }
+  uint8_t g() const { return (uint8_t)(rgba >> 8); }
+  uint8_t b() const { return (uint8_t)rgba; }
+};
+
+// one cluster: the indices of its points in the input cloud
+struct PointIndices {
+  std::vector<int> indices;
 };
 
 struct Normal {
@@ -44,11 +60,23 @@ struct PointCloud {
 
 namespace io {
 
-// pcl::io::loadPCDFile(path, cloud) for PointXYZ: PCD v0.5-0.7, DATA ascii or binary (little-endian records), fields x,
-// y, z of TYPE F and SIZE 4 or 8 (other fields skipped); binary_compressed is refused with a message.  Returns 0, or
-// -1 when the file is missing, malformed or truncated (the cloud is then left empty).  is_dense = every point finite.
-inline int loadPCDFile(const std::string& path, PointCloud<PointXYZ>& cloud) {
-  cloud = PointCloud<PointXYZ>();
+// The reader behind both loadPCDFile overloads: PCD v0.5-0.7, DATA ascii or binary (little-endian records), fields x,
+// y, z of TYPE F and SIZE 4 or 8 and, when `colour` is asked for, a field rgb or rgba of SIZE 4 (TYPE F: the packed
+// colour's bits as a float, what convertPLYtoPCD writes; TYPE U / I: the packed integer); other fields are skipped and
+// a file without a colour field gives colour 0; binary_compressed is refused with a message.  Returns 0, or -1 when
+// the file is missing, malformed or truncated.  is_dense = every point finite.
+struct PcdRecord {
+  float v[3];
+  uint32_t c;
+};
+struct PcdFile {
+  std::vector<PcdRecord> points;
+  uint32_t width = 0, height = 0;
+  bool is_dense = true;
+  float origin[3] = {0, 0, 0};
+};
+inline int readPCD(const std::string& path, bool colour, PcdFile& file) {
+  file = PcdFile();
   FILE* f = std::fopen(path.c_str(), "rb");
   if (!f) {
     std::fprintf(stderr, "[pcd] cannot open %s\n", path.c_str());
@@ -118,10 +146,21 @@ inline int loadPCDFile(const std::string& path, PointCloud<PointXYZ>& cloud) {
     std::fprintf(stderr, "[pcd] %s: unknown DATA '%s'\n", path.c_str(), data.c_str());
     return -1;
   }
-  int col[3] = {-1, -1, -1}, off[3] = {0, 0, 0}, fsz[3] = {0, 0, 0};
+  int col[4] = {-1, -1, -1, -1}, off[4] = {0, 0, 0, 0}, fsz[4] = {0, 0, 0, 0};
+  bool colour_is_float = true;
   int ncol = 0, rec = 0;
   for (size_t i = 0; i < names.size(); ++i) {
     const int a = names[i] == "x" ? 0 : names[i] == "y" ? 1 : names[i] == "z" ? 2 : -1;
+    if (colour && (names[i] == "rgb" || names[i] == "rgba")) {
+      if (sizes[i] != 4 || counts[i] != 1 || (types[i] != "F" && types[i] != "U" && types[i] != "I")) {
+        std::fprintf(stderr, "[pcd] %s: field %s must be one 4-byte value\n", path.c_str(), names[i].c_str());
+        return -1;
+      }
+      col[3] = ncol;
+      off[3] = rec;
+      fsz[3] = 4;
+      colour_is_float = types[i] == "F";
+    }
     if (a >= 0) {
       if (types[i] != "F" || (sizes[i] != 4 && sizes[i] != 8) || counts[i] != 1) {
         std::fprintf(stderr, "[pcd] %s: field %s must be one float\n", path.c_str(), names[i].c_str());
@@ -142,7 +181,7 @@ inline int loadPCDFile(const std::string& path, PointCloud<PointXYZ>& cloud) {
     std::fprintf(stderr, "[pcd] %s: no x y z fields\n", path.c_str());
     return -1;
   }
-  PointCloud<PointXYZ> out;
+  PcdFile out;
   out.points.resize((size_t)points);
   bool dense = true;
   if (data == "binary") {
@@ -162,7 +201,9 @@ inline int loadPCDFile(const std::string& path, PointCloud<PointXYZ>& cloud) {
           v[a] = (float)d;
         }
       }
-      out.points[(size_t)k] = PointXYZ(v[0], v[1], v[2]);
+      PcdRecord q = {{v[0], v[1], v[2]}, 0};
+      if (col[3] >= 0) std::memcpy(&q.c, r + off[3], 4);
+      out.points[(size_t)k] = q;
     }
   } else {
     const char* p = buf.empty() ? "" : &buf[0];
@@ -171,6 +212,7 @@ inline int loadPCDFile(const std::string& path, PointCloud<PointXYZ>& cloud) {
     std::string tok;
     for (long long k = 0; k < points; ++k) {
       float v[3] = {0, 0, 0};
+      uint32_t packed = 0;
       for (int c = 0; c < ncol; ++c) {
         while (p < end && (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n')) ++p;
         const char* s = p;
@@ -189,18 +231,55 @@ inline int loadPCDFile(const std::string& path, PointCloud<PointXYZ>& cloud) {
               return -1;
             }
           }
+        if (c == col[3]) {
+          tok.assign(s, p - s);
+          char* q = nullptr;
+          if (colour_is_float) {
+            const float fc = std::strtof(tok.c_str(), &q);  // (8 digits give the packed bits back, subnormals included)
+            std::memcpy(&packed, &fc, 4);
+          } else {
+            packed = (uint32_t)std::strtoll(tok.c_str(), &q, 10);
+          }
+          if (q == tok.c_str()) {
+            std::fprintf(stderr, "[pcd] %s: bad number '%s'\n", path.c_str(), tok.c_str());
+            return -1;
+          }
+        }
       }
-      out.points[(size_t)k] = PointXYZ(v[0], v[1], v[2]);
+      PcdRecord q = {{v[0], v[1], v[2]}, packed};
+      out.points[(size_t)k] = q;
     }
   }
-  for (const PointXYZ& q : out.points) dense = dense && std::isfinite(q.x) && std::isfinite(q.y) && std::isfinite(q.z);
+  for (const PcdRecord& q : out.points) dense = dense && std::isfinite(q.v[0]) && std::isfinite(q.v[1]) && std::isfinite(q.v[2]);
   out.width = (uint32_t)width;
   out.height = (uint32_t)height;
   out.is_dense = dense;
-  for (int k = 0; k < 3; ++k) out.sensor_origin_[k] = vp[k];
-  out.sensor_origin_[3] = 0;
-  cloud = out;
+  for (int k = 0; k < 3; ++k) out.origin[k] = vp[k];
+  file = out;
   return 0;
+}
+
+template <typename T, typename F>
+inline int loadPCDInto(const std::string& path, bool colour, PointCloud<T>& cloud, F make) {
+  cloud = PointCloud<T>();
+  PcdFile f;
+  if (readPCD(path, colour, f) != 0) return -1;
+  cloud.points.resize(f.points.size());
+  for (size_t k = 0; k < f.points.size(); ++k) cloud.points[k] = make(f.points[k]);
+  cloud.width = f.width;
+  cloud.height = f.height;
+  cloud.is_dense = f.is_dense;
+  for (int k = 0; k < 3; ++k) cloud.sensor_origin_[k] = f.origin[k];
+  cloud.sensor_origin_[3] = 0;
+  return 0;
+}
+
+// pcl::io::loadPCDFile(path, cloud) for PointXYZ and for PointXYZRGB (the cloud is left empty on failure)
+inline int loadPCDFile(const std::string& path, PointCloud<PointXYZ>& cloud) {
+  return loadPCDInto(path, false, cloud, [](const PcdRecord& q) { return PointXYZ(q.v[0], q.v[1], q.v[2]); });
+}
+inline int loadPCDFile(const std::string& path, PointCloud<PointXYZRGB>& cloud) {
+  return loadPCDInto(path, true, cloud, [](const PcdRecord& q) { return PointXYZRGB(q.v[0], q.v[1], q.v[2], q.c & 0x00FFFFFFu); });
 }
 
 }  // namespace io
