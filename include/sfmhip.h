@@ -429,6 +429,71 @@ int sfmhip_cloud_segment_last_timing(sfmhip_cloud* cloud, double* ms5);
  * Dendrometry::estimate's "Total Height": the sqrt of the double sum of squares of the float differences. */
 int sfmhip_cloud_minmax(sfmhip_cloud* cloud, float* mn /* 3 */, float* mx /* 3 */, double* height);
 
+/* ---- the second half of create_mesh: Poisson surface reconstruction (reference src/Sfm.cpp:1365-1381) ----
+ * pcl::Poisson at depth 7 on the cloud and its flipped normals, as a screened Poisson solve on the same device-resident
+ * cloud.  The rules (PCL 1.8.1 parity is UNPINNED -- PCL is absent and its solver is an adaptive octree):
+ *   deviations: the grid is uniform at full depth (PCL: adaptive octree), the extraction is marching tetrahedra (PCL:
+ *   marching cubes).  PCL setters with no counterpart: samplesPerNode, isoDivide, solverDivide, manifold,
+ *   outputPolygons; confidence has no effect on unit normals.
+ *   1. samples: the finite points whose normal is finite and non-zero; the others are skipped.  No usable sample: an
+ *      empty mesh, status OK.  depth 1..8 (7), scale 1..16 (1.1), point_weight >= 0 (4), cg_rtol in [0, 1) (1e-8),
+ *      cg_max_iter (0 = 4 * 2^depth); outside: SFMHIP_ERR_ARG.
+ *   2. cube: centre = midpoint of the samples' box (f64), side = scale * largest extent (extent 0: side 1),
+ *      N = 2^depth cells per side, h = side / N, unknowns at the cell centres, u = (p - origin) / h - 1/2.
+ *   3. splat: B(t) = 3/4 - t^2 (|t| < 1/2), (3/2 - |t|)^2 / 2 (|t| < 3/2), 0; V_c = sum B(u_p - c) n_p and
+ *      W_c = sum B(u_p - c) over the samples of the 27 cells around c, in f64, gathered per cell (no atomics):
+ *      neighbour cells ascending in (z, y, x), samples ascending by input index.  Nothing lands outside the cube.
+ *   4. system: (L + point_weight diag(W)) chi = -div V in h = 1 units; L the 7-point negative Laplacian with chi = 0
+ *      outside, div by central differences with V = 0 outside.
+ *   5. conjugate gradients in f64 from chi = 0 until |r|^2 <= cg_rtol^2 |b|^2 or cg_max_iter steps; dot products in
+ *      the fixed order of csrc/poisson.h (bricks of 16 x 4 x 4 cells, a 256-entry tree per brick, then the bricks by
+ *      residue class mod 256 and the same tree); no contraction.  The decision is taken on the device.
+ *   6. iso-value: the mean of the trilinear chi at the samples, summed in the same fixed order.
+ *   7. extraction on the (N - 1)^3 cubes between cell centres, each split into the six tetrahedra around its main
+ *      diagonal; a corner is inside iff chi < iso; one vertex per crossed edge at linear interpolation, id from (lower
+ *      corner, edge class 0..6); triangles wound so that their normals point towards chi > iso.  Vertices ascending
+ *      by edge id, triangles by (cube, tetrahedron, case order).  float32 xyz in cloud coordinates, int32 x 3.
+ * normals: n rows of normal_stride floats, nx ny nz first -- 4 is the layout sfmhip_cloud_normals writes (the curvature
+ * in the fourth float is not read), 3 is packed.
+ * Hitting cg_max_iter is not an error: compare cg_iterations and cg_relative_residual of the summary with the options.
+ * The default cap does not reach cg_rtol 1e-8 at depth 7 (about 6 * 2^depth steps are needed); create_mesh passes
+ * 8 * 2^depth.  The handle keeps the call's device blocks (over 300 MB at depth 7) for its next call until it is
+ * destroyed. */
+typedef struct {
+  int32_t depth;
+  double scale, point_weight, cg_rtol;
+  int32_t cg_max_iter;   /* 0: 4 * 2^depth */
+  int32_t normal_stride; /* 3 or 4 (default) */
+} sfmhip_poisson_opts;
+
+typedef struct {
+  int32_t n_samples, n_vertices, n_triangles, cg_iterations;
+  double cg_relative_residual; /* |r| / |b| when the solve stopped */
+  double iso_value;
+  double origin[3], cell; /* the cube's low corner and h */
+  int32_t grid;           /* N */
+} sfmhip_poisson_summary;
+
+typedef struct sfmhip_mesh sfmhip_mesh;
+void sfmhip_poisson_default_opts(sfmhip_poisson_opts* opts);
+int sfmhip_cloud_poisson(sfmhip_cloud* cloud, const float* normals, const sfmhip_poisson_opts* opts, sfmhip_mesh** out,
+                         sfmhip_poisson_summary* summary);
+int sfmhip_mesh_counts(const sfmhip_mesh* mesh, int32_t* n_vertices, int32_t* n_triangles);
+int sfmhip_mesh_download(const sfmhip_mesh* mesh, float* vertices /* 3 nv */, int32_t* triangles /* 3 nt */);
+void sfmhip_mesh_destroy(sfmhip_mesh* mesh);
+/* staged: rules 1-4.  V: 3 N^3 (axis-major, cells x-fastest), W and rhs: N^3. */
+int sfmhip_cloud_poisson_splat(sfmhip_cloud* cloud, const float* normals, const sfmhip_poisson_opts* opts, double* V, double* W,
+                               double* rhs, sfmhip_poisson_summary* summary);
+/* staged: rule 5 from a given right-hand side.  rr_bb (may be NULL): the final and the initial squared residual. */
+int sfmhip_poisson_solve(sfmhip_ctx* ctx, int depth, const double* rhs, const double* W, double point_weight, double cg_rtol,
+                         int cg_max_iter, double* chi, int32_t* iterations, double* rr_bb);
+/* staged: rule 7 from a given field on an n^3 grid (any n in 2..256), grid point (x, y, z) at origin + (x + 1/2) cell. */
+int sfmhip_poisson_extract(sfmhip_ctx* ctx, int n, const double* chi, double iso, const double* origin /* 3 */, double cell,
+                           sfmhip_mesh** out);
+/* host-clock ms of the last sfmhip_cloud_poisson call on this handle: samples + splat, solve, iso-value + extraction,
+ * the whole call. */
+int sfmhip_cloud_poisson_last_timing(sfmhip_cloud* cloud, double* ms4);
+
 /* ---- adjustBundle solver core (reference src/BundleAdjustment.cpp:46-175) ---- */
 typedef struct {
   int max_iterations;           /* 500   src/BundleAdjustment.cpp:118 */

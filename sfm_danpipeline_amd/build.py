@@ -15,7 +15,7 @@ SO = os.path.join(HERE, "libsfmhip.so")
 # and want v_fma_f64 -- "fast-honor-pragmas", not "fast": the one function that must NOT contract, the trust-region decision
 # lm_decide (the same bits on the host and on the device), says so with a pragma, which plain "fast" ignores
 SOURCES = {"context.hip": "off", "match.hip": "off", "triangulate.hip": "off", "incremental.hip": "off",
-           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "segment.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
+           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "segment.hip": "off", "poisson.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -130,6 +130,13 @@ def build_cloud_demo(force=False):
     normals, all on the unfiltered cloud as the reference calls them) on a PLY file (needs the GPU)."""
     return _build_host_exe(os.path.join(HERE, "sfm_cloud_selftest"),
                            ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "cloud_selftest.cpp"), force)
+
+
+def build_mesh_demo(force=False):
+    """map3D's last call in the host mirror (create_mesh: the normals, their flip, then Poisson at depth 7) on a MAP3D.pcd;
+    writes the mesh as a binary PLY (needs the GPU)."""
+    return _build_host_exe(os.path.join(HERE, "sfm_mesh_selftest"),
+                           ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "mesh_selftest.cpp"), force)
 
 
 def build_segment_demo(force=False):

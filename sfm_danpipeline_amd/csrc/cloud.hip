@@ -455,6 +455,7 @@ extern "C" void sfmhip_cloud_destroy(sfmhip_cloud* c) {
   c->rg.release();
   c->kg.release();
   if (c->seg && c->seg_free) c->seg_free(c->seg);
+  if (c->psn && c->psn_free) c->psn_free(c->psn);
   hipFree(c->xyz);
   hipFree(c->tmp);
   for (int b = 0; b < 4; ++b) hipFree(c->ibuf[b]);

@@ -91,6 +91,9 @@ struct sfmhip_cloud {
   long long cbuf_n = 0;
   void* seg = nullptr;           // segment.hip's state on this handle (the subset grid and its buffers), freed with it
   void (*seg_free)(void*) = nullptr;
+  double psn_ms[4] = {0, 0, 0, 0};  // poisson.hip: stage times of the last sfmhip_cloud_poisson call on this handle
+  void* psn = nullptr;           // poisson.hip's grow-only device blocks on this handle, freed with it
+  void (*psn_free)(void*) = nullptr;
 };
 
 namespace sfmgrid {

@@ -209,8 +209,18 @@ class StructFromMotion {
   void removePoints(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PointCloud<pcl::PointXYZ>::Ptr& filterCloud);
   // the first half of create_mesh (reference include/Sfm.h:186, src/Sfm.cpp:1346-1366): NormalEstimation with
   // setKSearch(10) towards the cloud's sensor origin, then every normal multiplied by -1.  normals has one entry per
-  // point of `cloud` (NaN where PCL writes NaN).  The Poisson half is not built.
+  // point of `cloud` (NaN where PCL writes NaN).
   void computeNormals(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PointCloud<pcl::Normal>::Ptr& normals);
+  // create_mesh (reference include/Sfm.h:186, src/Sfm.cpp:1346-1381): computeNormals (with its -1 flip), the cloud and
+  // its normals concatenated, then pcl::Poisson with setDepth(7), setPointWeight(4), setScale(1.1) -- here
+  // sfmhip_cloud_poisson on the same device cloud (a uniform 128^3 grid for PCL's octree, marching
+  // tetrahedra for its cubes; parity UNPINNED).  Ignored PCL setters, having no counterpart: setSamplesPerNode(1),
+  // setIsoDivide(8), setSolverDivide(8), setManifold(false), setOutputPolygons(false); setConfidence(1) has no effect on
+  // unit normals.  The solve runs with cg_max_iter = 8 * 2^depth = 1024: the library's default of 4 * 2^depth = 512 steps
+  // does not reach cg_rtol 1e-8 at depth 7 (a 200 k-point sphere takes 538); a solve that still ends at the cap is
+  // reported on stderr with its residual.  mesh.cloud takes the vertices, mesh.polygons the triangles.  vizualizeMesh is
+  // not built (GUI).
+  void create_mesh(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PolygonMesh& mesh);
 
   const std::vector<cv::Mat>& colorImages() const { return mColorImages; }
   const std::vector<cv::Mat>& grayImages() const { return mGrayImages; }

@@ -1,5 +1,5 @@
 // SfmCloud.cpp -- map3D's step 10 on the dense cloud (reference src/Sfm.cpp:94-102, bodies :1323-1383) in the host
-// mirror: cloudPointFilter, removePoints and the normal half of create_mesh over sfmhip_cloud_* (cloud.hip).  Kept out
+// mirror: cloudPointFilter, removePoints and create_mesh (normals, then Poisson) over sfmhip_cloud_* (cloud.hip, poisson.hip).  Kept out
 // of Sfm.cpp / SfmIO.cpp, which the oracle's sanitizer builds link against a CPU stub of the C ABI.
 #include <cstdio>
 #include <cstdlib>
@@ -102,4 +102,39 @@ void StructFromMotion::computeNormals(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud
   r.is_dense = dense;
   for (int a = 0; a < 4; ++a) r.sensor_origin_[a] = cloud->sensor_origin_[a];
   *normals = r;
+}
+
+void StructFromMotion::create_mesh(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PolygonMesh& mesh) {
+  pcl::PointCloud<pcl::Normal>::Ptr normals(new pcl::PointCloud<pcl::Normal>);
+  computeNormals(cloud, normals);  // (flipped already)
+  // pcl::concatenateFields(*cloud, *normals, *cloud_smoothed_normals): the points are on the device already, so only
+  // the normals are laid out, in the 4-float rows sfmhip_cloud_poisson reads
+  std::vector<float> nrm(4 * cloud->size() + 4);
+  for (size_t i = 0; i < cloud->size(); ++i) {
+    const pcl::Normal& q = normals->points[i];
+    nrm[4 * i] = q.normal_x, nrm[4 * i + 1] = q.normal_y, nrm[4 * i + 2] = q.normal_z, nrm[4 * i + 3] = q.curvature;
+  }
+  sfmhip_poisson_opts o;
+  sfmhip_poisson_default_opts(&o);  // setDepth(7), setPointWeight(4), setScale(1.1); rows of 4 floats
+  // the default cap of 4 * 2^depth steps ends conjugate gradients short of cg_rtol at depth 7 (about
+  // 6 * 2^depth steps are needed); twice the default lets the solve converge
+  o.cg_max_iter = 8 << o.depth;
+  sfmhip_mesh* m = nullptr;
+  sfmhip_poisson_summary s;
+  check(sfmhip_cloud_poisson(device_cloud(*cloud), nrm.data(), &o, &m, &s), "sfmhip_cloud_poisson");
+  if (s.cg_iterations >= o.cg_max_iter && s.cg_relative_residual > o.cg_rtol)
+    std::fprintf(stderr, "create_mesh: the Poisson solve stopped at its cap of %d steps with relative residual %.3e (cg_rtol %.1e)\n",
+                 (int)o.cg_max_iter, s.cg_relative_residual, o.cg_rtol);
+  std::vector<float> v(3 * (size_t)s.n_vertices + 3);
+  std::vector<int32_t> t(3 * (size_t)s.n_triangles + 3);
+  check(sfmhip_mesh_download(m, v.data(), t.data()), "sfmhip_mesh_download");
+  sfmhip_mesh_destroy(m);
+  mesh = pcl::PolygonMesh();
+  mesh.cloud.points.resize((size_t)s.n_vertices);
+  for (int i = 0; i < s.n_vertices; ++i) mesh.cloud.points[i] = pcl::PointXYZ(v[3 * i], v[3 * i + 1], v[3 * i + 2]);
+  mesh.cloud.width = (uint32_t)s.n_vertices;
+  mesh.cloud.height = 1;
+  mesh.polygons.resize((size_t)s.n_triangles);
+  for (int i = 0; i < s.n_triangles; ++i)
+    mesh.polygons[i].vertices = {(uint32_t)t[3 * i], (uint32_t)t[3 * i + 1], (uint32_t)t[3 * i + 2]};
 }

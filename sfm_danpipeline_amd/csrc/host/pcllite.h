@@ -58,6 +58,24 @@ struct PointCloud {
   }
 };
 
+// a point with its normal: what create_mesh hands to pcl::Poisson (pcl::concatenateFields of the cloud and its normals)
+struct PointNormal {
+  float x, y, z, normal_x, normal_y, normal_z, curvature;
+  PointNormal() : x(0), y(0), z(0), normal_x(0), normal_y(0), normal_z(0), curvature(0) {}
+};
+
+// one polygon: indices into the mesh's cloud
+struct Vertices {
+  std::vector<uint32_t> vertices;
+};
+
+// pcl::PolygonMesh keeps its vertices as a PCLPointCloud2 blob; the stand-in keeps them as the PointXYZ cloud that
+// pcl::fromPCLPointCloud2 would read out of it.  polygons: triangles (Poisson's outputPolygons is off)
+struct PolygonMesh {
+  PointCloud<PointXYZ> cloud;
+  std::vector<Vertices> polygons;
+};
+
 namespace io {
 
 // The reader behind both loadPCDFile overloads: PCD v0.5-0.7, DATA ascii or binary (little-endian records), fields x,
