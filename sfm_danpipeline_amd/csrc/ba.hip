@@ -5530,33 +5530,21 @@ extern "C" int sfmhip_ba_linearize_obs(sfmhip_ctx* ctx, int n, const double* cam
   SFM_HIP_TRY(hipSetDevice(ctx->device));
   double *d_in = nullptr, *d_out = nullptr;
   const size_t nin = (size_t)n * 11, nout = (size_t)n * 22;
-  int rc = sfm_dev_alloc(&d_in, nin);
-  if (rc == SFMHIP_OK) rc = sfm_dev_alloc(&d_out, nout);
-  if (rc != SFMHIP_OK) {
-    hipFree(d_in);
-    hipFree(d_out);
-    return rc;
-  }
+  DevBufs bufs;
+  SFM_TRY(bufs.alloc(&d_in, nin));
+  SFM_TRY(bufs.alloc(&d_out, nout));
   hipStream_t st = ctx->stream;
-  hipError_t e = hipMemcpyAsync(d_in, cams6, sizeof(double) * 6 * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_in + 6 * (size_t)n, pts3, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_in + 9 * (size_t)n, obs_xy, sizeof(double) * 2 * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(ba_linearize_obs_kernel, dim3((n + 127) / 128), dim3(128), 0, st, d_in, d_in + 6 * (size_t)n, focal,
-                       d_in + 9 * (size_t)n, n, d_out, d_out + 2 * (size_t)n, d_out + 14 * (size_t)n, d_out + 20 * (size_t)n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(r, d_out, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(Jc, d_out + 2 * (size_t)n, sizeof(double) * 12 * n, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(Jp, d_out + 14 * (size_t)n, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(Jf, d_out + 20 * (size_t)n, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  hipFree(d_in);
-  hipFree(d_out);
-  if (e != hipSuccess) {
-    g_sfmhip_last_hip_error = (int)e;
-    return SFMHIP_ERR_HIP;
-  }
+  SFM_HIP_TRY(hipMemcpyAsync(d_in, cams6, sizeof(double) * 6 * n, hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemcpyAsync(d_in + 6 * (size_t)n, pts3, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemcpyAsync(d_in + 9 * (size_t)n, obs_xy, sizeof(double) * 2 * n, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(ba_linearize_obs_kernel, dim3((n + 127) / 128), dim3(128), 0, st, d_in, d_in + 6 * (size_t)n, focal,
+                     d_in + 9 * (size_t)n, n, d_out, d_out + 2 * (size_t)n, d_out + 14 * (size_t)n, d_out + 20 * (size_t)n);
+  SFM_HIP_TRY(hipGetLastError());
+  SFM_HIP_TRY(hipMemcpyAsync(r, d_out, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipMemcpyAsync(Jc, d_out + 2 * (size_t)n, sizeof(double) * 12 * n, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipMemcpyAsync(Jp, d_out + 14 * (size_t)n, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipMemcpyAsync(Jf, d_out + 20 * (size_t)n, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipStreamSynchronize(st));
   return SFMHIP_OK;
 }
 

@@ -1,5 +1,6 @@
 // common.h -- context object and error plumbing shared by the HIP translation units.
 #pragma once
+#include <chrono>
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,4 +85,24 @@ static inline int sfm_dev_alloc(T** p, size_t n) {
   }
   *p = (T*)v;
   return SFMHIP_OK;
+}
+
+struct DevBufs {  // device memory of one call (or one object), freed with it
+  std::vector<void*> p;
+  DevBufs() = default;
+  DevBufs(const DevBufs&) = delete;
+  DevBufs& operator=(const DevBufs&) = delete;
+  ~DevBufs() {
+    for (void* q : p) hipFree(q);
+  }
+  template <typename T>
+  int alloc(T** out, size_t n) {
+    const int rc = sfm_dev_alloc(out, n);
+    if (rc == SFMHIP_OK) p.push_back((void*)*out);
+    return rc;
+  }
+};
+
+static inline double sfm_now_ms() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }

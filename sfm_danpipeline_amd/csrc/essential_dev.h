@@ -5,8 +5,7 @@
 #include "common.h"
 
 struct EssentialDev {
-  // every buffer below is freed with the object
-  std::vector<void*> bufs;
+  DevBufs bufs;  // every buffer below is freed with the object
   double* d_left = nullptr;   // the pixel coordinates as given: 2 doubles per match
   double* d_right = nullptr;
   double* d_p1 = nullptr;     // normalised with (fx, fy, cx, cy): findEssentialMat's points
@@ -16,17 +15,6 @@ struct EssentialDev {
   unsigned char* d_has = nullptr;   // per pair: 0 no model, 1 a RANSAC model, 2 exactly five matches
   unsigned char* d_mask = nullptr;  // the RANSAC mask, 1 byte per match (want_mask only)
   std::vector<unsigned char> has;
-  EssentialDev() = default;
-  EssentialDev(const EssentialDev&) = delete;
-  EssentialDev& operator=(const EssentialDev&) = delete;
-  ~EssentialDev() {
-    for (void* p : bufs) hipFree(p);
-  }
-  int alloc(void** p, size_t bytes) {
-    if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) return SFMHIP_ERR_ALLOC;
-    bufs.push_back(*p);
-    return SFMHIP_OK;
-  }
 };
 
 // findEssentialMat(left, right, K, RANSAC, prob, threshold) for a batch of pairs (arguments checked by the caller).

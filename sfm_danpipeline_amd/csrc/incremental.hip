@@ -162,19 +162,6 @@ __global__ void init_state_kernel(const unsigned char* __restrict__ near, unsign
   if (i < n) state[i] = near[i] ? 2 : 0;
 }
 
-struct DevBuf {  // frees on scope exit
-  std::vector<void*> p;
-  ~DevBuf() {
-    for (void* q : p) hipFree(q);
-  }
-  template <typename T>
-  int alloc(T** out, size_t n) {
-    const int rc = sfm_dev_alloc(out, n);
-    if (rc == SFMHIP_OK) p.push_back((void*)*out);
-    return rc;
-  }
-};
-
 }  // namespace
 
 extern "C" int sfmhip_find_2d3d(sfmhip_ctx* ctx, const int32_t* trk_ptr, const int32_t* trk_view,
@@ -197,7 +184,7 @@ extern "C" int sfmhip_find_2d3d(sfmhip_ctx* ctx, const int32_t* trk_ptr, const i
   for (int m = 0; m < n_match; ++m) tbl_n = key_h[m] + 1 > tbl_n ? key_h[m] + 1 : tbl_n;
   if (tbl_n <= 0) return SFMHIP_OK;
   const int nblk = (n_cloud + BLK - 1) / BLK;
-  DevBuf buf;
+  DevBufs buf;
   int *d_ptr, *d_view, *d_feat, *d_key, *d_oth, *d_first, *d_val, *d_cnt, *d_total, *d_oi, *d_ov;
   SFM_TRY(buf.alloc(&d_ptr, (size_t)n_cloud + 1));
   SFM_TRY(buf.alloc(&d_view, (size_t)n_ent));
@@ -253,7 +240,7 @@ extern "C" int sfmhip_merge_new_points(sfmhip_ctx* ctx, const double* cloud_xyz,
     while (thr > 0 && !(std::sqrt(thr) < r)) thr = std::nextafter(thr, 0.0);
     while (std::sqrt(std::nextafter(thr, INFINITY)) < r) thr = std::nextafter(thr, INFINITY);
   }
-  DevBuf buf;
+  DevBufs buf;
   double *d_cloud = nullptr, *d_new = nullptr;
   unsigned char *d_far = nullptr, *d_state = nullptr;
   int* d_und = nullptr;

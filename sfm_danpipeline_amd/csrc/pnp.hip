@@ -360,28 +360,6 @@ __global__ __launch_bounds__(256) void pnp_epnp_group(const int* __restrict__ of
   }
 }
 
-struct DevBufs {  // device memory of one call, freed with the object
-  std::vector<void*> v;
-  ~DevBufs() {
-    for (void* p : v) hipFree(p);
-  }
-  template <typename T>
-  int alloc(T** p, size_t n) {
-    const int rc = sfm_dev_alloc(p, n);
-    if (rc == SFMHIP_OK) v.push_back(*p);
-    return rc;
-  }
-};
-
-#define PNP_HIP(expr)                          \
-  do {                                         \
-    const hipError_t e__ = (expr);             \
-    if (e__ != hipSuccess) {                   \
-      g_sfmhip_last_hip_error = (int)e__;      \
-      return SFMHIP_ERR_HIP;                   \
-    }                                          \
-  } while (0)
-
 // the device side of ransac_replay
 struct DeviceBackend {
   hipStream_t st;
@@ -413,23 +391,23 @@ struct DeviceBackend {
       SFM_TRY(bufs.alloc(&d_samples, samples.size()));
       cap_samples = samples.size();
     }
-    PNP_HIP(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * nj, hipMemcpyHostToDevice, st));
-    PNP_HIP(hipMemcpyAsync(d_samples, samples.data(), sizeof(int) * samples.size(), hipMemcpyHostToDevice, st));
-    if (ev[0]) PNP_HIP(hipEventRecord(ev[0], st));
+    SFM_HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * nj, hipMemcpyHostToDevice, st));
+    SFM_HIP_TRY(hipMemcpyAsync(d_samples, samples.data(), sizeof(int) * samples.size(), hipMemcpyHostToDevice, st));
+    if (ev[0]) SFM_HIP_TRY(hipEventRecord(ev[0], st));
     hipLaunchKernelGGL(pnp_solve, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, st, (const Job*)d_jobs, (int)nj, chunk,
                        (const int*)d_samples, d_xyz, d_xy, p, d_work, d_models, d_ok);
-    if (ev[0]) PNP_HIP(hipEventRecord(ev[1], st));
+    if (ev[0]) SFM_HIP_TRY(hipEventRecord(ev[1], st));
     hipLaunchKernelGGL(pnp_count, dim3((unsigned)slots), dim3(256), 0, st, (const Job*)d_jobs, chunk, d_xyz, d_xy, p, d_thr2,
                        (const double*)d_models, (const int*)d_ok, d_counts);
-    if (ev[0]) PNP_HIP(hipEventRecord(ev[2], st));
-    PNP_HIP(hipGetLastError());
-    PNP_HIP(hipMemcpyAsync(ok.data(), d_ok, sizeof(int) * slots, hipMemcpyDeviceToHost, st));
-    PNP_HIP(hipMemcpyAsync(counts.data(), d_counts, sizeof(int) * slots, hipMemcpyDeviceToHost, st));
-    PNP_HIP(hipStreamSynchronize(st));
+    if (ev[0]) SFM_HIP_TRY(hipEventRecord(ev[2], st));
+    SFM_HIP_TRY(hipGetLastError());
+    SFM_HIP_TRY(hipMemcpyAsync(ok.data(), d_ok, sizeof(int) * slots, hipMemcpyDeviceToHost, st));
+    SFM_HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, sizeof(int) * slots, hipMemcpyDeviceToHost, st));
+    SFM_HIP_TRY(hipStreamSynchronize(st));
     if (ev[0]) {
       float a = 0, b = 0;
-      PNP_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
-      PNP_HIP(hipEventElapsedTime(&b, ev[1], ev[2]));
+      SFM_HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+      SFM_HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
       ms_solve += a;
       ms_count += b;
     }
@@ -444,7 +422,7 @@ struct DeviceBackend {
       for (int i = 0; i < kb.n; ++i) kb.k[i] = keeps[first + i];
       hipLaunchKernelGGL(pnp_keep_best, dim3((unsigned)((6 * kb.n + 255) / 256)), dim3(256), 0, st, kb, (const double*)d_models, d_best);
     }
-    PNP_HIP(hipGetLastError());
+    SFM_HIP_TRY(hipGetLastError());
     return SFMHIP_OK;
   }
 };

@@ -20,7 +20,6 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <vector>
 
@@ -69,19 +68,12 @@ Pool* pool_of(sfmhip_cloud* c) {
 struct Bufs {
   Pool* pool;
   size_t k = 0;
-  std::vector<void*> own;
+  DevBufs own;
   explicit Bufs(Pool* q = nullptr) : pool(q) {}
-  ~Bufs() {
-    for (void* q : own) hipFree(q);
-  }
   template <typename T>
   int get(T** out, size_t n) {
     n = std::max(n, (size_t)1);
-    if (!pool) {
-      SFM_TRY(sfm_dev_alloc(out, n));
-      own.push_back(*out);
-      return SFMHIP_OK;
-    }
+    if (!pool) return own.alloc(out, n);
     if (k == pool->p.size()) {
       pool->p.push_back(nullptr);
       pool->bytes.push_back(0);
@@ -100,10 +92,6 @@ struct Bufs {
     return SFMHIP_OK;
   }
 };
-
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // the chunk tree of poisson.h over the 256 threads of a workgroup; every thread gets the value
 __device__ __forceinline__ double block_tree(double v, double* sh4) {
@@ -581,7 +569,7 @@ extern "C" int sfmhip_cloud_poisson(sfmhip_cloud* c, const float* normals, const
   Ctl h = {};
   double iso = 0.0;
   sfmhip_mesh* mesh = new sfmhip_mesh();
-  const double t0 = now_ms();
+  const double t0 = sfm_now_ms();
   double t1 = t0, t2 = t0;
   int rc = make_samples(c, normals, opts->normal_stride, o, B, S);
   if (rc == SFMHIP_OK && S.m > 0) {
@@ -593,13 +581,13 @@ extern "C" int sfmhip_cloud_poisson(sfmhip_cloud* c, const float* normals, const
     if (rc == SFMHIP_OK) rc = B.get(&chi, nc);
     if (rc == SFMHIP_OK) rc = splat_rhs(st, S, o.point_weight, V4, dg, r);
     if (rc == SFMHIP_OK && hipStreamSynchronize(st) != hipSuccess) rc = SFMHIP_ERR_HIP;
-    t1 = now_ms();
+    t1 = sfm_now_ms();
     if (rc == SFMHIP_OK) rc = solve(st, B, S.g.N, r, dg, o.cg_rtol, max_iter_of(o), chi, &h);
-    t2 = now_ms();
+    t2 = sfm_now_ms();
     if (rc == SFMHIP_OK) rc = iso_value(st, B, S, chi, &iso);
     if (rc == SFMHIP_OK) rc = extract(st, B, chi, S.g, iso, mesh);
   }
-  const double t3 = now_ms();
+  const double t3 = sfm_now_ms();
   if (rc != SFMHIP_OK) {
     delete mesh;
     return rc;

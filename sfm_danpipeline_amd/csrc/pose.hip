@@ -117,61 +117,51 @@ int run_pose(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, PoseArgs a, c
                o_off = a.off ? 0 : take(sizeof(int) * (n_pairs + 1)), o_l = up_pts ? take(16 * total) : 0,
                o_r = up_pts ? take(16 * total) : 0, o_E = up_E ? take(sizeof(double) * 9 * n_pairs) : 0,
                o_min = up_mask ? take(total) : 0;
+  DevBufs bufs;
   unsigned char* d = nullptr;
-  SFM_HIP_TRY(hipMalloc((void**)&d, off_b));
-  int rc = SFMHIP_OK;
-  auto fail = [&](hipError_t e) {
-    if (e != hipSuccess) {
-      g_sfmhip_last_hip_error = (int)e;
-      rc = SFMHIP_ERR_HIP;
-    }
-    return e != hipSuccess;
-  };
-  do {
-    a.tiles = (const int2*)(d + o_tiles);
-    a.counts = (int*)(d + o_counts);
-    a.codes = d + o_codes;
-    a.R = (double*)(d + o_R);
-    a.t = (double*)(d + o_t);
-    a.n_good = (int*)(d + o_ng);
-    a.mask_out = d + o_mask;
-    a.flags = (int*)(d + o_flags);
-    if (!a.off) {
-      if (fail(hipMemcpyAsync(d + o_off, offsets, sizeof(int) * (n_pairs + 1), hipMemcpyHostToDevice, st))) break;
-      a.off = (const int*)(d + o_off);
-    }
-    if (up_pts && total) {
-      if (fail(hipMemcpyAsync(d + o_l, h_left, 16 * total, hipMemcpyHostToDevice, st))) break;
-      if (fail(hipMemcpyAsync(d + o_r, h_right, 16 * total, hipMemcpyHostToDevice, st))) break;
-      a.xy1 = (const double2*)(d + o_l);
-      a.xy2 = (const double2*)(d + o_r);
-    }
-    if (up_E) {
-      if (fail(hipMemcpyAsync(d + o_E, h_E, sizeof(double) * 9 * n_pairs, hipMemcpyHostToDevice, st))) break;
-      a.E = (const double*)(d + o_E);
-    }
-    if (up_mask && total) {
-      if (fail(hipMemcpyAsync(d + o_min, h_mask_in, total, hipMemcpyHostToDevice, st))) break;
-      a.mask_in = d + o_min;
-    }
-    if (!tiles.empty() && fail(hipMemcpyAsync(d + o_tiles, tiles.data(), sizeof(int2) * tiles.size(), hipMemcpyHostToDevice, st)))
-      break;
-    if (fail(hipMemsetAsync(d + o_counts, 0, sizeof(int) * 4 * n_pairs, st))) break;
-    if (fail(hipMemsetAsync(d + o_flags, 0, sizeof(int), st))) break;
-    if (!tiles.empty()) hipLaunchKernelGGL(pose_candidates, dim3((unsigned)tiles.size()), dim3(TILE), 0, st, a);
-    hipLaunchKernelGGL(pose_select, dim3((unsigned)n_pairs), dim3(TILE), 0, st, a);
-    if (fail(hipGetLastError())) break;
-    if (fail(hipMemcpyAsync(R, d + o_R, sizeof(double) * 9 * n_pairs, hipMemcpyDeviceToHost, st))) break;
-    if (fail(hipMemcpyAsync(t, d + o_t, sizeof(double) * 3 * n_pairs, hipMemcpyDeviceToHost, st))) break;
-    if (fail(hipMemcpyAsync(n_good, d + o_ng, sizeof(int) * n_pairs, hipMemcpyDeviceToHost, st))) break;
-    if (mask_out && total && fail(hipMemcpyAsync(mask_out, d + o_mask, total, hipMemcpyDeviceToHost, st))) break;
-    int flags = 0;
-    if (fail(hipMemcpyAsync(&flags, d + o_flags, sizeof(int), hipMemcpyDeviceToHost, st))) break;
-    if (fail(hipStreamSynchronize(st))) break;
-    ctx->pose_flags = flags;
-  } while (0);
-  hipFree(d);
-  return rc;
+  SFM_TRY(bufs.alloc(&d, off_b));
+  a.tiles = (const int2*)(d + o_tiles);
+  a.counts = (int*)(d + o_counts);
+  a.codes = d + o_codes;
+  a.R = (double*)(d + o_R);
+  a.t = (double*)(d + o_t);
+  a.n_good = (int*)(d + o_ng);
+  a.mask_out = d + o_mask;
+  a.flags = (int*)(d + o_flags);
+  if (!a.off) {
+    SFM_HIP_TRY(hipMemcpyAsync(d + o_off, offsets, sizeof(int) * (n_pairs + 1), hipMemcpyHostToDevice, st));
+    a.off = (const int*)(d + o_off);
+  }
+  if (up_pts && total) {
+    SFM_HIP_TRY(hipMemcpyAsync(d + o_l, h_left, 16 * total, hipMemcpyHostToDevice, st));
+    SFM_HIP_TRY(hipMemcpyAsync(d + o_r, h_right, 16 * total, hipMemcpyHostToDevice, st));
+    a.xy1 = (const double2*)(d + o_l);
+    a.xy2 = (const double2*)(d + o_r);
+  }
+  if (up_E) {
+    SFM_HIP_TRY(hipMemcpyAsync(d + o_E, h_E, sizeof(double) * 9 * n_pairs, hipMemcpyHostToDevice, st));
+    a.E = (const double*)(d + o_E);
+  }
+  if (up_mask && total) {
+    SFM_HIP_TRY(hipMemcpyAsync(d + o_min, h_mask_in, total, hipMemcpyHostToDevice, st));
+    a.mask_in = d + o_min;
+  }
+  if (!tiles.empty())
+    SFM_HIP_TRY(hipMemcpyAsync(d + o_tiles, tiles.data(), sizeof(int2) * tiles.size(), hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemsetAsync(d + o_counts, 0, sizeof(int) * 4 * n_pairs, st));
+  SFM_HIP_TRY(hipMemsetAsync(d + o_flags, 0, sizeof(int), st));
+  if (!tiles.empty()) hipLaunchKernelGGL(pose_candidates, dim3((unsigned)tiles.size()), dim3(TILE), 0, st, a);
+  hipLaunchKernelGGL(pose_select, dim3((unsigned)n_pairs), dim3(TILE), 0, st, a);
+  SFM_HIP_TRY(hipGetLastError());
+  SFM_HIP_TRY(hipMemcpyAsync(R, d + o_R, sizeof(double) * 9 * n_pairs, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipMemcpyAsync(t, d + o_t, sizeof(double) * 3 * n_pairs, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipMemcpyAsync(n_good, d + o_ng, sizeof(int) * n_pairs, hipMemcpyDeviceToHost, st));
+  if (mask_out && total) SFM_HIP_TRY(hipMemcpyAsync(mask_out, d + o_mask, total, hipMemcpyDeviceToHost, st));
+  int flags = 0;
+  SFM_HIP_TRY(hipMemcpyAsync(&flags, d + o_flags, sizeof(int), hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipStreamSynchronize(st));
+  ctx->pose_flags = flags;
+  return SFMHIP_OK;
 }
 
 bool offsets_ok(int n_pairs, const int32_t* offsets) {

@@ -745,22 +745,12 @@ int sfm_essential_ransac(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, c
   int flags_any = 0;
   ctx->score_flags = 0;
 
-  struct Bufs {  // the loop's scratch (what the caller reads lives in dev)
-    std::vector<void*> v;
-    ~Bufs() {
-      for (void* p : v) hipFree(p);
-    }
-  } bufs;
-  auto dalloc = [&](void** p, size_t bytes) -> int {
-    if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) return SFMHIP_ERR_ALLOC;
-    bufs.v.push_back(*p);
-    return SFMHIP_OK;
-  };
-  const size_t pts_bytes = sizeof(double) * 2 * (size_t)std::max<long long>(total, 1);
-  SFM_TRY(dev.alloc((void**)&dev.d_left, pts_bytes));
-  SFM_TRY(dev.alloc((void**)&dev.d_right, pts_bytes));
-  SFM_TRY(dev.alloc((void**)&dev.d_p1, pts_bytes));
-  SFM_TRY(dev.alloc((void**)&dev.d_p2, pts_bytes));
+  DevBufs bufs;  // the loop's scratch (what the caller reads lives in dev)
+  const size_t pts_n = 2 * (size_t)std::max<long long>(total, 1);
+  SFM_TRY(dev.bufs.alloc(&dev.d_left, pts_n));
+  SFM_TRY(dev.bufs.alloc(&dev.d_right, pts_n));
+  SFM_TRY(dev.bufs.alloc(&dev.d_p1, pts_n));
+  SFM_TRY(dev.bufs.alloc(&dev.d_p2, pts_n));
   double *d_p1 = dev.d_p1, *d_p2 = dev.d_p2;
   if (total > 0) {
     const int nb = (int)((2 * total + 255) / 256);
@@ -780,9 +770,9 @@ int sfm_essential_ransac(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, c
   double* d_bestE = nullptr;
   int2* d_upd = nullptr;
   std::vector<int2> upd;
-  SFM_TRY(dev.alloc((void**)&d_bestE, sizeof(double) * 9 * n_pairs));
+  SFM_TRY(dev.bufs.alloc(&d_bestE, 9 * (size_t)n_pairs));
   dev.d_bestE = d_bestE;
-  SFM_TRY(dalloc((void**)&d_upd, sizeof(int2) * n_pairs));
+  SFM_TRY(bufs.alloc(&d_upd, (size_t)n_pairs));
   SFM_HIP_TRY(hipMemsetAsync(d_bestE, 0, sizeof(double) * 9 * n_pairs, st));
   for (int p = 0; p < n_pairs; ++p) {
     PairState& s = ps[p];
@@ -826,18 +816,18 @@ int sfm_essential_ransac(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, c
     if (jobs.empty()) break;
     const size_t nj = jobs.size(), slots = nj * (size_t)chunk;
     if (nj > cap_jobs) {
-      SFM_TRY(dalloc((void**)&d_jobs, sizeof(ScoreJob) * nj));
+      SFM_TRY(bufs.alloc(&d_jobs, nj));
       cap_jobs = nj;
     }
     if (slots > cap_slots) {
-      SFM_TRY(dalloc((void**)&d_nm, sizeof(int) * slots));
-      SFM_TRY(dalloc((void**)&d_counts, sizeof(int) * slots * MAX_MODELS));
-      SFM_TRY(dalloc((void**)&d_models, sizeof(double) * slots * MAX_MODELS * 9));
-      SFM_TRY(dalloc((void**)&d_work, sizeof(double) * ((slots + 63) / 64 * 64) * FP_WORK));
+      SFM_TRY(bufs.alloc(&d_nm, slots));
+      SFM_TRY(bufs.alloc(&d_counts, slots * MAX_MODELS));
+      SFM_TRY(bufs.alloc(&d_models, slots * MAX_MODELS * 9));
+      SFM_TRY(bufs.alloc(&d_work, (slots + 63) / 64 * 64 * FP_WORK));
       cap_slots = slots;
     }
     if (h_samples.size() > cap_samples) {
-      SFM_TRY(dalloc((void**)&d_samples, sizeof(int) * h_samples.size()));
+      SFM_TRY(bufs.alloc(&d_samples, h_samples.size()));
       cap_samples = h_samples.size();
     }
     SFM_HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(ScoreJob) * nj, hipMemcpyHostToDevice, st));
@@ -899,9 +889,9 @@ int sfm_essential_ransac(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, c
   ctx->score_flags = flags_any;
   dev.has = has;
   if (want_mask) {
-    SFM_TRY(dev.alloc((void**)&dev.d_off, sizeof(int) * (n_pairs + 1)));
-    SFM_TRY(dev.alloc((void**)&dev.d_has, n_pairs));
-    SFM_TRY(dev.alloc((void**)&dev.d_mask, (size_t)std::max<long long>(total, 1)));
+    SFM_TRY(dev.bufs.alloc(&dev.d_off, (size_t)n_pairs + 1));
+    SFM_TRY(dev.bufs.alloc(&dev.d_has, (size_t)n_pairs));
+    SFM_TRY(dev.bufs.alloc(&dev.d_mask, (size_t)std::max<long long>(total, 1)));
     SFM_HIP_TRY(hipMemcpyAsync(dev.d_off, offsets, sizeof(int) * (n_pairs + 1), hipMemcpyHostToDevice, st));
     SFM_HIP_TRY(hipMemcpyAsync(dev.d_has, has.data(), n_pairs, hipMemcpyHostToDevice, st));
     if (total > 0) {
@@ -962,27 +952,19 @@ extern "C" int sfmhip_score_five_point(sfmhip_ctx* ctx, int n_samples, const dou
   hipStream_t st = ctx->stream;
   double *d_q1 = nullptr, *d_q2 = nullptr, *d_m = nullptr;
   int* d_n = nullptr;
-  int rc = SFMHIP_OK;
-  if ((rc = sfm_dev_alloc(&d_q1, 10 * (size_t)n_samples)) || (rc = sfm_dev_alloc(&d_q2, 10 * (size_t)n_samples)) ||
-      (rc = sfm_dev_alloc(&d_m, 90 * (size_t)n_samples)) || (rc = sfm_dev_alloc(&d_n, (size_t)n_samples))) {
-    hipFree(d_q1), hipFree(d_q2), hipFree(d_m), hipFree(d_n);
-    return rc;
-  }
-  hipError_t e = hipMemcpyAsync(d_q1, q1, sizeof(double) * 10 * n_samples, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_q2, q2, sizeof(double) * 10 * n_samples, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_m, 0, sizeof(double) * 90 * n_samples, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(five_point_samples, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_q1, d_q2, n_samples, d_m, d_n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(models, d_m, sizeof(double) * 90 * n_samples, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(n_models, d_n, sizeof(int) * n_samples, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  hipFree(d_q1), hipFree(d_q2), hipFree(d_m), hipFree(d_n);
-  if (e != hipSuccess) {
-    g_sfmhip_last_hip_error = (int)e;
-    return SFMHIP_ERR_HIP;
-  }
+  DevBufs bufs;
+  SFM_TRY(bufs.alloc(&d_q1, 10 * (size_t)n_samples));
+  SFM_TRY(bufs.alloc(&d_q2, 10 * (size_t)n_samples));
+  SFM_TRY(bufs.alloc(&d_m, 90 * (size_t)n_samples));
+  SFM_TRY(bufs.alloc(&d_n, (size_t)n_samples));
+  SFM_HIP_TRY(hipMemcpyAsync(d_q1, q1, sizeof(double) * 10 * n_samples, hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemcpyAsync(d_q2, q2, sizeof(double) * 10 * n_samples, hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemsetAsync(d_m, 0, sizeof(double) * 90 * n_samples, st));
+  hipLaunchKernelGGL(five_point_samples, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_q1, d_q2, n_samples, d_m, d_n);
+  SFM_HIP_TRY(hipGetLastError());
+  SFM_HIP_TRY(hipMemcpyAsync(models, d_m, sizeof(double) * 90 * n_samples, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipMemcpyAsync(n_models, d_n, sizeof(int) * n_samples, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipStreamSynchronize(st));
   return SFMHIP_OK;
 }
 
@@ -1012,26 +994,18 @@ extern "C" int sfmhip_score_homography_kernel(sfmhip_ctx* ctx, int n_samples, co
   float *d_M = nullptr, *d_m = nullptr;
   double* d_H = nullptr;
   int* d_ok = nullptr;
-  int rc = SFMHIP_OK;
-  if ((rc = sfm_dev_alloc(&d_M, 8 * (size_t)n_samples)) || (rc = sfm_dev_alloc(&d_m, 8 * (size_t)n_samples)) ||
-      (rc = sfm_dev_alloc(&d_H, 9 * (size_t)n_samples)) || (rc = sfm_dev_alloc(&d_ok, (size_t)n_samples))) {
-    hipFree(d_M), hipFree(d_m), hipFree(d_H), hipFree(d_ok);
-    return rc;
-  }
-  hipError_t e = hipMemcpyAsync(d_M, M, sizeof(float) * 8 * n_samples, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_m, m, sizeof(float) * 8 * n_samples, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(homography_samples, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_M, d_m, n_samples, d_H, d_ok);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(H, d_H, sizeof(double) * 9 * n_samples, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(ok, d_ok, sizeof(int) * n_samples, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  hipFree(d_M), hipFree(d_m), hipFree(d_H), hipFree(d_ok);
-  if (e != hipSuccess) {
-    g_sfmhip_last_hip_error = (int)e;
-    return SFMHIP_ERR_HIP;
-  }
+  DevBufs bufs;
+  SFM_TRY(bufs.alloc(&d_M, 8 * (size_t)n_samples));
+  SFM_TRY(bufs.alloc(&d_m, 8 * (size_t)n_samples));
+  SFM_TRY(bufs.alloc(&d_H, 9 * (size_t)n_samples));
+  SFM_TRY(bufs.alloc(&d_ok, (size_t)n_samples));
+  SFM_HIP_TRY(hipMemcpyAsync(d_M, M, sizeof(float) * 8 * n_samples, hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemcpyAsync(d_m, m, sizeof(float) * 8 * n_samples, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(homography_samples, dim3((n_samples + 63) / 64), dim3(64), 0, st, d_M, d_m, n_samples, d_H, d_ok);
+  SFM_HIP_TRY(hipGetLastError());
+  SFM_HIP_TRY(hipMemcpyAsync(H, d_H, sizeof(double) * 9 * n_samples, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipMemcpyAsync(ok, d_ok, sizeof(int) * n_samples, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipStreamSynchronize(st));
   return SFMHIP_OK;
 }
 
@@ -1050,17 +1024,7 @@ extern "C" int sfmhip_score_homography(sfmhip_ctx* ctx, int n_pairs, const int32
   hipStream_t st = ctx->stream;
   constexpr int MODEL_POINTS = 4;
   const int MAX_ITERS = std::max(max_iters, 1);
-  struct Bufs {
-    std::vector<void*> v;
-    ~Bufs() {
-      for (void* p : v) hipFree(p);
-    }
-  } bufs;
-  auto dalloc = [&](void** p, size_t bytes) -> int {
-    if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) return SFMHIP_ERR_ALLOC;
-    bufs.v.push_back(*p);
-    return SFMHIP_OK;
-  };
+  DevBufs bufs;
   // the points as float (findHomography converts them to CV_32F before anything else)
   std::vector<float> h1(2 * (size_t)std::max<long long>(total, 1)), h2(h1.size());
   for (long long i = 0; i < 2 * total; ++i) {
@@ -1068,8 +1032,8 @@ extern "C" int sfmhip_score_homography(sfmhip_ctx* ctx, int n_pairs, const int32
     h2[i] = (float)right_xy[i];
   }
   float *d_p1 = nullptr, *d_p2 = nullptr;
-  SFM_TRY(dalloc((void**)&d_p1, sizeof(float) * h1.size()));
-  SFM_TRY(dalloc((void**)&d_p2, sizeof(float) * h2.size()));
+  SFM_TRY(bufs.alloc(&d_p1, h1.size()));
+  SFM_TRY(bufs.alloc(&d_p2, h2.size()));
   SFM_HIP_TRY(hipMemcpyAsync(d_p1, h1.data(), sizeof(float) * h1.size(), hipMemcpyHostToDevice, st));
   SFM_HIP_TRY(hipMemcpyAsync(d_p2, h2.data(), sizeof(float) * h2.size(), hipMemcpyHostToDevice, st));
   struct PairState {
@@ -1084,8 +1048,8 @@ extern "C" int sfmhip_score_homography(sfmhip_ctx* ctx, int n_pairs, const int32
   double* d_bestH = nullptr;
   int2* d_upd = nullptr;
   std::vector<int2> upd;
-  SFM_TRY(dalloc((void**)&d_bestH, sizeof(double) * 9 * n_pairs));
-  SFM_TRY(dalloc((void**)&d_upd, sizeof(int2) * n_pairs));
+  SFM_TRY(bufs.alloc(&d_bestH, 9 * (size_t)n_pairs));
+  SFM_TRY(bufs.alloc(&d_upd, (size_t)n_pairs));
   SFM_HIP_TRY(hipMemsetAsync(d_bestH, 0, sizeof(double) * 9 * n_pairs, st));
   for (int p = 0; p < n_pairs; ++p) {
     PairState& s = ps[p];
@@ -1130,17 +1094,17 @@ extern "C" int sfmhip_score_homography(sfmhip_ctx* ctx, int n_pairs, const int32
     if (jobs.empty()) break;
     const size_t nj = jobs.size(), slots = nj * (size_t)chunk;
     if (nj > cap_jobs) {
-      SFM_TRY(dalloc((void**)&d_jobs, sizeof(HJob) * nj));
+      SFM_TRY(bufs.alloc(&d_jobs, nj));
       cap_jobs = nj;
     }
     if (slots > cap_slots) {
-      SFM_TRY(dalloc((void**)&d_nm, sizeof(int) * slots));
-      SFM_TRY(dalloc((void**)&d_counts, sizeof(int) * slots));
-      SFM_TRY(dalloc((void**)&d_models, sizeof(double) * slots * 9));
+      SFM_TRY(bufs.alloc(&d_nm, slots));
+      SFM_TRY(bufs.alloc(&d_counts, slots));
+      SFM_TRY(bufs.alloc(&d_models, slots * 9));
       cap_slots = slots;
     }
     if (h_samples.size() > cap_samples) {
-      SFM_TRY(dalloc((void**)&d_samples, sizeof(int) * h_samples.size()));
+      SFM_TRY(bufs.alloc(&d_samples, h_samples.size()));
       cap_samples = h_samples.size();
     }
     SFM_HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(HJob) * nj, hipMemcpyHostToDevice, st));
@@ -1200,10 +1164,10 @@ extern "C" int sfmhip_score_homography(sfmhip_ctx* ctx, int n_pairs, const int32
     int* d_off = nullptr;
     float* d_tt = nullptr;
     unsigned char *d_has = nullptr, *d_mask = nullptr;
-    SFM_TRY(dalloc((void**)&d_off, sizeof(int) * (n_pairs + 1)));
-    SFM_TRY(dalloc((void**)&d_tt, sizeof(float) * n_pairs));
-    SFM_TRY(dalloc((void**)&d_has, n_pairs));
-    SFM_TRY(dalloc((void**)&d_mask, (size_t)total));
+    SFM_TRY(bufs.alloc(&d_off, (size_t)n_pairs + 1));
+    SFM_TRY(bufs.alloc(&d_tt, (size_t)n_pairs));
+    SFM_TRY(bufs.alloc(&d_has, (size_t)n_pairs));
+    SFM_TRY(bufs.alloc(&d_mask, (size_t)total));
     SFM_HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int) * (n_pairs + 1), hipMemcpyHostToDevice, st));
     SFM_HIP_TRY(hipMemcpyAsync(d_tt, tts.data(), sizeof(float) * n_pairs, hipMemcpyHostToDevice, st));
     SFM_HIP_TRY(hipMemcpyAsync(d_has, has.data(), n_pairs, hipMemcpyHostToDevice, st));

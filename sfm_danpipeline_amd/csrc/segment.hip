@@ -23,7 +23,6 @@
 #include <rocprim/device/device_reduce_by_key.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <vector>
 
@@ -50,24 +49,6 @@ SegState* seg_state(sfmhip_cloud* c) {
     c->seg_free = seg_state_free;
   }
   return (SegState*)c->seg;
-}
-
-// the device buffers of one call
-struct Bufs {
-  std::vector<void*> p;
-  ~Bufs() {
-    for (void* q : p) hipFree(q);
-  }
-  template <typename T>
-  int get(T** out, size_t n) {
-    SFM_TRY(sfm_dev_alloc(out, std::max(n, (size_t)1)));
-    p.push_back(*out);
-    return SFMHIP_OK;
-  }
-};
-
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 __global__ void seg_gather(const float* xyz, const int* ind, int m, float* out) {
@@ -380,17 +361,17 @@ struct Work {
   int n_seg = 0, rounds = 0;
 };
 
-int subset_knn(sfmhip_cloud* c, SegState* s, Bufs& B, const int32_t* indices, int m, int k, Work& w) {
+int subset_knn(sfmhip_cloud* c, SegState* s, DevBufs& B, const int32_t* indices, int m, int k, Work& w) {
   hipStream_t st = c->ctx->stream;
   if ((unsigned long long)m * (unsigned)k > (unsigned long long)INT_MAX) return SFMHIP_ERR_UNSUPPORTED;
   w.m = m;
   w.k = k;
-  SFM_TRY(B.get(&w.ind, (size_t)m));
-  SFM_TRY(B.get(&w.xyz, (size_t)3 * m));
-  SFM_TRY(B.get(&w.knn_idx, (size_t)m * k));
-  SFM_TRY(B.get(&w.knn_d2, (size_t)m * k));
+  SFM_TRY(B.alloc(&w.ind, (size_t)m));
+  SFM_TRY(B.alloc(&w.xyz, (size_t)3 * m));
+  SFM_TRY(B.alloc(&w.knn_idx, (size_t)m * k));
+  SFM_TRY(B.alloc(&w.knn_d2, (size_t)m * k));
   unsigned* mm = nullptr;
-  SFM_TRY(B.get(&mm, 7));
+  SFM_TRY(B.alloc(&mm, 7));
   SFM_HIP_TRY(hipMemcpyAsync(w.ind, indices, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(seg_gather, dim3(blocks(m, 256)), dim3(256), 0, st, c->xyz, w.ind, m, w.xyz);
   SFM_HIP_TRY(hipGetLastError());
@@ -420,16 +401,16 @@ int subset_knn(sfmhip_cloud* c, SegState* s, Bufs& B, const int32_t* indices, in
   return SFMHIP_OK;
 }
 
-int grow(sfmhip_cloud* c, Bufs& B, const uint32_t* rgb_all, const int32_t* indices, const sfmseg::Opts& o, Work& w) {
+int grow(sfmhip_cloud* c, DevBufs& B, const uint32_t* rgb_all, const int32_t* indices, const sfmseg::Opts& o, Work& w) {
   hipStream_t st = c->ctx->stream;
   const int m = w.m;
   std::vector<uint32_t> rgb((size_t)m);
   for (int r = 0; r < m; ++r) rgb[r] = rgb_all[indices[r]] & 0x00FFFFFFu;
-  SFM_TRY(B.get(&w.rgb, (size_t)m));
-  SFM_TRY(B.get(&w.lab, (size_t)m));
-  SFM_TRY(B.get(&w.seg, (size_t)m));
+  SFM_TRY(B.alloc(&w.rgb, (size_t)m));
+  SFM_TRY(B.alloc(&w.lab, (size_t)m));
+  SFM_TRY(B.alloc(&w.seg, (size_t)m));
   int* changed = nullptr;
-  SFM_TRY(B.get(&changed, 1));
+  SFM_TRY(B.alloc(&changed, 1));
   SFM_HIP_TRY(hipMemcpyAsync(w.rgb, rgb.data(), sizeof(uint32_t) * (size_t)m, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(seg_grow_init, dim3(blocks(m, 256)), dim3(256), 0, st, w.knn_idx, w.k, m, w.lab);
   SFM_HIP_TRY(hipGetLastError());
@@ -457,20 +438,20 @@ struct DevTables {
   unsigned* colour = nullptr;
 };
 
-int number_segments(sfmhip_cloud* c, Bufs& B, Work& w, DevTables& d) {
+int number_segments(sfmhip_cloud* c, DevBufs& B, Work& w, DevTables& d) {
   hipStream_t st = c->ctx->stream;
   const int m = w.m;
   int *flags = nullptr, *off = nullptr;
-  SFM_TRY(B.get(&flags, (size_t)m));
-  SFM_TRY(B.get(&off, (size_t)m));
+  SFM_TRY(B.alloc(&flags, (size_t)m));
+  SFM_TRY(B.alloc(&off, (size_t)m));
   hipLaunchKernelGGL(seg_root_flags, dim3(blocks(m, 256)), dim3(256), 0, st, w.lab, m, flags);
   SFM_HIP_TRY(hipGetLastError());
   SFM_TRY(scan_ints(c, flags, off, (size_t)m));
   SFM_TRY(scan_total(c, flags, off, (size_t)m, &w.n_seg));
   if (w.n_seg < 0 || w.n_seg > m) return SFMHIP_ERR_STATE;
-  SFM_TRY(B.get(&d.acc, (size_t)4 * w.n_seg));
-  SFM_TRY(B.get(&d.count, (size_t)w.n_seg));
-  SFM_TRY(B.get(&d.colour, (size_t)3 * w.n_seg));
+  SFM_TRY(B.alloc(&d.acc, (size_t)4 * w.n_seg));
+  SFM_TRY(B.alloc(&d.count, (size_t)w.n_seg));
+  SFM_TRY(B.alloc(&d.colour, (size_t)3 * w.n_seg));
   SFM_HIP_TRY(hipMemsetAsync(d.acc, 0, sizeof(unsigned) * 4 * (size_t)std::max(w.n_seg, 1), st));
   hipLaunchKernelGGL(seg_assign, dim3(blocks(m, 256)), dim3(256), 0, st, w.lab, off, w.rgb, m, w.seg, d.acc);
   SFM_HIP_TRY(hipGetLastError());
@@ -479,7 +460,7 @@ int number_segments(sfmhip_cloud* c, Bufs& B, Work& w, DevTables& d) {
   return SFMHIP_OK;
 }
 
-int segment_tables(sfmhip_cloud* c, Bufs& B, const sfmseg::Opts& o, Work& w, const DevTables& d, sfmseg::SegTables& t) {
+int segment_tables(sfmhip_cloud* c, DevBufs& B, const sfmseg::Opts& o, Work& w, const DevTables& d, sfmseg::SegTables& t) {
   hipStream_t st = c->ctx->stream;
   const int m = w.m, S = w.n_seg;
   t.n_seg = S;
@@ -492,8 +473,8 @@ int segment_tables(sfmhip_cloud* c, Bufs& B, const sfmseg::Opts& o, Work& w, con
   SFM_HIP_TRY(hipMemcpyAsync(t.count.data(), d.count, sizeof(int) * (size_t)S, hipMemcpyDeviceToHost, st));
   SFM_HIP_TRY(hipMemcpyAsync(t.colour.data(), d.colour, sizeof(unsigned) * 3 * (size_t)S, hipMemcpyDeviceToHost, st));
   int *cnt = nullptr, *off = nullptr;
-  SFM_TRY(B.get(&cnt, (size_t)m));
-  SFM_TRY(B.get(&off, (size_t)m));
+  SFM_TRY(B.alloc(&cnt, (size_t)m));
+  SFM_TRY(B.alloc(&off, (size_t)m));
   hipLaunchKernelGGL(seg_cross, dim3(blocks(m, 256)), dim3(256), 0, st, w.knn_idx, w.knn_d2, w.k, w.seg, m, S, 0, cnt, nullptr, nullptr,
                      nullptr);
   SFM_HIP_TRY(hipGetLastError());
@@ -504,10 +485,10 @@ int segment_tables(sfmhip_cloud* c, Bufs& B, const sfmseg::Opts& o, Work& w, con
   if (ne == 0) return SFMHIP_OK;
   unsigned long long *k0 = nullptr, *k1 = nullptr;
   float *v0 = nullptr, *v1 = nullptr;
-  SFM_TRY(B.get(&k0, (size_t)ne));
-  SFM_TRY(B.get(&k1, (size_t)ne));
-  SFM_TRY(B.get(&v0, (size_t)ne));
-  SFM_TRY(B.get(&v1, (size_t)ne));
+  SFM_TRY(B.alloc(&k0, (size_t)ne));
+  SFM_TRY(B.alloc(&k1, (size_t)ne));
+  SFM_TRY(B.alloc(&v0, (size_t)ne));
+  SFM_TRY(B.alloc(&v1, (size_t)ne));
   hipLaunchKernelGGL(seg_cross, dim3(blocks(m, 256)), dim3(256), 0, st, w.knn_idx, w.knn_d2, w.k, w.seg, m, S, 1, cnt, off, k0, v0);
   SFM_HIP_TRY(hipGetLastError());
   unsigned sbits = 1;
@@ -531,8 +512,8 @@ int segment_tables(sfmhip_cloud* c, Bufs& B, const sfmseg::Opts& o, Work& w, con
   if (np < 1 || np > ne) return SFMHIP_ERR_STATE;
   // every segment's neighbours ascending by (d2, segment): a stable sort by (a, d2) of pairs that are ascending in b
   int *b0 = nullptr, *b1 = nullptr;
-  SFM_TRY(B.get(&b0, (size_t)np));
-  SFM_TRY(B.get(&b1, (size_t)np));
+  SFM_TRY(B.alloc(&b0, (size_t)np));
+  SFM_TRY(B.alloc(&b1, (size_t)np));
   hipLaunchKernelGGL(seg_pair_keys, dim3(blocks(np, 256)), dim3(256), 0, st, k0, v0, np, S, k1, b0);
   SFM_HIP_TRY(hipGetLastError());
   need = 0;
@@ -542,10 +523,10 @@ int segment_tables(sfmhip_cloud* c, Bufs& B, const sfmseg::Opts& o, Work& w, con
   SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp, need, k1, k0, b0, b1, (size_t)np, 0u, 32u + sbits, st));
   int *start = nullptr, *end = nullptr, *ncnt = nullptr, *noff = nullptr, *nseg = nullptr;
   float* nd2 = nullptr;
-  SFM_TRY(B.get(&start, (size_t)S));
-  SFM_TRY(B.get(&end, (size_t)S));
-  SFM_TRY(B.get(&ncnt, (size_t)S));
-  SFM_TRY(B.get(&noff, (size_t)S));
+  SFM_TRY(B.alloc(&start, (size_t)S));
+  SFM_TRY(B.alloc(&end, (size_t)S));
+  SFM_TRY(B.alloc(&ncnt, (size_t)S));
+  SFM_TRY(B.alloc(&noff, (size_t)S));
   SFM_HIP_TRY(hipMemsetAsync(start, 0, sizeof(int) * (size_t)S, st));
   SFM_HIP_TRY(hipMemsetAsync(end, 0, sizeof(int) * (size_t)S, st));
   hipLaunchKernelGGL(seg_pair_ranges, dim3(blocks(np, 256)), dim3(256), 0, st, k0, np, start, end);
@@ -555,8 +536,8 @@ int segment_tables(sfmhip_cloud* c, Bufs& B, const sfmseg::Opts& o, Work& w, con
   int total = 0;
   SFM_TRY(scan_total(c, ncnt, noff, (size_t)S, &total));
   if (total < 1 || total > np) return SFMHIP_ERR_STATE;
-  SFM_TRY(B.get(&nseg, (size_t)total));
-  SFM_TRY(B.get(&nd2, (size_t)total));
+  SFM_TRY(B.alloc(&nseg, (size_t)total));
+  SFM_TRY(B.alloc(&nd2, (size_t)total));
   hipLaunchKernelGGL(seg_nbr_write, dim3(blocks(np, 256)), dim3(256), 0, st, k0, b1, np, start, ncnt, noff, nseg, nd2);
   SFM_HIP_TRY(hipGetLastError());
   t.nbr_seg.resize((size_t)total);
@@ -598,9 +579,9 @@ extern "C" void sfmhip_segment_default_opts(sfmhip_segment_opts* o) {
 extern "C" int sfmhip_cloud_minmax(sfmhip_cloud* c, float* mn, float* mx, double* height) {
   if (!c || !mn || !mx) return SFMHIP_ERR_ARG;
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
-  Bufs B;
+  DevBufs B;
   unsigned* d = nullptr;
-  SFM_TRY(B.get(&d, 7));
+  SFM_TRY(B.alloc(&d, 7));
   int count = 0;
   SFM_TRY(minmax_dev(c, c->xyz, c->n, d, mn, mx, &count));
   if (height) *height = sfmseg::height(mn, mx);
@@ -610,7 +591,7 @@ extern "C" int sfmhip_cloud_minmax(sfmhip_cloud* c, float* mn, float* mx, double
 extern "C" int sfmhip_cloud_subset_knn(sfmhip_cloud* c, const int32_t* indices, int n_idx, int k, int32_t* idx, float* d2) {
   if (!c || k < 1 || k > sfmseg::KMAX || !idx || !d2 || !indices_valid(c, indices, n_idx)) return SFMHIP_ERR_ARG;
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
-  Bufs B;
+  DevBufs B;
   Work w;
   SFM_TRY(subset_knn(c, seg_state(c), B, indices, n_idx, k, w));
   const size_t e = (size_t)n_idx * k;
@@ -629,7 +610,7 @@ extern "C" int sfmhip_cloud_segment_grow(sfmhip_cloud* c, const uint32_t* rgb, c
   const sfmseg::Opts o = to_opts(opts);
   if (!sfmseg::opts_valid(o)) return SFMHIP_ERR_ARG;
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
-  Bufs B;
+  DevBufs B;
   Work w;
   DevTables d;
   SFM_TRY(subset_knn(c, seg_state(c), B, indices, n_idx, o.region_neighbour_number, w));
@@ -653,28 +634,28 @@ extern "C" int sfmhip_cloud_segment_rgb(sfmhip_cloud* c, const uint32_t* rgb, co
   if (!sfmseg::opts_valid(o)) return SFMHIP_ERR_ARG;
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
   SegState* s = seg_state(c);
-  Bufs B;
+  DevBufs B;
   Work w;
   DevTables d;
   sfmseg::SegTables t;
-  const double t0 = now_ms();
+  const double t0 = sfm_now_ms();
   SFM_TRY(subset_knn(c, s, B, indices, n_idx, o.region_neighbour_number, w));
-  const double t1 = now_ms();
+  const double t1 = sfm_now_ms();
   SFM_TRY(grow(c, B, rgb, indices, o, w));
-  const double t2 = now_ms();
+  const double t2 = sfm_now_ms();
   SFM_TRY(number_segments(c, B, w, d));
   SFM_TRY(segment_tables(c, B, o, w, d, t));
   std::vector<int> seg((size_t)n_idx);
   SFM_HIP_TRY(hipMemcpyAsync(seg.data(), w.seg, sizeof(int) * (size_t)n_idx, hipMemcpyDeviceToHost, c->ctx->stream));
   SFM_HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-  const double t3 = now_ms();
+  const double t3 = sfm_now_ms();
   std::vector<int> seg_region, point_cluster;
   int n_regions = 0, nc = 0;
   sfmseg::regions_from_tables(o, t, seg.data(), n_idx, seg_region, n_regions, point_cluster, nc);
   for (int i = 0; i < c->n; ++i) labels[i] = -1;
   for (int r = 0; r < n_idx; ++r) labels[indices[r]] = point_cluster[r];
   *n_clusters = nc;
-  const double t4 = now_ms();
+  const double t4 = sfm_now_ms();
   s->ms[0] = t1 - t0;
   s->ms[1] = t2 - t1;
   s->ms[2] = t3 - t2;

@@ -85,28 +85,18 @@ extern "C" int sfmhip_triangulate(sfmhip_ctx* ctx, const double P1[12], const do
   // one device slab: xy1 | xy2 | X | err | keep
   const size_t off_xy2 = n * 16, off_X = off_xy2 + n * 16, off_err = off_X + n * 24, off_keep = off_err + n * 8;
   const size_t bytes = off_keep + n;
+  DevBufs bufs;
   unsigned char* d = nullptr;
-  SFM_HIP_TRY(hipMalloc((void**)&d, bytes));
+  SFM_TRY(bufs.alloc(&d, bytes));
   hipStream_t st = ctx->stream;
-  int rc = SFMHIP_OK;
-  auto fail = [&](hipError_t e) {
-    if (e != hipSuccess) {
-      g_sfmhip_last_hip_error = (int)e;
-      rc = SFMHIP_ERR_HIP;
-    }
-    return e != hipSuccess;
-  };
-  do {
-    if (fail(hipMemcpyAsync(d, xy1, n * 16, hipMemcpyHostToDevice, st))) break;
-    if (fail(hipMemcpyAsync(d + off_xy2, xy2, n * 16, hipMemcpyHostToDevice, st))) break;
-    hipLaunchKernelGGL(triangulate_kernel, dim3((m + 255) / 256), dim3(256), 0, st, p, (const double2*)d,
-                       (const double2*)(d + off_xy2), m, (double*)(d + off_X), (float*)(d + off_err), d + off_keep);
-    if (fail(hipGetLastError())) break;
-    if (fail(hipMemcpyAsync(X, d + off_X, n * 24, hipMemcpyDeviceToHost, st))) break;
-    if (err && fail(hipMemcpyAsync(err, d + off_err, n * 8, hipMemcpyDeviceToHost, st))) break;
-    if (fail(hipMemcpyAsync(keep, d + off_keep, n, hipMemcpyDeviceToHost, st))) break;
-    if (fail(hipStreamSynchronize(st))) break;
-  } while (0);
-  hipFree(d);
-  return rc;
+  SFM_HIP_TRY(hipMemcpyAsync(d, xy1, n * 16, hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemcpyAsync(d + off_xy2, xy2, n * 16, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(triangulate_kernel, dim3((m + 255) / 256), dim3(256), 0, st, p, (const double2*)d,
+                     (const double2*)(d + off_xy2), m, (double*)(d + off_X), (float*)(d + off_err), d + off_keep);
+  SFM_HIP_TRY(hipGetLastError());
+  SFM_HIP_TRY(hipMemcpyAsync(X, d + off_X, n * 24, hipMemcpyDeviceToHost, st));
+  if (err) SFM_HIP_TRY(hipMemcpyAsync(err, d + off_err, n * 8, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipMemcpyAsync(keep, d + off_keep, n, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipStreamSynchronize(st));
+  return SFMHIP_OK;
 }
