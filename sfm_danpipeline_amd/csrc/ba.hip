@@ -33,6 +33,7 @@
 // diag | scalars] is summed by the caller's all-reduce (RCCL over xGMI) once per iteration,
 // every rank then solves the same reduced system and back-substitutes its own points.
 #include "common.h"
+#include "ba_chains_plan.h"
 #include "ba_front_plan.h"
 #include "ba_setup.h"
 #include <algorithm>
@@ -43,7 +44,6 @@
 #include <cstring>
 #include <mutex>
 #include <functional>
-#include <map>
 #include <thread>
 #include <vector>
 #include <float.h>
@@ -2585,19 +2585,18 @@ __global__ __launch_bounds__(C2_WAVES * 64) void chol_step2(double* __restrict__
   chol_step2_body(A, y, X, ld, nt, nt, k2, tiles_per_wg, info, (int)blockIdx.x, sAll, xb, dfr, catchup);
 }
 
-// Several independent matrices ("chains": the interiors of a dissected camera graph, see NdPlan) at the same
+// Several independent matrices ("chains": the interiors of a dissected camera graph, see ba_chains_plan.h) at the same
 // panel pair k2 in ONE launch.  ALL panel workgroups come first in the grid, the trailing workgroups after them
 // (the panel workgroups are the long ones: they start in the first round; the host keeps their number within the
 // device's CUs).
-constexpr int ND_MAX = 8;
 struct ChainSet {
   int n;
-  double* A[ND_MAX];
-  double* y[ND_MAX];
-  double* X[ND_MAX];
-  int ld[ND_MAX], nt[ND_MAX], nxc[ND_MAX], tpw[ND_MAX];
-  int pan0[ND_MAX + 1];  // first panel workgroup of chain c (pan0[n]: all panel workgroups)
-  int trl0[ND_MAX + 1];  // first trailing workgroup of chain c, counted from pan0[n]
+  double* A[cplan::CP_MAX];
+  double* y[cplan::CP_MAX];
+  double* X[cplan::CP_MAX];
+  int ld[cplan::CP_MAX], nt[cplan::CP_MAX], nxc[cplan::CP_MAX], tpw[cplan::CP_MAX];
+  int pan0[cplan::CP_MAX + 1];  // first panel workgroup of chain c (pan0[n]: all panel workgroups)
+  int trl0[cplan::CP_MAX + 1];  // first trailing workgroup of chain c, counted from pan0[n]
 };
 __global__ __launch_bounds__(C2_WAVES * 64) void chol_step2_chains(ChainSet cs, int k2, int* __restrict__ info) {
   extern __shared__ __attribute__((aligned(16))) double sAll[];
@@ -2723,7 +2722,7 @@ __global__ __launch_bounds__(256) void chol_back_block(const double* __restrict_
 // ---------------------------------------------------------------- dissected reduced system
 // S is dense by storage only: its block pattern is the camera co-visibility graph.  When that graph has small
 // vertex separators (an ordered capture: cfg4's ring, banded plus a cyclic corner), the cameras are ordered
-// [interior 1 | interior 2 | ... | separator + focal] with no edge between two interiors (NdPlan, host), and
+// [interior 1 | interior 2 | ... | separator + focal] with no edge between two interiors (ba_chains_plan.h), and
 //   [ D_1          C_1^T ]        L_ii = chol(D_i),  L_Si = C_i L_ii^-T   (P independent "chains", one launch
 //   [      D_2     C_2^T ]                                                 of chol_step2_chains per panel pair)
 //   [ C_1  C_2 ... D_S   ]        D_S' = D_S - sum_i L_Si L_Si^T,  L_SS = chol(D_S')
@@ -2742,7 +2741,7 @@ struct NdChain {
 };
 struct NdSet {
   int n;  // chains; c[n] is the separator
-  NdChain c[ND_MAX + 1];
+  NdChain c[cplan::CP_MAX + 1];
 };
 
 // fills the chains from S (after ba_finalize: the LM diagonal is on it), g and the identity.
@@ -2965,7 +2964,7 @@ __global__ __launch_bounds__(1024) void nd_xy(NdSet ns, int c_lo, double* __rest
 }
 // nd_w: y_i[c] -= sum_s L_i(o + s, c) z_S[s]; a wave per interior column (flat index over the chains)
 struct NdCols {
-  int col0[ND_MAX + 1];
+  int col0[cplan::CP_MAX + 1];
 };
 __global__ __launch_bounds__(256) void nd_w(NdSet ns, NdCols cols) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -3622,7 +3621,7 @@ struct sfmhip_ba {
   int n_pairs_pp = 0;
   long long tree_dbg_ints = 0, tree_dbg_doubles = 0;  // (sizes of the front tree's tables and pool: diagnostic builds)
   int* d_bs_ids = nullptr;  // ba_backsub_runs' records, 16 ints per chunk, large chunks first
-  // dissected reduced system (NdPlan below): built at the first solve (with world > 1 the camera graph is the
+  // dissected reduced system (ba_nd_build below): built at the first solve (with world > 1 the camera graph is the
   // union over the ranks, which needs the all-reduce)
   std::vector<unsigned long long> h_adj;  // camera co-visibility, nc x ceil(nc/64) bit rows (this rank's points)
   bool nd_ready = false, nd_on = false, nd_kept = false;  // nd_kept: the front plan came from the context's last one-shot problem
@@ -3630,7 +3629,6 @@ struct sfmhip_ba {
   NdCols nd_cols{};
   int nd_max_ni = 0;
   double* nd_buf = nullptr;  // all chain matrices, vectors and X blocks (nd_gather writes what the factorisation reads)
-  size_t nd_buf_count = 0;
   int4* nd_gather_jobs = nullptr;
   int nd_n_gather = 0;
   bool chol_chains_attr_set = false;
@@ -3703,6 +3701,20 @@ static int ba_alloc(sfmhip_ba* b, T** p, size_t n) {
   b->allocs.push_back((void*)*p);
   return SFMHIP_OK;
 }
+
+// SFMHIP_PROFILE_CREATE: the host time of every stage of a set-up or a tear-down, one line on stderr per lap
+struct LapTimer {
+  const char* tag;
+  int width;  // of the stage names (the lines of one function align)
+  const bool on = getenv("SFMHIP_PROFILE_CREATE") != nullptr;
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  void lap(const char* what) {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "[%s] %-*s %7.2f ms\n", tag, width, what, std::chrono::duration<double, std::milli>(now - t).count());
+    t = now;
+  }
+};
 
 #ifdef SFM_FRONT_STAMPS
 extern "C" int sfmhip_debug_front_stamps(unsigned long long* out, int n_fronts) {
@@ -3832,14 +3844,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   if (!ctx || !out || n_cam <= 0 || n_pt < 0 || n_obs < 0) return SFMHIP_ERR_ARG;
   if (n_obs && (!obs_cam || !obs_pt || !obs_xy)) return SFMHIP_ERR_ARG;
   SFM_HIP_TRY(hipSetDevice(ctx->device));
-  const bool prof_ = getenv("SFMHIP_PROFILE_CREATE") != nullptr;
-  auto tp_ = std::chrono::steady_clock::now();
-  auto lap_ = [&](const char* what) {
-    if (!prof_) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[sfmhip_ba_create] %-22s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tp_).count());
-    tp_ = now;
-  };
+  LapTimer prof{"sfmhip_ba_create", 22};
   sfmhip_ba* b = new sfmhip_ba();
   b->ctx = ctx;
   b->use_arena = arena;
@@ -3876,7 +3881,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
     in.n_cu = ctx->n_cu;
     in.deterministic = b->elim_deterministic;
     in.short_pieces = getenv("SFMHIP_BA_SHORT_PIECES") ? atoi(getenv("SFMHIP_BA_SHORT_PIECES")) : 512;  // (read per problem)
-    if (prof_) in.lap = lap_;
+    if (prof.on) in.lap = [&prof](const char* what) { prof.lap(what); };
     bsetup::Scratch own_scratch;
     SFM_TRY(bsetup::build(in, arena ? hs->setup : own_scratch, S));
   }
@@ -3992,7 +3997,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   auto up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
     return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
   };
-  lap_("hipMalloc x27");
+  prof.lap("hipMalloc x27");
   SFM_HIP_TRY(up(d_optr, S.optr.data(), S.optr.size() * 4));
   SFM_HIP_TRY(up(d_ocam, S.ocam.data(), S.ocam.size() * 4));
   SFM_HIP_TRY(up(b->d_obs_src, b->obs_src.data(), b->obs_src.size() * 4));
@@ -4029,7 +4034,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   SFM_HIP_TRY(up(b->d_pair_cams, S.pair_cams.data(), S.pair_cams.size() * sizeof(int2)));
   SFM_HIP_TRY(up(b->d_pair_ent, S.pair_ent.data(), S.pair_ent.size() * sizeof(int2)));
   b->n_pairs_pp = (int)S.pair_cams.size();
-  lap_("uploads");
+  prof.lap("uploads");
   const size_t sc_bytes = (sizeof(double) * (SC + 64 + RED2_N + 1) + 255) & ~(size_t)255, ring_bytes = sizeof(LmDev) * LM_RING;
   if (arena) {
     // (the records the device writes to the host: the context's pinned block, made once -- 0.5 ms per problem otherwise)
@@ -4065,7 +4070,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   d.lm_host = (double*)b->h_ring_dev;
   for (auto& e : b->ev) SFM_HIP_TRY(hipEventCreate(&e));
   b->h_pts_in.assign(3 * (size_t)n_pt, 0.0);
-  lap_("pinned + events");
+  prof.lap("pinned + events");
   guard.b = nullptr;
   *out = b;
   return SFMHIP_OK;
@@ -4444,345 +4449,169 @@ static int ba_finish_pending(sfmhip_ba* b) {
   return SFMHIP_OK;
 }
 
-// ---------------------------------------------------------------- NdPlan: dissection of the camera graph
-// Order: reverse Cuthill-McKee positions pi; a cut at position p puts every camera at or behind p that sees a
-// camera before p into the separator; what is left falls into connected components that do not see each
-// other (interiors).  Cuts are chosen from a grid of positions (1..3 cuts) to minimise the number of
-// two-panel launches on the dependency chain, max_i tiles_i / 2 + tiles_S / 2 + a constant for the gather /
-// combine / three-step solve; the dense factorisation stays when that does not win by 20 %.
+// ---------------------------------------------------------------- the dissected reduced system: which plan, and its upload
+// world > 1: the camera graph becomes the union over the ranks (bits as doubles through the caller's sum all-reduce; set-up,
+// once), and the exchange list of a linearisation is built from it
+static int ba_union_adjacency(sfmhip_ba* b, std::vector<unsigned long long>& adj) {
+  const int nc = b->nc, wpr = (nc + 63) / 64;
+  std::vector<double> h((size_t)nc * nc);
+  for (int i = 0; i < nc; ++i)
+    for (int j = 0; j < nc; ++j) h[(size_t)i * nc + j] = (adj[(size_t)i * wpr + (j >> 6)] >> (j & 63)) & 1ull ? 1.0 : 0.0;
+  double* dbuf = nullptr;
+  SFM_TRY(ba_alloc(b, &dbuf, h.size()));
+  SFM_HIP_TRY(hipMemcpy(dbuf, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  SFM_TRY(ba_allreduce(b, dbuf, h.size()));
+  SFM_HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+  SFM_HIP_TRY(hipMemcpy(h.data(), dbuf, h.size() * 8, hipMemcpyDeviceToHost));
+  for (int i = 0; i < nc; ++i)
+    for (int j = 0; j < nc; ++j)
+      if (h[(size_t)i * nc + j] > 0.5) adj[(size_t)i * wpr + (j >> 6)] |= 1ull << (j & 63);
+  // ---- the exchange of a linearisation: only the blocks of camera pairs that some rank's points see together,
+  // when that is less than half of the packed triangle
+  std::vector<int2> xb;
+  for (int a = 0; a < nc; ++a)
+    for (int c = a; c < nc; ++c)
+      if (c == a || ((adj[(size_t)a * wpr + (c >> 6)] >> (c & 63)) & 1ull) || ((adj[(size_t)c * wpr + (a >> 6)] >> (a & 63)) & 1ull))
+        xb.push_back(make_int2(a, c));
+  const size_t tri = (size_t)b->ld * (b->ld + 1) / 2;
+  if (xb.size() * 36 + b->dim < tri / 2) {
+    SFM_TRY(ba_alloc(b, &b->d_xblocks, xb.size()));
+    SFM_HIP_TRY(hipMemcpy(b->d_xblocks, xb.data(), xb.size() * sizeof(int2), hipMemcpyHostToDevice));
+    b->n_xblocks = (int)xb.size();
+  }
+  return SFMHIP_OK;
+}
+
+// the front tree (ba_front_plan.h): every front on one CU.  *on: the graph has such a plan, and it is on the device.
+static int ba_tree_attach(sfmhip_ba* b, const std::vector<unsigned long long>& adj, int wpr, bool* on) {
+  const int nc = b->nc;
+  *on = false;
+  fplan::Plan P;
+  fplan::Flat fl;
+  LapTimer prof{"ba_nd_build", 22};
+  // (a one-shot problem: the plan of the last one, when the camera graph and the device are the same -- BaHostScratch)
+  BaHostScratch* const hs = ba_plan_cache_on() && b->use_arena && b->world == 1 ? ba_host_scratch(b->ctx) : nullptr;
+  const bool kept = hs && hs->nd_valid && hs->nd_nc == nc && hs->nd_n_cu == b->ctx->n_cu && hs->nd_adj == adj;
+  b->nd_kept = kept;
+  if (kept) {
+    P = hs->nd_P;
+    fl = hs->nd_fl;
+  } else {
+    // components up to this many columns become leaves: the largest size whose fronts fit (a leaf of three tiles under a
+    // border of five does not)
+    for (int leaf : {96, 64, 32}) {
+      P = fplan::build_plan(nc, adj.data(), wpr, leaf);
+      if (P.ok) break;
+    }
+    if (P.ok) fl = fplan::flatten(P);
+    if (hs) {  // (a refused plan is kept as well: the next call does not search for it again)
+      hs->nd_valid = true, hs->nd_nc = nc, hs->nd_n_cu = b->ctx->n_cu, hs->nd_adj = adj, hs->nd_P = P, hs->nd_fl = fl;
+    }
+  }
+  prof.lap(kept ? "front plan (kept)" : "front plan");
+  if (!P.ok) {
+    if (getenv("SFMHIP_BA_ND_VERBOSE")) fprintf(stderr, "[sfmhip] no front tree: %s\n", P.why);
+    return SFMHIP_OK;
+  }
+  int* d_ints = nullptr;
+  int* d_up = nullptr;
+  int* d_down = nullptr;
+  unsigned* d_flags = nullptr;
+  double* pool = nullptr;
+  SFM_TRY(ba_alloc(b, &d_ints, fl.ints.size()));
+  SFM_TRY(ba_alloc(b, &d_up, fl.up_roles.size()));
+  SFM_TRY(ba_alloc(b, &d_down, fl.down_order.size()));
+  const size_t n_flags = (size_t)fl.n_fronts + (size_t)fl.n_tflags;  // per front: z in place; per contribution tile
+  SFM_TRY(ba_alloc(b, &d_flags, n_flags));
+  SFM_TRY(ba_alloc(b, &pool, fl.n_doubles));
+  SFM_HIP_TRY(hipMemcpy(d_ints, fl.ints.data(), fl.ints.size() * sizeof(int), hipMemcpyHostToDevice));
+  SFM_HIP_TRY(hipMemcpy(d_up, fl.up_roles.data(), fl.up_roles.size() * sizeof(int), hipMemcpyHostToDevice));
+  SFM_HIP_TRY(hipMemcpy(d_down, fl.down_order.data(), fl.down_order.size() * sizeof(int), hipMemcpyHostToDevice));
+  SFM_HIP_TRY(hipMemset(d_flags, 0, n_flags * sizeof(unsigned)));
+  SFM_HIP_TRY(hipMemset(pool, 0, fl.n_doubles * sizeof(double)));
+
+  b->tree_fs.ints = d_ints;
+  b->tree_fs.up_order = d_up;
+  b->tree_fs.down_order = d_down;
+  b->tree_fs.pool = pool;
+  b->tree_dbg_ints = (long long)fl.ints.size(), b->tree_dbg_doubles = (long long)fl.n_doubles;
+  b->tree_fs.flag_down = d_flags;
+  b->tree_fs.tflag = d_flags + fl.n_fronts;
+  double* zq = nullptr;
+  SFM_TRY(ba_alloc(b, &zq, 2 * (size_t)b->ld));
+  {
+    std::vector<unsigned long long> pend(2 * (size_t)b->ld, FR_Z_PENDING);
+    SFM_HIP_TRY(hipMemcpy(zq, pend.data(), pend.size() * 8, hipMemcpyHostToDevice));
+  }
+  prof.lap("plan uploads");
+  b->tree_fs.zq = zq;
+  b->tree_fs.zq_ld = b->ld;
+  b->tree_fs.n_fronts = fl.n_fronts;
+
+  b->tree_levels = fl.levels;
+  b->tree_chain_tiles = P.chain_tiles;
+  b->tree_chain_blocks = P.chain_blocks;
+  b->tree_max_T = P.max_T;
+  b->tree_on = *on = true;
+  b->nd_on = true;  // (what the two share: the deferred ba_finalize, the pre-zeroed second buffer)
+  if (getenv("SFMHIP_BA_ND_VERBOSE"))
+    fprintf(stderr, "[sfmhip] reduced system as a front tree: %d fronts, %d levels, %d tile steps (%d block steps) on the chain, fronts of up to %d tiles; dense %d tiles\n",
+            fl.n_fronts, fl.levels, P.chain_tiles, P.chain_blocks, P.max_T, b->ld / CB);
+  return SFMHIP_OK;
+}
+
+// chains + separator (ba_chains_plan.h): one buffer for every chain's M | X | y, the index maps, nd_gather's job list
+static int ba_chains_attach(sfmhip_ba* b, const cplan::Flat& fl) {
+  NdSet& ns = b->nd;
+  ns.n = fl.n;
+  SFM_TRY(ba_alloc(b, &b->nd_buf, fl.total));
+  for (int i = 0; i <= fl.n; ++i) {
+    NdChain& c = ns.c[i];
+    c.ld = fl.c[i].ld, c.ni = fl.c[i].ni, c.N = fl.c[i].N;
+    c.M = b->nd_buf + fl.offM[i];
+    c.X = b->nd_buf + fl.offX[i];
+    c.y = b->nd_buf + fl.offy[i];
+    int* dinv = nullptr;
+    SFM_TRY(ba_alloc(b, &dinv, fl.inv[i].size()));
+    SFM_HIP_TRY(hipMemcpy(dinv, fl.inv[i].data(), fl.inv[i].size() * 4, hipMemcpyHostToDevice));
+    c.inv = dinv;
+    b->nd_cols.col0[i] = fl.col0[i];
+  }
+  SFM_TRY(ba_alloc(b, &b->nd_gather_jobs, fl.jobs.size()));
+  SFM_HIP_TRY(hipMemcpy(b->nd_gather_jobs, fl.jobs.data(), fl.jobs.size() * sizeof(int4), hipMemcpyHostToDevice));
+  b->nd_n_gather = (int)fl.jobs.size();
+  b->nd_max_ni = fl.max_ni;
+  b->nd_on = true;
+  return SFMHIP_OK;
+}
+
+// SFMHIP_BA_ND -- "0": dense always; "1": chains + separator whenever a cut exists (tests); "2": the front tree or dense;
+// unset: the front tree, else chains + separator when its cost model wins over dense by 20 %, else dense
 static int ba_nd_build(sfmhip_ba* b) {
   b->nd_ready = true;
   b->nd_on = false;
-  const int nc = b->nc;
-  const char* env = getenv("SFMHIP_BA_ND");  // "0": dense always; "1": dissect whenever a cut exists (tests)
   if (b->h_adj.empty()) return SFMHIP_OK;
-  const bool force = env && env[0] == '1';
-  const int wpr = (nc + 63) / 64;
+  const char* env = getenv("SFMHIP_BA_ND");
+  const char mode = env ? env[0] : 0;
+  const int nc = b->nc, wpr = (nc + 63) / 64, dense_tiles = b->ld / CB;
   std::vector<unsigned long long> adj = b->h_adj;
-  if (b->world > 1) {
-    // union over the ranks: bits as doubles through the caller's sum all-reduce (set-up, once)
-    std::vector<double> h((size_t)nc * nc);
-    for (int i = 0; i < nc; ++i)
-      for (int j = 0; j < nc; ++j) h[(size_t)i * nc + j] = (adj[(size_t)i * wpr + (j >> 6)] >> (j & 63)) & 1ull ? 1.0 : 0.0;
-    double* dbuf = nullptr;
-    SFM_TRY(ba_alloc(b, &dbuf, h.size()));
-    SFM_HIP_TRY(hipMemcpy(dbuf, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-    SFM_TRY(ba_allreduce(b, dbuf, h.size()));
-    SFM_HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    SFM_HIP_TRY(hipMemcpy(h.data(), dbuf, h.size() * 8, hipMemcpyDeviceToHost));
-    for (int i = 0; i < nc; ++i)
-      for (int j = 0; j < nc; ++j)
-        if (h[(size_t)i * nc + j] > 0.5) adj[(size_t)i * wpr + (j >> 6)] |= 1ull << (j & 63);
-    // ---- the exchange of a linearisation: only the blocks of camera pairs that some rank's points see together,
-    // when that is less than half of the packed triangle
-    std::vector<int2> xb;
-    for (int a = 0; a < nc; ++a)
-      for (int c = a; c < nc; ++c)
-        if (c == a || ((adj[(size_t)a * wpr + (c >> 6)] >> (c & 63)) & 1ull) || ((adj[(size_t)c * wpr + (a >> 6)] >> (a & 63)) & 1ull))
-          xb.push_back(make_int2(a, c));
-    const size_t tri = (size_t)b->ld * (b->ld + 1) / 2;
-    if (xb.size() * 36 + b->dim < tri / 2) {
-      SFM_TRY(ba_alloc(b, &b->d_xblocks, xb.size()));
-      SFM_HIP_TRY(hipMemcpy(b->d_xblocks, xb.data(), xb.size() * sizeof(int2), hipMemcpyHostToDevice));
-      b->n_xblocks = (int)xb.size();
-    }
+  if (b->world > 1) SFM_TRY(ba_union_adjacency(b, adj));
+  if (mode == '0') return SFMHIP_OK;
+  if (mode != '1') {
+    bool tree = false;
+    SFM_TRY(ba_tree_attach(b, adj, wpr, &tree));
+    if (tree || mode == '2') return SFMHIP_OK;
   }
-  if (env && env[0] == '0') return SFMHIP_OK;
-  // ---- the front tree first (SFMHIP_BA_ND=2 or unset): every front on one CU; "1" keeps the chains + separator plan below
-  if (!(env && env[0] == '1')) {
-    // components up to this many columns become leaves: the largest size whose fronts fit (a leaf of three tiles under a
-    // border of five does not)
-    fplan::Plan P;
-    fplan::Flat fl;
-    const bool prof_ = getenv("SFMHIP_PROFILE_CREATE") != nullptr;
-    auto tp_ = std::chrono::steady_clock::now();
-    auto lap_ = [&](const char* what) {
-      if (!prof_) return;
-      const auto now = std::chrono::steady_clock::now();
-      fprintf(stderr, "[ba_nd_build] %-22s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tp_).count());
-      tp_ = now;
-    };
-    // (a one-shot problem: the plan of the last one, when the camera graph and the device are the same -- BaHostScratch)
-    BaHostScratch* const hs = ba_plan_cache_on() && b->use_arena && b->world == 1 ? ba_host_scratch(b->ctx) : nullptr;
-    const bool kept = hs && hs->nd_valid && hs->nd_nc == nc && hs->nd_n_cu == b->ctx->n_cu && hs->nd_adj == adj;
-    b->nd_kept = kept;
-    if (kept) {
-      P = hs->nd_P;
-      fl = hs->nd_fl;
-    } else {
-      for (int leaf : {96, 64, 32}) {
-        P = fplan::build_plan(nc, adj.data(), wpr, leaf);
-        if (P.ok) break;
-      }
-      if (P.ok) fl = fplan::flatten(P);
-      if (hs) {  // (a refused plan is kept as well: the next call does not search for it again)
-        hs->nd_valid = true, hs->nd_nc = nc, hs->nd_n_cu = b->ctx->n_cu, hs->nd_adj = adj, hs->nd_P = P, hs->nd_fl = fl;
-      }
-    }
-    lap_(kept ? "front plan (kept)" : "front plan");
-    if (P.ok) {
-      int* d_ints = nullptr;
-      int* d_up = nullptr;
-      int* d_down = nullptr;
-      unsigned* d_flags = nullptr;
-      double* pool = nullptr;
-      SFM_TRY(ba_alloc(b, &d_ints, fl.ints.size()));
-      SFM_TRY(ba_alloc(b, &d_up, fl.up_roles.size()));
-      SFM_TRY(ba_alloc(b, &d_down, fl.down_order.size()));
-      const size_t n_flags = (size_t)fl.n_fronts + (size_t)fl.n_tflags;  // per front: z in place; per contribution tile
-      SFM_TRY(ba_alloc(b, &d_flags, n_flags));
-      SFM_TRY(ba_alloc(b, &pool, fl.n_doubles));
-      SFM_HIP_TRY(hipMemcpy(d_ints, fl.ints.data(), fl.ints.size() * sizeof(int), hipMemcpyHostToDevice));
-      SFM_HIP_TRY(hipMemcpy(d_up, fl.up_roles.data(), fl.up_roles.size() * sizeof(int), hipMemcpyHostToDevice));
-      SFM_HIP_TRY(hipMemcpy(d_down, fl.down_order.data(), fl.down_order.size() * sizeof(int), hipMemcpyHostToDevice));
-      SFM_HIP_TRY(hipMemset(d_flags, 0, n_flags * sizeof(unsigned)));
-      SFM_HIP_TRY(hipMemset(pool, 0, fl.n_doubles * sizeof(double)));
-
-      b->tree_fs.ints = d_ints;
-      b->tree_fs.up_order = d_up;
-      b->tree_fs.down_order = d_down;
-      b->tree_fs.pool = pool;
-      b->tree_dbg_ints = (long long)fl.ints.size(), b->tree_dbg_doubles = (long long)fl.n_doubles;
-      b->tree_fs.flag_down = d_flags;
-      b->tree_fs.tflag = d_flags + fl.n_fronts;
-      double* zq = nullptr;
-      SFM_TRY(ba_alloc(b, &zq, 2 * (size_t)b->ld));
-      {
-        std::vector<unsigned long long> pend(2 * (size_t)b->ld, FR_Z_PENDING);
-        SFM_HIP_TRY(hipMemcpy(zq, pend.data(), pend.size() * 8, hipMemcpyHostToDevice));
-      }
-      lap_("plan uploads");
-      b->tree_fs.zq = zq;
-      b->tree_fs.zq_ld = b->ld;
-      b->tree_fs.n_fronts = fl.n_fronts;
-
-      b->tree_levels = fl.levels;
-      b->tree_chain_tiles = P.chain_tiles;
-      b->tree_chain_blocks = P.chain_blocks;
-      b->tree_max_T = P.max_T;
-      b->tree_on = true;
-      b->nd_on = true;  // (what the two share: the deferred ba_finalize, the pre-zeroed second buffer)
-      if (getenv("SFMHIP_BA_ND_VERBOSE"))
-        fprintf(stderr, "[sfmhip] reduced system as a front tree: %d fronts, %d levels, %d tile steps (%d block steps) on the chain, fronts of up to %d tiles; dense %d tiles\n",
-                fl.n_fronts, fl.levels, P.chain_tiles, P.chain_blocks, P.max_T, b->ld / CB);
-      return SFMHIP_OK;
-    }
-    if (getenv("SFMHIP_BA_ND_VERBOSE")) fprintf(stderr, "[sfmhip] no front tree: %s\n", P.why);
-    if (env && env[0] == '2') return SFMHIP_OK;
-  }
-  std::vector<std::vector<int>> nb(nc);
-  for (int i = 0; i < nc; ++i)
-    for (int j = 0; j < nc; ++j)
-      if (j != i && ((adj[(size_t)i * wpr + (j >> 6)] >> (j & 63)) & 1ull)) nb[i].push_back(j);
-  // ---- RCM positions (every connected component from a pseudo-peripheral start)
-  std::vector<int> order, pos(nc, -1), lvl(nc);
-  order.reserve(nc);
-  auto bfs = [&](int start, std::vector<int>& out) {
-    out.clear();
-    std::fill(lvl.begin(), lvl.end(), -1);
-    out.push_back(start);
-    lvl[start] = 0;
-    for (size_t h = 0; h < out.size(); ++h) {
-      const int u = out[h];
-      std::vector<int> nx;
-      for (int v : nb[u])
-        if (lvl[v] < 0 && pos[v] < 0) {
-          lvl[v] = lvl[u] + 1;
-          nx.push_back(v);
-        }
-      std::sort(nx.begin(), nx.end(), [&](int a, int c) { return nb[a].size() != nb[c].size() ? nb[a].size() < nb[c].size() : a < c; });
-      for (int v : nx) out.push_back(v);
-    }
-  };
-  std::vector<int> comp;
-  for (int s0 = 0; s0 < nc; ++s0) {
-    if (pos[s0] >= 0) continue;
-    int start = s0;
-    for (int rep = 0; rep < 2; ++rep) {  // farthest vertex of the farthest vertex
-      bfs(start, comp);
-      start = comp.back();
-    }
-    bfs(start, comp);
-    for (int v : comp) {
-      pos[v] = (int)order.size();
-      order.push_back(v);
-    }
-  }
-  std::vector<int> minpos(nc);
-  for (int v = 0; v < nc; ++v) {
-    int m = pos[v];
-    for (int u : nb[v]) m = std::min(m, pos[u]);
-    minpos[v] = m;
-  }
-  // ---- evaluate a set of cuts: separator, components (chains by LPT when more than ND_MAX), launches
-  struct Eval {
-    double cost = 1e300;
-    std::vector<int> sep;                  // cameras
-    std::vector<std::vector<int>> chains;  // cameras of every chain, ascending
-  };
-  const int dense_tiles = b->ld / CB, n_cu_ = b->ctx->n_cu;
-  auto evaluate = [&](const std::vector<int>& cuts, Eval& e) {
-    std::vector<char> in_sep(nc, 0);
-    for (int v = 0; v < nc; ++v)
-      for (int p : cuts)
-        if (pos[v] >= p && minpos[v] < p) in_sep[v] = 1;
-    std::vector<int> root(nc);
-    for (int v = 0; v < nc; ++v) root[v] = v;
-    std::function<int(int)> find = [&](int x) {
-      while (root[x] != x) x = root[x] = root[root[x]];
-      return x;
-    };
-    for (int v = 0; v < nc; ++v)
-      if (!in_sep[v])
-        for (int u : nb[v])
-          if (!in_sep[u]) root[find(u)] = find(v);
-    std::map<int, std::vector<int>> comps;
-    e.sep.clear();
-    for (int v = 0; v < nc; ++v) {
-      if (in_sep[v]) e.sep.push_back(v);
-      else comps[find(v)].push_back(v);
-    }
-    if (comps.size() < 2) return;
-    std::vector<std::vector<int>> cl;
-    for (auto& kv : comps) cl.push_back(kv.second);
-    std::sort(cl.begin(), cl.end(), [](const std::vector<int>& a, const std::vector<int>& c) {
-      return a.size() != c.size() ? a.size() > c.size() : a[0] < c[0];
-    });
-    const int nch = (int)std::min<size_t>(cl.size(), ND_MAX);
-    e.chains.assign(nch, {});
-    for (auto& c : cl) {
-      int best = 0;
-      for (int k = 1; k < nch; ++k)
-        if (e.chains[k].size() < e.chains[best].size()) best = k;
-      e.chains[best].insert(e.chains[best].end(), c.begin(), c.end());
-    }
-    int max_t = 0;
-    for (auto& c : e.chains) {
-      std::sort(c.begin(), c.end());
-      max_t = std::max(max_t, (int)((6 * c.size() + 63) / 64) * 2);
-    }
-    const int sep_t = (int)((6 * e.sep.size() + 1 + 63) / 64) * 2;
-    e.cost = 0.5 * max_t + 0.5 * sep_t + 2.5;
-    // the panel workgroups of a launch in one round of workgroups (a second round doubles the launch): launch 0
-    // has N_i + 2 per chain
-    int pan = 0;
-    for (auto& c : e.chains) pan += (int)((6 * c.size() + 63) / 64) * 2 + sep_t + 2;
-    if (pan > n_cu_) e.cost = 1e300;
-  };
-  Eval best;
-  {
-    const int G = nc > 1024 ? 12 : 24;
-    std::vector<int> grid;
-    for (int k = 1; k < G; ++k) grid.push_back((int)((long long)nc * k / G));
-    Eval e;
-    for (size_t i = 0; i < grid.size(); ++i) {  // at most three cuts
-      evaluate({grid[i]}, e);
-      if (e.cost < best.cost) best = e;
-      for (size_t j = i + 1; j < grid.size(); ++j) {
-        evaluate({grid[i], grid[j]}, e);
-        if (e.cost < best.cost) best = e;
-        if (nc <= 1024)
-          for (size_t k = j + 1; k < grid.size(); k += 2) {
-            evaluate({grid[i], grid[j], grid[k]}, e);
-            if (e.cost < best.cost) best = e;
-          }
-      }
-    }
-  }
-  if (best.chains.empty() || best.cost >= 1e299 || !(force || best.cost <= 0.8 * (0.5 * dense_tiles))) return SFMHIP_OK;
-  {  // what nd_backsolve holds in LDS
-    size_t max_c = 0;
-    for (auto& c : best.chains) max_c = std::max(max_c, c.size());
-    (void)max_c;
-  }
-  // ---- chains: index maps, buffers, job lists
-  const int P = (int)best.chains.size();
-  if (getenv("SFMHIP_BA_ND_VERBOSE")) {  // the plan's invariants: a partition of the cameras, no edge between two chains
-    std::vector<int> owner(nc, -2);
-    int bad = 0;
-    for (int c : best.sep) owner[c] = -1;
-    for (int i = 0; i < P; ++i)
-      for (int c : best.chains[i]) {
-        if (owner[c] != -2) ++bad;
-        owner[c] = i;
-      }
-    for (int c = 0; c < nc; ++c) {
-      if (owner[c] == -2) ++bad;
-      for (int u : nb[c])
-        if (owner[c] >= 0 && owner[u] >= 0 && owner[u] != owner[c]) ++bad;
-    }
-    fprintf(stderr, "[sfmhip] dissection check: %d violations\n", bad);
-  }
-  const int NS = (int)((6 * best.sep.size() + 1 + 63) / 64) * 2;
-  std::vector<int> invS((size_t)NS * 32, -1);
-  {
-    int k = 0;
-    for (int c : best.sep)
-      for (int j = 0; j < 6; ++j) invS[k++] = 6 * c + j;
-    invS[k++] = 6 * nc;  // the focal
-  }
-  NdSet& ns = b->nd;
-  ns.n = P;
-  std::vector<std::vector<int>> inv(P);
-  size_t total = 0;
-  std::vector<size_t> offM(P + 1), offy(P + 1), offX(P + 1);
-  b->nd_max_ni = 0;
-  for (int i = 0; i <= P; ++i) {
-    const int ni = i < P ? (int)((6 * best.chains[i].size() + 63) / 64) * 2 : NS;
-    const int N = i < P ? ni + NS : NS;
-    if (i < P) {
-      inv[i].assign((size_t)N * 32, -1);
-      int k = 0;
-      for (int c : best.chains[i])
-        for (int j = 0; j < 6; ++j) inv[i][k++] = 6 * c + j;
-      for (int k2 = 0; k2 < NS * 32; ++k2) inv[i][(size_t)ni * 32 + k2] = invS[k2];
-      b->nd_max_ni = std::max(b->nd_max_ni, ni);
-    }
-    ns.c[i].ld = N * 32;
-    ns.c[i].ni = ni;
-    ns.c[i].N = N;
-    offM[i] = total;
-    total += (size_t)N * 32 * N * 32;
-    offX[i] = total;
-    total += (size_t)N * 32 * N * 32;
-    offy[i] = total;
-    total += (size_t)N * 32;
-  }
-  SFM_TRY(ba_alloc(b, &b->nd_buf, total));
-  b->nd_buf_count = total;
-  std::vector<int4> gj;
-  b->nd_cols.col0[0] = 0;
-  for (int i = 0; i <= P; ++i) {
-    NdChain& c = ns.c[i];
-    c.M = b->nd_buf + offM[i];
-    c.X = b->nd_buf + offX[i];
-    c.y = b->nd_buf + offy[i];
-    int* dinv = nullptr;
-    const std::vector<int>& hv = i < P ? inv[i] : invS;
-    SFM_TRY(ba_alloc(b, &dinv, hv.size()));
-    SFM_HIP_TRY(hipMemcpy(dinv, hv.data(), hv.size() * 4, hipMemcpyHostToDevice));
-    c.inv = dinv;
-    if (i < P) b->nd_cols.col0[i + 1] = b->nd_cols.col0[i] + c.ni * 32;
-    for (int tr = 0; tr < c.N; ++tr) {
-      for (int tc = 0; tc <= std::min(tr, c.ni - 1); ++tc) gj.push_back(make_int4(i, tr, tc, 0));
-      gj.push_back(make_int4(i, tr, 0, 1));
-      // what the factorisation reads before it writes: the lower right block of M (zero), the interior rows of X
-      // (the identity; its tiles left of the diagonal are read too) -- no memset of the chain buffers
-      for (int tc = c.ni; tc <= tr; ++tc) gj.push_back(make_int4(i, tr, tc, 2));
-      // (a chain's X is only formed up to its interior columns: nxc in chol_step2_chains)
-      if (tr < c.ni)
-        for (int tc = 0; tc < (i < P ? c.ni : c.N); ++tc) gj.push_back(make_int4(i, tr, tc, 3));
-    }
-  }
-  gj.push_back(make_int4(0, 0, 0, 4));  // (ba_finalize's part, when it is deferred to the gather)
-  SFM_TRY(ba_alloc(b, &b->nd_gather_jobs, gj.size()));
-  SFM_HIP_TRY(hipMemcpy(b->nd_gather_jobs, gj.data(), gj.size() * sizeof(int4), hipMemcpyHostToDevice));
-  b->nd_n_gather = (int)gj.size();
-  b->nd_on = true;
-  if (getenv("SFMHIP_BA_ND_VERBOSE")) {
-    fprintf(stderr, "[sfmhip] reduced system dissected: %d chains (", P);
-    for (int i = 0; i < P; ++i) fprintf(stderr, "%s%d", i ? "," : "", ns.c[i].ni);
-    fprintf(stderr, " tiles) + separator %d tiles (%zu cameras); dense %d tiles\n", NS, best.sep.size(), dense_tiles);
+  const cplan::Plan P = cplan::build_plan(nc, adj.data(), wpr, dense_tiles, b->ctx->n_cu, mode == '1');
+  if (!P.ok) return SFMHIP_OK;
+  const bool verbose = getenv("SFMHIP_BA_ND_VERBOSE") != nullptr;
+  if (verbose) fprintf(stderr, "[sfmhip] dissection check: %d violations\n", cplan::violations(P, nc, adj.data(), wpr));
+  const cplan::Flat fl = cplan::flatten(P, nc);
+  SFM_TRY(ba_chains_attach(b, fl));
+  if (verbose) {
+    fprintf(stderr, "[sfmhip] reduced system dissected: %d chains (", fl.n);
+    for (int i = 0; i < fl.n; ++i) fprintf(stderr, "%s%d", i ? "," : "", fl.c[i].ni);
+    fprintf(stderr, " tiles) + separator %d tiles (%zu cameras); dense %d tiles\n", fl.NS, P.sep.size(), dense_tiles);
   }
   return SFMHIP_OK;
 }
@@ -4824,6 +4653,14 @@ static void nd_census(sfmhip_ba* b, const char* stage) {
   }
 }
 
+// the workgroups of a dissected solve's first launch that zero the other [S | g | ... | red2] buffer (allocated at the first
+// solve) -- all nz doubles of it but X: an even number, ld is a multiple of 64 and SC + 64 + RED2_N even; 0: nothing to zero;
+// < 0: an error code
+static int ba_zero_wgs(sfmhip_ba* b, size_t nz) {
+  if (b->prezero && !b->red_alt && nz % 2 == 0) SFM_TRY(ba_alloc(b, &b->red_alt, nz));
+  return b->prezero && b->red_alt ? (int)((nz + ND_ZERO_SLICE - 1) / ND_ZERO_SLICE) : 0;
+}
+
 // the front tree: one up-sweep launch (assembly, factorisation, forward substitution; its spare workgroups zero the other
 // reduced-system buffer and do ba_finalize's bookkeeping), one down-sweep launch (backward substitution, candidate cameras)
 static int ba_reduced_solve_tree(sfmhip_ba* b) {
@@ -4833,10 +4670,9 @@ static int ba_reduced_solve_tree(sfmhip_ba* b) {
     SFM_HIP_TRY(hipFuncSetAttribute((const void*)front_up, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BYTES));
     b->tree_attr_set = true;
   }
-  const bool prezero = b->prezero;
   const size_t nz = b->red_count - b->ssz;
-  if (prezero && !b->red_alt && nz % 2 == 0) SFM_TRY(ba_alloc(b, &b->red_alt, nz));
-  const int zwg = prezero && b->red_alt ? (int)((nz + ND_ZERO_SLICE - 1) / ND_ZERO_SLICE) : 0;
+  const int zwg = ba_zero_wgs(b, nz);
+  if (zwg < 0) return zwg;
   const int nF = b->tree_fs.n_fronts;
   // grid: the fronts, then the zeroing workgroups, then one more for the bookkeeping
   const int grid = nF + zwg + 1;
@@ -4874,10 +4710,9 @@ static int ba_reduced_solve_nd(sfmhip_ba* b) {
     SFM_HIP_TRY(hipFuncSetAttribute((const void*)chol_step2, hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS_BYTES));
     b->chol_chains_attr_set = true;
   }
-  const bool prezero = b->prezero;
-  const size_t nz = b->red_count - b->ssz;  // everything but X (an even number of doubles: ld is a multiple of 64, SC + 64 + RED2_N even)
-  if (prezero && !b->red_alt && nz % 2 == 0) SFM_TRY(ba_alloc(b, &b->red_alt, nz));
-  const int zwg = prezero && b->red_alt ? (int)((nz + ND_ZERO_SLICE - 1) / ND_ZERO_SLICE) : 0;
+  const size_t nz = b->red_count - b->ssz;
+  const int zwg = ba_zero_wgs(b, nz);
+  if (zwg < 0) return zwg;
   hipLaunchKernelGGL(nd_gather, dim3(b->nd_n_gather + zwg), dim3(256), 0, st, ns, b->nd_gather_jobs, b->nd_n_gather, d.red,
                      d.red + b->ssz, d.ld, d, b->fin_pending ? 1 : 0, b->fin_radius, b->fin_lo, b->fin_hi, b->world, b->red_alt,
                      (long long)nz);
@@ -5631,25 +5466,18 @@ extern "C" int sfmhip_ba_last_timing(sfmhip_ba* b, double seconds[4], int* launc
 
 extern "C" void sfmhip_ba_destroy(sfmhip_ba* b) {
   if (!b) return;
-  const bool prof_ = getenv("SFMHIP_PROFILE_CREATE") != nullptr;
-  auto tp_ = std::chrono::steady_clock::now();
-  auto lap_ = [&](const char* what) {
-    if (!prof_) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[sfmhip_ba_destroy] %-21s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tp_).count());
-    tp_ = now;
-  };
+  LapTimer prof{"sfmhip_ba_destroy", 21};
   hipSetDevice(b->ctx->device);
   const size_t n_free = b->allocs.size();
   for (void* p : b->allocs) hipFree(p);
-  if (prof_) fprintf(stderr, "[sfmhip_ba_destroy] %zu hipFree\n", n_free);
-  lap_("hipFree");
+  if (prof.on) fprintf(stderr, "[sfmhip_ba_destroy] %zu hipFree\n", n_free);
+  prof.lap("hipFree");
   if (b->h_sc && !b->pinned_shared) hipHostFree(b->h_sc);
   if (b->h_ring && !b->pinned_shared) hipHostFree(b->h_ring);
-  lap_("hipHostFree");
+  prof.lap("hipHostFree");
   for (auto& e : b->ev)
     if (e) hipEventDestroy(e);
-  lap_("events");
+  prof.lap("events");
   if (b->use_arena && b->ctx->ba_host_scratch) {  // (a one-shot problem: its large vectors go back to the context's)
     BaHostScratch* hs = (BaHostScratch*)b->ctx->ba_host_scratch;
     hs->setup.obs_src.swap(b->obs_src);
@@ -5657,7 +5485,7 @@ extern "C" void sfmhip_ba_destroy(sfmhip_ba* b) {
     hs->h_pts_in.swap(b->h_pts_in);
   }
   delete b;
-  lap_("host memory");
+  prof.lap("host memory");
 }
 
 // New measurements for a problem of unchanged structure (the same obs_cam / obs_pt arrays as at its creation): the sorted
