@@ -632,6 +632,67 @@ int sfmhip_ba_lm_decide(sfmhip_lm_state* state, const sfmhip_lm_inputs* in);
 int sfmhip_ba_last_timing(sfmhip_ba* ba, double seconds[4], int* launches);
 void sfmhip_ba_destroy(sfmhip_ba* ba);
 
+/* ---- Dense multi-view stereo: map3D step 7 (reference src/Sfm.cpp:62-67 shells out to pmvs2) ----
+ * Plane-sweep depth maps per reference view, then cross-view consistency fusion into one coloured, oriented cloud.
+ * Parity with pmvs2 is UNPINNED (it expands patches; its output is not comparable point for point); the contract is
+ * this rule list, whose arithmetic is csrc/mvs.h (compiled by g++ and hipcc; the device equals the host build bit for bit).
+ *  1 images: one 8-bit gray image per view (+ optional BGR), one size, one K, [R|t] per view (x_cam = R X + t, 12 doubles
+ *    row-major).  `level` L halves L times with the 2x2 box mean (a+b+c+d+2)>>2, an odd last row / column dropped;
+ *    fx, fy halve, cx' = (cx + 0.5) / 2 - 0.5 (cy likewise).
+ *  2 hypotheses: n_planes fronto-parallel planes of the reference view, uniform in inverse depth, index 0 at dmax and
+ *    n_planes - 1 at dmin; per plane and source the host forms the 3x3 homography reference pixel -> source pixel in f64.
+ *  3 sample: three f64 dot products (h0 x + h1 y) + h2 and two divisions, floor, fractions quantised to 1/32 round half up
+ *    (32 carries), integer bilinear blend rounded to a 12-bit sample (8.4 fixed point, 0 ... 4080); invalid unless all four
+ *    taps are inside the image and the point is in front of the source; the reference pixel's sample is 16 I.
+ *  4 score: window (2 window + 1)^2 inside the reference image; integer sums N, r, r^2, q, q^2, rq (u32, window <= 7);
+ *    NCC = (N rq - r q) / sqrt((N r^2 - (r)^2)(N q^2 - (q)^2)), terms in i64, one f64 product, sqrt and division.  A source
+ *    counts if all its window samples are valid and its variance term is > 0; a reference pixel whose own variance term is
+ *    0 or below var_min has no depth; a hypothesis scores the mean of its n_best largest NCCs (summed in descending order)
+ *    and is invalid with fewer than n_best sources.
+ *  5 winner: largest score, lowest index on ties, accepted if >= ncc_min; three-point parabola refinement in inverse depth
+ *    when the winner is interior and both neighbours are valid.  Outputs: index (-1: none), depth (f32, 0: none), score.
+ *  6 sources (sfmhip_mvs_run): the n_src other views with the nearest camera centres, ties by lower index.
+ *  7 fusion: lift pixel p of view r at depth z to X; view v is consistent if X projects (rounded to the nearest pixel) onto a
+ *    pixel with depth zv, |zv - z_in_v| <= eps z_in_v; keep X if 1 + consistent views >= min_views and r is the lowest view
+ *    among itself and the consistent ones; order view, row, column; normal = unit vector from X to the centre of r; colour
+ *    0x00RRGGBB from the level-L BGR image (gray replicated without one). */
+typedef struct sfmhip_mvs sfmhip_mvs;
+typedef struct sfmhip_mvs_opts {
+  int32_t n_planes;  /* 128; 3 ... 256 */
+  int32_t window;    /* 3; 1 ... 7 */
+  int32_t n_src;     /* 4; 1 ... 8 */
+  int32_t n_best;    /* 2; 1 ... 4 */
+  int32_t min_views; /* 3 (the host mirror passes the reference's minImageNum 5) */
+  int32_t pad;
+  double ncc_min;    /* 0.7 */
+  double eps;        /* 0.01 */
+  double var_min;    /* 614656 = 49^2 16^2: gray values of standard deviation 1 at window 3, in 12-bit units */
+} sfmhip_mvs_opts;
+void sfmhip_mvs_default_opts(sfmhip_mvs_opts* opts);
+/* gray[v]: rows x cols bytes; bgr: NULL or n_views pointers to rows x cols x 3.  SFMHIP_ERR_ARG: n_views < 2, a size of 0
+ * (also after `level` halvings), a null image. */
+int sfmhip_mvs_create(sfmhip_ctx* ctx, int n_views, int rows, int cols, const uint8_t* const* gray, const uint8_t* const* bgr,
+                      const double* K9, const double* poses12, int level, sfmhip_mvs** out);
+void sfmhip_mvs_destroy(sfmhip_mvs* h);
+/* The working level: its size and K; with view >= 0 also that view's gray (and BGR) image.  Every output is nullable. */
+int sfmhip_mvs_level(sfmhip_mvs* h, int32_t* rows, int32_t* cols, double* K9, int view, uint8_t* gray, uint8_t* bgr);
+/* Rules 2-5 for one reference view against the given sources; the depth map stays on the handle for the fusion.  idx, depth,
+ * score: rows x cols of the working level, nullable.  SFMHIP_ERR_ARG: dmin >= dmax or <= 0, options out of range, ref among
+ * the sources, a source twice or out of range. */
+int sfmhip_mvs_depthmap(sfmhip_mvs* h, int ref, int n_src, const int32_t* src, double dmin, double dmax, const sfmhip_mvs_opts* opts,
+                        int32_t* idx, float* depth, float* score);
+/* Test hook: a hand-made depth map for one view (0 = no depth). */
+int sfmhip_mvs_set_depthmap(sfmhip_mvs* h, int view, const float* depth);
+/* Rule 7 over the depth maps the handle holds (a view without one contributes nothing). */
+int sfmhip_mvs_fuse(sfmhip_mvs* h, const sfmhip_mvs_opts* opts, int32_t* n_points);
+/* Rule 6, every view's depth map between dmin[v] and dmax[v], then the fusion. */
+int sfmhip_mvs_run(sfmhip_mvs* h, const double* dmin, const double* dmax, const sfmhip_mvs_opts* opts, int32_t* n_points);
+/* The last fusion's points: xyz and normals 3 floats each, rgb one word each; nullable. */
+int sfmhip_mvs_download(const sfmhip_mvs* h, float* xyz, float* normals, uint32_t* rgb);
+/* ms of the last sfmhip_mvs_run / sfmhip_mvs_fuse: depth maps, fusion, whole call.  The depth maps are timed apart only under
+ * sfmhip_set_timing (one more stream synchronisation); without it [0] is 0 and [1] holds both. */
+int sfmhip_mvs_last_timing(const sfmhip_mvs* h, double ms3[3]);
+
 #ifdef __cplusplus
 }
 #endif

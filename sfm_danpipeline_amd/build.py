@@ -15,7 +15,7 @@ SO = os.path.join(HERE, "libsfmhip.so")
 # and want v_fma_f64 -- "fast-honor-pragmas", not "fast": the one function that must NOT contract, the trust-region decision
 # lm_decide (the same bits on the host and on the device), says so with a pragma, which plain "fast" ignores
 SOURCES = {"context.hip": "off", "match.hip": "off", "triangulate.hip": "off", "incremental.hip": "off",
-           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "segment.hip": "off", "poisson.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
+           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "segment.hip": "off", "poisson.hip": "off", "mvs.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -137,6 +137,13 @@ def build_mesh_demo(force=False):
     writes the mesh as a binary PLY (needs the GPU)."""
     return _build_host_exe(os.path.join(HERE, "sfm_mesh_selftest"),
                            ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "mesh_selftest.cpp"), force)
+
+
+def build_dense_demo(force=False):
+    """map3D's step 7 in the host mirror (StructFromMotion::densify: sfmhip_mvs_run over the registered views) on a directory
+    of frames, a calibration file and a file of poses and sparse points; writes denseCloud's PLY (needs the GPU)."""
+    return _build_host_exe(os.path.join(HERE, "sfm_dense_selftest"),
+                           ("Sfm.cpp", "SfmIO.cpp", "SfmDense.cpp", "BundleAdjustment.cpp", "dense_selftest.cpp"), force)
 
 
 def build_segment_demo(force=False):

@@ -190,6 +190,13 @@ class StructFromMotion {
   // visualize/%04d.jpg = a byte copy of the input file (what the reference's `cp -f` does; its imwrite
   // targets the command string and writes nothing), txt/%04d.txt = "CONTOUR" + K*P.  Does NOT run pmvs2.
   void PMVS2();
+  // step 7 of map3D (reference src/Sfm.cpp:62-67: std::system("pmvs2 denseCloud/ options.txt")), csrc/host/SfmDense.cpp:
+  // sfmhip_mvs_run over the registered views (nGoodViews) at level 1 and min_views 5 (options.txt's level and minImageNum;
+  // rules and the deviations from pmvs2 in DESIGN.md f-10, parity UNPINNED).  A view's depth range is the smallest and the
+  // largest depth of the sparse-cloud points it observes, widened by 25 %; a view with fewer than 8 such points is left
+  // out.  Writes the binary little-endian PLY (x y z nx ny nz red green blue) that convertPLYtoPCD reads and returns the
+  // point count (0: fewer than two usable views, a device error or an unwritable file, with a line on stderr).
+  size_t densify(const std::string& plyPath = "denseCloud/models/options.txt.ply");
   // reference src/Sfm.cpp:69-81 (step 8 of map3D): denseCloud/models/options.txt.ply -> MAP3D.pcd.  The reference
   // does this with pcl::PLYReader + pcl::io::savePCDFile (ASCII, PointXYZRGB); here a PLY reader (ascii and
   // binary_little_endian; x y z [nx ny nz] [diffuse_]red green blue) and a PCD v0.7 ASCII writer in the layout PCL
