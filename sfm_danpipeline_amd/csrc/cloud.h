@@ -35,6 +35,14 @@ SFM_CLOUD_INLINE float canon(float x) { return x != x ? qnan() : x; }
 SFM_CLOUD_INLINE bool finite3(float x, float y, float z) {
   return x - x == 0.0f && y - y == 0.0f && z - z == 0.0f;  // (inf - inf and NaN - NaN are NaN)
 }
+// an order-preserving map of floats to unsigned (-0 below +0, the infinities at the ends of the numbers), so that a
+// bounding box is a min / max reduction over integers whose result does not depend on the order of the operands
+SFM_CLOUD_INLINE uint32_t ord_key(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+SFM_CLOUD_INLINE float ord_val(uint32_t k) { return bits_f((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 // FLANN L2_Simple: ((dx*dx) + dy*dy) + dz*dz in float, no contraction
 SFM_CLOUD_INLINE float dist2(float ax, float ay, float az, float bx, float by, float bz) {

@@ -23,7 +23,6 @@
 #include "cloud.h"
 #include "cloud_grid.h"
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -44,6 +43,26 @@ int sfmgrid::grow_tmp(sfmhip_cloud* c, size_t bytes) {
   c->tmp_bytes = 0;
   SFM_TRY(sfm_dev_alloc((unsigned char**)&c->tmp, bytes));
   c->tmp_bytes = bytes;
+  return SFMHIP_OK;
+}
+
+int sfmgrid::scan(sfmhip_cloud* c, const int* in, int* out, size_t n, int* total) {
+  size_t need = 0;
+  long long t = 0;
+  SFM_TRY(sfm_scan_bytes(n, c->ctx->stream, &need));
+  SFM_TRY(grow_tmp(c, need));
+  SFM_TRY(sfm_exclusive_scan(c->tmp, c->tmp_bytes, in, out, n, c->ctx->stream, total ? &t : nullptr));
+  if (total) *total = (int)t;
+  return SFMHIP_OK;
+}
+
+int sfmgrid::cell_sort(sfmhip_cloud* c, long long ncell, int* keys_in, int* keys_out, int* vals_in, int* vals_out, int n) {
+  unsigned bits = 1;
+  while (bits < 31 && (1ll << bits) <= ncell) ++bits;
+  size_t need = 0;
+  SFM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, keys_in, keys_out, vals_in, vals_out, (unsigned)n, 0u, bits, c->ctx->stream));
+  SFM_TRY(grow_tmp(c, need));
+  SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp, need, keys_in, keys_out, vals_in, vals_out, (unsigned)n, 0u, bits, c->ctx->stream));
   return SFMHIP_OK;
 }
 
@@ -104,14 +123,8 @@ __global__ __launch_bounds__(CHUNK) void cloud_radius_count(GridDev g, const int
   for (int z = max(cz - 1, 0); z <= min(cz + 1, g.D[2] - 1); ++z)
     for (int y = max(cy - 1, 0); y <= min(cy + 1, g.D[1] - 1); ++y) {
       const int row = (z * g.D[1] + y) * g.D[0];
-      int s = INT_MAX, e = 0;
-      for (int x = x0; x <= x1; ++x) {
-        const int st = g.start[row + x], en = g.end[row + x];
-        if (en > st) {
-          s = min(s, st);
-          e = max(e, en);
-        }
-      }
+      int s, e;
+      row_span(g, row, x0, x1, &s, &e);
       for (int b = s; b < e; b += CHUNK) {
         __syncthreads();
         if (b + lane < e) tile[lane] = g.pts[b + lane];
@@ -131,14 +144,8 @@ done:
 template <int N>
 __device__ __forceinline__ void scan_cells(const GridDev& g, int row, int xa, int xb, const float4& p, float (&d)[N], int (&id)[N],
                                            int k, float& kd, int& ki) {
-  int s = INT_MAX, e = 0;
-  for (int x = xa; x <= xb; ++x) {
-    const int st = g.start[row + x], en = g.end[row + x];
-    if (en > st) {
-      s = min(s, st);
-      e = max(e, en);
-    }
-  }
+  int s, e;
+  row_span(g, row, xa, xb, &s, &e);
   for (int j = s; j < e; ++j) {
     const float4 q = g.pts[j];
     const float dd = sfmcloud::dist2(p.x, p.y, p.z, q.x, q.y, q.z);
@@ -281,13 +288,7 @@ int sfmgrid::grid_build(sfmhip_cloud* c, const GridSrc& src, Grid& g, double cel
     GridDev gd = g.dev(src.n_valid);
     hipLaunchKernelGGL(cloud_keys, dim3(blocks(src.n, 256)), dim3(256), 0, st, src.xyz, src.n, gd, (int)g.ncell, kin, vin);
     SFM_HIP_TRY(hipGetLastError());
-    unsigned bits = 1;
-    while (bits < 31 && (1ll << bits) <= g.ncell) ++bits;  // (the invalid key is ncell)
-    size_t need = 0;
-    SFM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, kin, g.keys, vin, vout, (unsigned)src.n, 0u, bits, st));
-    SFM_TRY(grow_tmp(c, need));
-    need = c->tmp_bytes;
-    SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp, need, kin, g.keys, vin, vout, (unsigned)src.n, 0u, bits, st));
+    SFM_TRY(cell_sort(c, g.ncell, kin, g.keys, vin, vout, src.n));
     if (src.n_valid > 0)
       hipLaunchKernelGGL(cloud_ranges, dim3(blocks(src.n_valid, 256)), dim3(256), 0, st, src.xyz, g.keys, vout, src.n_valid, g.start,
                          g.end, g.pts, nonempty);
@@ -307,16 +308,7 @@ int sfmgrid::grid_build(sfmhip_cloud* c, const GridSrc& src, Grid& g, double cel
     int *nch = c->cbuf[0], *off = c->cbuf[1];
     hipLaunchKernelGGL(cloud_chunk_counts, dim3(blocks(g.ncell, 256)), dim3(256), 0, st, g.start, g.end, g.ncell, nch);
     SFM_HIP_TRY(hipGetLastError());
-    size_t need = 0;
-    SFM_HIP_TRY(rocprim::exclusive_scan(nullptr, need, nch, off, 0, (size_t)g.ncell, rocprim::plus<int>(), st));
-    SFM_TRY(grow_tmp(c, need));
-    need = c->tmp_bytes;
-    SFM_HIP_TRY(rocprim::exclusive_scan(c->tmp, need, nch, off, 0, (size_t)g.ncell, rocprim::plus<int>(), st));
-    int last[2] = {0, 0};
-    SFM_HIP_TRY(hipMemcpyAsync(&last[0], off + g.ncell - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-    SFM_HIP_TRY(hipMemcpyAsync(&last[1], nch + g.ncell - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-    g.n_chunks = last[0] + last[1];
+    SFM_TRY(scan(c, nch, off, (size_t)g.ncell, &g.n_chunks));
     SFM_TRY(sfm_dev_alloc(&g.chunks, (size_t)std::max(g.n_chunks, 1)));
     hipLaunchKernelGGL(cloud_chunks, dim3(blocks(g.ncell, 256)), dim3(256), 0, st, g.start, g.end, nch, off, g.ncell, g.chunks);
     SFM_HIP_TRY(hipGetLastError());
@@ -359,11 +351,7 @@ int knn_grid(sfmhip_cloud* c) {
 int compact(sfmhip_cloud* c, int32_t* idx_out, int32_t* n_out) {
   hipStream_t st = c->ctx->stream;
   int *flags = c->ibuf[0], *off = c->ibuf[1], *out = c->ibuf[2], *dn = c->ibuf[3];
-  size_t need = 0;
-  SFM_HIP_TRY(rocprim::exclusive_scan(nullptr, need, flags, off, 0, (size_t)c->n, rocprim::plus<int>(), st));
-  SFM_TRY(grow_tmp(c, need));
-  need = c->tmp_bytes;
-  SFM_HIP_TRY(rocprim::exclusive_scan(c->tmp, need, flags, off, 0, (size_t)c->n, rocprim::plus<int>(), st));
+  SFM_TRY(scan(c, flags, off, (size_t)c->n, nullptr));  // (c->n >= 1: the entry points return early on an empty cloud)
   hipLaunchKernelGGL(cloud_scatter, dim3(blocks(c->n, 256)), dim3(256), 0, st, flags, off, c->n, out, dn);
   SFM_HIP_TRY(hipGetLastError());
   int m = 0;

@@ -1,6 +1,7 @@
-// cloud_grid.h -- the device-resident cloud (sfmhip_cloud) and its uniform grids, shared by cloud.hip (map3D's step 10)
-// and segment.hip (the colour region growing after it).  The bodies of the host functions declared here live in
-// cloud.hip; the two device helpers are inline.
+// cloud_grid.h -- the device-resident cloud (sfmhip_cloud), its uniform grids and the primitives the cloud family shares:
+// cloud.hip (map3D's step 10), segment.hip (the colour region growing after it), poisson.hip (create_mesh) and, for
+// blocks(), mvs.hip.  The bodies of the host functions declared here (grid builds, the handle's scan and cell sort) live
+// in cloud.hip; the device helpers (cell_of, block_bound, row_span, the min / max kernel) are inline.
 //
 // Spatial index: cell coordinates floor((x - lo) / cell) in double, clamped to the grid (a far outlier lands in a
 // border cell instead of stretching the grid: clamping keeps two points whose true cells are adjacent in adjacent
@@ -9,6 +10,7 @@
 // and are in no cell.
 #pragma once
 #include "common.h"
+#include "cloud.h"
 #include <cmath>
 
 namespace sfmgrid {
@@ -101,6 +103,11 @@ namespace sfmgrid {
 inline unsigned blocks(long long n, int b) { return (unsigned)((n + b - 1) / b); }
 int grow_tmp(sfmhip_cloud* c, size_t bytes);
 int ensure_ibuf(sfmhip_cloud* c);
+// common.h's exclusive scan of n >= 1 ints through the handle's tmp, on its stream; with `total`, the sum of `in`
+int scan(sfmhip_cloud* c, const int* in, int* out, size_t n, int* total);
+// rocPRIM's stable radix sort of n (cell id, point) pairs through the handle's tmp, over the bits that hold ids up to
+// and including ncell (the key of a point that is in no cell)
+int cell_sort(sfmhip_cloud* c, long long ncell, int* keys_in, int* keys_out, int* vals_in, int* vals_out, int n);
 GridSrc whole_cloud(const sfmhip_cloud* c);
 // build `g` over `src` with cells of `cell` (grown by 2 until the grid fits CELL_CAP); chunk list for the radius kernel if asked
 int grid_build(sfmhip_cloud* c, const GridSrc& src, Grid& g, double cell, bool chunks);
@@ -126,6 +133,51 @@ __device__ __forceinline__ double block_bound(const GridDev& g, const float4& p,
     if (c[a] + R < g.D[a] - 1) b = fmin(b, fmax(0.0, (g.o[a] + (double)(c[a] + R + 1) * g.cell) - pv[a]));
   }
   return b;
+}
+
+// cells xa..xb of one x row merged into one span of sorted points [*s, *e) (the cells of a row are contiguous in
+// sorted order; *s >= *e when all are empty)
+__device__ __forceinline__ void row_span(const GridDev& g, int row, int xa, int xb, int* s, int* e) {
+  *s = INT_MAX;
+  *e = 0;
+  for (int x = xa; x <= xb; ++x) {
+    const int st = g.start[row + x], en = g.end[row + x];
+    if (en > st) {
+      *s = min(*s, st);
+      *e = max(*e, en);
+    }
+  }
+}
+
+// the ordered keys (cloud.h) of the per-axis minima out[0..2] and maxima out[3..5] of the points ok(i, v) accepts
+// (v: the three coordinates of point i) and their count out[6], by integer atomics: order-free
+template <class Ok>
+__global__ __launch_bounds__(256) void cloud_minmax(const float* xyz, int n, Ok ok, unsigned* out) {
+  unsigned lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u}, cnt = 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float v[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+    if (!ok(i, v)) continue;
+    ++cnt;
+    for (int a = 0; a < 3; ++a) {
+      const unsigned key = sfmcloud::ord_key(v[a]);
+      lo[a] = min(lo[a], key);
+      hi[a] = max(hi[a], key);
+    }
+  }
+  for (int off = 32; off >= 1; off >>= 1) {
+    cnt += __shfl_xor(cnt, off);
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = min(lo[a], (unsigned)__shfl_xor(lo[a], off));
+      hi[a] = max(hi[a], (unsigned)__shfl_xor(hi[a], off));
+    }
+  }
+  if ((threadIdx.x & 63) == 0 && cnt) {
+    for (int a = 0; a < 3; ++a) {
+      atomicMin(out + a, lo[a]);
+      atomicMax(out + 3 + a, hi[a]);
+    }
+    atomicAdd(out + 6, cnt);
+  }
 }
 #endif
 

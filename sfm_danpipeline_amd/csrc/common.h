@@ -103,6 +103,13 @@ struct DevBufs {  // device memory of one call (or one object), freed with it
   }
 };
 
+// rocPRIM's exclusive plus-scan of n ints on `st`, defined once (context.hip).  The caller owns the temporary storage:
+// sfm_scan_bytes says how much n needs, sfm_exclusive_scan runs on a block of at least that.  With `total` it also
+// returns out[n - 1] + in[n - 1] (two async 4-byte copies and one stream synchronisation), so n >= 1 there: every
+// caller returns early on an empty input.
+int sfm_scan_bytes(size_t n, hipStream_t st, size_t* bytes);
+int sfm_exclusive_scan(void* tmp, size_t tmp_bytes, const int* in, int* out, size_t n, hipStream_t st, long long* total);
+
 static inline double sfm_now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }

@@ -1,5 +1,7 @@
-// context.hip -- sfmhip context lifetime and error strings (include/sfmhip.h).
+// context.hip -- sfmhip context lifetime and error strings (include/sfmhip.h), and the one instantiation of rocPRIM's
+// int scan (common.h).
 #include "common.h"
+#include <rocprim/device/device_scan.hpp>
 #include <string.h>
 
 thread_local int g_sfmhip_last_hip_error = 0;
@@ -124,6 +126,23 @@ int sfm_ctx_dev_scratch(sfmhip_ctx* ctx, int which, size_t bytes, void** out) {
     ctx->dev_scratch_bytes[which] = want;
   }
   *out = ctx->dev_scratch[which];
+  return SFMHIP_OK;
+}
+
+int sfm_scan_bytes(size_t n, hipStream_t st, size_t* bytes) {
+  *bytes = 0;
+  SFM_HIP_TRY(rocprim::exclusive_scan(nullptr, *bytes, (const int*)nullptr, (int*)nullptr, 0, n, rocprim::plus<int>(), st));
+  return SFMHIP_OK;
+}
+
+int sfm_exclusive_scan(void* tmp, size_t tmp_bytes, const int* in, int* out, size_t n, hipStream_t st, long long* total) {
+  SFM_HIP_TRY(rocprim::exclusive_scan(tmp, tmp_bytes, in, out, 0, n, rocprim::plus<int>(), st));
+  if (!total) return SFMHIP_OK;
+  int last[2] = {0, 0};
+  SFM_HIP_TRY(hipMemcpyAsync(&last[0], out + n - 1, sizeof(int), hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipMemcpyAsync(&last[1], in + n - 1, sizeof(int), hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipStreamSynchronize(st));
+  *total = (long long)last[0] + last[1];
   return SFMHIP_OK;
 }
 

@@ -2,11 +2,12 @@
 // (one workgroup per 16x16 reference tile, warped 12-bit samples and separable integer box sums in LDS, the winner and its
 // neighbours in registers: no cost volume in HBM), and the fusion (flag, scan, emit).  The arithmetic is mvs.h's.
 #include "common.h"
+#include "cloud_grid.h"
 #include "mvs.h"
-#include <rocprim/device/device_scan.hpp>
 #include <string.h>
 
 using namespace sfmmvs;
+using sfmgrid::blocks;
 
 struct sfmhip_mvs {
   sfmhip_ctx* ctx = nullptr;
@@ -32,8 +33,6 @@ struct sfmhip_mvs {
 };
 
 namespace {
-
-inline unsigned blocks(long long n, int b) { return (unsigned)((n + b - 1) / b); }
 
 // rule 1: one level of the pyramid for all views (ch interleaved channels)
 __global__ void mvs_halve(const uint8_t* __restrict__ in, int n, int rows, int cols, int ch, uint8_t* __restrict__ out) {
@@ -212,18 +211,15 @@ int fuse(sfmhip_mvs* h, const Opts& o, int32_t* n_points) {
   hipLaunchKernelGGL(mvs_fuse_flag, dim3(blocks((long long)total, 256)), dim3(256), 0, st, A, h->flag);
   SFM_HIP_TRY(hipGetLastError());
   size_t need = 0;
-  SFM_HIP_TRY(rocprim::exclusive_scan(nullptr, need, h->flag, h->offs, 0, total, rocprim::plus<int>(), st));
+  SFM_TRY(sfm_scan_bytes(total, st, &need));
   if (need > h->scan_bytes) {
     unsigned char* t = nullptr;
     SFM_TRY(h->own.alloc(&t, need));
     h->scan_tmp = t, h->scan_bytes = need;
   }
-  SFM_HIP_TRY(rocprim::exclusive_scan(h->scan_tmp, need, h->flag, h->offs, 0, total, rocprim::plus<int>(), st));
-  int last[2] = {0, 0};
-  SFM_HIP_TRY(hipMemcpyAsync(&last[0], h->offs + total - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-  SFM_HIP_TRY(hipMemcpyAsync(&last[1], h->flag + total - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-  SFM_HIP_TRY(hipStreamSynchronize(st));
-  const size_t m = (size_t)last[0] + (size_t)last[1];
+  long long kept = 0;
+  SFM_TRY(sfm_exclusive_scan(h->scan_tmp, need, h->flag, h->offs, total, st, &kept));  // (total >= 2: sfmhip_mvs_create)
+  const size_t m = (size_t)kept;
   h->xyz.assign(3 * m, 0.0f), h->nrm.assign(3 * m, 0.0f), h->rgb.assign(m, 0u);
   if (m) {
     DevBufs B;

@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include "cloud.h"
 #ifndef __HIPCC__
 #include <algorithm>
 #include <thread>
@@ -65,17 +66,7 @@ SFM_PSN_INLINE bool usable(const float* p, const float* nrm) {
   return finite_f(p[0]) && finite_f(p[1]) && finite_f(p[2]) && finite_f(nrm[0]) && finite_f(nrm[1]) && finite_f(nrm[2]) &&
          (nrm[0] != 0.f || nrm[1] != 0.f || nrm[2] != 0.f);
 }
-// an unsigned key that orders as the float does (the bounding box by integer atomicMin / atomicMax: order-free)
-SFM_PSN_INLINE uint32_t ord_key(float f) {
-  const uint32_t u = f_bits(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-SFM_PSN_INLINE float ord_val(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
+// the bounding box of the usable samples: cloud.h's ordered keys under integer atomicMin / atomicMax (order-free)
 
 // ---------------------------------------------------------------------------------------------- rule 2: the cube
 inline Cube make_cube(const float lo[3], const float hi[3], int depth, double scale) {

@@ -13,12 +13,10 @@
 //   psn_update  chi += alpha p, r -= alpha q, the brick's part of r.r;
 //   psn_reduce  r.r, beta, the iteration count and the decision to stop, all in a record on the device.
 // A stopped solve makes the remaining launches of a batch return at once; the host reads the record every CG_BATCH steps.
-// Extraction: crossed edges per grid point and triangles per cube are counted, scanned by rocPRIM and written in place.
+// Extraction: crossed edges per grid point and triangles per cube are counted, scanned (common.h) and written in place.
 #include "common.h"
 #include "cloud_grid.h"
 #include "poisson.h"
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -104,35 +102,14 @@ __device__ __forceinline__ double block_tree(double v, double* sh4) {
 }
 
 // ---------------------------------------------------------------------------------------------- samples
-// out: ordered keys of the per-axis minima [0..2] and maxima [3..5] of the usable samples, their count [6]
-__global__ __launch_bounds__(256) void psn_minmax(const float* xyz, const float* nrm, int stride, int n, unsigned* out) {
-  unsigned lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u}, cnt = 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+struct UsableSample {  // cloud_minmax's predicate: the points that are samples (rule 1)
+  const float* nrm;
+  int stride;
+  __device__ bool operator()(long long i, const float* p) const {
     const float q[3] = {nrm[stride * i], nrm[stride * i + 1], nrm[stride * i + 2]};
-    if (!usable(p, q)) continue;
-    ++cnt;
-    for (int a = 0; a < 3; ++a) {
-      const unsigned key = ord_key(p[a]);
-      lo[a] = min(lo[a], key);
-      hi[a] = max(hi[a], key);
-    }
+    return usable(p, q);
   }
-  for (int off = 32; off >= 1; off >>= 1) {
-    cnt += __shfl_xor(cnt, off);
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = min(lo[a], (unsigned)__shfl_xor(lo[a], off));
-      hi[a] = max(hi[a], (unsigned)__shfl_xor(hi[a], off));
-    }
-  }
-  if ((threadIdx.x & 63) == 0 && cnt) {
-    for (int a = 0; a < 3; ++a) {
-      atomicMin(out + a, lo[a]);
-      atomicMax(out + 3 + a, hi[a]);
-    }
-    atomicAdd(out + 6, cnt);
-  }
-}
+};
 
 __global__ void psn_keys(const float* xyz, const float* nrm, int stride, int n, Cube g, int invalid, int* keys, int* vals) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -347,20 +324,6 @@ __global__ __launch_bounds__(256) void psn_emit_triangles(const double* chi, int
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-int scan_total(hipStream_t st, Bufs& B, const int* in, int* out, size_t n, long long* total) {
-  size_t need = 0;
-  SFM_HIP_TRY(rocprim::exclusive_scan(nullptr, need, in, out, 0, n, rocprim::plus<int>(), st));
-  unsigned char* tmp = nullptr;
-  SFM_TRY(B.get(&tmp, need));
-  SFM_HIP_TRY(rocprim::exclusive_scan(tmp, need, in, out, 0, n, rocprim::plus<int>(), st));
-  int last[2] = {0, 0};
-  SFM_HIP_TRY(hipMemcpyAsync(&last[0], out + n - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-  SFM_HIP_TRY(hipMemcpyAsync(&last[1], in + n - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-  SFM_HIP_TRY(hipStreamSynchronize(st));
-  *total = (long long)last[0] + last[1];
-  return SFMHIP_OK;
-}
-
 struct Samp {
   Cube g;
   int m = 0;
@@ -388,7 +351,9 @@ int make_samples(sfmhip_cloud* c, const float* normals, int stride, const Opts& 
   SFM_HIP_TRY(hipMemcpyAsync(d_mm, mm, sizeof mm, hipMemcpyHostToDevice, st));
   if (n > 0) {
     SFM_HIP_TRY(hipMemcpyAsync(d_nrm, normals, sizeof(float) * (size_t)stride * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(psn_minmax, dim3(std::min(blocks(n, 256), 1024u)), dim3(256), 0, st, c->xyz, d_nrm, stride, n, d_mm);
+    const UsableSample ok{d_nrm, stride};
+    hipLaunchKernelGGL(sfmgrid::cloud_minmax<UsableSample>, dim3(std::min(blocks(n, 256), 1024u)), dim3(256), 0, st, c->xyz, n, ok,
+                       d_mm);
     SFM_HIP_TRY(hipGetLastError());
   }
   SFM_HIP_TRY(hipMemcpyAsync(mm, d_mm, sizeof mm, hipMemcpyDeviceToHost, st));
@@ -397,7 +362,7 @@ int make_samples(sfmhip_cloud* c, const float* normals, int stride, const Opts& 
   if (S.m < 0 || S.m > n) return SFMHIP_ERR_STATE;
   float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
   if (S.m > 0)
-    for (int a = 0; a < 3; ++a) lo[a] = ord_val(mm[a]), hi[a] = ord_val(mm[3 + a]);
+    for (int a = 0; a < 3; ++a) lo[a] = sfmcloud::ord_val(mm[a]), hi[a] = sfmcloud::ord_val(mm[3 + a]);
   S.g = make_cube(lo, hi, o.depth, o.scale);
   if (S.m == 0) return SFMHIP_OK;
   const size_t nc = (size_t)S.g.N * S.g.N * S.g.N;
@@ -411,12 +376,7 @@ int make_samples(sfmhip_cloud* c, const float* normals, int stride, const Opts& 
   SFM_HIP_TRY(hipMemsetAsync(S.end, 0, sizeof(int) * nc, st));
   hipLaunchKernelGGL(psn_keys, dim3(blocks(n, 256)), dim3(256), 0, st, c->xyz, d_nrm, stride, n, S.g, (int)nc, kin, vin);
   SFM_HIP_TRY(hipGetLastError());
-  unsigned bits = 1;
-  while (bits < 31 && (1ull << bits) <= nc) ++bits;  // (the invalid key is nc)
-  size_t need = 0;
-  SFM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, kin, kout, vin, vout, (unsigned)n, 0u, bits, st));
-  SFM_TRY(sfmgrid::grow_tmp(c, need));
-  SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp, need, kin, kout, vin, vout, (unsigned)n, 0u, bits, st));
+  SFM_TRY(sfmgrid::cell_sort(c, (long long)nc, kin, kout, vin, vout, n));
   hipLaunchKernelGGL(psn_ranges, dim3(blocks(S.m, 256)), dim3(256), 0, st, c->xyz, d_nrm, stride, kout, vout, S.m, S.start, S.end,
                      S.pts, S.nrs);
   SFM_HIP_TRY(hipGetLastError());
@@ -508,8 +468,15 @@ int extract(hipStream_t st, Bufs& B, const double* chi, const Cube& g, double is
   hipLaunchKernelGGL(psn_classify_cubes, dim3(blocks((long long)nq, 256)), dim3(256), 0, st, chi, N, iso, d_T, tcnt);
   SFM_HIP_TRY(hipGetLastError());
   long long nv = 0, nt = 0;
-  SFM_TRY(scan_total(st, B, vcnt, voff, nc, &nv));
-  SFM_TRY(scan_total(st, B, tcnt, toff, nq, &nt));
+  auto scan = [&](const int* in, int* out, size_t n, long long* total) {  // (the temporary: one request to B per scan; n >= 1)
+    size_t need = 0;
+    unsigned char* tmp = nullptr;
+    SFM_TRY(sfm_scan_bytes(n, st, &need));
+    SFM_TRY(B.get(&tmp, need));
+    return sfm_exclusive_scan(tmp, need, in, out, n, st, total);
+  };
+  SFM_TRY(scan(vcnt, voff, nc, &nv));
+  SFM_TRY(scan(tcnt, toff, nq, &nt));
   if (nv < 0 || nt < 0 || nv > 7 * (long long)nc || nt > 12 * (long long)nq || 3 * nt > 0x7FFFFFFFll) return SFMHIP_ERR_STATE;
   mesh->verts.assign(3 * (size_t)nv, 0.f);
   mesh->tris.assign(3 * (size_t)nt, 0);

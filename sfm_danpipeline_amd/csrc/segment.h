@@ -56,15 +56,6 @@ SFM_CLOUD_INLINE int seg_colour_diff(const unsigned* a, const unsigned* b) {
   return dr * dr + dg * dg + db * db;
 }
 
-// an order-preserving map of finite floats to unsigned (-0 below +0), so that min / max are reductions over integers
-// whose result does not depend on the order of the operands
-SFM_CLOUD_INLINE uint32_t ord_key(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-SFM_CLOUD_INLINE float ord_val(uint32_t k) { return sfmcloud::bits_f((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-
 // Dendrometry::estimate's "Total Height": cv::norm of the Point3f difference = sqrt of the double sum of squares
 inline double height(const float mn[3], const float mx[3]) {
   const float dx = mx[0] - mn[0], dy = mx[1] - mn[1], dz = mx[2] - mn[2];
@@ -74,20 +65,20 @@ inline double height(const float mn[3], const float mx[3]) {
 inline void minmax_host(int n, const float* xyz, float mn[3], float mx[3]) {
   uint32_t lo[3], hi[3];
   for (int a = 0; a < 3; ++a) {
-    lo[a] = ord_key(FLT_MAX);
-    hi[a] = ord_key(-FLT_MAX);
+    lo[a] = sfmcloud::ord_key(FLT_MAX);
+    hi[a] = sfmcloud::ord_key(-FLT_MAX);
   }
   for (int i = 0; i < n; ++i) {
     const float* p = xyz + 3 * (size_t)i;
     if (!sfmcloud::finite3(p[0], p[1], p[2])) continue;
     for (int a = 0; a < 3; ++a) {
-      lo[a] = std::min(lo[a], ord_key(p[a]));
-      hi[a] = std::max(hi[a], ord_key(p[a]));
+      lo[a] = std::min(lo[a], sfmcloud::ord_key(p[a]));
+      hi[a] = std::max(hi[a], sfmcloud::ord_key(p[a]));
     }
   }
   for (int a = 0; a < 3; ++a) {
-    mn[a] = ord_val(lo[a]);
-    mx[a] = ord_val(hi[a]);
+    mn[a] = sfmcloud::ord_val(lo[a]);
+    mx[a] = sfmcloud::ord_val(hi[a]);
   }
 }
 

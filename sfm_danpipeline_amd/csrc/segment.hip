@@ -7,7 +7,8 @@
 // seg_knn: one wave per point, in cell order, over a grid of the indexed points.  The wave keeps the sorted (d2, index)
 // list of 128 slots two per lane (lane l: slots 2l, 2l + 1); candidates are tested a lane each, and every candidate
 // that beats the k-th entry is inserted by one shift (a lane-to-lane move of the odd slots).  The ring search and its
-// stopping rule are cloud_knn's: the nearest face of the searched block against the k-th d2.
+// stopping rule restate cloud.hip's cloud_knn line for line (the nearest face of the searched block against the k-th d2);
+// a change to either is a change to both.
 // seg_grow_round: min-label propagation over the directed graph u -> v (v among u's first 30 entries, colour
 // difference to u within the point threshold), atomicMin in place plus pointer jumping, until a round changes nothing;
 // the segment of v is the smallest u that reaches it, segment numbers are the ranks of those minima (f-8, rule 4).
@@ -21,7 +22,6 @@
 #include "segment.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_reduce_by_key.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -60,38 +60,9 @@ __global__ void seg_gather(const float* xyz, const int* ind, int m, float* out) 
   out[3 * (size_t)r + 2] = xyz[3 * j + 2];
 }
 
-// out: the ordered keys (segment.h) of the per-axis minima [0..2] and maxima [3..5] of the finite points, their count [6]
-__global__ __launch_bounds__(256) void seg_minmax(const float* xyz, int n, unsigned* out) {
-  unsigned lo[3], hi[3], cnt = 0;
-  for (int a = 0; a < 3; ++a) {
-    lo[a] = 0xFFFFFFFFu;
-    hi[a] = 0u;
-  }
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float v[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-    if (!sfmcloud::finite3(v[0], v[1], v[2])) continue;
-    ++cnt;
-    for (int a = 0; a < 3; ++a) {
-      const unsigned key = sfmseg::ord_key(v[a]);
-      lo[a] = min(lo[a], key);
-      hi[a] = max(hi[a], key);
-    }
-  }
-  for (int off = 32; off >= 1; off >>= 1) {
-    cnt += __shfl_xor(cnt, off);
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = min(lo[a], (unsigned)__shfl_xor(lo[a], off));
-      hi[a] = max(hi[a], (unsigned)__shfl_xor(hi[a], off));
-    }
-  }
-  if ((threadIdx.x & 63) == 0 && cnt) {
-    for (int a = 0; a < 3; ++a) {
-      atomicMin(out + a, lo[a]);
-      atomicMax(out + 3 + a, hi[a]);
-    }
-    atomicAdd(out + 6, cnt);
-  }
-}
+struct FinitePoint {  // cloud_minmax's predicate: the finite points
+  __device__ bool operator()(long long, const float* v) const { return sfmcloud::finite3(v[0], v[1], v[2]); }
+};
 
 __global__ __launch_bounds__(64 * WAVES) void seg_knn(GridDev g, double abs_eps, int k, int* out_idx, float* out_d2) {
   const int lane = threadIdx.x & 63;
@@ -109,14 +80,8 @@ __global__ __launch_bounds__(64 * WAVES) void seg_knn(GridDev g, double abs_eps,
   const int klane = (k - 1) >> 1;
   const bool kodd = ((k - 1) & 1) != 0;
   auto scan_row = [&](int row, int xa, int xb) {
-    int s = INT_MAX, e = 0;
-    for (int x = xa; x <= xb; ++x) {
-      const int st = g.start[row + x], en = g.end[row + x];
-      if (en > st) {
-        s = min(s, st);
-        e = max(e, en);
-      }
-    }
+    int s, e;
+    row_span(g, row, xa, xb, &s, &e);
     for (int b = s; b < e; b += 64) {
       const int j = b + lane;
       float cd = inf;
@@ -298,43 +263,23 @@ __global__ void seg_nbr_write(const unsigned long long* keys, const int* b, int 
   nbr_d2[o] = __int_as_float((int)(unsigned)(keys[e] & 0xFFFFFFFFull));
 }
 
-int scan_ints(sfmhip_cloud* c, const int* in, int* out, size_t n) {
-  size_t need = 0;
-  hipStream_t st = c->ctx->stream;
-  SFM_HIP_TRY(rocprim::exclusive_scan(nullptr, need, in, out, 0, n, rocprim::plus<int>(), st));
-  SFM_TRY(grow_tmp(c, need));
-  need = c->tmp_bytes;
-  SFM_HIP_TRY(rocprim::exclusive_scan(c->tmp, need, in, out, 0, n, rocprim::plus<int>(), st));
-  return SFMHIP_OK;
-}
-
-// total of an exclusive scan: off[n - 1] + in[n - 1]
-int scan_total(sfmhip_cloud* c, const int* in, const int* off, size_t n, int* total) {
-  int last[2] = {0, 0};
-  hipStream_t st = c->ctx->stream;
-  SFM_HIP_TRY(hipMemcpyAsync(&last[0], off + n - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-  SFM_HIP_TRY(hipMemcpyAsync(&last[1], in + n - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-  SFM_HIP_TRY(hipStreamSynchronize(st));
-  *total = last[0] + last[1];
-  return SFMHIP_OK;
-}
-
 int minmax_dev(sfmhip_cloud* c, const float* d_xyz, int n, unsigned* d_out7, float mn[3], float mx[3], int* count) {
   hipStream_t st = c->ctx->stream;
   unsigned init[7];
   for (int a = 0; a < 3; ++a) {
-    init[a] = sfmseg::ord_key(FLT_MAX);
-    init[3 + a] = sfmseg::ord_key(-FLT_MAX);
+    init[a] = sfmcloud::ord_key(FLT_MAX);
+    init[3 + a] = sfmcloud::ord_key(-FLT_MAX);
   }
   init[6] = 0;
   SFM_HIP_TRY(hipMemcpyAsync(d_out7, init, sizeof init, hipMemcpyHostToDevice, st));
-  if (n > 0) hipLaunchKernelGGL(seg_minmax, dim3(std::min(blocks(n, 256), 1024u)), dim3(256), 0, st, d_xyz, n, d_out7);
+  if (n > 0) hipLaunchKernelGGL(cloud_minmax<FinitePoint>, dim3(std::min(blocks(n, 256), 1024u)), dim3(256), 0, st, d_xyz, n, FinitePoint(),
+                                d_out7);
   SFM_HIP_TRY(hipGetLastError());
   SFM_HIP_TRY(hipMemcpyAsync(init, d_out7, sizeof init, hipMemcpyDeviceToHost, st));
   SFM_HIP_TRY(hipStreamSynchronize(st));
   for (int a = 0; a < 3; ++a) {
-    mn[a] = sfmseg::ord_val(init[a]);
-    mx[a] = sfmseg::ord_val(init[3 + a]);
+    mn[a] = sfmcloud::ord_val(init[a]);
+    mx[a] = sfmcloud::ord_val(init[3 + a]);
   }
   *count = (int)init[6];
   return SFMHIP_OK;
@@ -446,8 +391,7 @@ int number_segments(sfmhip_cloud* c, DevBufs& B, Work& w, DevTables& d) {
   SFM_TRY(B.alloc(&off, (size_t)m));
   hipLaunchKernelGGL(seg_root_flags, dim3(blocks(m, 256)), dim3(256), 0, st, w.lab, m, flags);
   SFM_HIP_TRY(hipGetLastError());
-  SFM_TRY(scan_ints(c, flags, off, (size_t)m));
-  SFM_TRY(scan_total(c, flags, off, (size_t)m, &w.n_seg));
+  SFM_TRY(scan(c, flags, off, (size_t)m, &w.n_seg));  // (m >= 1: indices_valid)
   if (w.n_seg < 0 || w.n_seg > m) return SFMHIP_ERR_STATE;
   SFM_TRY(B.alloc(&d.acc, (size_t)4 * w.n_seg));
   SFM_TRY(B.alloc(&d.count, (size_t)w.n_seg));
@@ -478,9 +422,8 @@ int segment_tables(sfmhip_cloud* c, DevBufs& B, const sfmseg::Opts& o, Work& w, 
   hipLaunchKernelGGL(seg_cross, dim3(blocks(m, 256)), dim3(256), 0, st, w.knn_idx, w.knn_d2, w.k, w.seg, m, S, 0, cnt, nullptr, nullptr,
                      nullptr);
   SFM_HIP_TRY(hipGetLastError());
-  SFM_TRY(scan_ints(c, cnt, off, (size_t)m));
   int ne = 0;
-  SFM_TRY(scan_total(c, cnt, off, (size_t)m, &ne));
+  SFM_TRY(scan(c, cnt, off, (size_t)m, &ne));
   if (ne < 0) return SFMHIP_ERR_STATE;
   if (ne == 0) return SFMHIP_OK;
   unsigned long long *k0 = nullptr, *k1 = nullptr;
@@ -532,9 +475,8 @@ int segment_tables(sfmhip_cloud* c, DevBufs& B, const sfmseg::Opts& o, Work& w, 
   hipLaunchKernelGGL(seg_pair_ranges, dim3(blocks(np, 256)), dim3(256), 0, st, k0, np, start, end);
   hipLaunchKernelGGL(seg_nbr_counts, dim3(blocks(S, 256)), dim3(256), 0, st, start, end, S, o.region_neighbour_number, ncnt);
   SFM_HIP_TRY(hipGetLastError());
-  SFM_TRY(scan_ints(c, ncnt, noff, (size_t)S));
   int total = 0;
-  SFM_TRY(scan_total(c, ncnt, noff, (size_t)S, &total));
+  SFM_TRY(scan(c, ncnt, noff, (size_t)S, &total));  // (S >= 1: the early return above)
   if (total < 1 || total > np) return SFMHIP_ERR_STATE;
   SFM_TRY(B.alloc(&nseg, (size_t)total));
   SFM_TRY(B.alloc(&nd2, (size_t)total));

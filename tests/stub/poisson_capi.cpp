@@ -17,6 +17,14 @@ extern "C" {
 
 double psn_bspline(double t) { return bspline(t); }
 
+// cloud.h's ordered keys as poisson.h sees them: key[i] = ord_key(f[i]), back[i] = ord_val(key[i])
+void psn_ord_keys(int n, const float* f, uint32_t* key, float* back) {
+  for (int i = 0; i < n; ++i) {
+    key[i] = sfmcloud::ord_key(f[i]);
+    back[i] = sfmcloud::ord_val(key[i]);
+  }
+}
+
 void psn_default_opts(PsnOpts* o) {
   const Opts r = reference_opts();
   o->depth = r.depth, o->scale = r.scale, o->point_weight = r.point_weight, o->cg_rtol = r.cg_rtol, o->cg_max_iter = r.cg_max_iter;

@@ -317,6 +317,14 @@ void seg_minmax(int n, const float* xyz, float* mn, float* mx, double* height) {
   *height = sfmseg::height(mn, mx);
 }
 
+// cloud.h's ordered keys as segment.h sees them: key[i] = ord_key(f[i]), back[i] = ord_val(key[i])
+void seg_ord_keys(int n, const float* f, uint32_t* key, float* back) {
+  for (int i = 0; i < n; ++i) {
+    key[i] = sfmcloud::ord_key(f[i]);
+    back[i] = sfmcloud::ord_val(key[i]);
+  }
+}
+
 // pcl::io::loadPCDFile for PointXYZRGB; returns the point count or -1; info = width, height, is_dense
 int seg_load_pcd(const char* path, float* xyz, uint32_t* rgb, int cap, int32_t* info) {
   pcl::PointCloud<pcl::PointXYZRGB> c;

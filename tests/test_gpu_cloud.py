@@ -127,6 +127,25 @@ def test_pairs_straddling_cell_faces_are_counted(ctx, cc):
     assert np.array_equal(got, stub_counts(cc, xyz, r))
 
 
+def test_compaction_at_block_boundaries(ctx, cc):
+    """Flags, scan, total, scatter around the scan's and the launches' block sizes: the n - 1 reads and the last block."""
+    rng = np.random.default_rng(12)
+    for n in (1, 2, 63, 64, 65, 256, 257, 1025):
+        xyz = rng.uniform(0, 0.01, (n, 3)).astype(np.float32)
+        xyz[:, 2] = np.where(np.arange(n) % 2 == 0, 0.5, 2.0)                       # z alternates inside / outside [0, 1]
+        bad = xyz.copy()
+        bad[-1, 1] = np.inf                                                          # a non-finite last point: never kept
+        with cloud.Cloud(xyz, ctx=ctx) as c, cloud.Cloud(bad, ctx=ctx) as cb:
+            for lo, hi, want in ((-10.0, 10.0, np.arange(n)), (5.0, 6.0, np.arange(0)), (0.0, 1.0, np.arange(0, n, 2))):
+                got = c.passthrough(2, lo, hi)
+                assert np.array_equal(got, want) and np.array_equal(got, stub_passthrough(cc, xyz, 2, lo, hi))
+                assert np.array_equal(cb.passthrough(2, lo, hi), stub_passthrough(cc, bad, 2, lo, hi))
+            assert np.array_equal(cb.passthrough(2, -10.0, 10.0), np.arange(n - 1))
+            kept = c.radius_outlier(5.0, 0)                                          # every point has itself within 5: all kept
+            assert np.array_equal(kept, np.arange(n)) and np.array_equal(kept, stub_outlier(cc, xyz, 5.0, 0))
+            assert np.array_equal(cb.radius_outlier(5.0, 0), stub_outlier(cc, bad, 5.0, 0))
+
+
 def test_handle_reuse_and_two_handles(ctx, cc):
     a = bench_cloud(60_000, seed=2)
     b = bench_cloud(30_000, seed=5)

@@ -53,6 +53,8 @@ def load_stub(so):
     lib.psn_extract.restype = vp
     lib.psn_sum.argtypes = [vp, ci]
     lib.psn_sum.restype = f64
+    lib.psn_ord_keys.argtypes = [ci, vp, vp, vp]
+    lib.psn_ord_keys.restype = None
     return lib
 
 
@@ -257,6 +259,11 @@ def test_bspline_is_the_quadratic_partition_of_unity(ps):
     assert (b[np.abs(t) >= 1.5] == 0).all() and b.max() == 0.75
     s = np.array([sum(ps.psn_bspline(float(x) - k) for k in (-2, -1, 0, 1, 2)) for x in np.linspace(-0.5, 0.5, 101)])
     assert np.abs(s - 1).max() < 1e-15
+
+
+def test_ord_keys_match_the_rule_both_headers_spelled(ps):
+    from tests.test_segment_cpu import check_ord_keys
+    check_ord_keys(ps.psn_ord_keys)
 
 
 def test_fixed_order_sum_is_a_sum(ps):

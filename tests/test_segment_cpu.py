@@ -44,6 +44,8 @@ def load_stub(so):
     lib.seg_minmax.argtypes = [ci, vp, vp, vp, vp]
     lib.seg_minmax.restype = None
     lib.seg_load_pcd.argtypes = [C.c_char_p, vp, vp, ci, vp]
+    lib.seg_ord_keys.argtypes = [ci, vp, vp, vp]
+    lib.seg_ord_keys.restype = None
     return lib
 
 
@@ -497,6 +499,35 @@ def test_bounds_against_numpy(sc):
     assert h == np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
     mn, mx, _ = stub_minmax(sc, np.zeros((0, 3), np.float32))
     assert (mn == np.float32(FLT_MAX)).all() and (mx == -np.float32(FLT_MAX)).all()
+
+
+def ord_key_cases():
+    """Bit patterns for the ordered keys: the zeros, the denormals' ends, the normals' ends, the infinities, quiet and
+    signalling NaNs of both signs, and a million random patterns."""
+    special = [0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x007FFFFF, 0x807FFFFF, 0x00800000, 0x80800000, 0x7F7FFFFF,
+               0xFF7FFFFF, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00000, 0x7F800001, 0xFF800001, 0x7FFFFFFF, 0xFFFFFFFF]
+    rnd = np.random.default_rng(11).integers(0, 2 ** 32, 1_000_000, dtype=np.uint64).astype(np.uint32)
+    return np.concatenate([np.array(special, np.uint32), rnd])
+
+
+def check_ord_keys(fn):
+    """The one ord_key / ord_val of csrc/cloud.h, through a stub's entry `fn`, against the rule segment.h and poisson.h
+    each used to spell out: the sign bit set on a non-negative float, every bit flipped on a negative one."""
+    u = ord_key_cases()
+    key, back = np.zeros(len(u), np.uint32), np.zeros(len(u), np.uint32)
+    fn(len(u), u.ctypes.data, key.ctypes.data, back.ctypes.data)
+    neg = (u & np.uint32(0x80000000)) != 0
+    assert np.array_equal(key, np.where(neg, ~u, u | np.uint32(0x80000000)))
+    assert np.array_equal(back, u)                                                    # ord_val inverts it, NaN payloads included
+    f = u.view(np.float32)
+    num = ~np.isnan(f)
+    o = np.argsort(key[num], kind="stable")
+    assert (np.diff(f[num][o].astype(np.float64)) >= 0).all()                         # ascending keys: ascending floats, -inf .. +inf
+    assert key[1] < key[0]                                                            # -0 below +0: the one pair of equal floats
+
+
+def test_ord_keys_match_the_rule_both_headers_spelled(sc):
+    check_ord_keys(sc.seg_ord_keys)
 
 
 # ---------------------------------------------------------------- the XYZRGB PCD reader (pcllite.h)
