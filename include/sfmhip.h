@@ -429,6 +429,93 @@ int sfmhip_cloud_segment_last_timing(sfmhip_cloud* cloud, double* ms5);
  * Dendrometry::estimate's "Total Height": the sqrt of the double sum of squares of the float differences. */
 int sfmhip_cloud_minmax(sfmhip_cloud* cloud, float* mn /* 3 */, float* mx /* 3 */, double* height);
 
+/* ---- dendrometry: the measurements Dendrometry::estimate leaves blank (reference src/DendrometryE.cpp:3-29) ----
+ * Tree height along the vertical, diameter at breast height (DAP / DBH), the stem taper profile, crown base height, live
+ * crown length and crown spread N-S / E-W of one tree's cloud.  The reference has no implementation; the contract is
+ * this rule list, whose arithmetic is csrc/dendro.h (compiled by g++ and hipcc without contraction; the device equals the
+ * host build bit for bit).
+ *  1 options: the table below; lengths are metres and are divided by `scale` (metres per cloud unit) once, in f64.
+ *    SFMHIP_ERR_ARG: |up| not 1 within 1e-6, north parallel to up, scale / slice / extent_bin not > 0, ransac_iters outside
+ *    1..4096, r_min < 0, r_max < r_min, a negative tolerance, a non-finite dbh_height, extent_q outside (0, 1], crown_factor not > 0, min_inliers < 1,
+ *    min_sectors outside 0..16, crown_run < 1, min_slice_pts < 3, an infinite ground.  north is projected off up and
+ *    normalised; east = north x up.
+ *  2 selection: the finite points (with labels: those with labels[i] == label, the layout sfmhip_cloud_segment_rgb writes)
+ *    whose frame coordinates are finite floats.  Empty: status OK, flag bit 0, NaN outputs.
+ *  3 frame: (e, n, h) = (east.p, north.p, up.p), each (a0 x + a1 y) + a2 z in f64, stored as float32.  h0 = ground / scale,
+ *    or the least h of the selection when ground is NaN; total_height = (max h - h0) scale.  No point at or above h0: as
+ *    empty.
+ *  4 slices of thickness t: k = floor((h - h0) / t) in f64, h < h0 dropped; S = k of the top point + 1, at most 4096, the
+ *    last slice takes what lies above it.  Within a slice the points keep ascending input index.
+ *  5 circle RANSAC on (e, n) per slice of >= min_slice_pts points.  Iteration j draws three positions
+ *    (u64(hash(seed, k, j, draw)) n_k) >> 32, hash = mix(mix(mix(mix(seed + 0x9E3779B9) ^ k) + 0x85EBCA6B ^ j) + 0xC2B2AE35 ^ draw)
+ *    in u32 with mix(x): x ^= x >> 16, x *= 0x7FEB352D, x ^= x >> 15, x *= 0x846CA68B, x ^= x >> 16 (+ binds before ^);
+ *    a repeated position skips the iteration.  Model: the circumcircle in f64 relative to the first point; skipped when the
+ *    determinant is 0 or r is outside [r_min, r_max].  Inlier: |sqrt(dx^2 + dy^2) - r| <= tol in f64.  Arc cover: a 16-bit
+ *    mask of the 22.5-degree sectors (counter-clockwise from +e) that hold inliers, from the signs of (dx, dy), |dx| against
+ *    |dy| and the smaller against 0.41421356237309503 times the larger.  Winner: the largest key (count << 32) |
+ *    (4095 - j) << 16 | mask over the iterations with an inlier.  Stem slice: count >= min_inliers and popcount(mask) >=
+ *    min_sectors.
+ *  6 refit of a stem slice on the winner's inliers (the set is not evaluated again): Kasa's algebraic fit in coordinates
+ *    relative to the RANSAC centre, then exactly 10 Gauss-Newton steps on d_i - r (a singular or non-finite step changes
+ *    nothing), then the RMS residual.  Each sum: point i of the slice adds to slot i mod 256 in ascending i, four 64-entry
+ *    trees with strides 32..1, (w0 + w1) + (w2 + w3).
+ *  7 DBH: x = dbh_height / t - 0.5, slices floor(x) and floor(x) + 1; both stem: radius and centre interpolated linearly
+ *    with weight x - floor(x); one: that slice, flag bit 1; none: NaN, flag bit 2.  dbh = 2 r scale.
+ *  8 extent of a slice: histogram of the distance to the vertical axis through the DBH centre, 1024 bins of extent_bin, the
+ *    last takes the rest; the upper edge of the bin where the cumulative count reaches ceil(extent_q n_k) (at least 1).
+ *  9 crown base: the lowest slice k with (k + 0.5) t > dbh_height whose crown_run slices k .. k + crown_run - 1 all exist,
+ *    hold >= min_slice_pts points and have extent > crown_factor r_dbh.  crown_base_height = k t scale, live_crown =
+ *    total_height - crown_base_height; none: NaN, flag bit 3.
+ * 10 spread over the selected points with h >= h0 + k t (compared in f64): E-W = (max e - min e) scale, N-S likewise with n,
+ *    max and min float32, the difference in f64.  NaN without a crown base. */
+typedef struct sfmhip_dendro_opts {
+  double up[3];          /* (0, 0, 1) */
+  double north[3];       /* (0, 1, 0) */
+  double scale;          /* 1: metres per cloud unit */
+  double ground;         /* NaN: the lowest selected point; else the ground height along up, metres */
+  double dbh_height;     /* 1.3 */
+  double slice;          /* 0.1 */
+  double inlier_tol;     /* 0.02 */
+  double r_min, r_max;   /* 0.02, 1.5 */
+  double extent_q;       /* 0.95 */
+  double extent_bin;     /* 0.05 */
+  double crown_factor;   /* 3 */
+  int32_t ransac_iters;  /* 256; 1 ... 4096 */
+  int32_t min_inliers;   /* 20 */
+  int32_t min_sectors;   /* 6 of 16 */
+  int32_t crown_run;     /* 3 */
+  int32_t min_slice_pts; /* 10 */
+  uint32_t seed;         /* 1 */
+} sfmhip_dendro_opts;
+typedef struct sfmhip_dendro_slice { /* one row of the stem taper table, cloud units; NaN where the slice is no stem slice */
+  int32_t count;   /* points of the slice */
+  int32_t stem;    /* 1: a stem slice */
+  int32_t inliers; /* the winner's count (0: no hypothesis had an inlier) */
+  int32_t mask;    /* ... and its sector mask */
+  double ce, cn;   /* refitted centre (e, n) */
+  double radius, rms;
+  double extent;   /* rule 8 (NaN: empty slice, or no DBH axis) */
+} sfmhip_dendro_slice;
+typedef struct sfmhip_dendro_result { /* metres */
+  double total_height, dbh, dbh_e, dbh_n /* the DBH centre */, crown_base_height, live_crown, spread_ns, spread_ew;
+  double ground;             /* h0 scale */
+  int32_t n_selected, n_slices;
+  int32_t crown_base_slice;  /* -1: none */
+  int32_t flags;             /* bit 0 empty selection, 1 DBH from one slice, 2 no DBH, 3 no crown base */
+} sfmhip_dendro_result;
+void sfmhip_dendro_default_opts(sfmhip_dendro_opts* opts);
+/* labels: NULL (every finite point) or n entries. */
+int sfmhip_cloud_dendrometry(sfmhip_cloud* cloud, const int32_t* labels, int32_t label, const sfmhip_dendro_opts* opts,
+                             sfmhip_dendro_result* out);
+/* The same call, returning the slice table: *n_slices rows exist, the first min(cap, *n_slices) are written; with out not
+ * NULL, the scalars too (one run of the pipeline for both). */
+int sfmhip_cloud_dendro_profile(sfmhip_cloud* cloud, const int32_t* labels, int32_t label, const sfmhip_dendro_opts* opts,
+                                int cap, sfmhip_dendro_slice* slices, int32_t* n_slices, sfmhip_dendro_result* out);
+/* host-clock ms of the last of these calls on the handle: frame + bounds, slice ordering, RANSAC, refit + table, extent + crown
+ * + spread, the whole call.  Slice ordering and RANSAC are timed apart only under sfmhip_set_timing (a stream synchronisation
+ * each); without it their device time shows in the refit's figure. */
+int sfmhip_cloud_dendro_last_timing(sfmhip_cloud* cloud, double ms6[6]);
+
 /* ---- the second half of create_mesh: Poisson surface reconstruction (reference src/Sfm.cpp:1365-1381) ----
  * pcl::Poisson at depth 7 on the cloud and its flipped normals, as a screened Poisson solve on the same device-resident
  * cloud.  The rules (PCL 1.8.1 parity is UNPINNED -- PCL is absent and its solver is an adaptive octree):

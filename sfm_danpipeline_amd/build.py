@@ -15,7 +15,7 @@ SO = os.path.join(HERE, "libsfmhip.so")
 # and want v_fma_f64 -- "fast-honor-pragmas", not "fast": the one function that must NOT contract, the trust-region decision
 # lm_decide (the same bits on the host and on the device), says so with a pragma, which plain "fast" ignores
 SOURCES = {"context.hip": "off", "match.hip": "off", "triangulate.hip": "off", "incremental.hip": "off",
-           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "segment.hip": "off", "poisson.hip": "off", "mvs.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
+           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "segment.hip": "off", "poisson.hip": "off", "dendro.hip": "off", "mvs.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -151,6 +151,14 @@ def build_segment_demo(force=False):
     Dendrometry::estimate) on a MAP3D.pcd with colours (needs the GPU)."""
     return _build_host_exe(os.path.join(HERE, "sfm_segment_selftest"),
                            ("Sfm.cpp", "SfmIO.cpp", "BundleAdjustment.cpp", "Segmentation.cpp", "DendrometryE.cpp", "segment_selftest.cpp"),
+                           force)
+
+
+def build_dendro_demo(force=False):
+    """The measurement the reference's Dendrometry leaves blank, in the host mirror (Dendrometry::measure and estimateTree over
+    sfmhip_cloud_dendrometry) on a MAP3D.pcd, optionally on one cluster of the colour segmentation (needs the GPU)."""
+    return _build_host_exe(os.path.join(HERE, "sfm_dendro_selftest"),
+                           ("Sfm.cpp", "SfmIO.cpp", "BundleAdjustment.cpp", "Segmentation.cpp", "DendrometryE.cpp", "dendro_selftest.cpp"),
                            force)
 
 

@@ -1,6 +1,6 @@
 // cloud_grid.h -- the device-resident cloud (sfmhip_cloud), its uniform grids and the primitives the cloud family shares:
-// cloud.hip (map3D's step 10), segment.hip (the colour region growing after it), poisson.hip (create_mesh) and, for
-// blocks(), mvs.hip.  The bodies of the host functions declared here (grid builds, the handle's scan and cell sort) live
+// cloud.hip (map3D's step 10), segment.hip (the colour region growing after it), poisson.hip (create_mesh), dendro.hip
+// (the dendrometry after the segmentation) and, for blocks(), mvs.hip.  The bodies of the host functions declared here (grid builds, the handle's scan and cell sort) live
 // in cloud.hip; the device helpers (cell_of, block_bound, row_span, the min / max kernel) are inline.
 //
 // Spatial index: cell coordinates floor((x - lo) / cell) in double, clamped to the grid (a far outlier lands in a
@@ -96,6 +96,8 @@ struct sfmhip_cloud {
   double psn_ms[4] = {0, 0, 0, 0};  // poisson.hip: stage times of the last sfmhip_cloud_poisson call on this handle
   void* psn = nullptr;           // poisson.hip's grow-only device blocks on this handle, freed with it
   void (*psn_free)(void*) = nullptr;
+  void* dnd = nullptr;           // dendro.hip's state on this handle (frame, slice tables, stage times), freed with it
+  void (*dnd_free)(void*) = nullptr;
 };
 
 namespace sfmgrid {

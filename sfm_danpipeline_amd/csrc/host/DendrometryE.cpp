@@ -1,5 +1,6 @@
 // DendrometryE.cpp -- Dendrometry::estimate (reference src/DendrometryE.cpp:3-29) in the host mirror: the bounds of the
-// cloud on the device (sfmhip_cloud_minmax) and the reference's printed lines, the empty ones included.
+// cloud on the device (sfmhip_cloud_minmax) and the reference's printed lines, the empty ones included; measure() and
+// estimateTree() fill them (one sfmhip_cloud_dendro_profile call: the scalars and the stem table).
 #include "DendrometryE.h"
 #include <cstdio>
 #include <cstdlib>
@@ -42,4 +43,55 @@ void Dendrometry::estimate(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL) {
 
   std::cout << "************************************************" << std::endl;
   std::cout << "************************************************" << std::endl;
+}
+
+int Dendrometry::measure(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_dendro_opts* opts) {
+  sfmhip_dendro_opts o;
+  if (opts)
+    o = *opts;
+  else
+    sfmhip_dendro_default_opts(&o);
+  const int n = (int)cloudPCL->size();
+  std::vector<float> xyz((size_t)3 * n + 3);
+  for (int i = 0; i < n; ++i) {
+    xyz[3 * (size_t)i] = cloudPCL->points[i].x;
+    xyz[3 * (size_t)i + 1] = cloudPCL->points[i].y;
+    xyz[3 * (size_t)i + 2] = cloudPCL->points[i].z;
+  }
+  sfmhip_cloud* dev = nullptr;
+  int rc = sfmhip_cloud_create(sfm_hip_context(), n, xyz.data(), &dev);
+  if (rc != SFMHIP_OK) return rc;
+  int32_t S = 0;
+  profile_.assign(4096, sfmhip_dendro_slice());
+  rc = sfmhip_cloud_dendro_profile(dev, labels, label, &o, (int)profile_.size(), profile_.data(), &S, &tree_);
+  profile_.resize(rc == SFMHIP_OK ? (size_t)S : 0);
+  sfmhip_cloud_destroy(dev);
+  return rc;
+}
+
+int Dendrometry::estimateTree(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_dendro_opts* opts) {
+  const int rc = measure(cloudPCL, labels, label, opts);
+  if (rc != SFMHIP_OK) {
+    std::fprintf(stderr, "[sfm] sfmhip_cloud_dendrometry: %s\n", sfmhip_error_string(rc));
+    return rc;
+  }
+  sfmhip_dendro_opts o;
+  if (opts)
+    o = *opts;
+  else
+    sfmhip_dendro_default_opts(&o);
+  std::cout << "************************************************" << std::endl;
+  std::cout << "              DENDROMETRY ESTIMATION            " << std::endl;
+  std::cout << "************************************************" << std::endl;
+  std::cout << "*** Measurements ***" << std::endl;
+  std::cout << "Total Height =" << tree_.total_height << std::endl;
+  std::cout << "Altura copa viva=" << tree_.live_crown << std::endl;
+  std::cout << "Altura base de copa=" << tree_.crown_base_height << std::endl;
+  std::cout << "Altura DAP=" << o.dbh_height << std::endl;
+  std::cout << "DAP=" << tree_.dbh << std::endl;
+  std::cout << "Amplitud N-S=" << tree_.spread_ns << std::endl;
+  std::cout << "Amplitud E-W=" << tree_.spread_ew << std::endl;
+  std::cout << "************************************************" << std::endl;
+  std::cout << "************************************************" << std::endl;
+  return rc;
 }

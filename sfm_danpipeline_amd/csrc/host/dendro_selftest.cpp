@@ -1,0 +1,37 @@
+// dendro_selftest.cpp -- the measurement the reference's Dendrometry leaves blank, needs the GPU:
+//   dendro_selftest <MAP3D.pcd> <out.bin> [label]
+// Without a label: Dendrometry::estimateTree() on every point of the PCD.  With one: the colour segmentation first
+// (Segmentation::color_based_growing_segmentation), then estimateTree() on that cluster.
+// out.bin: the sfmhip_dendro_result, i32 slices, then that many sfmhip_dendro_slice rows.
+// Exit 3: the cloud is empty or no cluster came out; 4: the library refused the call.
+#include <cstdio>
+#include <cstdlib>
+#include "DendrometryE.h"
+#include "Segmentation.h"
+
+int main(int argc, char** argv) {
+  if (argc < 3) return 2;
+  Dendrometry den;
+  int rc;
+  if (argc > 3) {
+    Segmentation seg;
+    seg.setInputFile(argv[1]);
+    if (seg.color_based_growing_segmentation() != 0) return 3;
+    rc = den.estimateTree(seg.cloud(), seg.labels().data(), std::atoi(argv[3]));
+  } else {
+    pcl::PointCloud<pcl::PointXYZRGB>::Ptr cloud(new pcl::PointCloud<pcl::PointXYZRGB>());
+    pcl::io::loadPCDFile(argv[1], *cloud);
+    if (cloud->size() <= 0) return 3;
+    rc = den.estimateTree(cloud, nullptr, 0);
+  }
+  if (rc != SFMHIP_OK) return 4;
+  FILE* o = fopen(argv[2], "wb");
+  if (!o) return 2;
+  const sfmhip_dendro_result& r = den.tree();
+  const int S = (int)den.stemProfile().size();
+  fwrite(&r, sizeof r, 1, o);
+  fwrite(&S, 4, 1, o);
+  fwrite(den.stemProfile().data(), sizeof(sfmhip_dendro_slice), (size_t)S, o);
+  fclose(o);
+  return 0;
+}
