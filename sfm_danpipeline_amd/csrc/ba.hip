@@ -25,7 +25,8 @@
 //   chol_step2 / chol_step2_chains   blocked Cholesky of S (two 32-column panels per launch) with the rhs carried
 //                     as an extra row (y = L^-1 g) and the identity as extra tile rows (X = L^-T): dense, or on
 //                     the independent chains + separator of a dissected camera graph (nd_gather, nd_combine,
-//                     nd_xy, nd_w).
+//                     nd_xy, nd_w).  The shape of a launch, the decode of its trailing tiles and the schedule of the
+//                     launches are ba_chol_plan.h's, host and kernel alike.
 //   ba_cand_cams      candidate cameras / focal and their rotation tables.
 //   ba_backsub        per point: back-substitution, model cost change, candidate point,
 //                     candidate cost.
@@ -34,6 +35,7 @@
 // every rank then solves the same reduced system and back-substitutes its own points.
 #include "common.h"
 #include "ba_chains_plan.h"
+#include "ba_chol_plan.h"
 #include "ba_front_plan.h"
 #include "ba_setup.h"
 #include <algorithm>
@@ -1735,7 +1737,7 @@ __global__ __launch_bounds__(1024) void ba_finalize(BaDev d, double radius, doub
 // workgroup, written to a buffer nothing else reads
 __device__ unsigned long long g_chol_stamps[32];
 #endif
-constexpr int CB = 32;
+using c2plan::CB;  // the tile width, 32
 constexpr int CBP = 34;  // LDS row pitch in doubles: 16-byte aligned rows, conflict-free tile writes
 
 // P[c][r] -= sum_kk Lc[c][kk] * Lr[r][kk] for the 16x16 sub-tiles (ci, ri) of a 32x32 tile.
@@ -1811,7 +1813,7 @@ __device__ __forceinline__ int lds_wait_ge(const int* flag, int need) {
 // execute in order, so data written before a counter update is visible to whoever saw the update.
 // Trailing workgroups (one wave per tile, four tiles each) fold the pending panels into the tiles
 // right of the block column.
-constexpr int C2_WAVES = 11;
+using c2plan::C2_WAVES;
 enum { F_PROG_A = 0, F_PROG_B, F_CNT_DAA, F_CNT_TA, F_CNT_DBA, F_YPROG, F_XPROG, F_STAGED, F_DBB_HI, F_TB_HI, F_DBA_S3, F_COUNT, F_TIMEOUT = 15 };
 // dynamic LDS of chol_step2 (doubles): five tiles | 1/diag of both panels | the pending panels' rows
 // of the block rows a and b (64 rows x 64 columns, [column][row], pitch PAB) and of the own tile row
@@ -2409,68 +2411,20 @@ __device__ __forceinline__ void chol2_report_timeout(double* sAll, int* __restri
   if (*(volatile const lds_int*)(s_flag + F_TIMEOUT) != 0 && (threadIdx.x & 63) == 0) atomicExch(info, -1);
 }
 
-// (bid: the workgroup's index within its matrix -- blockIdx.x when a launch factors one matrix)
-// (nxc: the tile columns of X that are wanted -- nt for a whole matrix, the interior tiles for a chain, whose X is
-// only used up to there: the trailing tiles of X right of that are not formed)
-// Deferred trailing updates (dfr = D > 1, large matrices): a launch rewrites every trailing tile for 64 columns of update, and at
-// 100+ tile rows that traffic -- not the MFMAs -- is what a launch waits for.  A tile column is only needed up to date when it becomes
-// the panel, so launch k2 touches the columns whose distance to the panels, counted in column pairs, is a multiple of D, and folds
-// the min(D, k2) pairs of panels they have missed (K = 64 D per visit): the columns next to the panels are among them every time.
-// chol_trail_tiles: the tiles of those columns (tc counted from the first column right of the panels), column by column.
-__host__ __device__ inline int chol_trail_tiles(int m2, int D) {
-  int n = 0;
-  for (int tc = 0; tc < m2; tc += (tc & 1) ? 2 * D - 1 : 1) n += m2 - tc;
-  return n;
-}
-
-// one trailing tile (t: its index in the launch's list -- the tiles of S, the rhs row, the tiles of X), one wave
+// one trailing tile (t: its index in the launch's list -- the tiles of S, the rhs row, the tiles of X: c2plan::decode), one wave
 __device__ __forceinline__ void chol2_trailing_tile(double* __restrict__ A, double* __restrict__ y, double* __restrict__ X, const int ld,
-                                                    const int k2, const int m2, const int xlo, const int mx, const int ntile,
-                                                    const int dfr, int t, const int lane, const int catchup = 0) {
-  const int ntrail = ntile + m2;
-  int ti_rel = 0;
-  const double* Rrow = A;  // the tile's row space
-  double* Wrow = A;
-  int rb_x = -1;
-  int npend = 1;  // pairs of panels to fold
-  if (t >= ntrail) {
-    t -= ntrail;
-    rb_x = (xlo + t / mx) * CB;
-    t %= mx;
-    Rrow = X;
-    Wrow = X;
-  } else if (dfr > 1) {
-    if (t >= ntile) {
-      t -= ntile;  // the rhs row: every column, every launch
-      ti_rel = m2;
-    } else {
-      int tc = 0;
-      while (t >= m2 - tc) {
-        t -= m2 - tc;
-        tc += (tc & 1) ? 2 * dfr - 1 : 1;
-      }
-      ti_rel = tc + t;
-      t = tc;
-      npend = min(dfr, k2);
-    }
-  } else {
-    while (true) {
-      const int w = ti_rel < m2 ? ti_rel + 1 : m2;
-      if (t < w) break;
-      t -= w;
-      ++ti_rel;
-    }
-    // (the launch that ends a run of deferred updates visits every column and folds what each has missed: a column whose
-    // distance to the panels is r pairs was last visited when that distance was the next multiple of `catchup` above r)
-    if (catchup > 1 && ti_rel < m2) npend = min(catchup - (t / 2) % catchup, k2);
-  }
-  const int c0 = (2 * k2 + 2) * CB;
-  const int rb = rb_x >= 0 ? rb_x : c0 + ti_rel * CB, cb = c0 + t * CB;
-  int p0 = (2 * k2 - 2 * npend) * CB;
+                                                    const int k2, const c2plan::Shape& sh, const int dfr, const int t, const int lane,
+                                                    const int catchup) {
+  const c2plan::Tile tl = c2plan::decode(sh, k2, dfr, catchup, t);
+  const double* Rrow = tl.kind == c2plan::TILE_X ? X : A;  // the tile's row space
+  double* Wrow = tl.kind == c2plan::TILE_X ? X : A;
+  const int rb = tl.rb * CB, cb = tl.cb * CB;
+  int npend = tl.npend;  // pairs of panels to fold
+  int p0 = 2 * tl.pair0 * CB;
   const int j16 = lane & 15, q = lane >> 4;
   double a[2][16], b[2][16];
   v4d acc[4];  // [2 * ci + ri]
-  if (rb_x < 0 && ti_rel == m2) {
+  if (tl.kind == c2plan::TILE_RHS) {
     // the rhs row: y[cb..] -= y[pending] L(cb.., pending)^T, tile row 0 only
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {
@@ -2535,47 +2489,41 @@ __device__ __forceinline__ void chol2_trailing_tile(double* __restrict__ A, doub
     }
 }
 
+// One workgroup of a launch on one matrix; what its index means is c2plan::Shape's.
+// (bid: the workgroup's index within its matrix -- blockIdx.x when a launch factors one matrix)
+// (nxc: the tile columns of X that are wanted -- nt for a whole matrix, the interior tiles for a chain, whose X is
+// only used up to there: the trailing tiles of X right of that are not formed)
 // (xb: 0, or the width in tile columns (even) of the diagonal blocks of X that are wanted: the inverse of a diagonal block of L
 // is made of that block alone, so the rows and columns of X outside it need not be formed -- chol_back_block)
 __device__ __forceinline__ void chol_step2_body(double* __restrict__ A, double* __restrict__ y, double* __restrict__ X,
                                                 int ld, int nt, int nxc, int k2, int tiles_per_wg, int* __restrict__ info,
                                                 const int bid, double* sAll, const int xb = 0, const int dfr = 1, const int catchup = 0) {
-  const int m2 = nt - 2 * k2 - 2;  // tile rows below the two panels (the rhs row comes on top)
-  const int npanel = m2 + 2;       // owner, m2 tile rows, rhs
-  const int xlo = xb ? 2 * k2 / xb * xb : 0;  // first row block of X that takes part
-  if (xb) nxc = min(nxc, xlo + xb);
-  const int nx = 2 * k2 + 2 - xlo;  // rows xlo..b of the identity block X (see below) take part as tile rows
-  if (bid < npanel + nx) {
-    if (bid >= npanel) {
+  const c2plan::Shape ps = c2plan::panel_shape(nt, k2, xb);
+  if (bid < ps.npanel + ps.nx) {
+    if (bid >= ps.npanel) {
       // X starts as the identity and rides along as nt more tile rows: X <- X L^-T, i.e. L^-T when the
       // factorisation ends, and the backward substitution becomes the product z = X y.  (Row block
       // r' is all zero left of column block r' and untouched until its own panel: rows 0..b here.)
-      chol2_panel<false>(A, y, X, ld, k2, info, false, (xlo + bid - npanel) * CB, sAll);
+      chol2_panel<false>(A, y, X, ld, k2, info, false, (ps.xlo + bid - ps.npanel) * CB, sAll);
       chol2_report_timeout(sAll, info);
       return;
     }
     const bool owner = bid == 0;
     const int r0 = (2 * k2 + 1 + bid) * CB;
-    if (bid == npanel - 1)
+    if (bid == ps.npanel - 1)
       chol2_panel<true>(A, y, A, ld, k2, info, false, r0, sAll);
     else
       chol2_panel<false>(A, y, A, ld, k2, info, owner, r0, sAll);
     chol2_report_timeout(sAll, info);
     return;
   }
-  // ---- trailing tiles (k2 >= 1), one wave each (its four sub-tiles share the operands): tile row
-  // ti_rel in [0, m2] (m2 = rhs) has min(ti_rel + 1, m2) tiles; then the tiles of X: rows 0..a-1 (the
-  // rows that are nonzero in the pending panels) x the m2 column blocks right of the panels
+  // ---- trailing tiles (k2 >= 1), one wave each (its four sub-tiles share the operands); tiles_per_wg of them a workgroup
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ntile = dfr > 1 ? chol_trail_tiles(m2, dfr) : m2 * (m2 + 1) / 2;
-  const int mx = max(0, nxc - 2 * k2 - 2);  // column blocks of X right of the panels
-  const int total = ntile + m2 + (2 * k2 - xlo) * mx;
-  // (four tiles per workgroup -- one wave per SIMD: a tile is 64 MFMAs -- while that fits one round of
-  // workgroups on the device; every workgroup of this kernel holds a CU's LDS)
+  const c2plan::Shape sh = c2plan::with_tiles(ps, nxc, k2, xb, dfr);
   if (wave >= tiles_per_wg) return;
-  const int t = (bid - npanel - nx) * tiles_per_wg + wave;
-  if (t >= total) return;
-  chol2_trailing_tile(A, y, X, ld, k2, m2, xlo, mx, ntile, dfr, t, lane, catchup);
+  const int t = (bid - sh.npanel - sh.nx) * tiles_per_wg + wave;
+  if (t >= sh.total) return;
+  chol2_trailing_tile(A, y, X, ld, k2, sh, dfr, t, lane, catchup);
 }
 
 __global__ __launch_bounds__(C2_WAVES * 64) void chol_step2(double* __restrict__ A, double* __restrict__ y,
@@ -2589,6 +2537,7 @@ __global__ __launch_bounds__(C2_WAVES * 64) void chol_step2(double* __restrict__
 // panel pair k2 in ONE launch.  ALL panel workgroups come first in the grid, the trailing workgroups after them
 // (the panel workgroups are the long ones: they start in the first round; the host keeps their number within the
 // device's CUs).
+static_assert(c2plan::MAX_CHAINS == cplan::CP_MAX, "c2plan::pack_chains packs what a ChainSet holds");
 struct ChainSet {
   int n;
   double* A[cplan::CP_MAX];
@@ -2643,7 +2592,7 @@ __global__ __launch_bounds__(1024) void chol_apply_inverse(const double* __restr
 // Launch K applies z_{K+1} to every tile column left of block K+1 (one workgroup per tile column, sums in a fixed order) and the
 // workgroups of block K's own columns then write their part X(., j) w_j of z_K; the parts are added, in column order, by every
 // workgroup of the next launch (one more launch for z_0): no counters, and the same S and g give the same z bit for bit.
-constexpr int DENSE_XB = 8, DENSE_XB_MIN_NT = 48, DENSE_DEFER4_MIN_NT = 100, DENSE_SWITCH_M2 = 40, DENSE_TPW8_ROUNDS = 4;
+using c2plan::DENSE_XB;
 __global__ __launch_bounds__(256) void chol_x_reset(double* __restrict__ X, int ld, int nt, int xb) {
   const int j = blockIdx.x, r0 = j / xb * xb * CB, r1 = min(nt, (j / xb + 1) * xb) * CB;
   for (int e = threadIdx.x; e < CB * (r1 - r0); e += 256) {
@@ -3604,6 +3553,7 @@ struct sfmhip_ba {
   double2* d_cxy = nullptr;
   int cam_split = 1;
   int dense_xb = 0;              // dense factorisation: X kept inside diagonal blocks of this many tile columns (0: all of X)
+  std::vector<c2plan::Launch> dense_sched;  // dense factorisation: its chol_step2 launches (c2plan::dense_schedule)
   double* d_back_part = nullptr;  // chol_back_block: the columns' parts of z_K
   double* d_cb_part = nullptr;  // ba_cam_blocks with cam_split > 1: 66 sums per (camera, slice); d_cb_cnt: arrivals per camera
   int* d_cb_cnt = nullptr;
@@ -3973,8 +3923,8 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   {
     // (the block width is not a knob: chol_back_block's registers and LDS and the sizes of d_back_part are built for DENSE_XB
     // tile columns)
-    const int nt = b->ld / CB;
-    b->dense_xb = nt >= DENSE_XB_MIN_NT ? DENSE_XB : 0;
+    b->dense_sched = c2plan::dense_schedule(b->ld / CB, b->ctx->n_cu);
+    b->dense_xb = c2plan::dense_xb(b->ld / CB);
     if (b->dense_xb) {
       BA_A(b->d_back_part, 2 * DENSE_XB * DENSE_XB * CB);  // (two sets: a launch reads the one the launch before wrote)
       // X outside its diagonal blocks is never written -- but the panel workgroups of a block's first pair of panels read the
@@ -4616,13 +4566,6 @@ static int ba_nd_build(sfmhip_ba* b) {
   return SFMHIP_OK;
 }
 
-// trailing tiles per workgroup of a chol_step2 launch: the fewest that keep the launch to one round of workgroups
-static void chol_launch_shape(int nt, int nxc, int k2, int* npan, int* ntrail) {
-  const int m2 = nt - 2 * k2 - 2, mx = std::max(0, nxc - 2 * k2 - 2);
-  *ntrail = k2 == 0 ? 0 : m2 * (m2 + 1) / 2 + m2 + 2 * k2 * mx;
-  *npan = m2 + 2 + 2 * k2 + 2;
-}
-
 // diagnostic (SFMHIP_BA_ND_DEBUG): NaN / magnitude census of every chain's buffers after a stage
 static void nd_census(sfmhip_ba* b, const char* stage) {
   hipStreamSynchronize(b->ctx->stream);
@@ -4721,33 +4664,19 @@ static int ba_reduced_solve_nd(sfmhip_ba* b) {
   int nl = 1;
   if (dbg) nd_census(b, "gather");
   for (int k2 = 0; 2 * k2 < b->nd_max_ni; ++k2, ++nl) {
+    int c_nt[cplan::CP_MAX], c_ni[cplan::CP_MAX];
+    for (int i = 0; i < P; ++i) c_nt[i] = ns.c[i].N, c_ni[i] = ns.c[i].ni;
+    const c2plan::ChainLaunch cl = c2plan::pack_chains(P, c_nt, c_ni, k2, b->ctx->n_cu);
     ChainSet cs{};
-    int tpw = 4, total = 0;
-    for (;; ++tpw) {
-      cs.n = 0;
-      int pan = 0, trl = 0;
-      for (int i = 0; i < P; ++i) {
-        if (2 * k2 >= ns.c[i].ni) continue;
-        int npan, ntrail;
-        chol_launch_shape(ns.c[i].N, ns.c[i].ni, k2, &npan, &ntrail);
-        const int j = cs.n++;
-        cs.A[j] = ns.c[i].M;
-        cs.y[j] = ns.c[i].y;
-        cs.X[j] = ns.c[i].X;
-        cs.ld[j] = ns.c[i].ld;
-        cs.nt[j] = ns.c[i].N;
-        cs.nxc[j] = ns.c[i].ni;
-        cs.tpw[j] = tpw;
-        cs.pan0[j] = pan;
-        cs.trl0[j] = trl;
-        pan += npan;
-        trl += (ntrail + tpw - 1) / tpw;
-      }
-      cs.pan0[cs.n] = pan;
-      cs.trl0[cs.n] = trl;
-      total = pan + trl;
-      if (total <= b->ctx->n_cu || tpw >= C2_WAVES) break;
+    cs.n = cl.n;
+    for (int j = 0; j < cl.n; ++j) {
+      const NdChain& c = ns.c[cl.chain[j]];
+      cs.A[j] = c.M, cs.y[j] = c.y, cs.X[j] = c.X;
+      cs.ld[j] = c.ld, cs.nt[j] = c.N, cs.nxc[j] = c.ni, cs.tpw[j] = cl.tpw;
     }
+    std::copy(cl.pan0, cl.pan0 + cl.n + 1, cs.pan0);
+    std::copy(cl.trl0, cl.trl0 + cl.n + 1, cs.trl0);
+    const int tpw = cl.tpw, total = cl.total;
     hipLaunchKernelGGL(chol_step2_chains, dim3(total), dim3(C2_WAVES * 64), C2_LDS_BYTES, st, cs, k2, d.info);
     if (dbg) {
       char nm[32];
@@ -4758,11 +4687,9 @@ static int ba_reduced_solve_nd(sfmhip_ba* b) {
   hipLaunchKernelGGL(nd_combine, dim3(sp.N * (sp.N + 1) / 2 + sp.N), dim3(256), 0, st, ns);
   ++nl;
   for (int k2 = 0; 2 * k2 < sp.N; ++k2, ++nl) {
-    int npan, ntrail, tpw = 4;
-    chol_launch_shape(sp.N, sp.N, k2, &npan, &ntrail);
-    while (tpw < C2_WAVES && npan + (ntrail + tpw - 1) / tpw > b->ctx->n_cu) ++tpw;
-    hipLaunchKernelGGL(chol_step2, dim3(npan + (ntrail + tpw - 1) / tpw), dim3(C2_WAVES * 64), C2_LDS_BYTES, st, sp.M, sp.y,
-                       sp.X, sp.ld, sp.N, k2, tpw, d.info, 0, 1, 0);
+    const c2plan::Grid g = c2plan::launch_grid(sp.N, sp.N, k2, b->ctx->n_cu);
+    hipLaunchKernelGGL(chol_step2, dim3(g.grid), dim3(C2_WAVES * 64), C2_LDS_BYTES, st, sp.M, sp.y, sp.X, sp.ld, sp.N, k2, g.tpw,
+                       d.info, 0, 1, 0);
   }
   // z_S = L_SS^-T y_S;  w_i = y_i - L_Si^T z_S;  z_i = L_ii^-T w_i
   hipLaunchKernelGGL(nd_xy, dim3(sp.N, 1), dim3(1024), 0, st, ns, P, d.z);
@@ -4780,42 +4707,16 @@ static int ba_reduced_solve(sfmhip_ba* b) {
   double* A = d.red;
   double* y = d.red + b->ssz;  // g becomes y = L^-1 g
   const int nt = b->ld / CB;
-  int nchol = 0;
-  {
-    // (once per problem object, not once per process: the attribute belongs to the device's code object,
-    // and contexts on several devices may share a process)
-    if (!b->chol_attr_set) {
-      SFM_HIP_TRY(hipFuncSetAttribute((const void*)chol_step2, hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS_BYTES));
-      b->chol_attr_set = true;
-    }
-    const int xb = b->dense_xb, dfr0 = !xb ? 1 : nt >= DENSE_DEFER4_MIN_NT ? 4 : 2;
-    // (measured, scripts/gpu_dense_sizes.py: worth it only behind visits of four pairs -- 640 cameras 624 -> 643 it/s at 40 tile
-    // rows, 618 at 72; behind visits of two pairs the undeferred tail is slower: 400 cameras 1433 -> 1407)
-    const int sw_m2 = dfr0 >= 4 ? DENSE_SWITCH_M2 : 0;
-    bool deferred = false;  // some earlier launch of this factorisation left columns behind
-    for (int k2 = 0; 2 * k2 < nt; ++k2, ++nchol) {
-      const int m2 = nt - 2 * k2 - 2;
-      // the updates are deferred while the trailing matrix is large; once a launch's visits of 64 dfr MFMAs would outlast its
-      // panel chain (few tiles left: m2 <= DENSE_SWITCH_M2 tile rows) one launch catches every column up and the rest run undeferred
-      const int dfr = m2 > sw_m2 ? dfr0 : 1;
-      const int catchup = dfr == 1 && deferred ? dfr0 : 0;
-      if (k2 > 0) deferred = dfr > 1;
-      // launch 0 has no pending update; later launches: the tiles right of the panels, and those of X
-      const int xlo = xb ? 2 * k2 / xb * xb : 0, mx = xb ? std::max(0, std::min(nt, xlo + xb) - 2 * k2 - 2) : m2;
-      const int ntrail = k2 == 0 ? 0 : (dfr > 1 ? chol_trail_tiles(m2, dfr) : m2 * (m2 + 1) / 2) + m2 + (2 * k2 - xlo) * mx;
-      const int npan = m2 + 2 + 2 * k2 + 2 - xlo;
-      int tpw = 4;  // trailing tiles per workgroup: the fewest that keep the launch to one round of workgroups
-      while (tpw < C2_WAVES && npan + (ntrail + tpw - 1) / tpw > b->ctx->n_cu) ++tpw;
-      // (deferred updates, K = 256 per visit: a workgroup of eleven such visits outlasts the panel workgroups twice over and
-      // the launch ends on the stragglers of a second round -- four visits, one per SIMD, measured best: scripts/gpu_dense_sizes.py)
-      if (dfr >= 4 || catchup >= 4) tpw = 4;
-      // (... unless that makes many rounds of workgroups: then two visits per SIMD, one's loads under the other's MFMAs -- 1400
-      // cameras 118.7 -> 125 it/s; at 640 cameras, under two rounds, the same choice loses 1-2 %)
-      if (dfr >= 4 && (ntrail + 3) / 4 > DENSE_TPW8_ROUNDS * b->ctx->n_cu) tpw = 8;
-      hipLaunchKernelGGL(chol_step2, dim3(npan + (ntrail + tpw - 1) / tpw), dim3(C2_WAVES * 64), C2_LDS_BYTES, st, A, y, d.xinv, d.ld, nt, k2,
-                         tpw, d.info, xb, dfr, catchup);
-    }
+  // (once per problem object, not once per process: the attribute belongs to the device's code object,
+  // and contexts on several devices may share a process)
+  if (!b->chol_attr_set) {
+    SFM_HIP_TRY(hipFuncSetAttribute((const void*)chol_step2, hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS_BYTES));
+    b->chol_attr_set = true;
   }
+  for (const c2plan::Launch& L : b->dense_sched)
+    hipLaunchKernelGGL(chol_step2, dim3(L.grid), dim3(C2_WAVES * 64), C2_LDS_BYTES, st, A, y, d.xinv, d.ld, nt, L.k2, L.tpw, d.info,
+                       L.xb, L.dfr, L.catchup);
+  const int nchol = (int)b->dense_sched.size();
   int nbs = 1;
   if (b->dense_xb) {
     // z block by block from the last (chol_back_block)

@@ -173,17 +173,29 @@ def test_dissected_reduced_system_walks_the_dense_iterates(ctx, orc, monkeypatch
     assert np.allclose(c1, co, rtol=BA_PARAM_RTOL, atol=1e-9) and np.allclose(p1, po, rtol=BA_PARAM_RTOL, atol=1e-9)
 
 
+@pytest.fixture(scope="module")
+def c2plan(tmp_path_factory):
+    """The CPU stub over csrc/ba_chol_plan.h (g++, no HIP), for the length of the dense schedule."""
+    from tests.test_chol_plan import build_stub
+    return build_stub(tmp_path_factory.mktemp("c2plan"))
+
+
 @pytest.mark.parametrize("shape,nd", [((96, 6000, 6), "0"), ((96, 6000, 6), "1"), ((180, 8000, 8), "0"), ((560, 8000, 8), "1"),
                                       ((260, 6000, 8), "0"), ((350, 6000, 8), "0"), ((560, 8000, 8), "0"), ((1400, 9000, 8), "0"), ((6, 300, 4), "2"), ((50, 5000, 10), "2"), ((96, 6000, 6), "2"),
-                                      ((200, 20000, 10), "2"), ((560, 8000, 8), "2"), ((1400, 9000, 8), "2")])
-def test_reduced_step_solves_the_reduced_system(ctx, monkeypatch, shape, nd):
+                                      ((200, 20000, 10), "2"), ((560, 8000, 8), "2"), ((1400, 9000, 8), "2"),
+                                      ((245, 8000, 8), "0"), ((255, 8000, 8), "0"), ((522, 8000, 8), "0"), ((533, 8000, 8), "0")])
+def test_reduced_step_solves_the_reduced_system(ctx, monkeypatch, c2plan, shape, nd):
     """(S + D/r) z = g, z from the solver's own factorisation (dense; dissected: chains + separator; the front tree),
     against numpy on the system the solver hands out.  560 cameras: six chains whose launches exceed one round of
     workgroups; 1400 cameras dense: 266 panel workgroups on 256 CUs (no workgroup of a launch may depend on another
     one's being resident: until round 2 the owner overwrote the diagonal tiles the others read); the front tree from one
     front (6 cameras) to 127 fronts in seven levels (1400 cameras).  Dense from 48 tile columns on: X only inside diagonal
     blocks of 8 tile columns, block-by-block backward substitution, trailing tiles visited every 2nd (260 / 350 cameras: 50 / 66
-    tile columns, a last block of two) or 4th launch (560: 106 columns; 1400: 264) with the panels they missed folded at once."""
+    tile columns, a last block of two) or 4th launch (560: 106 columns; 1400: 264) with the panels they missed folded at once.
+    On the schedule's thresholds (csrc/ba_chol_plan.h): 245 cameras, 46 tile columns, the last size with all of X; 255: 48, the
+    first with X in blocks; 522: 98, the last visited every 2nd launch; 533: 100, the first visited every 4th, with a catch-up
+    launch.  Dense: the solve makes the launches of c2plan::dense_schedule (its length from the CPU stub of
+    tests/test_chol_plan.py) and those of the backward substitution, no more."""
     monkeypatch.setenv("SFMHIP_BA_ND", nd)
     nc, npt, k = shape
     pb = synth.ba_problem(nc, npt, k, seed=5)
@@ -196,6 +208,18 @@ def test_reduced_step_solves_the_reduced_system(ctx, monkeypatch, shape, nd):
     assert np.linalg.norm(S @ z - g) <= 1e-12 * np.linalg.norm(g)
     zr = np.linalg.solve(S, g)
     assert np.abs(z - zr).max() <= 1e-9 * np.abs(zr).max()
+    if nd == "0":
+        # launches of the solve alone: a reduced_step is a reduced_system (linearisation, elimination) and the solve
+        l0 = prob.last_timing()["launches"]
+        prob.reduced_system(1e4)
+        l1 = prob.last_timing()["launches"]
+        prob.reduced_step(1e4)
+        l2 = prob.last_timing()["launches"]
+        nt = lay["dense_tiles"]
+        assert nt == (6 * nc + 1 + 63) // 64 * 2
+        xb = c2plan.c2plan_dense_xb(nt)
+        n_back = -(-nt // xb) + 1 if xb else 1      # chol_back_block per block of X and one more; chol_apply_inverse
+        assert (l2 - l1) - (l1 - l0) == c2plan.c2plan_dense_schedule(nt, 256, None, 0) + n_back
     prob.close()
 
 
