@@ -11,6 +11,7 @@
 // that points observed by the same ascending camera list ("signature") are contiguous and cut
 // into chunks; the reduced matrix S is a dense (6Nc+1)^2 row-major array of which only the
 // upper triangle is formed (= a column-major lower triangle for the Cholesky kernels).
+// The reduced-system buffer [S | g | F^T b | diag | scalars | red2 | X]: ba_red_layout.h.
 //
 // Kernels per LM iteration:
 //   ba_eliminate_mfma<NB>  ONE linearisation forms all of S for the points in long runs.  A workgroup owns a run of
@@ -37,6 +38,7 @@
 #include "ba_chains_plan.h"
 #include "ba_chol_plan.h"
 #include "ba_front_plan.h"
+#include "ba_red_layout.h"
 #include "ba_setup.h"
 #include <algorithm>
 #include <atomic>
@@ -54,20 +56,8 @@
 namespace {
 
 constexpr int CAMD = 40;     // doubles per camera table: R[9] t[3] dR/dw[27] pad
-using bsetup::SC;            // scalar slots at the tail of the all-reduce buffer (+ world)
-// red2, the step evaluation's scalars at the tail of the reduced-system buffer: [0..4) the four totals (candidate cost, model cost
-// change, |step|^2, |candidate|^2) that step_finish leaves -- the sums of the workgroups' slots in BaDev::step_part, added in a
-// fixed order; [0, 8) is what several ranks all-reduce -- | (RED2_SLOTS x 4: the slots round 4's atomics landed in, unused since
-// round 5, kept for the layout) | RED2_TMP | RED2_INFO (an int: the reduced solve's status) | pad.
-constexpr int RED2_SLOTS = 32, RED2_SUM_N = 8 + 4 * RED2_SLOTS, RED2_TMP = RED2_SUM_N, RED2_INFO = RED2_SUM_N + 1,
-              RED2_N = RED2_SUM_N + 8;
-// red2[RED2_TIMEOUT]: 1 when a bounded spin of this rank's reduced solve or step evaluation ran out; summed over the ranks by the
-// step evaluation's all-reduce, so that EVERY rank stops and repeats the solve (a rank-local stop would leave its peers waiting
-// in an all-reduce the stopped rank never issues)
-constexpr int RED2_TIMEOUT = 4;
-// the reduced solve's status word (RED2_INFO): > 0 a pivot was not positive; -1 a hand-off of the reduced solve never arrived
-// (the front tree then runs level by level); -2 a slot of the step evaluation's sums never arrived (no fallback: SFMHIP_ERR_TIMEOUT)
-constexpr int INFO_FINISHER_TIMEOUT = -2;
+using namespace redl;      // SC, the RED2_* slots, INFO_FINISHER_TIMEOUT: the reduced-system buffer's layout (ba_red_layout.h)
+constexpr int H_SC_N = redl::host_scalars_n();  // the scalars ba_publish hands to the host; the sequence number lands behind them
 using bsetup::Chunk;  // a piece of a run of ba_eliminate_mfma (the set-up's, ba_setup.h)
 
 struct BaDev {
@@ -91,12 +81,12 @@ struct BaDev {
   double* iscale_p; // np*3: 1 / scale_p (the elimination's gradient maximum multiplies by it: three reciprocals per point and iteration less)
   double* scale_f;  // 1
   double* diag;     // dim (clamped)
-  // reduced system: red = [S ld*ld | g ld | gF ld | dc ld | sc SC+world], ld = dim rounded up
-  // to 32 (row stride of S; the padded diagonal is 1, everything else in the padding 0)
+  // reduced system: red = [S | g | gF | dc | sc | ... | X] (ba_red_layout.h), ld = dim rounded up
+  // to 64 (row stride of S; the padded diagonal is 1, everything else in the padding 0)
   double* red;
   double* z;     // dim solution
   double* xinv;  // ld x ld, column-major like S's triangle: the identity on entry to the factorisation, L^-T after it
-  double* red2;  // 16 scalars of the step evaluation (the slots behind them are no longer used: step_part)
+  double* red2;  // RED2_N scalars of the step evaluation
   int* info;     // cholesky failure flag
   // trust-region loop on the device (round 5)
   struct LmDev* lm;   // null: the host decides (radius by kernel argument, the host swaps the parameter sets)
@@ -249,10 +239,49 @@ __device__ __forceinline__ void lm_view(BaDev& d, double& radius) {
 }
 
 __device__ __forceinline__ double* red_S(const BaDev& d) { return d.red; }
-__device__ __forceinline__ double* red_g(const BaDev& d) { return d.red + (size_t)d.ld * d.ld; }
-__device__ __forceinline__ double* red_gF(const BaDev& d) { return d.red + (size_t)d.ld * d.ld + d.ld; }
-__device__ __forceinline__ double* red_dc(const BaDev& d) { return d.red + (size_t)d.ld * d.ld + 2 * d.ld; }
-__device__ __forceinline__ double* red_sc(const BaDev& d) { return d.red + (size_t)d.ld * d.ld + 3 * d.ld; }
+__device__ __forceinline__ double* red_g(const BaDev& d) { return redl::g(d.red, d.ld); }
+__device__ __forceinline__ double* red_gF(const BaDev& d) { return redl::gF(d.red, d.ld); }
+__device__ __forceinline__ double* red_dc(const BaDev& d) { return redl::dc(d.red, d.ld); }
+__device__ __forceinline__ double* red_sc(const BaDev& d) { return redl::sc(d.red, d.ld); }
+
+// ---------------------------------------------------------------- what rides on a reduced solve's first launch (Riders, host side)
+// The LM bookkeeping of a linearisation, by one workgroup of WG threads: the clamped column norms into diag, the gradient
+// maximum over the camera / focal columns and the ranks' slots into scv[3], z zeroed where the solve's kernels add into it
+// (nd_gather's job kind 4; front_up's spare workgroup leaves z to the down-sweep).  ba_finalize does the same inside its own loops.
+template <int WG, bool ZERO_Z>
+__device__ __forceinline__ void rider_bookkeeping(const BaDev& d, double lm_lo, double lm_hi, int world) {
+  __shared__ double shm[WG / 64];
+  const double* gF = red_gF(d);
+  const double* dc = red_dc(d);
+  double* scv = red_sc(d);
+  double gm = 0;
+  for (int i = threadIdx.x; i < d.dim; i += WG) {
+    d.diag[i] = fmin(fmax(dc[i], lm_lo), lm_hi);
+    const double sc = i < 6 * d.nc ? d.scale_c[i] : *d.scale_f;
+    gm = fmax(gm, fabs(gF[i] / sc));
+  }
+  if (ZERO_Z)
+    for (int i = threadIdx.x; i < d.ld; i += WG) d.z[i] = 0.0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) gm = fmax(gm, __shfl_down(gm, o));
+  if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = gm;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < WG / 64; ++w) gm = fmax(gm, shm[w]);
+    for (int r = 0; r < world; ++r) gm = fmax(gm, scv[SC + r]);
+    scv[3] = gm;  // gradient max norm (unscaled), all parameter blocks, all ranks
+  }
+}
+// Slice zi of the OTHER reduced-system buffer, zeroed by one workgroup of WG threads: the next linearisation starts on it
+// without a memset of its own (an 11.8 MB fill is 5 us as a launch in the stream, nothing beside the solve's first launch)
+constexpr int ND_ZERO_SLICE = 8192;  // doubles per workgroup
+template <int WG>
+__device__ __forceinline__ void rider_zero_slice(double* __restrict__ zero_ptr, long long zero_n, int zi) {
+  const long long lo = (long long)zi * ND_ZERO_SLICE;
+  double2* p2 = (double2*)(zero_ptr + lo);
+  const long long n2 = (zero_n - lo < ND_ZERO_SLICE ? zero_n - lo : ND_ZERO_SLICE) / 2;
+  for (long long i = threadIdx.x; i < n2; i += WG) p2[i] = make_double2(0.0, 0.0);
+}
 
 __device__ __forceinline__ void atomic_add_f64(double* p, double v) { unsafeAtomicAdd(p, v); }
 __device__ __forceinline__ void atomic_max_pos_f64(double* p, double v) {
@@ -1240,9 +1269,8 @@ __global__ __launch_bounds__(256) void ba_gather_rows(const double* __restrict__
       __syncthreads();
     }
     if (t < 7) {  // (seven different addresses: one read-modify-write each, side by side)
-      const size_t ssz = (size_t)ld * ld;
-      const size_t at[7] = {(size_t)fo * ld + fo, ssz + fo, ssz + 2 * (size_t)ld + fo, ssz + (size_t)ld + fo, ssz + 3 * (size_t)ld,
-                            (size_t)gmax_off, ssz + 3 * (size_t)ld + 2};
+      const size_t at[7] = {(size_t)fo * ld + fo, redl::g(ld) + fo, redl::dc(ld) + fo, redl::gF(ld) + fo, redl::sc(ld),
+                            (size_t)gmax_off, redl::sc(ld) + 2};
       const double v = s_acc[t * T], o = red[at[t]];
       red[at[t]] = t < 2 ? o - v : t == 5 ? fmax(o, v) : o + v;  // S -= Gram (F^T F folded in), g likewise; dc, F^T b, cost, nfail +=
     }
@@ -1324,15 +1352,14 @@ __global__ __launch_bounds__(256) void ba_gather_rows(const double* __restrict__
     }
   }
   double* Srow = red + (size_t)gr * ld;
-  const size_t ssz = (size_t)ld * ld;
   for (int c = lane; c < nacc; c += 64) {
     const double a = acc[c];
     if (a != 0.0) {
       double* at = c < nT       ? Srow + 6 * clist[c / 6] + c % 6
                    : c == nT     ? Srow + fo
-                   : c == nT + 1 ? red + ssz + gr
-                   : c == nT + 2 ? red + ssz + 2 * (size_t)ld + gr
-                                 : red + ssz + (size_t)ld + gr;
+                   : c == nT + 1 ? redl::g(red, ld) + gr
+                   : c == nT + 2 ? redl::dc(red, ld) + gr
+                                 : redl::gF(red, ld) + gr;
       // (rmw == 0: the MFMA path is the only writer of these entries between the memset and here -- no pair-path points)
       const double o = rmw ? *at : 0.0;
       *at = c <= nT + 1 ? o - a : o + a;  // S -= Gram (F^T F folded in), g likewise; the diagonal and F^T b +=
@@ -1690,7 +1717,8 @@ __global__ __launch_bounds__(64) void ba_pp_pairs(BaDev d, const int* __restrict
   }
 }
 
-// LM diagonal of the camera/focal columns onto S; gradient max over those columns
+// LM diagonal of the camera/focal columns onto S; gradient max over those columns.  (rider_bookkeeping's work fused with the
+// kernel's own loops over the diagonal: the split form takes other registers, and a launch that must stay what it is)
 __global__ __launch_bounds__(1024) void ba_finalize(BaDev d, double radius, double lm_lo, double lm_hi, int world,
                                                     int add_diag) {
   __shared__ double sh[16];
@@ -2698,43 +2726,17 @@ struct NdSet {
 // fin != 0: ba_finalize's work rides along (one launch less per LM iteration) -- the LM diagonal is added to the
 // diagonal elements as the tiles are copied (S itself stays undamped), and one more workgroup (job kind 4) leaves the
 // clamped column norms, the gradient maximum and a zeroed z.
-constexpr int ND_ZERO_SLICE = 8192;  // doubles per workgroup of nd_gather's zeroing role
 __global__ __launch_bounds__(256) void nd_gather(NdSet ns, const int4* __restrict__ jobs, int n_jobs, const double* __restrict__ S,
                                                  const double* __restrict__ g, int ldS, BaDev d, int fin, double radius,
                                                  double lm_lo, double lm_hi, int world, double* __restrict__ zero_ptr, long long zero_n) {
-  if ((int)blockIdx.x >= n_jobs) {
-    // the workgroups behind the jobs zero the OTHER reduced-system buffer, slice by slice: the next linearisation starts on it
-    // without a memset of its own (an 11.8 MB fill is 5 us as a launch in the stream, nothing beside this kernel's jobs)
-    const long long lo = (long long)((int)blockIdx.x - n_jobs) * ND_ZERO_SLICE;
-    double2* p2 = (double2*)(zero_ptr + lo);
-    const long long n2 = (zero_n - lo < ND_ZERO_SLICE ? zero_n - lo : ND_ZERO_SLICE) / 2;
-    for (long long i = threadIdx.x; i < n2; i += 256) p2[i] = make_double2(0.0, 0.0);
+  if ((int)blockIdx.x >= n_jobs) {  // (the workgroups behind the jobs)
+    rider_zero_slice<256>(zero_ptr, zero_n, (int)blockIdx.x - n_jobs);
     return;
   }
   if (d.lm) radius = d.lm->radius;
   const int4 job = jobs[blockIdx.x];
   if (job.w == 4) {
-    if (!fin) return;
-    __shared__ double shm[4];
-    const double* gF = red_gF(d);
-    const double* dc = red_dc(d);
-    double* scv = red_sc(d);
-    double gm = 0;
-    for (int i = threadIdx.x; i < d.dim; i += 256) {
-      d.diag[i] = fmin(fmax(dc[i], lm_lo), lm_hi);
-      const double sc = i < 6 * d.nc ? d.scale_c[i] : *d.scale_f;
-      gm = fmax(gm, fabs(gF[i] / sc));
-    }
-    for (int i = threadIdx.x; i < d.ld; i += 256) d.z[i] = 0.0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) gm = fmax(gm, __shfl_down(gm, o));
-    if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = gm;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      gm = fmax(fmax(shm[0], shm[1]), fmax(shm[2], shm[3]));
-      for (int r = 0; r < world; ++r) gm = fmax(gm, scv[SC + r]);
-      scv[3] = gm;  // gradient max norm (unscaled), all parameter blocks, all ranks
-    }
+    if (fin) rider_bookkeeping<256, true>(d, lm_lo, lm_hi, world);
     return;
   }
   const NdChain ch = ns.c[job.x];
@@ -3500,6 +3502,45 @@ struct LmState {
   LmDev s{};              // the trust-region record (the host's copy; the device's own while a device loop runs)
 };
 
+// Which route solves the reduced system (ba_nd_build picks it at the first solve), and each route's own state
+enum class Route { Dense, Chains, Tree };
+struct DenseRoute {
+  std::vector<c2plan::Launch> sched;  // its chol_step2 launches (c2plan::dense_schedule)
+  int xb = 0;                         // X kept inside diagonal blocks of this many tile columns (0: all of X)
+  double* d_back_part = nullptr;      // chol_back_block: the columns' parts of z_K
+};
+struct ChainsRoute {  // chains + separator (ba_chains_plan.h)
+  NdSet set{};
+  NdCols cols{};
+  int max_ni = 0;
+  int4* jobs = nullptr;   // nd_gather's job list
+  int n_jobs = 0;
+};
+struct TreeRoute {  // front tree (ba_front_plan.h / ba_front.h): the multifrontal factorisation, one workgroup per front
+  FrontSet fs{};
+  unsigned epoch = 0;
+  int levels = 0, chain_tiles = 0, chain_blocks = 0, max_T = 0;
+  bool by_level = false;   // a hand-off between fronts timed out once: one launch per tree level from then on
+  bool plan_kept = false;  // the front plan came from the context's last one-shot problem
+  long long dbg_ints = 0, dbg_doubles = 0;  // (sizes of the tree's tables and pool: diagnostic builds)
+};
+
+// What rides on the first launch of a chains or tree solve (nd_gather / front_up) instead of taking launches of its own:
+// ba_finalize's bookkeeping for the linearisation before it, and the zeroing of a second [S | g | ... | red2] buffer (no X),
+// so that the next linearisation starts on a clean buffer instead of behind a memset launch.
+struct Riders {
+  bool prezero = !(getenv("SFMHIP_BA_PREZERO") && atoi(getenv("SFMHIP_BA_PREZERO")) == 0);  // (read when the problem is created)
+  bool pending = false;  // a finalisation waits for the next solve, with these arguments
+  double radius = 0, lm_lo = 0, lm_hi = 0;
+  double* alt = nullptr;  // the buffer that is not d.red (allocated at the first solve)
+  bool alt_clean = false, is_alt = false;  // alt is zeroed; d.red is the second buffer
+  void defer_finalize(double r, double lo, double hi) { pending = true, radius = r, lm_lo = lo, lm_hi = hi; }
+  // (the bodies enqueued behind a stop of the device's loop did nothing: neither buffer is what the host thinks)
+  void forget() { pending = false, alt_clean = false; }
+  // the first launch of a solve with `zero_wgs` zeroing workgroups is in the stream
+  void taken(int zero_wgs) { pending = false, alt_clean = alt_clean || zero_wgs > 0; }
+};
+
 struct sfmhip_ba {
   sfmhip_ctx* ctx = nullptr;
   LmState lm;
@@ -3510,7 +3551,6 @@ struct sfmhip_ba {
   unsigned lm_seq = 0;          // decisions made on this problem so far (monotonic: a stale ring slot never matches)
   double* d_step_part = nullptr;
   size_t step_part_n = 0;
-  bool tree_by_level = false;   // a hand-off between fronts timed out once: one launch per tree level from then on
   int spin_timeouts = 0;
   int nc = 0, np_in = 0, no_in = 0;  // as given
   int np = 0, no = 0;                // with >= 1 observation, sorted order
@@ -3529,7 +3569,6 @@ struct sfmhip_ba {
   unsigned char* d_cam_used = nullptr;
   bool cam_used_known = false;
   double* d_flag = nullptr;  // one double: rank-consistent decisions (ba_agree_flag)
-  bool chol_attr_set = false;
   // plan
   Chunk* d_chunks = nullptr;
   bool elim_deterministic = !(getenv("SFMHIP_BA_DETERMINISTIC") && atoi(getenv("SFMHIP_BA_DETERMINISTIC")) == 0);  // (the default since round 3)
@@ -3552,9 +3591,6 @@ struct sfmhip_ba {
   int* d_cpt = nullptr;
   double2* d_cxy = nullptr;
   int cam_split = 1;
-  int dense_xb = 0;              // dense factorisation: X kept inside diagonal blocks of this many tile columns (0: all of X)
-  std::vector<c2plan::Launch> dense_sched;  // dense factorisation: its chol_step2 launches (c2plan::dense_schedule)
-  double* d_back_part = nullptr;  // chol_back_block: the columns' parts of z_K
   double* d_cb_part = nullptr;  // ba_cam_blocks with cam_split > 1: 66 sums per (camera, slice); d_cb_cnt: arrivals per camera
   int* d_cb_cnt = nullptr;
   int* d_fb_points = nullptr;  // the pair path's points (sorted indices), their first T row
@@ -3569,35 +3605,18 @@ struct sfmhip_ba {
   int2* d_pair_cams = nullptr;
   int2* d_pair_ent = nullptr;
   int n_pairs_pp = 0;
-  long long tree_dbg_ints = 0, tree_dbg_doubles = 0;  // (sizes of the front tree's tables and pool: diagnostic builds)
   int* d_bs_ids = nullptr;  // ba_backsub_runs' records, 16 ints per chunk, large chunks first
-  // dissected reduced system (ba_nd_build below): built at the first solve (with world > 1 the camera graph is the
+  // the reduced solve's route (ba_nd_build below): picked at the first solve (with world > 1 the camera graph is the
   // union over the ranks, which needs the all-reduce)
   std::vector<unsigned long long> h_adj;  // camera co-visibility, nc x ceil(nc/64) bit rows (this rank's points)
-  bool nd_ready = false, nd_on = false, nd_kept = false;  // nd_kept: the front plan came from the context's last one-shot problem
-  NdSet nd{};
-  NdCols nd_cols{};
-  int nd_max_ni = 0;
-  double* nd_buf = nullptr;  // all chain matrices, vectors and X blocks (nd_gather writes what the factorisation reads)
-  int4* nd_gather_jobs = nullptr;
-  int nd_n_gather = 0;
-  bool chol_chains_attr_set = false;
-  // front tree (ba_front_plan.h / ba_front.h): the multifrontal factorisation, one workgroup per front
-  bool tree_on = false, tree_attr_set = false, solve_cand = false;
-  FrontSet tree_fs{};
-  unsigned tree_epoch = 0;
-  int tree_levels = 0, tree_chain_tiles = 0, tree_chain_blocks = 0, tree_max_T = 0;
-  // ba_finalize deferred to the next nd_gather (the LM loop's linearisations, when the dissected solve follows)
-  bool fin_pending = false, defer_fin = false;
-  double fin_radius = 0, fin_lo = 0, fin_hi = 0;
+  bool route_ready = false, lds_attrs_set = false;
+  Route route = Route::Dense;
+  DenseRoute dense;
+  ChainsRoute chains;
+  TreeRoute tree;
+  Riders riders;
   // device storage owned
   std::vector<void*> allocs;
-  size_t red_count = 0;
-  // dissected solve: a second [S | g | ... | red2] buffer that nd_gather's spare workgroups zero while they are at it, so
-  // that the next linearisation starts on a clean buffer instead of behind a memset launch
-  double* red_alt = nullptr;
-  bool alt_clean = false, red_is_alt = false;
-  bool prezero = !(getenv("SFMHIP_BA_PREZERO") && atoi(getenv("SFMHIP_BA_PREZERO")) == 0);  // (read when the problem is created)
   double* d_red_pack = nullptr;  // world > 1: the all-reduce payload (packed upper triangle of S + tail)
   int2* d_xblocks = nullptr;     // world > 1, sparse camera graph: the co-visible camera pairs (a <= b) that are exchanged
   int n_xblocks = 0;             // 0: the dense exchange
@@ -3652,6 +3671,29 @@ static int ba_alloc(sfmhip_ba* b, T** p, size_t n) {
   return SFMHIP_OK;
 }
 
+// d.red2 and d.info follow d.red; X lies behind the first buffer only (the second one, the riders', has none)
+static void ba_red_views(sfmhip_ba* b) {
+  BaDev& d = b->d;
+  d.red2 = d.red + redl::red2(d.ld);
+  d.info = (int*)(d.red + redl::info(d.ld));
+  if (!b->riders.is_alt) d.xinv = d.red + redl::X(d.ld);
+}
+
+// a set-up list on the device: allocated through ba_alloc, copied in one piece, *count its length
+template <typename D, typename H>
+static int ba_put(sfmhip_ba* b, D** dst, const std::vector<H>& src, int* count = nullptr) {
+  static_assert(sizeof(D) % sizeof(H) == 0, "whole elements");
+  const size_t n = src.size() / (sizeof(D) / sizeof(H));
+  SFM_TRY(ba_alloc(b, dst, n));
+  if (n) SFM_HIP_TRY(hipMemcpy(*dst, src.data(), n * sizeof(D), hipMemcpyHostToDevice));
+  if (count) *count = (int)n;
+  return SFMHIP_OK;
+}
+template <typename D, typename H>
+static int ba_put(sfmhip_ba* b, const D** dst, const std::vector<H>& src, int* count = nullptr) {
+  return ba_put(b, const_cast<D**>(dst), src, count);
+}
+
 // SFMHIP_PROFILE_CREATE: the host time of every stage of a set-up or a tear-down, one line on stderr per lap
 struct LapTimer {
   const char* tag;
@@ -3674,11 +3716,11 @@ extern "C" int sfmhip_debug_front_stamps(unsigned long long* out, int n_fronts) 
 #ifdef SFM_FRONT_STAMPS
 // the front tree's tables and its pool (L | y | contribution tiles per front) as they are after the last solve
 extern "C" int sfmhip_debug_tree_dump(sfmhip_ba* b, int* ints, long long n_ints, double* pool, long long n_doubles, long long sizes[2]) {
-  if (!b || !b->tree_on) return -1;
-  sizes[0] = b->tree_dbg_ints, sizes[1] = b->tree_dbg_doubles;
+  if (!b || b->route != Route::Tree) return -1;
+  sizes[0] = b->tree.dbg_ints, sizes[1] = b->tree.dbg_doubles;
   hipDeviceSynchronize();
-  if (ints && n_ints >= sizes[0]) hipMemcpy(ints, b->tree_fs.ints, sizes[0] * sizeof(int), hipMemcpyDeviceToHost);
-  if (pool && n_doubles >= sizes[1]) hipMemcpy(pool, b->tree_fs.pool, sizes[1] * sizeof(double), hipMemcpyDeviceToHost);
+  if (ints && n_ints >= sizes[0]) hipMemcpy(ints, b->tree.fs.ints, sizes[0] * sizeof(int), hipMemcpyDeviceToHost);
+  if (pool && n_doubles >= sizes[1]) hipMemcpy(pool, b->tree.fs.pool, sizes[1] * sizeof(double), hipMemcpyDeviceToHost);
   return 0;
 }
 extern "C" int sfmhip_debug_front_ubench(int mode, unsigned long long* out24) {
@@ -3853,139 +3895,80 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
   d.no = b->no;
   d.dim = b->dim;
   d.ld = b->ld;
-  int rc = SFMHIP_OK;
-  int *d_optr = nullptr, *d_ocam = nullptr;
-  double2* d_oxy = nullptr;
-  // [S | g | F^T b | diag | SC scalars + one slot per rank (<= 64) | the step evaluation's 8 sums, a
-  // scratch double, the factorisation's status]: the tail past the all-reduced part is zeroed with
-  // the rest at every linearisation and comes back to the host in the same copy as the scalars
-  b->red_count = b->ssz + 3 * (size_t)b->ld + SC + 64 + RED2_N + b->ssz;  // ... | X (chol_step2), zeroed with the rest
-#define BA_A(ptr, n)                         \
-  if (rc == SFMHIP_OK) rc = ba_alloc(b, &(ptr), (size_t)(n))
-  BA_A(d_optr, b->np + 1);
-  BA_A(d_ocam, b->no);
-  BA_A(d_oxy, b->no);
-  BA_A(b->d_obs_src, b->no);
-  BA_A(d.cams, 6 * n_cam);
-  BA_A(d.pts, 3 * (size_t)b->np);
-  BA_A(d.focal, 1);
-  BA_A(d.camd, (size_t)CAMD * n_cam);
-  BA_A(d.cams_c, 6 * n_cam);
-  BA_A(d.pts_c, 3 * (size_t)b->np);
-  BA_A(d.focal_c, 1);
-  BA_A(d.camd_c, (size_t)CAMD * n_cam);
-  BA_A(d.scale_c, 6 * n_cam);
-  BA_A(d.scale_p, 3 * (size_t)b->np);
-  BA_A(d.iscale_p, 3 * (size_t)b->np);
-  BA_A(d.scale_f, 1);
-  BA_A(d.diag, b->ld);
-  BA_A(d.red, b->red_count);
-  BA_A(d.z, b->ld);
-  if (rc == SFMHIP_OK) {
-    d.red2 = d.red + b->ssz + 3 * (size_t)b->ld + SC + 64;
-    d.info = (int*)(d.red2 + RED2_INFO);
-    d.xinv = d.red2 + RED2_N;
-  }
-  BA_A(b->d_cam_used, n_cam);
-  BA_A(b->d_flag, 2);
-  BA_A(b->d_chunks, S.chunks.size());
+  // (in this order: a one-shot problem carves its addresses out of the context's block one after the other)
+  SFM_TRY(ba_put(b, &d.optr, S.optr));
+  SFM_TRY(ba_put(b, &d.ocam, S.ocam));
+  SFM_TRY(ba_alloc(b, &b->d_oxy_w, b->no));
+  d.oxy = b->d_oxy_w;
+  SFM_TRY(ba_put(b, &b->d_obs_src, b->obs_src));
+  SFM_TRY(ba_upload_xy(b, obs_xy, n_obs));
+  SFM_TRY(ba_alloc(b, &d.cams, 6 * n_cam));
+  SFM_TRY(ba_alloc(b, &d.pts, 3 * (size_t)b->np));
+  SFM_TRY(ba_alloc(b, &d.focal, 1));
+  SFM_TRY(ba_alloc(b, &d.camd, (size_t)CAMD * n_cam));
+  SFM_TRY(ba_alloc(b, &d.cams_c, 6 * n_cam));
+  SFM_TRY(ba_alloc(b, &d.pts_c, 3 * (size_t)b->np));
+  SFM_TRY(ba_alloc(b, &d.focal_c, 1));
+  SFM_TRY(ba_alloc(b, &d.camd_c, (size_t)CAMD * n_cam));
+  SFM_TRY(ba_alloc(b, &d.scale_c, 6 * n_cam));
+  SFM_TRY(ba_alloc(b, &d.scale_p, 3 * (size_t)b->np));
+  SFM_TRY(ba_alloc(b, &d.iscale_p, 3 * (size_t)b->np));
+  SFM_TRY(ba_alloc(b, &d.scale_f, 1));
+  SFM_TRY(ba_alloc(b, &d.diag, b->ld));
+  SFM_TRY(ba_alloc(b, &d.red, redl::count(b->ld)));
+  SFM_TRY(ba_alloc(b, &d.z, b->ld));
+  ba_red_views(b);
+  SFM_TRY(ba_put(b, &b->d_cam_used, b->h_cam_used));
+  SFM_TRY(ba_alloc(b, &b->d_flag, 2));
+  SFM_TRY(ba_put(b, &b->d_chunks, S.chunks, &b->n_chunks));
   if (!S.gth_dest[0].empty() || !S.gth_dest[1].empty() || !S.grow_hdr.empty()) {
-    BA_A(b->d_slab, S.chunks.size() * (size_t)ELIM_SLAB);
+    SFM_TRY(ba_alloc(b, &b->d_slab, S.chunks.size() * (size_t)ELIM_SLAB));
     for (int m = 0; m < 2; ++m) {
-      BA_A(b->d_gth_ptr[m], S.gth_ptr[m].size());
-      BA_A(b->d_gth_src[m], S.gth_src[m].size());
-      BA_A(b->d_gth_dest[m], S.gth_dest[m].size());
+      SFM_TRY(ba_put(b, &b->d_gth_ptr[m], S.gth_ptr[m]));
+      SFM_TRY(ba_put(b, &b->d_gth_src[m], S.gth_src[m]));
+      SFM_TRY(ba_put(b, &b->d_gth_dest[m], S.gth_dest[m], &b->n_gth[m]));
     }
     if (!S.grow_hdr.empty()) {
-      BA_A(b->d_grow_hdr, S.grow_hdr.size());
-      BA_A(b->d_grow_head, S.grow_head.size());
-      BA_A(b->d_grow_src, S.grow_over.size());
-      BA_A(b->d_grow_colmap, S.grow_colmap.size());
+      SFM_TRY(ba_put(b, &b->d_grow_hdr, S.grow_hdr, &b->n_grow));
+      SFM_TRY(ba_put(b, &b->d_grow_head, S.grow_head));
+      SFM_TRY(ba_put(b, &b->d_grow_src, S.grow_over));
+      SFM_TRY(ba_put(b, &b->d_grow_colmap, S.grow_colmap));
     }
   }
-  for (int c = 0; c < 8; ++c) BA_A(b->d_chunk_ids[c], S.ids[c].size());
-  BA_A(b->d_sig_cams, S.sig_cams.size());
-  BA_A(b->d_cptr, S.cptr.size());
-  BA_A(b->d_cpt, S.cpt.size());
-  BA_A(b->d_cxy, S.cpt.size());
-  BA_A(b->d_fb_points, S.fb.size());
-  BA_A(b->d_pp_obase, S.pp_obase.size());
-  BA_A(b->d_cslot, S.cslot.size());
-  BA_A(b->d_ppT, 18 * S.cslot.size());
-  BA_A(b->d_tfu, 6 * S.fb.size());
+  for (int c = 0; c < 8; ++c) SFM_TRY(ba_put(b, &b->d_chunk_ids[c], S.ids[c], &b->n_chunk_ids[c]));
+  SFM_TRY(ba_put(b, &b->d_sig_cams, S.sig_cams));
+  SFM_TRY(ba_put(b, &b->d_cptr, S.cptr));
+  SFM_TRY(ba_put(b, &b->d_cpt, S.cpt));
+  SFM_TRY(ba_put(b, &b->d_cxy, S.cxy));  // (pairs of doubles)
+  SFM_TRY(ba_put(b, &b->d_fb_points, S.fb, &b->n_fb));
+  SFM_TRY(ba_put(b, &b->d_pp_obase, S.pp_obase));
+  SFM_TRY(ba_put(b, &b->d_cslot, S.cslot));
+  SFM_TRY(ba_alloc(b, &b->d_ppT, 18 * S.cslot.size()));
+  SFM_TRY(ba_alloc(b, &b->d_tfu, 6 * S.fb.size()));
   b->n_pp_part = (int)((S.fb.size() * PP_LANES + 255) / 256);
-  BA_A(b->d_pp_part, 8 * (size_t)b->n_pp_part);
+  SFM_TRY(ba_alloc(b, &b->d_pp_part, 8 * (size_t)b->n_pp_part));
   if (b->cam_split > 1) {
-    BA_A(b->d_cb_part, 66 * (size_t)n_cam * b->cam_split);
-    BA_A(b->d_cb_cnt, n_cam);
-    if (rc == SFMHIP_OK && hipMemset(b->d_cb_cnt, 0, sizeof(int) * (size_t)n_cam) != hipSuccess) rc = SFMHIP_ERR_HIP;
+    SFM_TRY(ba_alloc(b, &b->d_cb_part, 66 * (size_t)n_cam * b->cam_split));
+    SFM_TRY(ba_alloc(b, &b->d_cb_cnt, n_cam));
+    SFM_HIP_TRY(hipMemset(b->d_cb_cnt, 0, sizeof(int) * (size_t)n_cam));
   }
-  {
+  b->dense.sched = c2plan::dense_schedule(b->ld / CB, b->ctx->n_cu);
+  b->dense.xb = c2plan::dense_xb(b->ld / CB);
+  if (b->dense.xb) {
     // (the block width is not a knob: chol_back_block's registers and LDS and the sizes of d_back_part are built for DENSE_XB
     // tile columns)
-    b->dense_sched = c2plan::dense_schedule(b->ld / CB, b->ctx->n_cu);
-    b->dense_xb = c2plan::dense_xb(b->ld / CB);
-    if (b->dense_xb) {
-      BA_A(b->d_back_part, 2 * DENSE_XB * DENSE_XB * CB);  // (two sets: a launch reads the one the launch before wrote)
-      // X outside its diagonal blocks is never written -- but the panel workgroups of a block's first pair of panels read the
-      // block's rows at the pending columns, which lie in the block before: zero once and for all (chol_x_reset clears the
-      // blocks themselves at every linearisation)
-      if (rc == SFMHIP_OK && hipMemset(d.xinv, 0, sizeof(double) * b->ssz) != hipSuccess) rc = SFMHIP_ERR_HIP;
-    }
+    SFM_TRY(ba_alloc(b, &b->dense.d_back_part, 2 * DENSE_XB * DENSE_XB * CB));  // (two sets: a launch reads the one the launch before wrote)
+    // X outside its diagonal blocks is never written -- but the panel workgroups of a block's first pair of panels read the
+    // block's rows at the pending columns, which lie in the block before: zero once and for all (chol_x_reset clears the
+    // blocks themselves at every linearisation)
+    SFM_HIP_TRY(hipMemset(d.xinv, 0, sizeof(double) * b->ssz));
   }
-  BA_A(b->d_pair_ptr, S.pair_ptr.size());
-  BA_A(b->d_pair_cams, S.pair_cams.size());
-  BA_A(b->d_pair_ent, S.pair_ent.size());
-#undef BA_A
-  if (rc != SFMHIP_OK) return rc;
-  d.optr = d_optr;
-  d.ocam = d_ocam;
-  d.oxy = d_oxy;
-  b->d_oxy_w = d_oxy;
-  for (int c = 0; c < 8; ++c) b->n_chunk_ids[c] = (int)S.ids[c].size();
-  b->n_fb = (int)S.fb.size();
-  auto up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-    return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
-  };
-  prof.lap("hipMalloc x27");
-  SFM_HIP_TRY(up(d_optr, S.optr.data(), S.optr.size() * 4));
-  SFM_HIP_TRY(up(d_ocam, S.ocam.data(), S.ocam.size() * 4));
-  SFM_HIP_TRY(up(b->d_obs_src, b->obs_src.data(), b->obs_src.size() * 4));
-  SFM_TRY(ba_upload_xy(b, obs_xy, n_obs));
-  SFM_HIP_TRY(up(b->d_cam_used, b->h_cam_used.data(), n_cam));
-  SFM_HIP_TRY(up(b->d_chunks, S.chunks.data(), S.chunks.size() * sizeof(Chunk)));
-  b->n_chunks = (int)S.chunks.size();
-  if (!S.bs_desc.empty()) {
-    SFM_TRY(ba_alloc(b, &b->d_bs_ids, S.bs_desc.size()));
-    SFM_HIP_TRY(hipMemcpy(b->d_bs_ids, S.bs_desc.data(), S.bs_desc.size() * sizeof(int), hipMemcpyHostToDevice));
-  }
-  for (int m = 0; m < 2 && b->d_slab; ++m) {
-    SFM_HIP_TRY(up(b->d_gth_ptr[m], S.gth_ptr[m].data(), S.gth_ptr[m].size() * 4));
-    SFM_HIP_TRY(up(b->d_gth_src[m], S.gth_src[m].data(), S.gth_src[m].size() * 4));
-    SFM_HIP_TRY(up(b->d_gth_dest[m], S.gth_dest[m].data(), S.gth_dest[m].size() * 4));
-    b->n_gth[m] = (int)S.gth_dest[m].size();
-  }
-  if (b->d_slab && !S.grow_hdr.empty()) {
-    SFM_HIP_TRY(up(b->d_grow_hdr, S.grow_hdr.data(), S.grow_hdr.size() * sizeof(int4)));
-    SFM_HIP_TRY(up(b->d_grow_head, S.grow_head.data(), S.grow_head.size() * sizeof(int4)));
-    SFM_HIP_TRY(up(b->d_grow_src, S.grow_over.data(), S.grow_over.size() * sizeof(int4)));
-    SFM_HIP_TRY(up(b->d_grow_colmap, S.grow_colmap.data(), S.grow_colmap.size() * 4));
-    b->n_grow = (int)S.grow_hdr.size();
-  }
-  for (int c = 0; c < 8; ++c) SFM_HIP_TRY(up(b->d_chunk_ids[c], S.ids[c].data(), S.ids[c].size() * 4));
-  SFM_HIP_TRY(up(b->d_sig_cams, S.sig_cams.data(), S.sig_cams.size() * 4));
-  SFM_HIP_TRY(up(b->d_cptr, S.cptr.data(), S.cptr.size() * 4));
-  SFM_HIP_TRY(up(b->d_cpt, S.cpt.data(), S.cpt.size() * 4));
-  SFM_HIP_TRY(up(b->d_cxy, S.cxy.data(), S.cxy.size() * 8));
-  SFM_HIP_TRY(up(b->d_fb_points, S.fb.data(), S.fb.size() * 4));
-  SFM_HIP_TRY(up(b->d_pp_obase, S.pp_obase.data(), S.pp_obase.size() * 4));
-  SFM_HIP_TRY(up(b->d_cslot, S.cslot.data(), S.cslot.size() * sizeof(int2)));
-  SFM_HIP_TRY(up(b->d_pair_ptr, S.pair_ptr.data(), S.pair_ptr.size() * 4));
-  SFM_HIP_TRY(up(b->d_pair_cams, S.pair_cams.data(), S.pair_cams.size() * sizeof(int2)));
-  SFM_HIP_TRY(up(b->d_pair_ent, S.pair_ent.data(), S.pair_ent.size() * sizeof(int2)));
-  b->n_pairs_pp = (int)S.pair_cams.size();
-  prof.lap("uploads");
-  const size_t sc_bytes = (sizeof(double) * (SC + 64 + RED2_N + 1) + 255) & ~(size_t)255, ring_bytes = sizeof(LmDev) * LM_RING;
+  SFM_TRY(ba_put(b, &b->d_pair_ptr, S.pair_ptr));
+  SFM_TRY(ba_put(b, &b->d_pair_cams, S.pair_cams, &b->n_pairs_pp));
+  SFM_TRY(ba_put(b, &b->d_pair_ent, S.pair_ent));
+  if (!S.bs_desc.empty()) SFM_TRY(ba_put(b, &b->d_bs_ids, S.bs_desc));
+  prof.lap("device lists");
+  const size_t sc_bytes = (sizeof(double) * (H_SC_N + 1) + 255) & ~(size_t)255, ring_bytes = sizeof(LmDev) * LM_RING;
   if (arena) {
     // (the records the device writes to the host: the context's pinned block, made once -- 0.5 ms per problem otherwise)
     if (ctx->ba_pinned_bytes < sc_bytes + ring_bytes) {
@@ -3998,11 +3981,11 @@ static int ba_create_impl(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, const
     b->h_sc = (double*)ctx->ba_pinned;
     b->h_ring = (LmDev*)((char*)ctx->ba_pinned + sc_bytes);
   } else {
-    SFM_HIP_TRY(hipHostMalloc((void**)&b->h_sc, sizeof(double) * (SC + 64 + RED2_N + 1), hipHostMallocDefault));
+    SFM_HIP_TRY(hipHostMalloc((void**)&b->h_sc, sizeof(double) * (H_SC_N + 1), hipHostMallocDefault));
     SFM_HIP_TRY(hipHostMalloc((void**)&b->h_ring, ring_bytes, hipHostMallocDefault));
   }
   SFM_HIP_TRY(hipHostGetDevicePointer((void**)&b->h_sc_dev, b->h_sc, 0));
-  b->h_sc[SC + 64 + RED2_N] = 0.0;
+  b->h_sc[H_SC_N] = 0.0;
   // the trust-region record, the host's ring of copies of it, the step evaluation's slots (a workgroup per run, blocks of 64
   // points of ba_backsub, then a pair per front / per wave of ba_cand_cams)
   memset(b->h_ring, 0, sizeof(LmDev) * LM_RING);  // (a shared block: the previous problem's records must not match this one's sequence numbers)
@@ -4032,8 +4015,8 @@ extern "C" int sfmhip_ba_set_allreduce(sfmhip_ba* b, sfmhip_allreduce_fn fn, voi
   if (world != b->world || rank != b->rank) {
     // the dissection plan and the sparse exchange list are built from the UNION of the ranks' camera graphs, and the
     // Jacobi scale from the sum of their column norms: both belong to the (rank, world) they were made for
-    b->nd_ready = false;
-    b->nd_on = false;
+    b->route_ready = false;
+    b->route = Route::Dense;
     b->n_xblocks = 0;
     b->scale_ready = false;
     b->lm = LmState();  // (an LM run in progress belongs to the old partition: the next iterate starts over)
@@ -4045,7 +4028,7 @@ extern "C" int sfmhip_ba_set_allreduce(sfmhip_ba* b, sfmhip_allreduce_fn fn, voi
   b->world = world;
   if (world > 1 && !b->d_red_pack) {
     SFM_HIP_TRY(hipSetDevice(b->ctx->device));
-    SFM_TRY(ba_alloc(b, &b->d_red_pack, (size_t)b->ld * (b->ld + 1) / 2 + 3 * (size_t)b->ld + SC + 64));
+    SFM_TRY(ba_alloc(b, &b->d_red_pack, redl::packed_count(b->ld)));
   }
   return SFMHIP_OK;
 }
@@ -4245,12 +4228,12 @@ static int ba_launch_eliminate(sfmhip_ba* b, double inv_radius, double lm_lo, do
                        (const double*)slab, (const int*)b->d_grow_colmap, (const int4*)b->d_grow_hdr,
                        (const int4*)b->d_grow_head, (const int4*)b->d_grow_src, b->n_grow, rw, b->ld, b->grow_accw, 6 * b->nc, b->n_chunks, (const int*)b->d_gth_ptr[0],
                        (const unsigned*)b->d_gth_src[0], (const int*)b->d_gth_dest[0], b->n_gth[0], b->d.red,
-                       (long long)(b->ssz + 3 * (size_t)b->ld + SC + b->rank), b->n_fb ? 1 : 0, (const LmDev*)b->d.lm);
+                       (long long)redl::rank_slot(b->ld, b->rank), b->n_fb ? 1 : 0, (const LmDev*)b->d.lm);
     ++nl;
   } else if (slab && nl && b->n_gth[m]) {
     hipLaunchKernelGGL(ba_gather_slabs, dim3((b->n_gth[m] + 15) / 16), dim3(256), 0, st, (const double*)slab,
                        (const int*)b->d_gth_ptr[m], (const unsigned*)b->d_gth_src[m], (const int*)b->d_gth_dest[m], b->n_gth[m],
-                       b->d.red, (long long)(b->ssz + 3 * (size_t)b->ld + SC + b->rank), (const LmDev*)b->d.lm);
+                       b->d.red, (long long)redl::rank_slot(b->ld, b->rank), (const LmDev*)b->d.lm);
     ++nl;
   }
   return nl;
@@ -4259,8 +4242,8 @@ static int ba_launch_eliminate(sfmhip_ba* b, double inv_radius, double lm_lo, do
 static int ba_prepare_scale(sfmhip_ba* b, int jacobi) {
   hipStream_t st = b->ctx->stream;
   BaDev& d = b->d;
-  const size_t tail = b->ssz + 2 * (size_t)b->ld;  // dc | sc
-  SFM_HIP_TRY(hipMemsetAsync(d.red + tail, 0, sizeof(double) * ((size_t)b->ld + SC + 64), st));
+  const size_t tail = redl::dc(b->ld);  // dc | sc | the ranks' slots
+  SFM_HIP_TRY(hipMemsetAsync(d.red + tail, 0, sizeof(double) * (redl::red2(b->ld) - tail), st));
   hipLaunchKernelGGL(ba_cam_prep, dim3((b->nc + 63) / 64), dim3(64), 0, st, d.cams, d.camd, b->nc, 1);
   b->camd_valid = true;
   if (b->np) hipLaunchKernelGGL(ba_point_norms, dim3((b->np + 255) / 256), dim3(256), 0, st, d, jacobi);
@@ -4297,36 +4280,42 @@ static int ba_prepare_scale(sfmhip_ba* b, int jacobi) {
   return SFMHIP_OK;
 }
 
-// linearise at the current x + eliminate with `radius`; leaves [S|g|gF|dc|sc] summed over ranks
-static int ba_linearize_eliminate(sfmhip_ba* b, double radius, const sfmhip_ba_opts* o, bool add_diag) {
+// A zeroed reduced-system buffer for a linearisation: the one that the spare workgroups of the last chains or tree solve
+// cleaned (stream order is the only dependency), or this one behind a memset (*filled).  X, the last ld*ld doubles, belongs to
+// the dense factorisation only and lies behind the first buffer.
+static int ba_fresh_red(sfmhip_ba* b, bool* filled) {
+  hipStream_t st = b->ctx->stream;
+  BaDev& d = b->d;
+  Riders& r = b->riders;
+  const bool dense = b->route == Route::Dense;
+  *filled = dense || !r.alt_clean;
+  if (dense ? r.is_alt : r.alt_clean) {  // (dense: back to the first buffer; else: to the clean one)
+    std::swap(d.red, r.alt);
+    r.is_alt = !r.is_alt;
+    ba_red_views(b);
+  }
+  r.alt_clean = false;
+  if (!*filled) return SFMHIP_OK;
+  const bool all_x = dense && !b->dense.xb;
+  SFM_HIP_TRY(hipMemsetAsync(d.red, 0, sizeof(double) * (all_x ? redl::count(b->ld) : redl::count_without_X(b->ld)), st));
+  if (dense && b->dense.xb) {  // (only the diagonal blocks of X are formed and read)
+    hipLaunchKernelGGL(chol_x_reset, dim3(b->ld / CB), dim3(256), 0, st, d.xinv, b->ld, b->ld / CB, b->dense.xb);
+    b->launches += 1;
+  }
+  return SFMHIP_OK;
+}
+
+// linearise at the current x + eliminate with `radius`; leaves [S|g|gF|dc|sc] summed over ranks.  defer_fin: a reduced solve
+// follows at once, and on the chains and tree routes its first launch does ba_finalize's part
+static int ba_linearize_eliminate(sfmhip_ba* b, double radius, const sfmhip_ba_opts* o, bool add_diag, bool defer_fin = false) {
   hipStream_t st = b->ctx->stream;
   BaDev& d = b->d;
   if (b->ctx->timing) {
     SFM_HIP_TRY(hipEventRecord(b->ev[0], st));
     b->ev_on[0] = true;
   }
-  // (X, the last ld*ld doubles, belongs to the dense factorisation only)
-  auto swap_red = [&]() {
-    std::swap(d.red, b->red_alt);
-    b->red_is_alt = !b->red_is_alt;
-    d.red2 = d.red + b->ssz + 3 * (size_t)b->ld + SC + 64;
-    d.info = (int*)(d.red2 + RED2_INFO);
-  };
   bool filled = true;
-  if (b->nd_on && b->alt_clean) {
-    swap_red();  // (the last nd_gather zeroed it; stream order is the only dependency)
-    b->alt_clean = false;
-    filled = false;
-  } else {
-    if (!b->nd_on && b->red_is_alt) swap_red();  // (the dense factorisation's X lives behind the first buffer)
-    b->alt_clean = false;
-    const bool all_x = !b->nd_on && !b->dense_xb;
-    SFM_HIP_TRY(hipMemsetAsync(d.red, 0, sizeof(double) * (all_x ? b->red_count : b->red_count - b->ssz), st));
-    if (!b->nd_on && b->dense_xb) {  // (only the diagonal blocks of X are formed and read)
-      hipLaunchKernelGGL(chol_x_reset, dim3(b->ld / CB), dim3(256), 0, st, d.xinv, b->ld, b->ld / CB, b->dense_xb);
-      b->launches += 1;
-    }
-  }
+  SFM_TRY(ba_fresh_red(b, &filled));
   if (!b->camd_valid) {
     hipLaunchKernelGGL(ba_cam_prep, dim3((b->nc + 63) / 64), dim3(64), 0, st, d.cams, d.camd, b->nc, 1);
     b->camd_valid = true;
@@ -4352,7 +4341,7 @@ static int ba_linearize_eliminate(sfmhip_ba* b, double radius, const sfmhip_ba_o
     b->ev_on[1] = true;
   }
   if (b->world > 1) {
-    const int tail_n = 3 * b->ld + SC + b->world;
+    const int tail_n = (int)redl::allreduce_tail(b->ld, b->world);
     const size_t tri = (size_t)b->ld * (b->ld + 1) / 2;
     if (b->n_xblocks > 0) {
       const int extra = (b->dim + tail_n + 63) / 64 < 64 ? (b->dim + tail_n + 63) / 64 : 64;
@@ -4376,12 +4365,11 @@ static int ba_linearize_eliminate(sfmhip_ba* b, double radius, const sfmhip_ba_o
     SFM_HIP_TRY(hipEventRecord(b->ev[2], st));
     b->ev_on[2] = true;
   }
-  if (b->defer_fin && b->nd_on && add_diag) {
-    b->fin_pending = true;
-    b->fin_radius = radius, b->fin_lo = o->min_lm_diagonal, b->fin_hi = o->max_lm_diagonal;
+  if (defer_fin && b->route != Route::Dense && add_diag) {
+    b->riders.defer_finalize(radius, o->min_lm_diagonal, o->max_lm_diagonal);
     return SFMHIP_OK;
   }
-  b->fin_pending = false;  // (this linearisation replaces one whose finalisation may still have been pending)
+  b->riders.pending = false;  // (this linearisation replaces one whose finalisation may still have been pending)
   hipLaunchKernelGGL(ba_finalize, dim3(1), dim3(1024), 0, st, d, radius, o->min_lm_diagonal, o->max_lm_diagonal,
                      b->world, add_diag ? 1 : 0);
   SFM_HIP_TRY(hipGetLastError());
@@ -4391,9 +4379,10 @@ static int ba_linearize_eliminate(sfmhip_ba* b, double radius, const sfmhip_ba_o
 
 // (a linearisation whose finalisation was left to a gather that will not come: before anyone reads its scalars)
 static int ba_finish_pending(sfmhip_ba* b) {
-  if (!b->fin_pending) return SFMHIP_OK;
-  b->fin_pending = false;
-  hipLaunchKernelGGL(ba_finalize, dim3(1), dim3(1024), 0, b->ctx->stream, b->d, b->fin_radius, b->fin_lo, b->fin_hi, b->world, 1);
+  Riders& r = b->riders;
+  if (!r.pending) return SFMHIP_OK;
+  r.pending = false;
+  hipLaunchKernelGGL(ba_finalize, dim3(1), dim3(1024), 0, b->ctx->stream, b->d, r.radius, r.lm_lo, r.lm_hi, b->world, 1);
   SFM_HIP_TRY(hipGetLastError());
   b->launches += 1;
   return SFMHIP_OK;
@@ -4425,9 +4414,7 @@ static int ba_union_adjacency(sfmhip_ba* b, std::vector<unsigned long long>& adj
         xb.push_back(make_int2(a, c));
   const size_t tri = (size_t)b->ld * (b->ld + 1) / 2;
   if (xb.size() * 36 + b->dim < tri / 2) {
-    SFM_TRY(ba_alloc(b, &b->d_xblocks, xb.size()));
-    SFM_HIP_TRY(hipMemcpy(b->d_xblocks, xb.data(), xb.size() * sizeof(int2), hipMemcpyHostToDevice));
-    b->n_xblocks = (int)xb.size();
+    SFM_TRY(ba_put(b, &b->d_xblocks, xb, &b->n_xblocks));
   }
   return SFMHIP_OK;
 }
@@ -4442,7 +4429,7 @@ static int ba_tree_attach(sfmhip_ba* b, const std::vector<unsigned long long>& a
   // (a one-shot problem: the plan of the last one, when the camera graph and the device are the same -- BaHostScratch)
   BaHostScratch* const hs = ba_plan_cache_on() && b->use_arena && b->world == 1 ? ba_host_scratch(b->ctx) : nullptr;
   const bool kept = hs && hs->nd_valid && hs->nd_nc == nc && hs->nd_n_cu == b->ctx->n_cu && hs->nd_adj == adj;
-  b->nd_kept = kept;
+  b->tree.plan_kept = kept;
   if (kept) {
     P = hs->nd_P;
     fl = hs->nd_fl;
@@ -4463,30 +4450,19 @@ static int ba_tree_attach(sfmhip_ba* b, const std::vector<unsigned long long>& a
     if (getenv("SFMHIP_BA_ND_VERBOSE")) fprintf(stderr, "[sfmhip] no front tree: %s\n", P.why);
     return SFMHIP_OK;
   }
-  int* d_ints = nullptr;
-  int* d_up = nullptr;
-  int* d_down = nullptr;
+  FrontSet& fs = b->tree.fs;
   unsigned* d_flags = nullptr;
-  double* pool = nullptr;
-  SFM_TRY(ba_alloc(b, &d_ints, fl.ints.size()));
-  SFM_TRY(ba_alloc(b, &d_up, fl.up_roles.size()));
-  SFM_TRY(ba_alloc(b, &d_down, fl.down_order.size()));
+  SFM_TRY(ba_put(b, &fs.ints, fl.ints));
+  SFM_TRY(ba_put(b, &fs.up_order, fl.up_roles));
+  SFM_TRY(ba_put(b, &fs.down_order, fl.down_order));
   const size_t n_flags = (size_t)fl.n_fronts + (size_t)fl.n_tflags;  // per front: z in place; per contribution tile
   SFM_TRY(ba_alloc(b, &d_flags, n_flags));
-  SFM_TRY(ba_alloc(b, &pool, fl.n_doubles));
-  SFM_HIP_TRY(hipMemcpy(d_ints, fl.ints.data(), fl.ints.size() * sizeof(int), hipMemcpyHostToDevice));
-  SFM_HIP_TRY(hipMemcpy(d_up, fl.up_roles.data(), fl.up_roles.size() * sizeof(int), hipMemcpyHostToDevice));
-  SFM_HIP_TRY(hipMemcpy(d_down, fl.down_order.data(), fl.down_order.size() * sizeof(int), hipMemcpyHostToDevice));
+  SFM_TRY(ba_alloc(b, &fs.pool, fl.n_doubles));
   SFM_HIP_TRY(hipMemset(d_flags, 0, n_flags * sizeof(unsigned)));
-  SFM_HIP_TRY(hipMemset(pool, 0, fl.n_doubles * sizeof(double)));
-
-  b->tree_fs.ints = d_ints;
-  b->tree_fs.up_order = d_up;
-  b->tree_fs.down_order = d_down;
-  b->tree_fs.pool = pool;
-  b->tree_dbg_ints = (long long)fl.ints.size(), b->tree_dbg_doubles = (long long)fl.n_doubles;
-  b->tree_fs.flag_down = d_flags;
-  b->tree_fs.tflag = d_flags + fl.n_fronts;
+  SFM_HIP_TRY(hipMemset(fs.pool, 0, fl.n_doubles * sizeof(double)));
+  b->tree.dbg_ints = (long long)fl.ints.size(), b->tree.dbg_doubles = (long long)fl.n_doubles;
+  fs.flag_down = d_flags;
+  fs.tflag = d_flags + fl.n_fronts;
   double* zq = nullptr;
   SFM_TRY(ba_alloc(b, &zq, 2 * (size_t)b->ld));
   {
@@ -4494,16 +4470,14 @@ static int ba_tree_attach(sfmhip_ba* b, const std::vector<unsigned long long>& a
     SFM_HIP_TRY(hipMemcpy(zq, pend.data(), pend.size() * 8, hipMemcpyHostToDevice));
   }
   prof.lap("plan uploads");
-  b->tree_fs.zq = zq;
-  b->tree_fs.zq_ld = b->ld;
-  b->tree_fs.n_fronts = fl.n_fronts;
-
-  b->tree_levels = fl.levels;
-  b->tree_chain_tiles = P.chain_tiles;
-  b->tree_chain_blocks = P.chain_blocks;
-  b->tree_max_T = P.max_T;
-  b->tree_on = *on = true;
-  b->nd_on = true;  // (what the two share: the deferred ba_finalize, the pre-zeroed second buffer)
+  fs.zq = zq;
+  fs.zq_ld = b->ld;
+  fs.n_fronts = fl.n_fronts;
+  b->tree.levels = fl.levels;
+  b->tree.chain_tiles = P.chain_tiles;
+  b->tree.chain_blocks = P.chain_blocks;
+  b->tree.max_T = P.max_T;
+  *on = true;
   if (getenv("SFMHIP_BA_ND_VERBOSE"))
     fprintf(stderr, "[sfmhip] reduced system as a front tree: %d fronts, %d levels, %d tile steps (%d block steps) on the chain, fronts of up to %d tiles; dense %d tiles\n",
             fl.n_fronts, fl.levels, P.chain_tiles, P.chain_blocks, P.max_T, b->ld / CB);
@@ -4512,34 +4486,37 @@ static int ba_tree_attach(sfmhip_ba* b, const std::vector<unsigned long long>& a
 
 // chains + separator (ba_chains_plan.h): one buffer for every chain's M | X | y, the index maps, nd_gather's job list
 static int ba_chains_attach(sfmhip_ba* b, const cplan::Flat& fl) {
-  NdSet& ns = b->nd;
+  NdSet& ns = b->chains.set;
   ns.n = fl.n;
-  SFM_TRY(ba_alloc(b, &b->nd_buf, fl.total));
+  double* buf = nullptr;  // all chain matrices, vectors and X blocks (nd_gather writes what the factorisation reads)
+  SFM_TRY(ba_alloc(b, &buf, fl.total));
   for (int i = 0; i <= fl.n; ++i) {
     NdChain& c = ns.c[i];
     c.ld = fl.c[i].ld, c.ni = fl.c[i].ni, c.N = fl.c[i].N;
-    c.M = b->nd_buf + fl.offM[i];
-    c.X = b->nd_buf + fl.offX[i];
-    c.y = b->nd_buf + fl.offy[i];
-    int* dinv = nullptr;
-    SFM_TRY(ba_alloc(b, &dinv, fl.inv[i].size()));
-    SFM_HIP_TRY(hipMemcpy(dinv, fl.inv[i].data(), fl.inv[i].size() * 4, hipMemcpyHostToDevice));
-    c.inv = dinv;
-    b->nd_cols.col0[i] = fl.col0[i];
+    c.M = buf + fl.offM[i];
+    c.X = buf + fl.offX[i];
+    c.y = buf + fl.offy[i];
+    SFM_TRY(ba_put(b, &c.inv, fl.inv[i]));
+    b->chains.cols.col0[i] = fl.col0[i];
   }
-  SFM_TRY(ba_alloc(b, &b->nd_gather_jobs, fl.jobs.size()));
-  SFM_HIP_TRY(hipMemcpy(b->nd_gather_jobs, fl.jobs.data(), fl.jobs.size() * sizeof(int4), hipMemcpyHostToDevice));
-  b->nd_n_gather = (int)fl.jobs.size();
-  b->nd_max_ni = fl.max_ni;
-  b->nd_on = true;
+  SFM_TRY(ba_put(b, &b->chains.jobs, fl.jobs, &b->chains.n_jobs));
+  b->chains.max_ni = fl.max_ni;
   return SFMHIP_OK;
 }
 
 // SFMHIP_BA_ND -- "0": dense always; "1": chains + separator whenever a cut exists (tests); "2": the front tree or dense;
 // unset: the front tree, else chains + separator when its cost model wins over dense by 20 %, else dense
 static int ba_nd_build(sfmhip_ba* b) {
-  b->nd_ready = true;
-  b->nd_on = false;
+  b->route_ready = true;
+  b->route = Route::Dense;
+  // (once per problem object, not once per process: the attribute belongs to the device's code object,
+  // and contexts on several devices may share a process)
+  if (!b->lds_attrs_set) {
+    SFM_HIP_TRY(hipFuncSetAttribute((const void*)chol_step2, hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS_BYTES));
+    SFM_HIP_TRY(hipFuncSetAttribute((const void*)chol_step2_chains, hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS_BYTES));
+    SFM_HIP_TRY(hipFuncSetAttribute((const void*)front_up, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BYTES));
+    b->lds_attrs_set = true;
+  }
   if (b->h_adj.empty()) return SFMHIP_OK;
   const char* env = getenv("SFMHIP_BA_ND");
   const char mode = env ? env[0] : 0;
@@ -4550,6 +4527,7 @@ static int ba_nd_build(sfmhip_ba* b) {
   if (mode != '1') {
     bool tree = false;
     SFM_TRY(ba_tree_attach(b, adj, wpr, &tree));
+    if (tree) b->route = Route::Tree;
     if (tree || mode == '2') return SFMHIP_OK;
   }
   const cplan::Plan P = cplan::build_plan(nc, adj.data(), wpr, dense_tiles, b->ctx->n_cu, mode == '1');
@@ -4558,6 +4536,7 @@ static int ba_nd_build(sfmhip_ba* b) {
   if (verbose) fprintf(stderr, "[sfmhip] dissection check: %d violations\n", cplan::violations(P, nc, adj.data(), wpr));
   const cplan::Flat fl = cplan::flatten(P, nc);
   SFM_TRY(ba_chains_attach(b, fl));
+  b->route = Route::Chains;
   if (verbose) {
     fprintf(stderr, "[sfmhip] reduced system dissected: %d chains (", fl.n);
     for (int i = 0; i < fl.n; ++i) fprintf(stderr, "%s%d", i ? "," : "", fl.c[i].ni);
@@ -4569,8 +4548,8 @@ static int ba_nd_build(sfmhip_ba* b) {
 // diagnostic (SFMHIP_BA_ND_DEBUG): NaN / magnitude census of every chain's buffers after a stage
 static void nd_census(sfmhip_ba* b, const char* stage) {
   hipStreamSynchronize(b->ctx->stream);
-  for (int i = 0; i <= b->nd.n; ++i) {
-    const NdChain& c = b->nd.c[i];
+  for (int i = 0; i <= b->chains.set.n; ++i) {
+    const NdChain& c = b->chains.set.c[i];
     const size_t n = (size_t)c.ld;
     std::vector<double> M(n * n), X(n * n), y(n);
     hipMemcpy(M.data(), c.M, n * n * 8, hipMemcpyDeviceToHost);
@@ -4583,7 +4562,7 @@ static void nd_census(sfmhip_ba* b, const char* stage) {
     for (size_t col = 0; col < n; ++col)
       for (size_t r = col; r < n; ++r) {
         const double v = M[col * n + r];
-        const bool w = col >= o && i < b->nd.n;
+        const bool w = col >= o && i < b->chains.set.n;
         if (v != v) {
           (w ? nanW : nanL)++;
           if (first_nan_col < 0) first_nan_col = (long)col, first_nan_row = (long)r;
@@ -4596,74 +4575,60 @@ static void nd_census(sfmhip_ba* b, const char* stage) {
   }
 }
 
-// the workgroups of a dissected solve's first launch that zero the other [S | g | ... | red2] buffer (allocated at the first
-// solve) -- all nz doubles of it but X: an even number, ld is a multiple of 64 and SC + 64 + RED2_N even; 0: nothing to zero;
-// < 0: an error code
-static int ba_zero_wgs(sfmhip_ba* b, size_t nz) {
-  if (b->prezero && !b->red_alt && nz % 2 == 0) SFM_TRY(ba_alloc(b, &b->red_alt, nz));
-  return b->prezero && b->red_alt ? (int)((nz + ND_ZERO_SLICE - 1) / ND_ZERO_SLICE) : 0;
+// the workgroups of a chains or tree solve's first launch that zero the other [S | g | ... | red2] buffer (allocated at the
+// first solve) -- all of it but X, count_without_X(), an even number; 0: nothing to zero; < 0: an error code
+static int ba_zero_wgs(sfmhip_ba* b) {
+  Riders& r = b->riders;
+  const size_t nz = redl::count_without_X(b->ld);
+  if (r.prezero && !r.alt) SFM_TRY(ba_alloc(b, &r.alt, nz));
+  return r.prezero ? (int)((nz + ND_ZERO_SLICE - 1) / ND_ZERO_SLICE) : 0;
 }
 
 // the front tree: one up-sweep launch (assembly, factorisation, forward substitution; its spare workgroups zero the other
 // reduced-system buffer and do ba_finalize's bookkeeping), one down-sweep launch (backward substitution, candidate cameras)
-static int ba_reduced_solve_tree(sfmhip_ba* b) {
+static int ba_reduced_solve_tree(sfmhip_ba* b, bool cand) {
   hipStream_t st = b->ctx->stream;
   BaDev& d = b->d;
-  if (!b->tree_attr_set) {
-    SFM_HIP_TRY(hipFuncSetAttribute((const void*)front_up, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BYTES));
-    b->tree_attr_set = true;
-  }
-  const size_t nz = b->red_count - b->ssz;
-  const int zwg = ba_zero_wgs(b, nz);
+  Riders& r = b->riders;
+  const int zwg = ba_zero_wgs(b);
   if (zwg < 0) return zwg;
-  const int nF = b->tree_fs.n_fronts;
+  const int nF = b->tree.fs.n_fronts;
   // grid: the fronts, then the zeroing workgroups, then one more for the bookkeeping
   const int grid = nF + zwg + 1;
-  const unsigned epoch = ++b->tree_epoch;
+  const unsigned epoch = ++b->tree.epoch;
+  // one launch for all levels; or one per tree level, the deepest first with the riders: what a solve falls back to once a
+  // hand-off between fronts has timed out
+  const bool by_level = b->tree.by_level;
+  const int top = b->tree.levels - 1;
   int nl = 0;
-  if (b->tree_by_level) {  // (one launch per tree level: what a solve falls back to once a hand-off between fronts has timed out)
-    for (int l = b->tree_levels - 1; l >= 0; --l, ++nl)
-      hipLaunchKernelGGL(front_up, dim3(l == b->tree_levels - 1 ? grid : nF), dim3(FR_WAVES * 64), FR_LDS_BYTES, st, b->tree_fs, d.red,
-                         d.red + b->ssz, d.ld, d, b->fin_pending ? 1 : 0, b->fin_radius, b->fin_lo, b->fin_hi, b->world, epoch, l, l,
-                         b->red_alt, (long long)nz, l == b->tree_levels - 1 ? zwg : 0);
-  } else {
-    hipLaunchKernelGGL(front_up, dim3(grid), dim3(FR_WAVES * 64), FR_LDS_BYTES, st, b->tree_fs, d.red, d.red + b->ssz, d.ld, d,
-                       b->fin_pending ? 1 : 0, b->fin_radius, b->fin_lo, b->fin_hi, b->world, epoch, 0, 1 << 30, b->red_alt,
-                       (long long)nz, zwg);
-    nl = 1;
-  }
-  if (zwg) b->alt_clean = true;
-  b->fin_pending = false;
-  hipLaunchKernelGGL(front_down, dim3(b->tree_fs.n_fronts), dim3(FD_THREADS), 0, st, b->tree_fs, d, b->d_cam_used, b->rank, epoch, b->solve_cand ? 1 : 0);
+  for (int l = top; l >= (by_level ? 0 : top); --l, ++nl)
+    hipLaunchKernelGGL(front_up, dim3(l == top ? grid : nF), dim3(FR_WAVES * 64), FR_LDS_BYTES, st, b->tree.fs, d.red, d.red + b->ssz,
+                       d.ld, d, r.pending ? 1 : 0, r.radius, r.lm_lo, r.lm_hi, b->world, epoch, by_level ? l : 0, by_level ? l : 1 << 30,
+                       r.alt, (long long)redl::count_without_X(b->ld), l == top ? zwg : 0);
+  r.taken(zwg);
+  hipLaunchKernelGGL(front_down, dim3(b->tree.fs.n_fronts), dim3(FD_THREADS), 0, st, b->tree.fs, d, b->d_cam_used, b->rank, epoch, cand ? 1 : 0);
   SFM_HIP_TRY(hipGetLastError());
   b->launches += nl + 1;
   return SFMHIP_OK;
 }
 
-static int ba_reduced_solve_nd(sfmhip_ba* b) {
-  if (b->tree_on) return ba_reduced_solve_tree(b);
+static int ba_reduced_solve_chains(sfmhip_ba* b) {
   const bool dbg = getenv("SFMHIP_BA_ND_DEBUG") != nullptr;
   hipStream_t st = b->ctx->stream;
   BaDev& d = b->d;
-  const NdSet& ns = b->nd;
+  const NdSet& ns = b->chains.set;
   const int P = ns.n;
   const NdChain& sp = ns.c[P];
-  if (!b->chol_chains_attr_set) {
-    SFM_HIP_TRY(hipFuncSetAttribute((const void*)chol_step2_chains, hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS_BYTES));
-    SFM_HIP_TRY(hipFuncSetAttribute((const void*)chol_step2, hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS_BYTES));
-    b->chol_chains_attr_set = true;
-  }
-  const size_t nz = b->red_count - b->ssz;
-  const int zwg = ba_zero_wgs(b, nz);
+  Riders& r = b->riders;
+  const int zwg = ba_zero_wgs(b);
   if (zwg < 0) return zwg;
-  hipLaunchKernelGGL(nd_gather, dim3(b->nd_n_gather + zwg), dim3(256), 0, st, ns, b->nd_gather_jobs, b->nd_n_gather, d.red,
-                     d.red + b->ssz, d.ld, d, b->fin_pending ? 1 : 0, b->fin_radius, b->fin_lo, b->fin_hi, b->world, b->red_alt,
-                     (long long)nz);
-  if (zwg) b->alt_clean = true;
-  b->fin_pending = false;
+  hipLaunchKernelGGL(nd_gather, dim3(b->chains.n_jobs + zwg), dim3(256), 0, st, ns, b->chains.jobs, b->chains.n_jobs, d.red,
+                     d.red + b->ssz, d.ld, d, r.pending ? 1 : 0, r.radius, r.lm_lo, r.lm_hi, b->world, r.alt,
+                     (long long)redl::count_without_X(b->ld));
+  r.taken(zwg);
   int nl = 1;
   if (dbg) nd_census(b, "gather");
-  for (int k2 = 0; 2 * k2 < b->nd_max_ni; ++k2, ++nl) {
+  for (int k2 = 0; 2 * k2 < b->chains.max_ni; ++k2, ++nl) {
     int c_nt[cplan::CP_MAX], c_ni[cplan::CP_MAX];
     for (int i = 0; i < P; ++i) c_nt[i] = ns.c[i].N, c_ni[i] = ns.c[i].ni;
     const c2plan::ChainLaunch cl = c2plan::pack_chains(P, c_nt, c_ni, k2, b->ctx->n_cu);
@@ -4693,38 +4658,31 @@ static int ba_reduced_solve_nd(sfmhip_ba* b) {
   }
   // z_S = L_SS^-T y_S;  w_i = y_i - L_Si^T z_S;  z_i = L_ii^-T w_i
   hipLaunchKernelGGL(nd_xy, dim3(sp.N, 1), dim3(1024), 0, st, ns, P, d.z);
-  hipLaunchKernelGGL(nd_w, dim3((b->nd_cols.col0[P] + 3) / 4), dim3(256), 0, st, ns, b->nd_cols);
-  hipLaunchKernelGGL(nd_xy, dim3(b->nd_max_ni, P), dim3(1024), 0, st, ns, 0, d.z);
+  hipLaunchKernelGGL(nd_w, dim3((b->chains.cols.col0[P] + 3) / 4), dim3(256), 0, st, ns, b->chains.cols);
+  hipLaunchKernelGGL(nd_xy, dim3(b->chains.max_ni, P), dim3(1024), 0, st, ns, 0, d.z);
   SFM_HIP_TRY(hipGetLastError());
   b->launches += nl + 3;
   return SFMHIP_OK;
 }
 
-static int ba_reduced_solve(sfmhip_ba* b) {
-  if (b->nd_on) return ba_reduced_solve_nd(b);
+static int ba_reduced_solve_dense(sfmhip_ba* b) {
   hipStream_t st = b->ctx->stream;
   BaDev& d = b->d;
   double* A = d.red;
   double* y = d.red + b->ssz;  // g becomes y = L^-1 g
   const int nt = b->ld / CB;
-  // (once per problem object, not once per process: the attribute belongs to the device's code object,
-  // and contexts on several devices may share a process)
-  if (!b->chol_attr_set) {
-    SFM_HIP_TRY(hipFuncSetAttribute((const void*)chol_step2, hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS_BYTES));
-    b->chol_attr_set = true;
-  }
-  for (const c2plan::Launch& L : b->dense_sched)
+  for (const c2plan::Launch& L : b->dense.sched)
     hipLaunchKernelGGL(chol_step2, dim3(L.grid), dim3(C2_WAVES * 64), C2_LDS_BYTES, st, A, y, d.xinv, d.ld, nt, L.k2, L.tpw, d.info,
                        L.xb, L.dfr, L.catchup);
-  const int nchol = (int)b->dense_sched.size();
+  const int nchol = (int)b->dense.sched.size();
   int nbs = 1;
-  if (b->dense_xb) {
+  if (b->dense.xb) {
     // z block by block from the last (chol_back_block)
-    const int xb = b->dense_xb, nB = (nt + xb - 1) / xb;
+    const int xb = b->dense.xb, nB = (nt + xb - 1) / xb;
     const size_t pn = (size_t)DENSE_XB * DENSE_XB * CB;
     for (int K = nB - 1; K >= -1; --K)
       hipLaunchKernelGGL(chol_back_block, dim3(K < 0 ? 1 : K == nB - 1 ? nt - K * xb : (K + 1) * xb), dim3(256), 0, st, A, d.xinv, y, d.z,
-                         d.ld, nt, xb, K, b->d_back_part + ((K + 1) & 1) * pn, b->d_back_part + (K & 1) * pn);
+                         d.ld, nt, xb, K, b->dense.d_back_part + ((K + 1) & 1) * pn, b->dense.d_back_part + (K & 1) * pn);
     nbs = nB + 1;
   } else {
     // z = L^-T y = X y
@@ -4733,6 +4691,15 @@ static int ba_reduced_solve(sfmhip_ba* b) {
   SFM_HIP_TRY(hipGetLastError());
   b->launches += nchol + nbs;
   return SFMHIP_OK;
+}
+
+// cand: the front tree's down-sweep also leaves the candidate cameras and their tables (an LM iteration's solve)
+static int ba_reduced_solve(sfmhip_ba* b, bool cand) {
+  switch (b->route) {
+    case Route::Tree: return ba_reduced_solve_tree(b, cand);
+    case Route::Chains: return ba_reduced_solve_chains(b);
+    default: return ba_reduced_solve_dense(b);
+  }
 }
 
 // (no point carries an observation: the step evaluation has no kernel of its own, the camera parts are still summed -- and the
@@ -4764,7 +4731,7 @@ static StepLayout ba_step_layout(sfmhip_ba* b) {
   const size_t nblk = ((size_t)L.npl + 63) / 64;  // blocks of 64 points
   L.n_bs_wg = L.npl <= 0 ? 0 : (int)((nblk + 4 / BS_WPP - 1) / (4 / BS_WPP));
   b->d.step_total = std::max(1, L.n_runs_wg + L.n_bs_wg);
-  b->d.cam_parts = b->tree_on ? b->tree_fs.n_fronts : (b->nc + 1 + 63) / 64;
+  b->d.cam_parts = b->route == Route::Tree ? b->tree.fs.n_fronts : (b->nc + 1 + 63) / 64;
   L.fits = 4 * (size_t)b->d.step_total + 2 * (size_t)b->d.cam_parts <= b->step_part_n;
   return L;
 }
@@ -4780,7 +4747,7 @@ static int ba_step_eval(sfmhip_ba* b, double radius, const sfmhip_ba_opts* o) {
   // rank; else by ba_decide behind the all-reduce)
   d.decide_here = d.lm && b->world == 1 && npl <= 0 ? 1 : 0;
   if (!L.fits) return SFMHIP_ERR_STATE;
-  if (!b->tree_on) hipLaunchKernelGGL(ba_cand_cams, dim3((b->nc + 1 + 63) / 64), dim3(64), 0, st, d, b->d_cam_used, b->rank);
+  if (b->route != Route::Tree) hipLaunchKernelGGL(ba_cand_cams, dim3((b->nc + 1 + 63) / 64), dim3(64), 0, st, d, b->d_cam_used, b->rank);
   int nbs = 0;
   if (runs) {
     d.step_last = npl > 0 ? 0 : 1;
@@ -4798,7 +4765,7 @@ static int ba_step_eval(sfmhip_ba* b, double radius, const sfmhip_ba_opts* o) {
     ++nbs;
   }
   SFM_HIP_TRY(hipGetLastError());
-  b->launches += (b->tree_on ? 0 : 1) + nbs;
+  b->launches += (b->route == Route::Tree ? 0 : 1) + nbs;
   SFM_TRY(ba_allreduce(b, d.red2, 8));
   if (d.lm && !d.decide_here) {  // (several ranks: every rank takes the same decision from the same all-reduced sums)
     hipLaunchKernelGGL(ba_decide, dim3(1), dim3(64), 0, st, d);
@@ -4825,8 +4792,6 @@ struct IterScalars {
 // go to the host in one piece: a one-workgroup kernel writes them into the pinned buffer and then a
 // sequence number behind them; the host spins on the sequence number.  (A blit + hipStreamSynchronize
 // costs ~15 us more per iteration: copy-kernel launch, completion interrupt, wake-up.)
-constexpr int H_SC_N = SC + 64 + RED2_N;
-static_assert(H_SC_N <= 256, "ba_publish copies one double per thread");
 __global__ __launch_bounds__(256) void ba_publish(const double* __restrict__ src, double* __restrict__ host, double seq) {
   const int i = threadIdx.x;
   if (i < H_SC_N) host[i] = src[i];
@@ -4841,9 +4806,8 @@ __global__ __launch_bounds__(256) void ba_publish(const double* __restrict__ src
 static int ba_read_scalars(sfmhip_ba* b, IterScalars* s, bool with_step) {
   hipStream_t st = b->ctx->stream;
   BaDev& d = b->d;
-  const size_t sc_off = b->ssz + 3 * (size_t)b->ld;
   b->h_seq += 1.0;
-  hipLaunchKernelGGL(ba_publish, dim3(1), dim3(256), 0, st, d.red + sc_off, b->h_sc_dev, b->h_seq);
+  hipLaunchKernelGGL(ba_publish, dim3(1), dim3(256), 0, st, d.red + redl::sc(b->ld), b->h_sc_dev, b->h_seq);
   SFM_HIP_TRY(hipGetLastError());
   {
     volatile double* flag = b->h_sc + H_SC_N;
@@ -4865,7 +4829,7 @@ static int ba_read_scalars(sfmhip_ba* b, IterScalars* s, bool with_step) {
   s->nfail = b->h_sc[2];
   s->gmax = b->h_sc[3];
   if (with_step) {
-    const double* step = b->h_sc + SC + 64;  // (red2[0..3]: the totals step_finish left, all-reduced)
+    const double* step = b->h_sc + (redl::red2(b->ld) - redl::sc(b->ld));  // (red2[0..3]: the totals step_finish left, all-reduced)
     s->cost_c = 0.5 * step[0];
     s->mcc = -step[1];
     s->step_n2 = step[2];
@@ -4903,7 +4867,7 @@ static int ba_begin(sfmhip_ba* b, const sfmhip_ba_opts* o) {
   SFM_HIP_TRY(hipSetDevice(b->ctx->device));
   for (double& t : b->t_acc) t = 0;
   b->launches = 0;
-  if (!b->nd_ready) SFM_TRY(ba_nd_build(b));
+  if (!b->route_ready) SFM_TRY(ba_nd_build(b));
   SFM_TRY(ba_prepare_scale(b, o->jacobi_scaling));
   b->lm = LmState();
   LmDev& s = b->lm.s;
@@ -4939,10 +4903,7 @@ static void lm_log(const sfmhip_ba* b, const LmDev& r) {
 // the linearisation at the current x with the current radius, if the reduced-system buffer does not hold it
 static int ba_ensure_lin(sfmhip_ba* b, const sfmhip_ba_opts* o) {
   if (b->lm.have_lin) return SFMHIP_OK;
-  b->defer_fin = true;  // (the dissected solve follows: its gather does ba_finalize's part)
-  const int rc = ba_linearize_eliminate(b, b->lm.s.radius, o, true);
-  b->defer_fin = false;
-  SFM_TRY(rc);
+  SFM_TRY(ba_linearize_eliminate(b, b->lm.s.radius, o, true, true));
   b->lm.have_lin = true;
   return SFMHIP_OK;
 }
@@ -4953,11 +4914,8 @@ static int ba_enqueue_body(sfmhip_ba* b, const sfmhip_ba_opts* o) {
   hipStream_t st = b->ctx->stream;
   SFM_TRY(ba_ensure_lin(b, o));
   b->lm.have_lin = false;
-  b->solve_cand = true;  // (the front tree's down-sweep leaves the candidate cameras and their tables)
-  if (!ba_step_layout(b).fits) return SFMHIP_ERR_STATE;  // (... and the camera parts of the step's norms, in the slots behind the step evaluation's)
-  const int rc_solve = ba_reduced_solve(b);
-  b->solve_cand = false;
-  SFM_TRY(rc_solve);
+  if (!ba_step_layout(b).fits) return SFMHIP_ERR_STATE;  // (the tree's down-sweep writes the camera parts of the step's norms behind the step evaluation's slots)
+  SFM_TRY(ba_reduced_solve(b, true));
   if (b->ctx->timing) {
     SFM_HIP_TRY(hipEventRecord(b->ev[3], st));
     b->ev_on[3] = true;
@@ -5001,8 +4959,8 @@ static int ba_handle_timeout(sfmhip_ba* b, int info) {
     SFM_HIP_TRY(hipStreamSynchronize(b->ctx->stream));  // (pend leaves scope; a time-out is no hot path)
   }
   if (info == INFO_FINISHER_TIMEOUT) return SFMHIP_ERR_TIMEOUT;  // (not a hand-off between fronts: one launch per level would not cure it)
-  if (b->tree_on && !b->tree_by_level) {
-    b->tree_by_level = true;
+  if (b->route == Route::Tree && !b->tree.by_level) {
+    b->tree.by_level = true;
     return SFMHIP_OK;
   }
   return SFMHIP_ERR_TIMEOUT;
@@ -5090,7 +5048,7 @@ static int ba_lm_loop(sfmhip_ba* b, const sfmhip_ba_opts* o, int iters, const st
     int B = batch_env ? batch_env : t_only ? 20 : 4;
     if (t_only) B = std::min(B, iters - done);
     else B = std::max(1, std::min(B, s.max_iter - s.iter));
-    const unsigned seq0 = b->lm_seq, epoch0 = b->tree_epoch;
+    const unsigned seq0 = b->lm_seq, epoch0 = b->tree.epoch;
     for (int i = 0; i < B && rc == SFMHIP_OK; ++i) {
       rc = ba_enqueue_body(b, o);
       if (rc == SFMHIP_OK && (i == B - 1 || o->verbose)) hipLaunchKernelGGL(ba_lm_publish, dim3(1), dim3(64), 0, st, b->d);
@@ -5108,9 +5066,8 @@ static int ba_lm_loop(sfmhip_ba* b, const sfmhip_ba_opts* o, int iters, const st
       // the last solve that ran (the down-sweep's mailbox alternates by epoch).
       const int ran = (int)(s.stop_seq - seq0);
       b->lm.have_lin = false;
-      b->alt_clean = false;
-      b->fin_pending = false;
-      if (b->tree_on) b->tree_epoch = epoch0 + (unsigned)ran;
+      b->riders.forget();
+      if (b->route == Route::Tree) b->tree.epoch = epoch0 + (unsigned)ran;
       if (s.stop == LM_STOP_TIMEOUT) {
         if ((rc = ba_handle_timeout(b, s.log_info)) != SFMHIP_OK) break;
         done -= B - ran + 1;  // (the solve that timed out is repeated)
@@ -5309,7 +5266,7 @@ extern "C" int sfmhip_ba_reduced_system(sfmhip_ba* b, double radius, double* S, 
   }
   if (g) SFM_HIP_TRY(hipMemcpyAsync(g, b->d.red + b->ssz, sizeof(double) * n, hipMemcpyDeviceToHost, st));
   double sc0 = 0;
-  SFM_HIP_TRY(hipMemcpyAsync(&sc0, b->d.red + b->ssz + 3 * (size_t)b->ld, sizeof(double), hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipMemcpyAsync(&sc0, b->d.red + redl::sc(b->ld), sizeof(double), hipMemcpyDeviceToHost, st));
   SFM_HIP_TRY(hipStreamSynchronize(st));
   if (S)
     for (int i = 0; i < n; ++i)
@@ -5324,12 +5281,12 @@ extern "C" int sfmhip_ba_reduced_step(sfmhip_ba* b, double radius, double* z, in
   SFM_HIP_TRY(hipSetDevice(b->ctx->device));
   sfmhip_ba_opts o;
   sfmhip_ba_default_opts(&o);
-  if (!b->nd_ready) SFM_TRY(ba_nd_build(b));
+  if (!b->route_ready) SFM_TRY(ba_nd_build(b));
   if (!b->scale_ready) SFM_TRY(ba_prepare_scale(b, o.jacobi_scaling));
   SFM_TRY(ba_flush_lin(b, &o));  // (as in sfmhip_ba_reduced_system: the hook's system is not the LM loop's)
   b->lm.have_lin = false;
   SFM_TRY(ba_linearize_eliminate(b, radius, &o, true));
-  SFM_TRY(ba_reduced_solve(b));
+  SFM_TRY(ba_reduced_solve(b, false));
   hipStream_t st = b->ctx->stream;
   int info = 0;
   SFM_HIP_TRY(hipMemcpyAsync(z, b->d.z, sizeof(double) * b->dim, hipMemcpyDeviceToHost, st));
@@ -5341,20 +5298,20 @@ extern "C" int sfmhip_ba_reduced_step(sfmhip_ba* b, double radius, double* z, in
 
 extern "C" int sfmhip_ba_reduced_layout(sfmhip_ba* b, int32_t layout[4]) {
   if (!b || !layout) return SFMHIP_ERR_ARG;
-  const bool chains = b->nd_on && !b->tree_on;
-  layout[0] = chains ? b->nd.n : 0;
-  layout[1] = chains ? b->nd_max_ni : 0;
-  layout[2] = chains ? b->nd.c[b->nd.n].N : 0;
-  layout[3] = b->nd_ready ? b->ld / CB : 0;
+  const bool chains = b->route == Route::Chains;
+  layout[0] = chains ? b->chains.set.n : 0;
+  layout[1] = chains ? b->chains.max_ni : 0;
+  layout[2] = chains ? b->chains.set.c[b->chains.set.n].N : 0;
+  layout[3] = b->route_ready ? b->ld / CB : 0;
   return SFMHIP_OK;
 }
 
 extern "C" int sfmhip_ba_reduced_tree(sfmhip_ba* b, int32_t tree[4]) {
   if (!b || !tree) return SFMHIP_ERR_ARG;
-  tree[0] = b->tree_on ? b->tree_fs.n_fronts : 0;
-  tree[1] = b->tree_on ? b->tree_levels : 0;
-  tree[2] = b->tree_on ? b->tree_chain_tiles : 0;
-  tree[3] = b->tree_on ? b->tree_max_T : 0;
+  tree[0] = b->route == Route::Tree ? b->tree.fs.n_fronts : 0;
+  tree[1] = b->route == Route::Tree ? b->tree.levels : 0;
+  tree[2] = b->route == Route::Tree ? b->tree.chain_tiles : 0;
+  tree[3] = b->route == Route::Tree ? b->tree.max_T : 0;
   return SFMHIP_OK;
 }
 
@@ -5484,7 +5441,7 @@ extern "C" int sfmhip_ba_solve(sfmhip_ctx* ctx, int n_cam, int n_pt, int n_obs, 
   pr.set_params_ms = lap();
   if (rc == SFMHIP_OK) rc = sfmhip_ba_run(b, opts, summary);
   pr.run_ms = lap();
-  pr.front_plan_reused = b && !pr.plan_reused && b->nd_kept ? 1 : 0;
+  pr.front_plan_reused = b && !pr.plan_reused && b->tree.plan_kept ? 1 : 0;
   if (rc == SFMHIP_OK) rc = sfmhip_ba_get_params(b, cams6, pts3, focal);
   pr.get_params_ms = lap();
   if (b && !pr.plan_reused) ctx->ba_arena_need = std::max(ctx->ba_arena_need, b->arena_need);

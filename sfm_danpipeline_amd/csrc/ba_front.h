@@ -528,32 +528,8 @@ __global__ __launch_bounds__(FR_WAVES * 64) void front_up(FrontSet fs, const dou
     const int b = (int)blockIdx.x;
     if (b >= nF) {
       const int zi = b - nF;
-      if (zi < n_zero) {
-        const long long lo = (long long)zi * ND_ZERO_SLICE;
-        double2* p2 = (double2*)(zero_ptr + lo);
-        const long long n2 = (zero_n - lo < ND_ZERO_SLICE ? zero_n - lo : ND_ZERO_SLICE) / 2;
-        for (long long i = threadIdx.x; i < n2; i += FR_WAVES * 64) p2[i] = make_double2(0.0, 0.0);
-      } else if (zi == n_zero && fin) {
-        __shared__ double shm[FR_WAVES];
-        const double* gF = red_gF(d);
-        const double* dc = red_dc(d);
-        double* scv = red_sc(d);
-        double gm = 0;
-        for (int i = threadIdx.x; i < d.dim; i += FR_WAVES * 64) {
-          d.diag[i] = fmin(fmax(dc[i], lm_lo), lm_hi);
-          const double sc = i < 6 * d.nc ? d.scale_c[i] : *d.scale_f;
-          gm = fmax(gm, fabs(gF[i] / sc));
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) gm = fmax(gm, __shfl_down(gm, o));
-        if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = gm;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-          for (int w = 1; w < FR_WAVES; ++w) gm = fmax(gm, shm[w]);
-          for (int r = 0; r < world; ++r) gm = fmax(gm, scv[SC + r]);
-          scv[3] = gm;
-        }
-      }
+      if (zi < n_zero) rider_zero_slice<FR_WAVES * 64>(zero_ptr, zero_n, zi);
+      else if (zi == n_zero && fin) rider_bookkeeping<FR_WAVES * 64, false>(d, lm_lo, lm_hi, world);
       return;
     }
   }

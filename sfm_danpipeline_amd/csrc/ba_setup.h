@@ -17,6 +17,7 @@
 #include <vector>
 #include <unistd.h>
 #include "../../include/sfmhip.h"
+#include "ba_red_layout.h"
 
 namespace bsetup {
 
@@ -25,7 +26,6 @@ constexpr int SHORT_RUN = 12;  // runs of at most this many points go to the pai
 // a chunk's slab: [Gram block, MFMA layout, NT x 256 <= 2560 | F^T F sums 36 x FP | Jf^2, Jf r, r^2 | gmax | nfail]
 constexpr int ELIM_SLAB_FF = 2560, ELIM_SLAB = 2944;
 constexpr int FP = 10;  // slots per row of the F^T F accumulators in LDS (the MFMA path takes signatures of n <= 10 cameras)
-constexpr int SC = 16;  // scalar slots at the tail of the all-reduce buffer (+ world)
 
 // the layouts of HIP's int2 / int4 (ba.hip asserts it): the lists below go to the device in one copy each
 struct I2 {
@@ -546,7 +546,7 @@ inline int build(const Input& in, Scratch& hs, Setup& out) {
   }
   if (out.elim_deterministic && !chunks.empty()) {
     const int ld = in.ld, fo = 6 * n_cam;
-    const long long ssz = (long long)ld * ld, o_g = ssz, o_gF = ssz + ld, o_dc = ssz + 2LL * ld, o_sc = ssz + 3LL * ld;
+    const long long o_g = (long long)redl::g(ld), o_gF = (long long)redl::gF(ld), o_dc = (long long)redl::dc(ld), o_sc = (long long)redl::sc(ld);
     std::vector<std::pair<long long, unsigned>> ent[2];  // (destination, source | sign)
     // rows of S by their own kernel role while a wave's accumulator fits the default LDS limit (until round 6 the accumulator was
     // a whole row, ld entries zeroed and scanned whatever the row held: at 640 cameras that outweighed what the row-wise reads
@@ -695,7 +695,7 @@ inline int build(const Input& in, Scratch& hs, Setup& out) {
       }
     }
     for (int m = 0; m < 2; ++m) {
-      const size_t range = (size_t)(o_sc + SC + 64) + 2;   // destinations + the GMAX key shifted to 0
+      const size_t range = redl::red2(ld) + 2;   // destinations + the GMAX key shifted to 0
       if (ent[m].size() * 16 < range) {
         // few entries for the range (the row lists carry S: what is left are the diagonal's entries): a stable sort of the
         // entries instead of three passes over ld^2 counters (cfg4: 31 k entries, 1.5 M destinations)

@@ -841,21 +841,30 @@ def test_front_tree_under_real_contention_walks_the_same_bits(ctx):
     ctx2.close()
 
 
-def test_second_reduced_system_buffer_changes_nothing(ctx, monkeypatch):
-    """The dissected solve's gather zeroes a second [S | g | ...] buffer on the side and the next linearisation swaps the two
-    instead of filling one (SFMHIP_BA_PREZERO=0: a memset per linearisation): the same systems bit for bit, the same LM run --
-    through accepted and rejected steps, a parameter reset in between, and a look at the reduced system afterwards"""
-    pb = synth.ba_problem(80, 40000, 10, seed=23)
+@pytest.mark.parametrize("nd,shape,seed", [(None, (80, 40000, 10), 23), ("1", (96, 6000, 6), 5)], ids=["tree", "chains"])
+def test_second_reduced_system_buffer_changes_nothing(ctx, monkeypatch, nd, shape, seed):
+    """The first launch of a chains or tree solve zeroes a second [S | g | ...] buffer on the side and the next linearisation swaps
+    the two instead of filling one (SFMHIP_BA_PREZERO=0: a memset per linearisation): the same systems bit for bit, the same LM
+    run -- through accepted and rejected steps, a parameter reset in between, and a look at the reduced system afterwards.  On the
+    default route (the front tree: front_up's spare workgroups) and on chains + separator (SFMHIP_BA_ND=1: nd_gather's)"""
+    if nd is None:
+        monkeypatch.delenv("SFMHIP_BA_ND", raising=False)
+    else:
+        monkeypatch.setenv("SFMHIP_BA_ND", nd)                # read when the problem plans its first solve
+    nc, npt, k = shape
+    pb = synth.ba_problem(nc, npt, k, seed=seed)
     monkeypatch.delenv("SFMHIP_BA_PREZERO", raising=False)
-    a = bundle.BaProblem(80, 40000, pb["obs_cam"], pb["obs_pt"], pb["obs_xy"], ctx=ctx)
+    a = bundle.BaProblem(nc, npt, pb["obs_cam"], pb["obs_pt"], pb["obs_xy"], ctx=ctx)
     monkeypatch.setenv("SFMHIP_BA_PREZERO", "0")
-    b = bundle.BaProblem(80, 40000, pb["obs_cam"], pb["obs_pt"], pb["obs_xy"], ctx=ctx)
+    b = bundle.BaProblem(nc, npt, pb["obs_cam"], pb["obs_pt"], pb["obs_xy"], ctx=ctx)
     monkeypatch.delenv("SFMHIP_BA_PREZERO")
     for prob in (a, b):
         prob.set_params(pb["cams0"], pb["pts0"], pb["focal0"])
     sa, sb = a.iterate(9), b.iterate(9)
     assert 0 < sa.successful_steps and (sa.successful_steps, sa.iterations) == (sb.successful_steps, sb.iterations)
     assert abs(sa.final_cost - sb.final_cost) <= 1e-12 * sb.final_cost
+    if nd == "1":
+        assert a.reduced_layout()["chains"] >= 2 and b.reduced_layout()["chains"] >= 2
     for prob in (a, b):                                # a new start on the same objects
         prob.set_params(pb["cams0"], pb["pts0"], pb["focal0"])
     sa, sb = a.iterate(4), b.iterate(4)
