@@ -516,6 +516,74 @@ int sfmhip_cloud_dendro_profile(sfmhip_cloud* cloud, const int32_t* labels, int3
  * each); without it their device time shows in the refit's figure. */
 int sfmhip_cloud_dendro_last_timing(sfmhip_cloud* cloud, double ms6[6]);
 
+/* ---- the ground plane: the vertical frame the dendrometry needs ----
+ * A structure-from-motion cloud stands in the first camera's frame: gravity points anywhere and the lowest point along z is
+ * no ground.  This call finds the dominant ground plane of the cloud by RANSAC, refits it and orients it so that the trees
+ * stand on it; sfmhip_dendro_opts_from_ground hands it to the dendrometry as up, north and ground.  Metric scale cannot
+ * come from the cloud: it stays the caller's `scale`.  The arithmetic is csrc/ground.h (compiled by g++ and hipcc without
+ * contraction; the device equals the host build bit for bit).  The rules:
+ *  1 selection: the finite points (with labels: those with labels[i] == label), listed in ascending input index (flag, the
+ *    handle's scan, emit).  Fewer than 3: status OK, flag bit 0, every double NaN, winner -1.  SFMHIP_ERR_ARG: ransac_iters
+ *    outside 1..4096, a negative or non-finite inlier_tol / inlier_rel, below_max outside [0, 1], a non-finite hint,
+ *    max_tilt_deg outside (0, 180], refit_rounds outside 0..8, min_inliers < 3, n_cam < 0, n_cam > 0 without centres.
+ *    An up_hint of length 0 is no hint; otherwise it is normalised once, hint / sqrt(hint . hint).
+ *  2 tolerance: tol = inlier_tol if > 0, else inlier_rel sqrt((dx dx + dy dy) + dz dz) with d = (f64)max - (f64)min of the
+ *    selection's float32 bounding box.
+ *  3 hypothesis j draws three positions of the list, (u64(hash(seed, 0x67726E64, j, draw)) n_sel) >> 32 with f-11 rule 5's
+ *    hash (csrc/draw_hash.h); a repeated position skips the iteration.  With the points a, b, c: u = b - a, v = c - a in f64,
+ *    m = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0), mm = (m0 m0 + m1 m1) + m2 m2; skipped when mm is 0 or not finite;
+ *    n = m / sqrt(mm).  With a hint: skipped when |(n0 h0 + n1 h1) + n2 h2| < cos(max_tilt_deg pi / 180) (the host's cos, once).
+ *  4 score, all integers: for every point of the list s = (n0 (x - a0) + n1 (y - a1)) + n2 (z - a2) in f64; inliers count
+ *    |s| <= tol, pos counts s > tol, neg counts s < -tol.
+ *  5 orientation: with camera centres, s as in rule 4: more centres with s > 0 than with s < 0 keeps n, fewer flips it, a tie
+ *    falls through; then pos > neg keeps n, pos < neg flips it; still tied, the sign that makes the first non-zero
+ *    component of n positive.  below = the count (pos or neg) on the side the oriented normal points away from.
+ *  6 winner: admissible iff inliers >= min_inliers and below <= floor(below_max n_sel) (f64 product); the winner holds the
+ *    largest 64-bit key inliers << 32 | (4095 - j).  None admissible: flag bit 1, NaN outputs (tol and n_selected stay),
+ *    winner -1.
+ *  7 refit, refit_rounds times: the inliers of the current plane; their centroid (three sums / N), then the six sums of
+ *    products of (p - centroid) in f64, each / N: the 3 x 3 covariance.  The normal is the third row of Vt of csrc/jacobi.h's
+ *    jacobi_svd<3, 3, 3, 3> on it, divided by its length, its sign flipped when its dot with the previous normal is < 0;
+ *    the plane passes through the centroid.  Each sum: the point at list position i adds to slot i mod 256 in ascending i,
+ *    non-inliers add nothing; four 64-entry trees with strides 32..1, then (w0 + w1) + (w2 + w3) (f-11 rule 6).  A round with
+ *    fewer than 3 inliers or a non-finite normal or centroid keeps the previous plane and sets flag bit 2.  The
+ *    orientation of rule 5 is decided once, on the winner, and every refit carries it.  inliers, above (s > tol), below
+ *    (s < -tol) and rms = sqrt(sum of s s over the inliers / inliers) are those of the final plane, counted once more.
+ *  8 frame: up = the final normal; offset = (up0 a0 + up1 a1) + up2 a2 with a the centroid (the winner's first point when
+ *    refit_rounds is 0).  north = h - (h . up) up, normalised, with h = north_hint / |north_hint|; when that length is not
+ *    > 1e-6 (or the hint is 0), h is the coordinate axis with the smallest |up| component (the lowest index on a tie) and
+ *    flag bit 3 is set.
+ * What the rules do not do: a scene whose largest plane is a wall at the edge of the cloud needs camera centres or an
+ * up_hint; sloping ground gives the slope's normal, not gravity; one plane, no terrain. */
+typedef struct sfmhip_ground_opts {
+  double inlier_tol;      /* 0: use inlier_rel; else cloud units */
+  double inlier_rel;      /* 0.005 of the selection's bounding-box diagonal */
+  double below_max;       /* 0.01: share of the selection allowed further than tol on the far side of the plane */
+  double up_hint[3];      /* (0,0,0): none */
+  double max_tilt_deg;    /* 180: with a hint, hypotheses tilted further from it are skipped */
+  double north_hint[3];   /* (0,1,0) */
+  int32_t ransac_iters;   /* 512; 1 ... 4096 */
+  int32_t min_inliers;    /* 100 */
+  int32_t refit_rounds;   /* 2; 0 ... 8 */
+  uint32_t seed;          /* 1 */
+} sfmhip_ground_opts;
+typedef struct sfmhip_ground_result {
+  double up[3], north[3]; /* unit, north orthogonal to up */
+  double offset;          /* up . p = offset on the plane, cloud units */
+  double rms, tol;        /* of the final plane's inliers; the tolerance used */
+  int32_t n_selected, inliers, below, above, winner /* iteration, -1 none */, flags;
+} sfmhip_ground_result;
+void sfmhip_ground_default_opts(sfmhip_ground_opts* opts);
+/* labels: NULL (every finite point) or n entries; cam_centres: NULL or 3 n_cam doubles in the cloud's frame. */
+int sfmhip_cloud_ground_plane(sfmhip_cloud* cloud, const int32_t* labels, int32_t label, const sfmhip_ground_opts* opts,
+                              const double* cam_centres, int n_cam, sfmhip_ground_result* out);
+/* host only: io->up, io->north and io->ground = offset * io->scale from a result that has a plane (SFMHIP_ERR_ARG otherwise) */
+int sfmhip_dendro_opts_from_ground(const sfmhip_ground_result* ground, sfmhip_dendro_opts* io);
+/* host-clock ms of the last sfmhip_cloud_ground_plane call on the handle: select + bounds + hypotheses, score, pick + refit,
+ * the whole call.  The score is timed apart only under sfmhip_set_timing (a stream synchronisation each side); without it its
+ * device time shows in the refit's figure. */
+int sfmhip_cloud_ground_last_timing(sfmhip_cloud* cloud, double ms4[4]);
+
 /* ---- the second half of create_mesh: Poisson surface reconstruction (reference src/Sfm.cpp:1365-1381) ----
  * pcl::Poisson at depth 7 on the cloud and its flipped normals, as a screened Poisson solve on the same device-resident
  * cloud.  The rules (PCL 1.8.1 parity is UNPINNED -- PCL is absent and its solver is an adaptive octree):

@@ -11,6 +11,7 @@
 #include <thread>
 #include <vector>
 #include "cloud.h"
+#include "draw_hash.h"
 
 #ifdef __HIPCC__
 #define SFM_DND_INLINE __host__ __device__ __forceinline__
@@ -153,24 +154,11 @@ inline int slice_count(float hmax, double h0, double t) {
   return (int)k + 1;
 }
 
-// rule 5, the draw: a counter-based hash of (seed, slice, iteration, draw)
-SFM_DND_INLINE uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
-SFM_DND_INLINE uint32_t draw_hash(uint32_t seed, uint32_t k, uint32_t j, uint32_t d) {
-  uint32_t x = mix32(seed + 0x9E3779B9u);
-  x = mix32(x ^ k);
-  x = mix32((x + 0x85EBCA6Bu) ^ j);
-  x = mix32((x + 0xC2B2AE35u) ^ d);
-  return x;
-}
+// rule 5, the draw: draw_hash.h's counter-based hash of (seed, slice, iteration, draw)
+using sfmdraw::draw_hash;
+using sfmdraw::mix32;
 SFM_DND_INLINE int draw_index(uint32_t seed, int k, int j, int d, int nk) {
-  return (int)(((uint64_t)draw_hash(seed, (uint32_t)k, (uint32_t)j, (uint32_t)d) * (uint64_t)(uint32_t)nk) >> 32);
+  return (int)sfmdraw::draw_index(seed, (uint32_t)k, (uint32_t)j, (uint32_t)d, (uint32_t)nk);
 }
 
 // rule 5, the model: the circumcircle of three points relative to the first

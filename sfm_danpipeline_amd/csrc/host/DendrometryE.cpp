@@ -1,6 +1,7 @@
 // DendrometryE.cpp -- Dendrometry::estimate (reference src/DendrometryE.cpp:3-29) in the host mirror: the bounds of the
 // cloud on the device (sfmhip_cloud_minmax) and the reference's printed lines, the empty ones included; measure() and
-// estimateTree() fill them (one sfmhip_cloud_dendro_profile call: the scalars and the stem table).
+// estimateTree() fill them (one sfmhip_cloud_dendro_profile call: the scalars and the stem table); findGround() and the
+// levelling overloads put sfmhip_cloud_ground_plane in front of them.
 #include "DendrometryE.h"
 #include <cstdio>
 #include <cstdlib>
@@ -94,4 +95,56 @@ int Dendrometry::estimateTree(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, 
   std::cout << "************************************************" << std::endl;
   std::cout << "************************************************" << std::endl;
   return rc;
+}
+
+int Dendrometry::findGround(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const double* cam_centres,
+                            int n_cam, const sfmhip_ground_opts* opts) {
+  sfmhip_ground_opts o;
+  if (opts)
+    o = *opts;
+  else
+    sfmhip_ground_default_opts(&o);
+  const int n = (int)cloudPCL->size();
+  std::vector<float> xyz((size_t)3 * n + 3);
+  for (int i = 0; i < n; ++i) {
+    xyz[3 * (size_t)i] = cloudPCL->points[i].x;
+    xyz[3 * (size_t)i + 1] = cloudPCL->points[i].y;
+    xyz[3 * (size_t)i + 2] = cloudPCL->points[i].z;
+  }
+  sfmhip_cloud* dev = nullptr;
+  int rc = sfmhip_cloud_create(sfm_hip_context(), n, xyz.data(), &dev);
+  if (rc != SFMHIP_OK) return rc;
+  rc = sfmhip_cloud_ground_plane(dev, labels, label, &o, cam_centres, n_cam, &ground_);
+  sfmhip_cloud_destroy(dev);
+  return rc;
+}
+
+// the options of a levelled call: `opts` (or the defaults) with the frame of the ground plane found over the whole cloud
+static int levelled_opts(Dendrometry& d, pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const sfmhip_ground_opts& ground_opts,
+                         const double* cam_centres, int n_cam, const sfmhip_dendro_opts* opts, sfmhip_dendro_opts* out) {
+  if (opts)
+    *out = *opts;
+  else
+    sfmhip_dendro_default_opts(out);
+  const int rc = d.findGround(cloudPCL, nullptr, 0, cam_centres, n_cam, &ground_opts);
+  if (rc != SFMHIP_OK) return rc;
+  return sfmhip_dendro_opts_from_ground(&d.ground(), out);
+}
+
+int Dendrometry::measure(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label,
+                         const sfmhip_ground_opts& ground_opts, const double* cam_centres, int n_cam, const sfmhip_dendro_opts* opts) {
+  sfmhip_dendro_opts o;
+  const int rc = levelled_opts(*this, cloudPCL, ground_opts, cam_centres, n_cam, opts, &o);
+  return rc != SFMHIP_OK ? rc : measure(cloudPCL, labels, label, &o);
+}
+
+int Dendrometry::estimateTree(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label,
+                              const sfmhip_ground_opts& ground_opts, const double* cam_centres, int n_cam, const sfmhip_dendro_opts* opts) {
+  sfmhip_dendro_opts o;
+  const int rc = levelled_opts(*this, cloudPCL, ground_opts, cam_centres, n_cam, opts, &o);
+  if (rc != SFMHIP_OK) {
+    std::fprintf(stderr, "[sfm] sfmhip_cloud_ground_plane: %s\n", sfmhip_error_string(rc));
+    return rc;
+  }
+  return estimateTree(cloudPCL, labels, label, &o);
 }

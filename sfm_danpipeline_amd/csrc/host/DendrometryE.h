@@ -2,6 +2,8 @@
 // sfmhip_cloud_minmax: pcl::getMinMax3D of the dense cloud and "Total Height" = cv::norm(max - min).  The numbers the
 // call prints stay readable afterwards (the reference only prints them).  measure() / estimateTree() are what the
 // reference leaves blank: sfmhip_cloud_dendro_profile on the cloud, or on one cluster of the segmentation.
+// findGround() is the vertical frame they need on a reconstruction's cloud: sfmhip_cloud_ground_plane;
+// the overloads of measure() / estimateTree() that take ground options level first.
 #pragma once
 #include <vector>
 #include "pcllite.h"
@@ -13,6 +15,7 @@ class Dendrometry {
   double height_ = 0;
   sfmhip_dendro_result tree_ = {};
   std::vector<sfmhip_dendro_slice> profile_;
+  sfmhip_ground_result ground_ = {};
 
  public:
   Dendrometry() {}
@@ -29,6 +32,18 @@ class Dendrometry {
   int measure(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_dendro_opts* opts = nullptr);
   // measure(), then the reference's printed block with every blank filled
   int estimateTree(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_dendro_opts* opts = nullptr);
+
+  // the ground plane of the points with labels[i] == label (labels == nullptr: of every finite point); cam_centres: nullptr or
+  // 3 n_cam doubles in the cloud's frame; opts == nullptr: sfmhip_ground_default_opts.  Returns the library's status.
+  int findGround(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const double* cam_centres = nullptr,
+                 int n_cam = 0, const sfmhip_ground_opts* opts = nullptr);
+  // findGround() over every finite point, then measure() / estimateTree() on the cluster with up, north and ground taken
+  // from it (opts' scale and the rest of its fields stay).  SFMHIP_ERR_ARG when no plane was found.
+  int measure(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_ground_opts& ground_opts,
+              const double* cam_centres, int n_cam, const sfmhip_dendro_opts* opts = nullptr);
+  int estimateTree(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_ground_opts& ground_opts,
+                   const double* cam_centres, int n_cam, const sfmhip_dendro_opts* opts = nullptr);
+  const sfmhip_ground_result& ground() const { return ground_; }
 
   const sfmhip_dendro_result& tree() const { return tree_; }
   const std::vector<sfmhip_dendro_slice>& stemProfile() const { return profile_; }

@@ -1,28 +1,40 @@
 // dendro_selftest.cpp -- the measurement the reference's Dendrometry leaves blank, needs the GPU:
-//   dendro_selftest <MAP3D.pcd> <out.bin> [label]
+//   dendro_selftest <MAP3D.pcd> <out.bin> [label] [--level[=inlier_tol]]
 // Without a label: Dendrometry::estimateTree() on every point of the PCD.  With one: the colour segmentation first
-// (Segmentation::color_based_growing_segmentation), then estimateTree() on that cluster.
+// (Segmentation::color_based_growing_segmentation), then estimateTree() on that cluster.  With --level, the ground plane of
+// the whole cloud is found first (Dendrometry::findGround, default options or the given tolerance in cloud units) and the
+// tree is measured in its frame; without it the output is what it always was.
 // out.bin: the sfmhip_dendro_result, i32 slices, then that many sfmhip_dendro_slice rows.
 // Exit 3: the cloud is empty or no cluster came out; 4: the library refused the call.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "DendrometryE.h"
 #include "Segmentation.h"
 
 int main(int argc, char** argv) {
   if (argc < 3) return 2;
+  bool level = false;
+  sfmhip_ground_opts gopts;
+  sfmhip_ground_default_opts(&gopts);
+  if (std::strncmp(argv[argc - 1], "--level", 7) == 0) {
+    level = true;
+    if (argv[argc - 1][7] == '=') gopts.inlier_tol = std::atof(argv[argc - 1] + 8);
+    --argc;
+  }
   Dendrometry den;
   int rc;
   if (argc > 3) {
     Segmentation seg;
     seg.setInputFile(argv[1]);
     if (seg.color_based_growing_segmentation() != 0) return 3;
-    rc = den.estimateTree(seg.cloud(), seg.labels().data(), std::atoi(argv[3]));
+    rc = level ? den.estimateTree(seg.cloud(), seg.labels().data(), std::atoi(argv[3]), gopts, nullptr, 0)
+               : den.estimateTree(seg.cloud(), seg.labels().data(), std::atoi(argv[3]));
   } else {
     pcl::PointCloud<pcl::PointXYZRGB>::Ptr cloud(new pcl::PointCloud<pcl::PointXYZRGB>());
     pcl::io::loadPCDFile(argv[1], *cloud);
     if (cloud->size() <= 0) return 3;
-    rc = den.estimateTree(cloud, nullptr, 0);
+    rc = level ? den.estimateTree(cloud, nullptr, 0, gopts, nullptr, 0) : den.estimateTree(cloud, nullptr, 0);
   }
   if (rc != SFMHIP_OK) return 4;
   FILE* o = fopen(argv[2], "wb");
