@@ -584,6 +584,86 @@ int sfmhip_dendro_opts_from_ground(const sfmhip_ground_result* ground, sfmhip_de
  * device time shows in the refit's figure. */
 int sfmhip_cloud_ground_last_timing(sfmhip_cloud* cloud, double ms4[4]);
 
+/* ---- individual trees: the stems of a plot and every point's tree ----
+ * The dendrometry and the ground plane take `labels, label` to say which points are the tree.  This call makes such labels:
+ * from the levelled cloud it finds the stems in a height band and gives every point above the ground the number of the
+ * tree it belongs to, by shortest paths through the occupied voxels from the stems.  There is no reference
+ * implementation; the contract is this rule list, whose arithmetic is csrc/trees.h (compiled by g++ and hipcc without
+ * contraction).  Every result is an integer, or an f64 expression of integers written in one order, and none depends on
+ * the order of evaluation: the device equals the host build byte for byte.
+ *  1 options: the table below; lengths are metres and are divided by `scale` (metres per cloud unit) once, in f64.  The
+ *    frame and its refusals are f-11 rule 1's (|up| not 1 within 1e-6, north parallel to up, scale not > 0).
+ *    SFMHIP_ERR_ARG also: a non-finite ground; ground_clear < 0; band_lo < ground_clear; band_hi <= band_lo; stem_cell,
+ *    voxel or max_stem_width not > 0 (in metres or in cloud units) or not finite; max_path < 0; min_cell_pts < 1;
+ *    min_stem_pts < 1; max_trees outside 1..4096.
+ *  2 selection and frame: f-11 rules 2 and 3.  Selected: the finite points (with labels_in: those with labels_in[i] ==
+ *    label) whose frame coordinates (e, n, h) = (east.p, north.p, up.p), each (a0 x + a1 y) + a2 z in f64 stored as
+ *    float32, are finite.  h0 = ground / scale.
+ *  3 classes: with d = (f64)h - h0, a selected point is above (the set A) when d >= clear, and in the band (B, a subset
+ *    of A) when lo <= d < hi.  Every point outside A gets tree -1.  A empty: status OK, flag bit 0, n_trees 0, all -1.
+ *    e_min, n_min and the maxima of e, n, h are float32, over A.
+ *  4 stem cells of size c: ix = floor(((f64)e - e_min) / c), iy likewise with n; De = ix of e_max + 1, Dn likewise;
+ *    De Dn > 2^24 (as f64): SFMHIP_ERR_ARG.  A cell is occupied when it holds >= min_cell_pts points of B.  Cell id =
+ *    iy De + ix.
+ *  5 stems: the 8-connected components of the occupied cells; a component's id is its least cell id.  A component is a
+ *    stem when it holds >= min_stem_pts points of B and (ix_max - ix_min + 1) c <= max_stem_width, likewise iy.  Stems are
+ *    numbered 0..T-1 by ascending component id; beyond max_trees the first max_trees are kept and flag bit 2 is set.
+ *    T = 0: flag bit 1, all -1, n_voxels 0.  Centre: with the i64 sums Se = sum count (2 ix + 1), Sn likewise and N = sum
+ *    count over the component's cells, e = e_min + (c (f64)Se) / (f64)(2 N), n likewise;
+ *    foot[a] = (e east[a] + n north[a]) + h0 up[a].
+ *  6 voxels of size v over A: (vx, vy, vz) = floor of ((f64)e - e_min, (f64)n - n_min, (f64)h - h0) / v; the dimensions
+ *    from the maxima; Dx Dy Dz >= 2^31 (as f64): SFMHIP_ERR_ARG (raise `voxel`).  Both caps are checked before any stem is
+ *    looked for.  The graph's nodes are the occupied voxels, its edges the 26-neighbourhood, with integer weights 10 for a
+ *    face step, 14 for an edge step, 17 for a corner step.
+ *  7 seeds: a voxel that holds a point of B whose cell belongs to stem s is a seed of s at cost 0.
+ *  8 labels: cost(v) = the least path weight from any seed; tree(v) = the lowest s among the stems whose seeds reach v at
+ *    that cost; -1 for a voxel no seed reaches and, with max_path > 0, for one whose cost exceeds
+ *    floor(10 (max_path / scale) / v).  This is the unique fixed point of key(v) = min(key(v), key(u) + w) over the edges
+ *    with key = (cost, s) in lexicographic order.
+ *  9 outputs: tree_of[i] = the tree of point i's voxel.  Stem row s: e, n, foot, cell_id (the component id), band_points
+ *    (N), band_cells, points (the points with tree s).  n_labelled counts the points with a tree, max_cost is the largest
+ *    cost of a voxel with a tree.
+ * What the rules do not do: the method is a shortest-path partition of a voxel graph, not a crown model; crowns that
+ * interpenetrate are split where the paths meet; a tree with no stem points in the band (an occluded one) is not found and
+ * its points go to a neighbour or to -1; low vegetation that bridges two stems above ground_clear does not harm the
+ * partition but ends up in somebody's tree. */
+typedef struct sfmhip_trees_opts {
+  double up[3];           /* (0, 0, 1) */
+  double north[3];        /* (0, 1, 0) */
+  double scale;           /* 1: metres per cloud unit */
+  double ground;          /* required: the ground height along up, metres (sfmhip_trees_default_opts leaves NaN) */
+  double ground_clear;    /* 0.3: points lower than this above the ground belong to no tree */
+  double band_lo, band_hi; /* 1.0, 1.6: the band the stems are looked for in */
+  double stem_cell;       /* 0.05 */
+  double max_stem_width;  /* 1.5 */
+  double voxel;           /* 0.15 */
+  double max_path;        /* 0: unlimited */
+  int32_t min_cell_pts;   /* 2 */
+  int32_t min_stem_pts;   /* 30 */
+  int32_t max_trees;      /* 4096; 1 ... 4096 */
+  int32_t pad;
+} sfmhip_trees_opts;
+typedef struct sfmhip_tree_stem { /* cloud units */
+  double e, n;      /* the stem's centre in the frame */
+  double foot[3];   /* ... and on the ground plane, in the cloud's coordinates */
+  int32_t cell_id, band_points, band_cells, points;
+} sfmhip_tree_stem;
+typedef struct sfmhip_trees_result {
+  int32_t n_selected, n_above, n_band, n_trees, n_voxels, n_labelled, max_cost;
+  int32_t flags; /* bit 0 nothing above the clearance, 1 no stem, 2 more stems than max_trees */
+} sfmhip_trees_result;
+void sfmhip_trees_default_opts(sfmhip_trees_opts* opts);
+/* host only: io->up, io->north and io->ground = offset * io->scale from a result that has a plane (SFMHIP_ERR_ARG otherwise) */
+int sfmhip_trees_opts_from_ground(const sfmhip_ground_result* ground, sfmhip_trees_opts* io);
+/* labels_in: NULL (every finite point) or n entries; tree_of: n entries on the host, the layout sfmhip_cloud_dendrometry
+ * takes as labels; out->n_trees stem rows exist, the first min(cap, n_trees) are written. */
+int sfmhip_cloud_trees(sfmhip_cloud* cloud, const int32_t* labels_in, int32_t label, const sfmhip_trees_opts* opts, int32_t* tree_of,
+                       int cap, sfmhip_tree_stem* stems, sfmhip_trees_result* out);
+/* host-clock ms of the last sfmhip_cloud_trees call on the handle: frame + bounds, stems, voxels + neighbours, sweeps, labels,
+ * the whole call; with sweeps not NULL, the sweeps it enqueued (a multiple of 16).  The voxel stage and the sweeps are timed
+ * apart only under sfmhip_set_timing (a stream synchronisation); without it the voxel stage's device time shows in the sweeps'. */
+int sfmhip_cloud_trees_last_timing(sfmhip_cloud* cloud, double ms6[6], int32_t* sweeps);
+
 /* ---- the second half of create_mesh: Poisson surface reconstruction (reference src/Sfm.cpp:1365-1381) ----
  * pcl::Poisson at depth 7 on the cloud and its flipped normals, as a screened Poisson solve on the same device-resident
  * cloud.  The rules (PCL 1.8.1 parity is UNPINNED -- PCL is absent and its solver is an adaptive octree):

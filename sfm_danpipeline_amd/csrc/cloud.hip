@@ -446,6 +446,7 @@ extern "C" void sfmhip_cloud_destroy(sfmhip_cloud* c) {
   if (c->psn && c->psn_free) c->psn_free(c->psn);
   if (c->dnd && c->dnd_free) c->dnd_free(c->dnd);
   if (c->gnd && c->gnd_free) c->gnd_free(c->gnd);
+  if (c->trs && c->trs_free) c->trs_free(c->trs);
   hipFree(c->xyz);
   hipFree(c->tmp);
   for (int b = 0; b < 4; ++b) hipFree(c->ibuf[b]);

@@ -1,6 +1,6 @@
 // cloud_grid.h -- the device-resident cloud (sfmhip_cloud), its uniform grids and the primitives the cloud family shares:
 // cloud.hip (map3D's step 10), segment.hip (the colour region growing after it), poisson.hip (create_mesh), dendro.hip
-// (the dendrometry after the segmentation), ground.hip (the ground plane that gives it its vertical) and, for blocks(), mvs.hip.  The bodies of the host functions declared here (grid builds, the handle's scan and cell sort) live
+// (the dendrometry after the segmentation), ground.hip (the ground plane that gives it its vertical), trees.hip (the trees of a plot) and, for blocks(), mvs.hip.  The bodies of the host functions declared here (grid builds, the handle's scan and cell sort) live
 // in cloud.hip; the device helpers (cell_of, block_bound, row_span, the min / max kernel) are inline.
 //
 // Spatial index: cell coordinates floor((x - lo) / cell) in double, clamped to the grid (a far outlier lands in a
@@ -100,6 +100,8 @@ struct sfmhip_cloud {
   void (*dnd_free)(void*) = nullptr;
   void* gnd = nullptr;           // ground.hip's state on this handle (selection list, hypotheses, counts, stage times), freed with it
   void (*gnd_free)(void*) = nullptr;
+  void* trs = nullptr;           // trees.hip's state on this handle (frame coordinates, cell and voxel tables, keys, stage times), freed with it
+  void (*trs_free)(void*) = nullptr;
 };
 
 namespace sfmgrid {

@@ -1,7 +1,8 @@
 // DendrometryE.cpp -- Dendrometry::estimate (reference src/DendrometryE.cpp:3-29) in the host mirror: the bounds of the
 // cloud on the device (sfmhip_cloud_minmax) and the reference's printed lines, the empty ones included; measure() and
 // estimateTree() fill them (one sfmhip_cloud_dendro_profile call: the scalars and the stem table); findGround() and the
-// levelling overloads put sfmhip_cloud_ground_plane in front of them.
+// levelling overloads put sfmhip_cloud_ground_plane in front of them; findTrees() and estimatePlot() put sfmhip_cloud_trees
+// between the two, for a plot of several trees.
 #include "DendrometryE.h"
 #include <cstdio>
 #include <cstdlib>
@@ -147,4 +148,66 @@ int Dendrometry::estimateTree(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, 
     return rc;
   }
   return estimateTree(cloudPCL, labels, label, &o);
+}
+
+int Dendrometry::findTrees(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_trees_opts& opts) {
+  const int n = (int)cloudPCL->size();
+  std::vector<float> xyz((size_t)3 * n + 3);
+  for (int i = 0; i < n; ++i) {
+    xyz[3 * (size_t)i] = cloudPCL->points[i].x;
+    xyz[3 * (size_t)i + 1] = cloudPCL->points[i].y;
+    xyz[3 * (size_t)i + 2] = cloudPCL->points[i].z;
+  }
+  sfmhip_cloud* dev = nullptr;
+  int rc = sfmhip_cloud_create(sfm_hip_context(), n, xyz.data(), &dev);
+  if (rc != SFMHIP_OK) return rc;
+  treeOf_.assign((size_t)n + 1, -1);
+  stems_.assign(4096, sfmhip_tree_stem());
+  rc = sfmhip_cloud_trees(dev, labels, label, &opts, treeOf_.data(), (int)stems_.size(), stems_.data(), &trees_);
+  treeOf_.resize((size_t)n);
+  stems_.resize(rc == SFMHIP_OK ? (size_t)trees_.n_trees : 0);
+  sfmhip_cloud_destroy(dev);
+  return rc;
+}
+
+int Dendrometry::estimatePlot(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const sfmhip_ground_opts& ground_opts,
+                              const double* cam_centres, int n_cam, const sfmhip_trees_opts* trees_opts, const sfmhip_dendro_opts* dendro_opts) {
+  sfmhip_dendro_opts d;
+  sfmhip_trees_opts t;
+  plot_.clear();
+  int rc = levelled_opts(*this, cloudPCL, ground_opts, cam_centres, n_cam, dendro_opts, &d);
+  if (rc == SFMHIP_OK) {
+    if (trees_opts)
+      t = *trees_opts;
+    else
+      sfmhip_trees_default_opts(&t);
+    rc = sfmhip_trees_opts_from_ground(&ground_, &t);
+  }
+  if (rc != SFMHIP_OK) {
+    std::fprintf(stderr, "[sfm] sfmhip_cloud_ground_plane: %s\n", sfmhip_error_string(rc));
+    return rc;
+  }
+  rc = findTrees(cloudPCL, nullptr, 0, t);
+  if (rc != SFMHIP_OK) {
+    std::fprintf(stderr, "[sfm] sfmhip_cloud_trees: %s\n", sfmhip_error_string(rc));
+    return rc;
+  }
+  std::cout << "************************************************" << std::endl;
+  std::cout << "              DENDROMETRY ESTIMATION            " << std::endl;
+  std::cout << "************************************************" << std::endl;
+  std::cout << "Trees=" << trees_.n_trees << std::endl;
+  for (int s = 0; s < trees_.n_trees; ++s) {
+    rc = measure(cloudPCL, treeOf_.data(), s, &d);
+    if (rc != SFMHIP_OK) {
+      std::fprintf(stderr, "[sfm] sfmhip_cloud_dendrometry: %s\n", sfmhip_error_string(rc));
+      return rc;
+    }
+    plot_.push_back(tree_);
+    std::cout << "Tree " << s << ": Total Height =" << tree_.total_height << " Altura copa viva=" << tree_.live_crown
+              << " Altura base de copa=" << tree_.crown_base_height << " Altura DAP=" << d.dbh_height << " DAP=" << tree_.dbh
+              << " Amplitud N-S=" << tree_.spread_ns << " Amplitud E-W=" << tree_.spread_ew << std::endl;
+  }
+  std::cout << "************************************************" << std::endl;
+  std::cout << "************************************************" << std::endl;
+  return rc;
 }

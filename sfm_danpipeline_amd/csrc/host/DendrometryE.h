@@ -3,7 +3,8 @@
 // call prints stay readable afterwards (the reference only prints them).  measure() / estimateTree() are what the
 // reference leaves blank: sfmhip_cloud_dendro_profile on the cloud, or on one cluster of the segmentation.
 // findGround() is the vertical frame they need on a reconstruction's cloud: sfmhip_cloud_ground_plane;
-// the overloads of measure() / estimateTree() that take ground options level first.
+// the overloads of measure() / estimateTree() that take ground options level first.  findTrees() cuts a levelled plot into
+// trees: sfmhip_cloud_trees; estimatePlot() is the chain ground plane -> trees -> one measurement per tree.
 #pragma once
 #include <vector>
 #include "pcllite.h"
@@ -16,6 +17,10 @@ class Dendrometry {
   sfmhip_dendro_result tree_ = {};
   std::vector<sfmhip_dendro_slice> profile_;
   sfmhip_ground_result ground_ = {};
+  sfmhip_trees_result trees_ = {};
+  std::vector<int> treeOf_;
+  std::vector<sfmhip_tree_stem> stems_;
+  std::vector<sfmhip_dendro_result> plot_;
 
  public:
   Dendrometry() {}
@@ -44,6 +49,19 @@ class Dendrometry {
   int estimateTree(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_ground_opts& ground_opts,
                    const double* cam_centres, int n_cam, const sfmhip_dendro_opts* opts = nullptr);
   const sfmhip_ground_result& ground() const { return ground_; }
+
+  // the trees of the points with labels[i] == label (labels == nullptr: of every finite point): treeOf()[i] is point i's tree
+  // or -1, stems() one row per tree.  opts must carry the frame and the ground (sfmhip_trees_opts_from_ground).
+  int findTrees(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_trees_opts& opts);
+  // findGround() over every finite point, findTrees() in its frame, then the measurement of every tree; prints one line per
+  // tree in estimateTree()'s wording.  trees_opts / dendro_opts == nullptr: the defaults; their scale stays the caller's.
+  // SFMHIP_ERR_ARG when no plane was found.
+  int estimatePlot(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const sfmhip_ground_opts& ground_opts, const double* cam_centres,
+                   int n_cam, const sfmhip_trees_opts* trees_opts = nullptr, const sfmhip_dendro_opts* dendro_opts = nullptr);
+  const sfmhip_trees_result& trees() const { return trees_; }
+  const std::vector<int>& treeOf() const { return treeOf_; }
+  const std::vector<sfmhip_tree_stem>& stems() const { return stems_; }
+  const std::vector<sfmhip_dendro_result>& plot() const { return plot_; }
 
   const sfmhip_dendro_result& tree() const { return tree_; }
   const std::vector<sfmhip_dendro_slice>& stemProfile() const { return profile_; }
