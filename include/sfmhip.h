@@ -194,7 +194,9 @@ int sfmhip_sift_detect_and_compute_device(sfmhip_ctx* ctx, const uint8_t* gray, 
 /* extractFeature's loop (reference src/Sfm.cpp:283-290) as one call: n_images gray images, several in flight on worker
  * streams of the context (an image's front end is ~100 small launches and two read-backs: latency the next image hides).
  * keypoints[i]: a host array of n_keypoints[i] x 6 floats allocated by the library (sfmhip_host_free); d_descriptors[i]: a
- * device array of n_keypoints[i] x 128 f32 (sfmhip_device_free).  Image by image the results of the one-image entry. */
+ * device array of n_keypoints[i] x 128 f32 (sfmhip_device_free).  Image by image the results of the one-image entry.
+ * An image the one-image entry would refuse (null, a side below 2) refuses the whole call with SFMHIP_ERR_ARG before
+ * any output is written; n_images = 0 is SFMHIP_OK. */
 int sfmhip_sift_batch(sfmhip_ctx* ctx, int n_images, const uint8_t* const* gray, const int32_t* rows, const int32_t* cols,
                       int n_octave_layers, double contrast_threshold, double edge_threshold, double sigma, float** keypoints,
                       void** d_descriptors, int32_t* n_keypoints);

@@ -729,8 +729,9 @@ extern "C" int sfmhip_sift_batch(sfmhip_ctx* ctx, int n_images, const uint8_t* c
                                  int n_octave_layers, double contrast_threshold, double edge_threshold, double sigma,
                                  float** keypoints, void** d_descriptors, int32_t* n_keypoints) {
   if (!ctx || n_images < 0 || (n_images && (!gray || !rows || !cols || !keypoints || !d_descriptors || !n_keypoints))) return SFMHIP_ERR_ARG;
-  for (int i = 0; i < n_images; ++i) {
+  for (int i = 0; i < n_images; ++i)  // (one bad image refuses the call before any output is written)
     if (!sift_args_ok(ctx, gray[i], rows[i], cols[i], n_octave_layers, sigma)) return SFMHIP_ERR_ARG;
+  for (int i = 0; i < n_images; ++i) {
     keypoints[i] = nullptr;
     d_descriptors[i] = nullptr;
     n_keypoints[i] = 0;

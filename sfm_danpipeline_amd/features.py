@@ -7,16 +7,22 @@ import numpy as np
 from ._lib import check, default_context, lib
 
 
-def sift_detect_and_compute(gray, n_octave_layers=3, contrast_threshold=0.04, edge_threshold=10.0, sigma=1.6, ctx=None):
+def sift_detect_and_compute(gray, n_octave_layers=3, contrast_threshold=0.04, edge_threshold=10.0, sigma=1.6, ctx=None,
+                            capacity=None):
     """gray: rows x cols uint8.  Returns (keypoints n x 6 float32 [x, y, size, angle, response, octave bits],
-    descriptors n x 128 float32) in OpenCV's keypoint order."""
+    descriptors n x 128 float32) in OpenCV's keypoint order.  capacity (>= 1; None: a guess from the image size): the
+    rows of the first attempt's output arrays; an image with more keypoints costs a second call with the reported count."""
     ctx = ctx or default_context()
     g = np.ascontiguousarray(gray, np.uint8)
     assert g.ndim == 2
     n = C.c_int32(0)
     args = (ctx.h, g.ctypes.data, g.shape[0], g.shape[1], int(n_octave_layers), float(contrast_threshold), float(edge_threshold),
             float(sigma))
-    cap = max(1024, g.size // 48)            # one pass when the guess holds; the call reports the count if it does not
+    if capacity is None:
+        capacity = max(1024, g.size // 48)     # one pass when the guess holds; the call reports the count if it does not
+    cap = int(capacity)
+    if cap < 1:
+        raise ValueError(f"capacity {capacity}: at least 1")
     for _ in range(2):
         k = np.zeros((cap, 6), np.float32)
         d = np.zeros((cap, 128), np.float32)

@@ -4,6 +4,7 @@ behaviour under a shift of the image content."""
 import numpy as np
 
 from oracle import sfm_oracle_sift as S
+from tests import sift_images as I
 
 
 def _blob_image(h, w, blobs, noise=0.0, seed=0):
@@ -63,3 +64,24 @@ def test_descriptors_survive_a_shift():
     keep = srt[:, 0] < 0.64 * srt[:, 1]                          # the ratio test of getMatching on squared distances
     shift = Ka[keep, :2] - Kb[nn[keep], :2]
     assert keep.sum() >= 10 and (np.abs(shift - [8, 4]).max(1) < 1.0).mean() > 0.8
+
+
+def test_generators_are_seeded_and_shaped():
+    for g in (lambda: I.texture(36, 129, 1), lambda: I.checker(40, 132), lambda: I.blocks(40, 150, 3), I.corner_blob, lambda: I.sliver(11, 40, 7)):
+        a, b = g(), g()
+        assert a.dtype == np.uint8 and a.ndim == 2 and np.array_equal(a, b)
+    t = I.texture(36, 129, 1).astype(np.float64)
+    assert abs(t.mean() - 128) < 3 and 45 < t.std() < 55 and not np.array_equal(I.texture(36, 129, 1), I.texture(36, 129, 2))
+    c = I.checker(40, 132)
+    assert set(np.unique(c)) == {0, 255} and c[0, 0] == c[6, 8] != c[7, 8] == c[6, 9] != c[7, 9]      # cells of 7 rows x 9 columns
+    b = I.blocks(40, 150, 3)
+    assert set(np.unique(b)) == {0, 255} and all((b[y:y + 4, x:x + 4] == b[y, x]).all() for y in range(0, 40, 4) for x in range(0, 150, 4))
+    assert [I.degenerate_image(s).shape for s in I.DEGENERATE_SHAPES] == list(I.DEGENERATE_SHAPES)
+    assert all(I.image(n).size <= 6500 for n in I.CASES)
+
+
+def test_the_gpu_cases_exercise_their_paths():
+    """tests/test_gpu_sift.py compares the device with the restatement on tests/sift_images.py's cases; here the
+    restatement alone shows that every case still has what it is there for (an edit to a generator cannot empty one):
+    keypoints, sites with several orientations, three octaves, windows beyond the border, thresholds that cut"""
+    I.check_groups()
