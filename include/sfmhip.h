@@ -930,6 +930,48 @@ int sfmhip_mvs_download(const sfmhip_mvs* h, float* xyz, float* normals, uint32_
  * sfmhip_set_timing (one more stream synchronisation); without it [0] is 0 and [1] holds both. */
 int sfmhip_mvs_last_timing(const sfmhip_mvs* h, double ms3[3]);
 
+/* ---- Lens distortion in front of the dense stereo: undistort the views ----
+ * The plane sweep warps with pinhole homographies, so pictures from a lens with distortion (k1 k2 p1 p2 k3, the five
+ * coefficients of the calibration file, as sfmhip_triangulate and sfmhip_pnp_ransac take them) are resampled once into the
+ * pinhole camera of the SAME K.  The reference hands pmvs2 the raw pictures; there is no library here to pin parity against:
+ * the contract is this rule list, whose arithmetic is csrc/undistort.h (compiled by g++ and hipcc; the device equals the host
+ * build bit for bit).
+ *  1 map: for destination pixel (x, y): xn = (x - cx) / fx, yn = (y - cy) / fy; the forward model of the projection
+ *    (csrc/camera.h project_point: r2, r4, r6, a1, a2, a3, cdist, xd, yd in that order, f64); u = xd fx + cx, v = yd fy + cy.
+ *    It depends on K, the coefficients and the size only: one map per call, shared by every view and channel.
+ *  2 quantise: fu = floor(u), wx = floor((u - fu) 32 + 0.5); wx = 32 carries (wx = 0, ix + 1); v likewise.  floor is taken
+ *    on the f64 value, negatives included (u = -1e-15 carries to ix = 0, wx = 0).
+ *  3 validity, after the carry: a tap of weight zero is not read; the pixel is valid iff every tap of non-zero weight lies
+ *    inside the source; a non-finite u or v is invalid.
+ *  4 blend: ((a (32 - wx) + b wx)(32 - wy) + (c (32 - wx) + d wx) wy + 512) >> 10 per channel, 8 bit; an invalid pixel is 0 in
+ *    every channel and 0 in the validity byte (1 otherwise).
+ *  5 hence all-zero coefficients give the input byte for byte, every pixel valid, for any K.
+ *  6 level masks: a pixel of level L is valid iff all 2^L x 2^L level-0 pixels under it are (a dropped odd row or column is
+ *    simply absent).
+ *  7 no depth at the seam: on a handle created with distortion, a reference pixel whose (2 window + 1)^2 window touches an
+ *    invalid level-L pixel gets index -1, depth 0, score 0, applied after rules 2-5 of the stereo; the sweep and its sampling
+ *    are untouched, so a black tap on the source side only lowers an NCC.
+ * Known limit: K is kept, so pincushion coefficients leave invalid (black) margins and barrel coefficients crop the picture;
+ * there is no new-camera-matrix or inscribed-rectangle step. */
+/* Rules 1-5 for n_images pictures of one size: src[i], dst[i]: rows x cols x channels bytes (channels 1, or 3 interleaved);
+ * valid: rows x cols bytes, nullable -- ONE mask, it is the same for every picture.  SFMHIP_ERR_ARG: a size or count of 0,
+ * channels other than 1 or 3, a null pointer, fx or fy of 0, a non-finite K entry or coefficient. */
+int sfmhip_image_undistort(sfmhip_ctx* ctx, int n_images, int rows, int cols, int channels, const uint8_t* const* src,
+                           const double K9[9], const double dist5[5], uint8_t* const* dst, uint8_t* valid);
+/* With sfmhip_set_timing on: the kernel time (ms, by events on the context's stream) of the last sfmhip_image_undistort call:
+ * ms2 = map, gather. */
+int sfmhip_image_undistort_last_timing(sfmhip_ctx* ctx, double ms2[2]);
+/* sfmhip_mvs_create on pictures of a lens with distortion: gray and BGR are undistorted on the device (rules 1-5, one map),
+ * then everything proceeds as in sfmhip_mvs_create with the same K; the handle keeps the level mask (rule 6) and
+ * sfmhip_mvs_depthmap / sfmhip_mvs_run apply rule 7.  SFMHIP_ERR_ARG as sfmhip_mvs_create and sfmhip_image_undistort; *out is
+ * null after a refusal. */
+int sfmhip_mvs_create_distorted(sfmhip_ctx* ctx, int n_views, int rows, int cols, const uint8_t* const* gray,
+                                const uint8_t* const* bgr, const double K9[9], const double dist5[5], const double* poses12, int level,
+                                sfmhip_mvs** out);
+/* The mask of the working level (rule 6), rows x cols bytes of sfmhip_mvs_level's size; all ones on a handle made by
+ * sfmhip_mvs_create. */
+int sfmhip_mvs_valid(sfmhip_mvs* h, uint8_t* valid);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,7 @@ struct sfmhip_ctx {
   int pose_flags = 0;   // OR of the decompositions' flags of the last pose call (pose.hip, sfmhip_pose_last_flags)
   int pnp_flags = 0;    // OR of the EPnP solves' flags of the last PnP call (pnp.hip, sfmhip_pnp_last_flags)
   double pnp_ms[3] = {0, 0, 0};  // solver / scoring / refit kernel time of the last sfmhip_pnp_ransac call (timing on)
+  double undistort_ms[2] = {0, 0};  // map / gather kernel time of the last sfmhip_image_undistort call (timing on)
   // sfmhip_ba_solve (ba.hip): where the last call's time went, and the problem it keeps for a next call of the same structure
   sfmhip_ba_solve_profile ba_profile = {};
   void* ba_cache = nullptr;
@@ -109,6 +110,17 @@ struct DevBufs {  // device memory of one call (or one object), freed with it
 // caller returns early on an empty input.
 int sfm_scan_bytes(size_t n, hipStream_t st, size_t* bytes);
 int sfm_exclusive_scan(void* tmp, size_t tmp_bytes, const int* in, int* out, size_t n, hipStream_t st, long long* total);
+
+// The lens-distortion resampling of undistort.hip for the callers inside the library (mvs.hip): launches on
+// `st`, no synchronisation, device pointers throughout.  map: rows x cols entries (sfmund::Packed), padded to a multiple of 4.
+namespace sfmund {
+struct Packed;
+}
+size_t sfm_undistort_map_entries(int rows, int cols);
+int sfm_undistort_map(hipStream_t st, int rows, int cols, const double* K9, const double* dist5, sfmund::Packed* map, uint8_t* valid);
+int sfm_undistort_apply(hipStream_t st, int n, int rows, int cols, int ch, const uint8_t* src, uint8_t* dst, const sfmund::Packed* map);
+int sfm_undistort_level_mask(hipStream_t st, int rows, int cols, int level, const uint8_t* valid0, uint8_t* out);
+int sfm_undistort_seam(hipStream_t st, int rows, int cols, int window, const uint8_t* valid, int32_t* idx, float* depth, float* score);
 
 static inline double sfm_now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();

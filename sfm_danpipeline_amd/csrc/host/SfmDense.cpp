@@ -49,8 +49,16 @@ size_t StructFromMotion::densify(const std::string& plyPath) {
   o.min_views = 5;  // options.txt: minImageNum 5
   sfmhip_mvs* m = nullptr;
   int32_t n = 0;
-  int rc = sfmhip_mvs_create(sfm_hip_context(), (int)gray.size(), rows, cols, gray.data(), colour ? bgr.data() : nullptr,
-                             cameraMatrix.K.data.data(), poses.data(), 1 /* options.txt: level 1 */, &m);
+  // the calibration file's distortion coefficients (k1 k2 p1 p2 k3): with any of them set the views are undistorted on the
+  // device first; all zero is the pinhole call, bit for bit what it always was
+  double dist[5] = {0, 0, 0, 0, 0};
+  for (int i = 0; i < 5 && i < (int)cameraMatrix.distCoef.data.size(); ++i) dist[i] = cameraMatrix.distCoef.data[i];
+  const bool distorted = std::any_of(dist, dist + 5, [](double d) { return d != 0.0; });
+  const int level = 1;  // options.txt: level 1
+  int rc = distorted ? sfmhip_mvs_create_distorted(sfm_hip_context(), (int)gray.size(), rows, cols, gray.data(), colour ? bgr.data() : nullptr,
+                                                   cameraMatrix.K.data.data(), dist, poses.data(), level, &m)
+                     : sfmhip_mvs_create(sfm_hip_context(), (int)gray.size(), rows, cols, gray.data(), colour ? bgr.data() : nullptr,
+                                         cameraMatrix.K.data.data(), poses.data(), level, &m);
   if (rc == SFMHIP_OK) rc = sfmhip_mvs_run(m, dmin.data(), dmax.data(), &o, &n);
   if (rc != SFMHIP_OK) {
     std::fprintf(stderr, "densify: %s\n", sfmhip_error_string(rc));
@@ -76,6 +84,6 @@ size_t StructFromMotion::densify(const std::string& plyPath) {
     std::fwrite(c, 1, 3, f);
   }
   std::fclose(f);
-  std::printf("densify: %zu views, %d points -> %s\n", gray.size(), (int)n, plyPath.c_str());
+  std::printf("densify: %zu views%s, %d points -> %s\n", gray.size(), distorted ? " (undistorted)" : "", (int)n, plyPath.c_str());
   return (size_t)n;
 }

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "cloud_grid.h"
 #include "mvs.h"
+#include "undistort.h"
 #include <string.h>
 
 using namespace sfmmvs;
@@ -18,6 +19,7 @@ struct sfmhip_mvs {
   uint8_t* gray = nullptr;  // n x rows x cols, the working level
   uint8_t* bgr = nullptr;   // n x rows x cols x 3, or null
   float* depth = nullptr;   // n x rows x cols, 0 = no depth
+  uint8_t* valid = nullptr; // rows x cols: the level mask of a handle created with distortion (f-14 rule 6), else null
   double* d_poses = nullptr;
   double* d_H = nullptr;    // MAX_PLANES x MAX_SRC x 9: one view's table (sfmhip_mvs_depthmap)
   double* run_H = nullptr;  // n tables of n_planes x MAX_SRC x 9 (sfmhip_mvs_run: one upload for all views)
@@ -201,6 +203,7 @@ int sweep(sfmhip_mvs* h, int ref, int n_src, const int32_t* src, double dmin, do
   A.idx = h->idx, A.score = h->score, A.depth = h->depth + (size_t)h->rows * h->cols * ref;
   hipLaunchKernelGGL(mvs_sweep, dim3(blocks(h->cols, TILE), blocks(h->rows, TILE)), dim3(TILE * TILE), 0, st, A);
   SFM_HIP_TRY(hipGetLastError());
+  if (h->valid) SFM_TRY(sfm_undistort_seam(st, h->rows, h->cols, o.window, h->valid, A.idx, A.depth, A.score));  // f-14 rule 7
   return SFMHIP_OK;
 }
 
@@ -239,7 +242,9 @@ int fuse(sfmhip_mvs* h, const Opts& o, int32_t* n_points) {
   return SFMHIP_OK;
 }
 
-int create(sfmhip_mvs* h, int n_views, int rows, int cols, const uint8_t* const* gray, const uint8_t* const* bgr, int level) {
+// dist5 (with K9, the level-0 camera matrix): null for pinhole views; else every level-0 picture goes through f-14's map first
+int create(sfmhip_mvs* h, int n_views, int rows, int cols, const uint8_t* const* gray, const uint8_t* const* bgr, int level,
+           const double* K9, const double* dist5) {
   hipStream_t st = h->ctx->stream;
   const size_t px0 = (size_t)rows * cols, px = (size_t)h->rows * h->cols, total = px * n_views;
   SFM_TRY(h->own.alloc(&h->gray, total));
@@ -253,16 +258,29 @@ int create(sfmhip_mvs* h, int n_views, int rows, int cols, const uint8_t* const*
   SFM_TRY(h->own.alloc(&h->offs, total));
   SFM_HIP_TRY(hipMemsetAsync(h->depth, 0, sizeof(float) * total, st));
   SFM_HIP_TRY(hipMemcpyAsync(h->d_poses, h->poses.data(), sizeof(double) * 12 * n_views, hipMemcpyHostToDevice, st));
+  DevBufs U;  // the map of the call and its level-0 mask (the loop below ends on a stream synchronisation)
+  sfmund::Packed* map = nullptr;
+  if (dist5) {
+    uint8_t* valid0 = nullptr;
+    SFM_TRY(U.alloc(&map, sfm_undistort_map_entries(rows, cols)));
+    SFM_TRY(U.alloc(&valid0, px0));
+    SFM_TRY(h->own.alloc(&h->valid, px));
+    SFM_TRY(sfm_undistort_map(st, rows, cols, K9, dist5, map, valid0));
+    SFM_TRY(sfm_undistort_level_mask(st, rows, cols, level, valid0, h->valid));
+  }
   for (int ch = 1; ch <= (bgr ? 3 : 1); ch += 2) {
     uint8_t* dst = ch == 1 ? h->gray : h->bgr;
     DevBufs B;  // the levels above the working one
-    uint8_t *a = dst, *b = nullptr;
+    uint8_t *a = dst, *b = nullptr, *raw = nullptr;
     if (level > 0) {
       SFM_TRY(B.alloc(&a, px0 * n_views * ch));
       SFM_TRY(B.alloc(&b, (px0 >> 2) * n_views * ch + 1));
     }
+    if (dist5) SFM_TRY(B.alloc(&raw, px0 * n_views * ch));
+    uint8_t* up = dist5 ? raw : a;
     for (int v = 0; v < n_views; ++v)
-      SFM_HIP_TRY(hipMemcpyAsync(a + px0 * v * ch, ch == 1 ? gray[v] : bgr[v], px0 * ch, hipMemcpyHostToDevice, st));
+      SFM_HIP_TRY(hipMemcpyAsync(up + px0 * v * ch, ch == 1 ? gray[v] : bgr[v], px0 * ch, hipMemcpyHostToDevice, st));
+    if (dist5) SFM_TRY(sfm_undistort_apply(st, n_views, rows, cols, ch, raw, a, map));  // all views of this buffer in one launch
     int r = rows, c = cols;
     for (int l = 0; l < level; ++l, r >>= 1, c >>= 1) {
       uint8_t* out = l == level - 1 ? dst : b;
@@ -285,8 +303,8 @@ extern "C" void sfmhip_mvs_default_opts(sfmhip_mvs_opts* o) {
   o->ncc_min = r.ncc_min, o->eps = r.eps, o->var_min = r.var_min;
 }
 
-extern "C" int sfmhip_mvs_create(sfmhip_ctx* ctx, int n_views, int rows, int cols, const uint8_t* const* gray, const uint8_t* const* bgr,
-                                 const double* K9, const double* poses12, int level, sfmhip_mvs** out) {
+static int make_handle(sfmhip_ctx* ctx, int n_views, int rows, int cols, const uint8_t* const* gray, const uint8_t* const* bgr,
+                       const double* K9, const double* dist5, const double* poses12, int level, sfmhip_mvs** out) {
   if (!ctx || !out || n_views < 2 || rows < 1 || cols < 1 || !gray || !K9 || !poses12 || level < 0 || level > 8) return SFMHIP_ERR_ARG;
   *out = nullptr;
   if ((rows >> level) < 1 || (cols >> level) < 1 || (double)n_views * rows * cols * 3.0 >= 2147483648.0) return SFMHIP_ERR_ARG;
@@ -298,12 +316,38 @@ extern "C" int sfmhip_mvs_create(sfmhip_ctx* ctx, int n_views, int rows, int col
   h->K = Cam{K9[0], K9[4], K9[2], K9[5]};
   for (int l = 0; l < level; ++l) h->K = halve_cam(h->K);
   h->poses.assign(poses12, poses12 + 12 * (size_t)n_views);
-  const int rc = create(h, n_views, rows, cols, gray, bgr, level);
+  const int rc = create(h, n_views, rows, cols, gray, bgr, level, K9, dist5);
   if (rc != SFMHIP_OK) {
     delete h;
     return rc;
   }
   *out = h;
+  return SFMHIP_OK;
+}
+
+extern "C" int sfmhip_mvs_create(sfmhip_ctx* ctx, int n_views, int rows, int cols, const uint8_t* const* gray, const uint8_t* const* bgr,
+                                 const double* K9, const double* poses12, int level, sfmhip_mvs** out) {
+  return make_handle(ctx, n_views, rows, cols, gray, bgr, K9, nullptr, poses12, level, out);
+}
+
+extern "C" int sfmhip_mvs_create_distorted(sfmhip_ctx* ctx, int n_views, int rows, int cols, const uint8_t* const* gray,
+                                           const uint8_t* const* bgr, const double* K9, const double* dist5, const double* poses12,
+                                           int level, sfmhip_mvs** out) {
+  if (out) *out = nullptr;
+  if (!sfmund::model_ok(K9, dist5)) return SFMHIP_ERR_ARG;
+  return make_handle(ctx, n_views, rows, cols, gray, bgr, K9, dist5, poses12, level, out);
+}
+
+extern "C" int sfmhip_mvs_valid(sfmhip_mvs* h, uint8_t* valid) {
+  if (!h || !valid) return SFMHIP_ERR_ARG;
+  const size_t px = (size_t)h->rows * h->cols;
+  if (!h->valid) {
+    memset(valid, 1, px);
+    return SFMHIP_OK;
+  }
+  SFM_HIP_TRY(hipSetDevice(h->ctx->device));
+  SFM_HIP_TRY(hipMemcpyAsync(valid, h->valid, px, hipMemcpyDeviceToHost, h->ctx->stream));
+  SFM_HIP_TRY(hipStreamSynchronize(h->ctx->stream));
   return SFMHIP_OK;
 }
 

@@ -3,7 +3,11 @@ cross-view consistency fusion into one coloured, oriented cloud (include/sfmhip.
 
 `densify(gray, K, poses, dmin, dmax)` returns (xyz [m, 3] float32, normals [m, 3] float32, rgb [m] uint32 0x00RRGGBB);
 `Mvs` is the staged form: depthmap(ref, src, dmin, dmax), set_depthmap, fuse, run.  Parity with pmvs2 is UNPINNED
-(DESIGN.md f-10): depth-map fusion for its patch expansion, camera-facing normals for its patch normals."""
+(DESIGN.md f-10): depth-map fusion for its patch expansion, camera-facing normals for its patch normals.
+
+`dist` (k1 k2 p1 p2 k3 of the calibration file) on either form: the views are undistorted on the device into the pinhole
+camera of the same K before anything else (undistort.py), `Mvs.valid()` is the mask of the working level and
+a reference pixel whose window touches an invalid pixel gets no depth."""
 import ctypes as C
 
 import numpy as np
@@ -43,9 +47,9 @@ def image_pointers(images, ch):
 
 class Mvs:
     """Views on the device at pyramid level `level`: gray [n, rows, cols] uint8 (bgr [n, rows, cols, 3] optional), one K
-    [3, 3], poses [n, 3, 4] = [R | t]."""
+    [3, 3], poses [n, 3, 4] = [R | t]; dist: None for pinhole views, else the five distortion coefficients."""
 
-    def __init__(self, gray, K, poses, bgr=None, level=1, ctx=None):
+    def __init__(self, gray, K, poses, bgr=None, level=1, ctx=None, dist=None):
         self.ctx = ctx or _lib.default_context()
         g, gp = image_pointers(gray, 1)
         bp = None
@@ -59,8 +63,15 @@ class Mvs:
             raise ValueError("poses must be [n, 3, 4]")
         rows, cols = g[0].shape if g else (0, 0)
         self.h = C.c_void_p()
-        _lib.check(_lib.lib().sfmhip_mvs_create(self.ctx.h, len(g), rows, cols, gp, bp, _p(K), _p(poses), int(level), C.byref(self.h)),
-                   "sfmhip_mvs_create")
+        if dist is None:
+            _lib.check(_lib.lib().sfmhip_mvs_create(self.ctx.h, len(g), rows, cols, gp, bp, _p(K), _p(poses), int(level), C.byref(self.h)),
+                       "sfmhip_mvs_create")
+        else:
+            dist = np.ascontiguousarray(dist, np.float64).reshape(-1)
+            if len(dist) != 5:
+                raise ValueError("dist must be the five coefficients k1 k2 p1 p2 k3")
+            _lib.check(_lib.lib().sfmhip_mvs_create_distorted(self.ctx.h, len(g), rows, cols, gp, bp, _p(K), _p(dist), _p(poses), int(level),
+                                                              C.byref(self.h)), "sfmhip_mvs_create_distorted")
         self.n, self.colour = len(g), bgr is not None
         r, c, k = C.c_int32(0), C.c_int32(0), np.zeros(9)
         _lib.check(_lib.lib().sfmhip_mvs_level(self.h, C.byref(r), C.byref(c), _p(k), -1, None, None), "sfmhip_mvs_level")
@@ -73,6 +84,12 @@ class Mvs:
         _lib.check(_lib.lib().sfmhip_mvs_level(self.h, None, None, None, int(view), _p(g), _p(b) if self.colour else None),
                    "sfmhip_mvs_level")
         return g, b
+
+    def valid(self):
+        """the mask of the working level [rows, cols] uint8: all ones without `dist`"""
+        m = np.zeros((self.rows, self.cols), np.uint8)
+        _lib.check(_lib.lib().sfmhip_mvs_valid(self.h, _p(m)), "sfmhip_mvs_valid")
+        return m
 
     def depthmap(self, ref, src, dmin, dmax, opts=None):
         """(winner index int32, depth float32, score float32), each [rows, cols]; the depth map stays on the handle"""
@@ -130,7 +147,7 @@ class Mvs:
             pass
 
 
-def densify(gray, K, poses, dmin, dmax, bgr=None, level=1, opts=None, ctx=None):
+def densify(gray, K, poses, dmin, dmax, bgr=None, level=1, opts=None, ctx=None, dist=None):
     """Step 7 in one call: (xyz, normals, rgb) of the fused cloud."""
-    with Mvs(gray, K, poses, bgr=bgr, level=level, ctx=ctx) as m:
+    with Mvs(gray, K, poses, bgr=bgr, level=level, ctx=ctx, dist=dist) as m:
         return m.run(dmin, dmax, opts)
