@@ -146,7 +146,9 @@ void sfmhip_matchplan_destroy(sfmhip_matchplan* plan);
 /* ---- triangulateViews numerics (reference src/Sfm.cpp:812-860) ----
  * P1,P2: cv::Matx34d row-major; K 3x3 row-major; dist k1,k2,p1,p2,k3; xy1/xy2: m gathered
  * pixel pairs (AlignedPoints, src/Sfm.cpp:694-711).  X: 3*m, keep: m (1 = both reprojection
- * errors <= max_err as float), err: 2*m floats or NULL. */
+ * errors <= max_err as float), err: 2*m floats or NULL.  The test is the reference's
+ * !(max_err < e1 || max_err < e2): a row whose error is NaN (a non-finite observation, say) is
+ * KEPT, with its NaN point, as in the reference; so is every row under a NaN max_err. */
 int sfmhip_triangulate(sfmhip_ctx* ctx, const double P1[12], const double P2[12],
                        const double K[9], const double dist[5], const double* xy1,
                        const double* xy2, int m, float max_err, double* X, float* err,
@@ -158,6 +160,12 @@ int sfmhip_triangulate(sfmhip_ctx* ctx, const double P1[12], const double P2[12]
  * of (trk_view, trk_feat), ascending view.  For every cloud point, in cloud order: its feature
  * in done_view, then the FIRST match (match order) whose queryIdx (done_view < new_view) or
  * trainIdx (otherwise) is that feature; emits (cloud index, feature index in the new view).
+ * As in the reference's loop (matched2DPointInNewView starts at -1 and the scan only stops at a
+ * value >= 0, src/Sfm.cpp:1062-1082), a match whose other-side index is negative is passed over:
+ * FIRST means the first match on the key whose other side is >= 0.  A point with no such match,
+ * no entry in done_view, or a feature that no match keys, emits nothing.  Feature indices are
+ * indices: a negative track feature or key-side index never matches anything (the reference's
+ * == would pair two equal negative values; getMatching produces none).
  * out_cloud/out_feat: n_cloud entries each. */
 int sfmhip_find_2d3d(sfmhip_ctx* ctx, const int32_t* trk_ptr, const int32_t* trk_view,
                      const int32_t* trk_feat, int n_cloud, int done_view, int new_view,

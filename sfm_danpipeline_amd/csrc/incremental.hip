@@ -17,13 +17,15 @@ constexpr int BLK = 256;
 constexpr int EMPTY = 0x7F7F7F7F;  // hipMemset pattern: larger than any match index
 
 // ---------------------------------------------------------------- find_2d3d
-// first[f] = index of the first match (in match order) whose key feature is f
-__global__ __launch_bounds__(BLK) void first_match_kernel(const int* __restrict__ key, int n_match,
-                                                          int* __restrict__ first, int tbl_n) {
+// first[f] = index of the first USABLE match (in match order) whose key feature is f.  The reference's scan only stops
+// at a match whose other-side index is >= 0 (matched2DPointInNewView starts at -1, src/Sfm.cpp:1062-1082): a match with
+// a negative other side is passed over and a later one on the same key still counts.
+__global__ __launch_bounds__(BLK) void first_match_kernel(const int* __restrict__ key, const int* __restrict__ other,
+                                                          int n_match, int* __restrict__ first, int tbl_n) {
   const int m = blockIdx.x * BLK + threadIdx.x;
   if (m < n_match) {
     const int f = key[m];
-    if (f >= 0 && f < tbl_n) atomicMin(first + f, m);
+    if (f >= 0 && f < tbl_n && other[m] >= 0) atomicMin(first + f, m);
   }
 }
 
@@ -205,7 +207,8 @@ extern "C" int sfmhip_find_2d3d(sfmhip_ctx* ctx, const int32_t* trk_ptr, const i
   SFM_HIP_TRY(hipMemcpyAsync(d_key, key_h, sizeof(int) * (size_t)n_match, hipMemcpyHostToDevice, st));
   SFM_HIP_TRY(hipMemcpyAsync(d_oth, oth_h, sizeof(int) * (size_t)n_match, hipMemcpyHostToDevice, st));
   SFM_HIP_TRY(hipMemsetAsync(d_first, 0x7F, sizeof(int) * (size_t)tbl_n, st));  // 0x7F7F7F7F > any index
-  hipLaunchKernelGGL(first_match_kernel, dim3((n_match + BLK - 1) / BLK), dim3(BLK), 0, st, d_key, n_match, d_first, tbl_n);
+  hipLaunchKernelGGL(first_match_kernel, dim3((n_match + BLK - 1) / BLK), dim3(BLK), 0, st, d_key, d_oth, n_match, d_first,
+                     tbl_n);
   hipLaunchKernelGGL(assoc_kernel, dim3(nblk), dim3(BLK), 0, st, d_ptr, d_view, d_feat, n_cloud, done_view, d_first, tbl_n,
                      d_oth, d_val, d_cnt);
   hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, st, d_cnt, nblk, d_total);

@@ -70,6 +70,21 @@ def test_find_2d3d_first_match_wins_and_empty(orc):
     assert len(oc) == 0
 
 
+def test_find_2d3d_passes_over_a_negative_other_side(orc):
+    """src/Sfm.cpp:1062-1082: matched2DPointInNewView starts at -1 and the scan only stops at a value >= 0, so a match
+    whose other-side index is negative is passed over and a later match on the same key still counts."""
+    cloud = [{1: 3}, {1: 4}]
+    ptr, views, feats = synth.tracks_to_csr(cloud)
+    oc, of = orc.find_2d3d(ptr, views, feats, 1, 0, [-1, 7, 9], [3, 3, 4])
+    assert list(oc) == [0, 1] and list(of) == [7, 9]
+    assert py_find_2d3d(cloud, 1, 0, [(-1, 3), (7, 3), (9, 4)]) == [(0, 7), (1, 9)]
+    # the left side too (done_view < new_view: queryIdx is the key), unusable matches before, between and after
+    matches = [(3, -5), (3, -1), (3, 8), (3, -2), (3, 6), (4, -9)]
+    oc, of = orc.find_2d3d(ptr, views, feats, 1, 2, [m[0] for m in matches], [m[1] for m in matches])
+    assert list(oc) == [0] and list(of) == [8]
+    assert py_find_2d3d(cloud, 1, 2, matches) == [(0, 8)]
+
+
 def test_merge_new_points_vs_literal_loop_and_chain(orc):
     rng = np.random.default_rng(3)
     cloud = rng.uniform(-1, 1, (200, 3))
