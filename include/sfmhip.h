@@ -383,6 +383,56 @@ int sfmhip_cloud_knn(sfmhip_cloud* cloud, int k, int32_t* idx, float* d2);
 /* NormalEstimation with setKSearch(k), k in 1..32, viewpoint vp[3]: out4 = n x (nx, ny, nz, curvature). */
 int sfmhip_cloud_normals(sfmhip_cloud* cloud, int k, const float* vp /* 3 */, float* out4);
 
+/* ---- thinning and noise removal on the same cloud: PCL 1.8.1's VoxelGrid and StatisticalOutlierRemoval ----
+ * The reference calls neither; the rules are PCL's as recalled (parity UNPINNED, PCL is not in the image; + marks what
+ * is ours).  csrc/cloud_filter.h holds them as code.
+ *   V1. leaf[3]: floats, each > 0 and finite (else SFMHIP_ERR_ARG); inv[a] = 1.0f / leaf[a] in float.
+ *   V2. min_p / max_p: the box of the finite points as floats.  d[a] = (int64)((max_p[a] - min_p[a]) * inv[a]) + 1 in float
+ *       arithmetic with a truncating cast; d[0] d[1] d[2] > INT32_MAX: SFMHIP_ERR_UNSUPPORTED, nothing written (PCL warns
+ *       and copies the input).  + The same refusal when floor(min_p[a] * inv[a]) or floor(max_p[a] * inv[a]) does not fit
+ *       an int32, when the product of the actual extents div[a] = max_b[a] - min_b[a] + 1 exceeds INT32_MAX, and when one
+ *       div[a] exceeds 2^24 (the float difference of V3 would no longer be exact).
+ *   V3. min_b[a] = (int)floor(min_p[a] * inv[a]); ijk[a] = (int)(floor(p[a] * inv[a]) - (float)min_b[a]), all in float;
+ *       idx = ijk[0] + ijk[1] div[0] + ijk[2] div[0] div[1].  A non-finite point is in no voxel.
+ *   V4. a voxel is emitted iff it holds at least min_points (>= 0) points; the output is in ascending idx.
+ *   V5. centroid: float sums of x, y and z, then sum / (float)count per component.  + The order: the voxel's points in
+ *       ascending input index, cut into consecutive blocks of 64; each block summed sequentially from 0.0f, the block
+ *       sums added sequentially in ascending order from 0.0f (a voxel of at most 64 points: one sequential sum).
+ *   V6. rgb (0x00RRGGBB per point): u64 channel sums, truncating integer division, top byte 0 -- PCL's float accumulate
+ *       and uint8 cast while a channel sum stays below 2^24.  normals (3 floats per point): summed by V5's order, then
+ *       each component divided by sqrt((x*x + y*y) + z*z) in float; a length of zero or NaN gives 0x7FC00000 in all three,
+ *       so a NaN input normal propagates.
+ *   V7. voxel_of[i]: the output row of point i's voxel, -1 for a non-finite point or a voxel V4 dropped.
+ *   S1. mean_k in 1..63; every finite point's mean_k + 1 nearest finite points by the d2 above, itself and its
+ *       duplicates included, in ascending d2.
+ *   S2. dist_sum = sum over k = 1..mean_k of sqrt((double)d2[k]), sequential in ascending k, in f64; mean_dist =
+ *       (float)(dist_sum / mean_k); 0 for a non-finite point, which is never kept.
+ *   S3. sum += (double)md, sq += (double)(md * md) (float product).  + The order: consecutive blocks of 256 input
+ *       indices, each summed sequentially from 0.0, the partials added sequentially in ascending order.  mean = sum / N,
+ *       var = (sq - sum * sum / N) / (N - 1) over the N finite points, + clamped to 0 from below; thr = mean + std_mul sqrt(var).
+ *   S4. kept iff (double)md <= thr; negative != 0: iff (double)md > thr.
+ *   S5. no finite point: SFMHIP_OK, nothing kept, threshold 0.  0 < N <= mean_k: SFMHIP_ERR_ARG, nothing written (PCL
+ *       reads stale list slots there).  std_mul must be finite. */
+/* rgb / normals: n / 3 n values or NULL.  out_xyz / out_rgb / out_normals: room for n / n / 3 n values, each may be NULL
+ * (an attribute without its input is not written).  voxel_of: n or NULL.  out_cloud: NULL, or it receives a new handle on
+ * the same context whose points are the centroids -- they are on the device already and are not uploaded again. */
+int sfmhip_cloud_voxel_grid(sfmhip_cloud* cloud, const float leaf[3], int min_points, const uint32_t* rgb, const float* normals,
+                            float* out_xyz, uint32_t* out_rgb, float* out_normals, int32_t* voxel_of, int32_t* n_out,
+                            sfmhip_cloud** out_cloud);
+/* idx_out: the kept input indices in input order (room for n); mean_dist: n or NULL; threshold: thr or NULL */
+int sfmhip_cloud_statistical_outlier(sfmhip_cloud* cloud, int mean_k, double std_mul, int negative, int32_t* idx_out,
+                                     int32_t* n_out, float* mean_dist, double* threshold);
+/* a new handle over the points indices[0..n_idx) of this one, gathered on the device: duplicates allowed, order kept;
+ * an index outside [0, n) is SFMHIP_ERR_ARG */
+int sfmhip_cloud_select(sfmhip_cloud* cloud, const int32_t* indices, int n_idx, sfmhip_cloud** out);
+/* the point count and the count of finite points (either may be NULL) */
+int sfmhip_cloud_size(const sfmhip_cloud* cloud, int32_t* n, int32_t* n_valid);
+/* the handle's points (what a handle born on the device holds) */
+int sfmhip_cloud_download(sfmhip_cloud* cloud, float* xyz /* 3 n */);
+/* With sfmhip_set_timing on (zeros while it is off): host-clock ms of the last voxel grid call on this handle -- key +
+ * sort, voxel reduce -- and of its last outlier call -- neighbour means, threshold + compaction. */
+int sfmhip_cloud_filter_last_timing(sfmhip_cloud* cloud, double ms4[4]);
+
 /* ---- colour region growing and the dendrometry bounds (reference src/Segmentation.cpp:3-66, src/DendrometryE.cpp:3-29) ----
  * pcl::RegionGrowingRGB over the index list of a PassThrough, on the same device-resident cloud.  The rules (DESIGN.md
  * f-8 has them in full; parity UNPINNED, PCL is not in the image; + marks what is our reading):

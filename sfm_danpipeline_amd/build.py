@@ -15,7 +15,7 @@ SO = os.path.join(HERE, "libsfmhip.so")
 # and want v_fma_f64 -- "fast-honor-pragmas", not "fast": the one function that must NOT contract, the trust-region decision
 # lm_decide (the same bits on the host and on the device), says so with a pragma, which plain "fast" ignores
 SOURCES = {"context.hip": "off", "match.hip": "off", "triangulate.hip": "off", "incremental.hip": "off",
-           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "segment.hip": "off", "poisson.hip": "off", "dendro.hip": "off", "ground.hip": "off", "trees.hip": "off", "mvs.hip": "off", "undistort.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
+           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "cloud_filter.hip": "off", "segment.hip": "off", "poisson.hip": "off", "dendro.hip": "off", "ground.hip": "off", "trees.hip": "off", "mvs.hip": "off", "undistort.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -130,6 +130,13 @@ def build_cloud_demo(force=False):
     normals, all on the unfiltered cloud as the reference calls them) on a PLY file (needs the GPU)."""
     return _build_host_exe(os.path.join(HERE, "sfm_cloud_selftest"),
                            ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "cloud_selftest.cpp"), force)
+
+
+def build_cloud_filter_demo(force=False):
+    """pcl::VoxelGrid and pcl::StatisticalOutlierRemoval as pcllite.h mirrors them, then computeNormals, on a PCD file; writes the
+    kept points and their normals as a binary PCD (needs the GPU)."""
+    return _build_host_exe(os.path.join(HERE, "sfm_cloud_filter_selftest"),
+                           ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "cloud_filter_selftest.cpp"), force)
 
 
 def build_mesh_demo(force=False):

@@ -15,6 +15,7 @@ PASS_AXIS, PASS_LO, PASS_HI = 0, 0.003, 0.83     # cloudPointFilter: setFilterFi
 RADIUS, MIN_PTS = 0.07, 150                      # removePoints: setRadiusSearch(0.07), setMinNeighborsInRadius(150)
 K_NORMALS = 10                                   # create_mesh: setKSearch(10)
 KMAX = 32
+MEAN_K_MAX = 63                                  # StatisticalOutlierRemoval's mean_k (one list slot per lane of a wave)
 AXES = {"x": 0, "y": 1, "z": 2}
 
 
@@ -75,6 +76,77 @@ class Cloud:
         out = np.empty((max(self.n, 1), 4), np.float32)
         _lib.check(_lib.lib().sfmhip_cloud_normals(self.h, int(k), _p(vp), _p(out)), "sfmhip_cloud_normals")
         return out[:self.n].copy()
+
+    @classmethod
+    def from_handle(cls, h, ctx):
+        """A cloud born on the device (the voxel grid's centroids, a selection): `xyz` is None until download()."""
+        self = cls.__new__(cls)
+        self.ctx, self.h, self.xyz = ctx, h, None
+        n = C.c_int32(0)
+        _lib.check(_lib.lib().sfmhip_cloud_size(self.h, C.byref(n), None), "sfmhip_cloud_size")
+        self.n = n.value
+        return self
+
+    def download(self):
+        """The points as float32 [n, 3] (kept as `xyz` from then on)."""
+        if self.xyz is None:
+            out = np.empty((max(self.n, 1), 3), np.float32)
+            _lib.check(_lib.lib().sfmhip_cloud_download(self.h, _p(out)), "sfmhip_cloud_download")
+            self.xyz = out[:self.n].copy()
+        return self.xyz
+
+    def select(self, idx):
+        """A new device cloud of the points idx (any order, duplicates allowed), gathered on the device."""
+        idx = np.ascontiguousarray(np.asarray(idx, np.int32).reshape(-1))
+        h = C.c_void_p()
+        _lib.check(_lib.lib().sfmhip_cloud_select(self.h, _p(idx) if len(idx) else None, len(idx), C.byref(h)), "sfmhip_cloud_select")
+        return Cloud.from_handle(h, self.ctx)
+
+    def voxel_grid(self, leaf, min_points=0, rgb=None, normals=None, return_cloud=False):
+        """PCL's VoxelGrid: a dict with `xyz` [m, 3] (the centroids, ascending voxel index), `voxel_of` [n]
+        (each point's output row, -1 for none), `rgb` [m] / `normals` [m, 3] when given (downsample_all_data) and, with
+        return_cloud, `cloud`: the centroids as a device cloud that was never on the host.  `leaf`: one size or three."""
+        lf = np.ascontiguousarray(np.broadcast_to(np.asarray(leaf, np.float32), (3,)))
+        n1 = max(self.n, 1)
+        col = None if rgb is None else np.ascontiguousarray(np.asarray(rgb, np.uint32).reshape(-1))
+        nrm = None if normals is None else np.ascontiguousarray(np.asarray(normals, np.float32).reshape(-1, 3))
+        if (col is not None and len(col) != self.n) or (nrm is not None and len(nrm) != self.n):
+            raise ValueError("rgb / normals must have one row per point")
+        oxyz, vox = np.empty((n1, 3), np.float32), np.empty(n1, np.int32)
+        ocol = None if col is None else np.empty(n1, np.uint32)
+        onrm = None if nrm is None else np.empty((n1, 3), np.float32)
+        m, h = C.c_int32(0), C.c_void_p()
+        opt = lambda a: None if a is None else _p(a)
+        _lib.check(_lib.lib().sfmhip_cloud_voxel_grid(self.h, _p(lf), int(min_points), opt(col), opt(nrm), _p(oxyz), opt(ocol), opt(onrm),
+                                                      _p(vox), C.byref(m), C.byref(h) if return_cloud else None),
+                   "sfmhip_cloud_voxel_grid")
+        out = {"xyz": oxyz[:m.value].copy(), "voxel_of": vox[:self.n].copy()}
+        if ocol is not None:
+            out["rgb"] = ocol[:m.value].copy()
+        if onrm is not None:
+            out["normals"] = onrm[:m.value].copy()
+        if return_cloud:
+            out["cloud"] = Cloud.from_handle(h, self.ctx)
+        return out
+
+    def statistical_outlier(self, mean_k=50, std_mul=1.0, negative=False, return_distances=False):
+        """Indices (input order) PCL's StatisticalOutlierRemoval keeps: mean distance to the mean_k nearest <= mean +
+        std_mul * stddev of those means (above it, if negative).  With return_distances: (indices, mean_dist [n], threshold)."""
+        if not 1 <= mean_k <= MEAN_K_MAX:
+            raise ValueError(f"mean_k must be in 1..{MEAN_K_MAX}")
+        out, m = np.empty(max(self.n, 1), np.int32), C.c_int32(0)
+        md, thr = np.empty(max(self.n, 1), np.float32), C.c_double(0.0)
+        _lib.check(_lib.lib().sfmhip_cloud_statistical_outlier(self.h, int(mean_k), float(std_mul), int(bool(negative)), _p(out),
+                                                               C.byref(m), _p(md), C.byref(thr)), "sfmhip_cloud_statistical_outlier")
+        kept = out[:m.value].copy()
+        return (kept, md[:self.n].copy(), thr.value) if return_distances else kept
+
+    def filter_last_timing(self):
+        """ms of the last voxel grid (key + sort, reduce) and outlier call (neighbour means, threshold + compaction) with
+        Context.set_timing on; zeros otherwise."""
+        ms = (C.c_double * 4)()
+        _lib.check(_lib.lib().sfmhip_cloud_filter_last_timing(self.h, ms), "sfmhip_cloud_filter_last_timing")
+        return list(ms)
 
     def close(self):
         if self.h:

@@ -342,13 +342,21 @@ int radius_grid(sfmhip_cloud* c, double radius) {
   return SFMHIP_OK;
 }
 
+}  // namespace
+
 // the k-NN grid: about KNN_OCCUPANCY points per occupied cell
-int knn_grid(sfmhip_cloud* c) {
+int sfmgrid::knn_grid(sfmhip_cloud* c) {
   if (c->kg.built) return SFMHIP_OK;
   return density_grid(c, whole_cloud(c), c->kg, KNN_OCCUPANCY);
 }
 
-int compact(sfmhip_cloud* c, int32_t* idx_out, int32_t* n_out) {
+double sfmgrid::knn_abs_eps(const sfmhip_cloud* c) {
+  double mag = 0;
+  for (int a = 0; a < 3; ++a) mag = std::max(mag, std::fabs(c->lo[a]) + std::fabs(c->hi[a]));
+  return (mag + c->kg.cell) * 1e-12;  // (the double rounding of a cell coordinate, with room to spare)
+}
+
+int sfmgrid::compact(sfmhip_cloud* c, int32_t* idx_out, int32_t* n_out) {
   hipStream_t st = c->ctx->stream;
   int *flags = c->ibuf[0], *off = c->ibuf[1], *out = c->ibuf[2], *dn = c->ibuf[3];
   SFM_TRY(scan(c, flags, off, (size_t)c->n, nullptr));  // (c->n >= 1: the entry points return early on an empty cloud)
@@ -363,6 +371,8 @@ int compact(sfmhip_cloud* c, int32_t* idx_out, int32_t* n_out) {
   *n_out = m;
   return SFMHIP_OK;
 }
+
+namespace {
 
 int radius_counts_dev(sfmhip_cloud* c, double radius, int cap, int* d_counts) {
   SFM_TRY(radius_grid(c, radius));
@@ -379,9 +389,7 @@ int run_knn(sfmhip_cloud* c, int k, int mode, const float* vp, int* d_idx, float
   SFM_TRY(knn_grid(c));
   hipStream_t st = c->ctx->stream;
   const GridDev g = c->kg.dev(c->n_valid);
-  double mag = 0;
-  for (int a = 0; a < 3; ++a) mag = std::max(mag, std::fabs(c->lo[a]) + std::fabs(c->hi[a]));
-  const double abs_eps = (mag + c->kg.cell) * 1e-12;  // (the double rounding of a cell coordinate, with room to spare)
+  const double abs_eps = knn_abs_eps(c);
   const float v0 = vp ? vp[0] : 0.f, v1 = vp ? vp[1] : 0.f, v2 = vp ? vp[2] : 0.f;
   if (c->n_valid > 0) {
     if (k <= 16)
@@ -400,40 +408,61 @@ int out_buffer(sfmhip_cloud* c, size_t bytes, void** p) { return sfm_ctx_dev_scr
 
 }  // namespace
 
-extern "C" int sfmhip_cloud_create(sfmhip_ctx* ctx, int n, const float* xyz, sfmhip_cloud** out) {
-  if (!ctx || !out || n < 0 || (n > 0 && !xyz)) return SFMHIP_ERR_ARG;
-  *out = nullptr;
-  SFM_HIP_TRY(hipSetDevice(ctx->device));
+namespace {
+
+int box_of(sfmhip_cloud* c) {
+  hipStream_t st = c->ctx->stream;
+  unsigned mm[7] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u};
+  if (c->n > 0) {
+    DevBufs B;
+    unsigned* d = nullptr;
+    SFM_TRY(B.alloc(&d, 7));
+    SFM_HIP_TRY(hipMemcpyAsync(d, mm, sizeof mm, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(cloud_minmax<FinitePoint>, dim3(std::min(blocks(c->n, 256), 1024u)), dim3(256), 0, st, c->xyz, c->n, FinitePoint(), d);
+    SFM_HIP_TRY(hipGetLastError());
+    SFM_HIP_TRY(hipMemcpyAsync(mm, d, sizeof mm, hipMemcpyDeviceToHost, st));
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+  }
+  c->n_valid = (int)mm[6];
+  for (int a = 0; a < 3; ++a) {
+    c->lo[a] = c->n_valid ? (double)sfmcloud::ord_val(mm[a]) : 0.0;
+    c->hi[a] = c->n_valid ? (double)sfmcloud::ord_val(mm[3 + a]) : 0.0;
+  }
+  return SFMHIP_OK;
+}
+
+}  // namespace
+
+int sfmgrid::adopt_device(sfmhip_ctx* ctx, float* d_xyz, int n, sfmhip_cloud** out) {
   sfmhip_cloud* c = new sfmhip_cloud();
   c->ctx = ctx;
   c->n = n;
-  bool any = false;
-  for (int i = 0; i < n; ++i) {
-    const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
-    if (!sfmcloud::finite3(x, y, z)) continue;
-    const double v[3] = {x, y, z};
-    for (int a = 0; a < 3; ++a) {
-      c->lo[a] = any ? std::min(c->lo[a], v[a]) : v[a];
-      c->hi[a] = any ? std::max(c->hi[a], v[a]) : v[a];
-    }
-    any = true;
-    ++c->n_valid;
-  }
-  int rc = sfm_dev_alloc(&c->xyz, (size_t)3 * std::max(n, 1));
-  if (rc == SFMHIP_OK && n > 0) {
-    hipError_t e = hipMemcpyAsync(c->xyz, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-      g_sfmhip_last_hip_error = (int)e;
-      rc = SFMHIP_ERR_HIP;
-    }
-  }
+  c->xyz = d_xyz;
+  const int rc = box_of(c);
   if (rc != SFMHIP_OK) {
     sfmhip_cloud_destroy(c);
     return rc;
   }
   *out = c;
   return SFMHIP_OK;
+}
+
+extern "C" int sfmhip_cloud_create(sfmhip_ctx* ctx, int n, const float* xyz, sfmhip_cloud** out) {
+  if (!ctx || !out || n < 0 || (n > 0 && !xyz)) return SFMHIP_ERR_ARG;
+  *out = nullptr;
+  SFM_HIP_TRY(hipSetDevice(ctx->device));
+  float* d = nullptr;
+  SFM_TRY(sfm_dev_alloc(&d, (size_t)3 * std::max(n, 1)));
+  if (n > 0) {
+    hipError_t e = hipMemcpyAsync(d, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+      g_sfmhip_last_hip_error = (int)e;
+      hipFree(d);
+      return SFMHIP_ERR_HIP;
+    }
+  }
+  return adopt_device(ctx, d, n, out);
 }
 
 extern "C" void sfmhip_cloud_destroy(sfmhip_cloud* c) {
@@ -447,6 +476,7 @@ extern "C" void sfmhip_cloud_destroy(sfmhip_cloud* c) {
   if (c->dnd && c->dnd_free) c->dnd_free(c->dnd);
   if (c->gnd && c->gnd_free) c->gnd_free(c->gnd);
   if (c->trs && c->trs_free) c->trs_free(c->trs);
+  if (c->flt && c->flt_free) c->flt_free(c->flt);
   hipFree(c->xyz);
   hipFree(c->tmp);
   for (int b = 0; b < 4; ++b) hipFree(c->ibuf[b]);

@@ -102,6 +102,9 @@ struct sfmhip_cloud {
   void (*gnd_free)(void*) = nullptr;
   void* trs = nullptr;           // trees.hip's state on this handle (frame coordinates, cell and voxel tables, keys, stage times), freed with it
   void (*trs_free)(void*) = nullptr;
+  void* flt = nullptr;           // cloud_filter.hip's grow-only device blocks on this handle (run tables, attributes, mean distances), freed with it
+  void (*flt_free)(void*) = nullptr;
+  double flt_ms[4] = {0, 0, 0, 0};  // cloud_filter.hip: key + sort, voxel reduce (last voxel grid); neighbour means, threshold + compaction (last outlier call)
 };
 
 namespace sfmgrid {
@@ -121,6 +124,15 @@ int grid_build(sfmhip_cloud* c, const GridSrc& src, Grid& g, double cell, bool c
 // points than `occupancy` (a surface fills few of the cells a volume estimate makes: cells shrink by the square root of
 // the excess)
 int density_grid(sfmhip_cloud* c, const GridSrc& src, Grid& g, double occupancy);
+// the handle's k-NN grid (about 16 points per occupied cell), built on first use, and the slack its ring searches give
+// the double rounding of a cell coordinate
+int knn_grid(sfmhip_cloud* c);
+double knn_abs_eps(const sfmhip_cloud* c);
+// both filters' compaction: the 0/1 flags in ibuf[0] -> the kept indices, in input order, on the host
+int compact(sfmhip_cloud* c, int32_t* idx_out, int32_t* n_out);
+// a handle over n points that are on the device already (d_xyz: 3 max(n, 1) floats from sfm_dev_alloc; the handle owns
+// it from here on, also when the call fails): the box by cloud_minmax, then n_valid
+int adopt_device(sfmhip_ctx* ctx, float* d_xyz, int n, sfmhip_cloud** out);
 
 #ifdef __HIPCC__
 __device__ __forceinline__ int cell_of(double v, double o, double cell, int D) {
@@ -157,6 +169,10 @@ __device__ __forceinline__ void row_span(const GridDev& g, int row, int xa, int 
 
 // the ordered keys (cloud.h) of the per-axis minima out[0..2] and maxima out[3..5] of the points ok(i, v) accepts
 // (v: the three coordinates of point i) and their count out[6], by integer atomics: order-free
+struct FinitePoint {  // cloud_minmax's predicate: the finite points
+  __device__ bool operator()(long long, const float* v) const { return sfmcloud::finite3(v[0], v[1], v[2]); }
+};
+
 template <class Ok>
 __global__ __launch_bounds__(256) void cloud_minmax(const float* xyz, int n, Ok ok, unsigned* out) {
   unsigned lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u}, cnt = 0;

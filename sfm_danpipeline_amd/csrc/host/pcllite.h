@@ -1,6 +1,7 @@
 // pcllite.h -- the few PCL 1.8.1 types map3D's step 10 passes around (reference src/Sfm.cpp:94-102, include/Sfm.h:182-186),
 // as plain stand-ins next to cvlite.h (PCL is not a dependency of this build), and the PCD reader that loads MAP3D.pcd
-// into them (pcl::io::loadPCDFile for PointXYZ and PointXYZRGB).  Header-only and C++14: the host mirror and the CPU tests include it.
+// into them (pcl::io::loadPCDFile for PointXYZ and PointXYZRGB), and pcl::VoxelGrid / pcl::StatisticalOutlierRemoval over the C
+// ABI.  Header-only and C++14: the host mirror and the CPU tests include it.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -12,6 +13,9 @@
 #include <sstream>
 #include <string>
 #include <vector>
+#include "../../../include/sfmhip.h"  // (the filter classes at the end forward to the C ABI)
+
+sfmhip_ctx* sfm_hip_context();  // hip_backend.h: the process-wide context of the host classes
 
 namespace pcl {
 
@@ -301,4 +305,138 @@ inline int loadPCDFile(const std::string& path, PointCloud<PointXYZRGB>& cloud) 
 }
 
 }  // namespace io
+
+// ---- pcl::VoxelGrid and pcl::StatisticalOutlierRemoval with PCL's setters and filter(output), forwarding to
+// sfmhip_cloud_voxel_grid / sfmhip_cloud_statistical_outlier (include/sfmhip.h, rules V1-V7 and S1-S5): code written
+// against PCL compiles against these.  Templates, so a program that never filters (the CPU tests) links without the library.
+namespace detail {
+
+template <typename T>
+struct Attr {  // what setDownsampleAllData averages besides x, y, z
+  static const bool rgb = false, normal = false;
+  static uint32_t colour(const T&) { return 0; }
+  static void set_colour(T&, uint32_t) {}
+  static void get_normal(const T&, float*) {}
+  static void set_normal(T&, const float*) {}
+};
+template <>
+struct Attr<PointXYZRGB> {
+  static const bool rgb = true, normal = false;
+  static uint32_t colour(const PointXYZRGB& p) { return p.rgba; }
+  static void set_colour(PointXYZRGB& p, uint32_t c) { p.rgba = c; }
+  static void get_normal(const PointXYZRGB&, float*) {}
+  static void set_normal(PointXYZRGB&, const float*) {}
+};
+template <>
+struct Attr<PointNormal> {  // (the curvature is not averaged: it is left 0)
+  static const bool rgb = false, normal = true;
+  static uint32_t colour(const PointNormal&) { return 0; }
+  static void set_colour(PointNormal&, uint32_t) {}
+  static void get_normal(const PointNormal& p, float* n) { n[0] = p.normal_x, n[1] = p.normal_y, n[2] = p.normal_z; }
+  static void set_normal(PointNormal& p, const float* n) { p.normal_x = n[0], p.normal_y = n[1], p.normal_z = n[2]; }
+};
+
+inline void filter_check(int rc, const char* what) {
+  if (rc != SFMHIP_OK) {
+    std::fprintf(stderr, "[pcl] %s: %s\n", what, sfmhip_error_string(rc));
+    std::abort();  // (no CPU fallback behind the drop-in)
+  }
+}
+
+template <typename T>
+inline sfmhip_cloud* upload(const PointCloud<T>& c) {
+  std::vector<float> xyz(3 * c.size() + 3);
+  for (size_t i = 0; i < c.size(); ++i) xyz[3 * i] = c.points[i].x, xyz[3 * i + 1] = c.points[i].y, xyz[3 * i + 2] = c.points[i].z;
+  sfmhip_cloud* h = nullptr;
+  filter_check(sfmhip_cloud_create(sfm_hip_context(), (int)c.size(), xyz.data(), &h), "sfmhip_cloud_create");
+  return h;
+}
+
+template <typename T>
+inline void like(const PointCloud<T>& in, size_t m, PointCloud<T>& out) {
+  out.points.resize(m);
+  out.width = (uint32_t)m;
+  out.height = 1;
+  out.is_dense = true;  // (both filters drop the non-finite points)
+  for (int a = 0; a < 4; ++a) out.sensor_origin_[a] = in.sensor_origin_[a];
+}
+
+}  // namespace detail
+
+template <typename PointT>
+class VoxelGrid {
+ public:
+  void setInputCloud(const typename PointCloud<PointT>::Ptr& cloud) { input_ = cloud; }
+  void setLeafSize(float lx, float ly, float lz) { leaf_[0] = lx, leaf_[1] = ly, leaf_[2] = lz; }
+  void setMinimumPointsNumberPerVoxel(unsigned int min_points) { min_points_ = min_points; }
+  void setDownsampleAllData(bool downsample) { all_data_ = downsample; }
+  // the centroids in ascending voxel index; a grid of more than INT32_MAX voxels warns and copies the input, as PCL does
+  void filter(PointCloud<PointT>& output) {
+    typedef detail::Attr<PointT> A;
+    const PointCloud<PointT> in = input_ ? *input_ : PointCloud<PointT>();
+    const size_t n = in.size();
+    const bool rgb = all_data_ && A::rgb, nrm = all_data_ && A::normal;
+    std::vector<uint32_t> col(rgb ? n + 1 : 0), ocol(rgb ? n + 1 : 0);
+    std::vector<float> nv(nrm ? 3 * n + 3 : 0), onv(nrm ? 3 * n + 3 : 0), oxyz(3 * n + 3);
+    for (size_t i = 0; i < n && rgb; ++i) col[i] = A::colour(in.points[i]);
+    for (size_t i = 0; i < n && nrm; ++i) A::get_normal(in.points[i], &nv[3 * i]);
+    sfmhip_cloud* h = detail::upload(in);
+    int32_t m = 0;
+    const int rc = sfmhip_cloud_voxel_grid(h, leaf_, (int)min_points_, rgb ? col.data() : nullptr, nrm ? nv.data() : nullptr, oxyz.data(),
+                                           rgb ? ocol.data() : nullptr, nrm ? onv.data() : nullptr, nullptr, &m, nullptr);
+    sfmhip_cloud_destroy(h);
+    if (rc == SFMHIP_ERR_UNSUPPORTED) {
+      std::fprintf(stderr, "[pcl::VoxelGrid::applyFilter] Leaf size is too small for the input dataset. Integer indices would overflow.\n");
+      output = in;
+      return;
+    }
+    detail::filter_check(rc, "sfmhip_cloud_voxel_grid");
+    PointCloud<PointT> out;
+    detail::like(in, (size_t)m, out);
+    for (int32_t r = 0; r < m; ++r) {
+      PointT p = PointT();
+      p.x = oxyz[3 * r], p.y = oxyz[3 * r + 1], p.z = oxyz[3 * r + 2];
+      if (rgb) A::set_colour(p, ocol[r]);
+      if (nrm) A::set_normal(p, &onv[3 * r]);
+      out.points[r] = p;
+    }
+    output = out;
+  }
+
+ private:
+  typename PointCloud<PointT>::Ptr input_;
+  float leaf_[3] = {0, 0, 0};
+  unsigned int min_points_ = 0;
+  bool all_data_ = true;
+};
+
+template <typename PointT>
+class StatisticalOutlierRemoval {
+ public:
+  void setInputCloud(const typename PointCloud<PointT>::Ptr& cloud) { input_ = cloud; }
+  void setMeanK(int mean_k) { mean_k_ = mean_k; }
+  void setStddevMulThresh(double std_mul) { std_mul_ = std_mul; }
+  void setNegative(bool negative) { negative_ = negative; }
+  // the kept points in input order (mean_k in 1..63; more finite points than mean_k)
+  void filter(PointCloud<PointT>& output) {
+    const PointCloud<PointT> in = input_ ? *input_ : PointCloud<PointT>();
+    std::vector<int32_t> idx(in.size() + 1);
+    int32_t m = 0;
+    sfmhip_cloud* h = detail::upload(in);
+    const int rc = sfmhip_cloud_statistical_outlier(h, mean_k_, std_mul_, negative_ ? 1 : 0, idx.data(), &m, nullptr, nullptr);
+    sfmhip_cloud_destroy(h);
+    detail::filter_check(rc, "sfmhip_cloud_statistical_outlier");
+    PointCloud<PointT> out;
+    detail::like(in, (size_t)m, out);
+    for (int32_t r = 0; r < m; ++r) out.points[r] = in.points[idx[r]];
+    output = out;
+  }
+
+ private:
+  typename PointCloud<PointT>::Ptr input_;
+  int mean_k_ = 1;          // PCL's defaults
+  double std_mul_ = 0.0;
+  bool negative_ = false;
+};
+
 }  // namespace pcl

@@ -60,10 +60,6 @@ __global__ void seg_gather(const float* xyz, const int* ind, int m, float* out) 
   out[3 * (size_t)r + 2] = xyz[3 * j + 2];
 }
 
-struct FinitePoint {  // cloud_minmax's predicate: the finite points
-  __device__ bool operator()(long long, const float* v) const { return sfmcloud::finite3(v[0], v[1], v[2]); }
-};
-
 __global__ __launch_bounds__(64 * WAVES) void seg_knn(GridDev g, double abs_eps, int k, int* out_idx, float* out_d2) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * WAVES + (threadIdx.x >> 6);
