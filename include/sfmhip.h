@@ -328,6 +328,27 @@ int sfmhip_pose_last_flags(sfmhip_ctx* ctx);
  *   7. on success EPnP runs once more on all inliers (the float points back as f64, undistortPoints in f64);
  *   8. which pose 3.4.1 returns †: the RANSAC model; the refit only decides success (EPnP always succeeds).  rvec / tvec
  *      follow that reading; rvec_ransac / tvec_ransac and rvec_refit / tvec_refit hand out both.
+ *  options and edges
+ *   9. max_iters == 0: no sample is drawn; a view of more than 5 correspondences has status 0, 0 inliers, 0 iterations and
+ *      zero outputs (a view of exactly 5 is still its one sample).  max_iters < 0 is refused.  `iterations` counts the
+ *      samples tried, skipped ones included, so it never exceeds max_iters;
+ *  10. confidence is clamped to [0, 1] inside RANSACUpdateNumIters: at or below 0 the limit drops to 0 with the first model
+ *      that has more than 4 inliers, and the loop ends there; at or above 1 the limit never drops and the loop runs
+ *      max_iters iterations.  Nothing is refused;
+ *  11. a threshold of 0 accepts exact reprojections only (in practice: no model, max_iters iterations); thr * thr is taken
+ *      to float32, so a threshold above 1.8e19 px is infinite and accepts every error that is not NaN;
+ *  12. non-finite input: the call returns (every loop of a solve has a fixed trip count).  A sample that holds a NaN or
+ *      an Inf object coordinate fails rule 4c's test, is skipped and sets bits 0 and 1 of sfmhip_pnp_last_flags; one that
+ *      holds a non-finite pixel sets bit 1 and gives a model with NaN entries, which has no inlier.  A correspondence with a non-finite
+ *      coordinate has a NaN error and is never an inlier, so it is outside the mask and the refit; a view of nothing
+ *      else has status 0 after max_iters iterations.  Other views are not affected;
+ *  13. Rodrigues(R) within 1e-5 of a half turn (|axis part| / 2 < 1e-5, trace < 1) takes the library's diagonal formula:
+ *      rx >= 0, so the vector may describe the turn's other sense (up to twice the angle's distance from pi away), and
+ *      an error d in a diagonal entry near -1 moves the rotation by up to 2 sqrt(d); within 1e-5 of the identity the
+ *      vector is exactly zero; a matrix with an entry outside [-100, 100) or NaN gives the zero vector.
+ * SFMHIP_ERR_ARG, with nothing written: ctx, offsets, K, dist, thresholds, status, rvec, tvec or inliers NULL; n_views < 0;
+ * max_iters < 0; offsets[0] != 0 or decreasing offsets; xyz or xy NULL with offsets[n_views] > 0.  n_views == 0 is
+ * SFMHIP_OK and writes nothing.
  * offsets: n_views + 1, offsets[0] = 0; xyz: 3 doubles, xy: 2 doubles (pixels) per correspondence; thresholds: pixels, one
  * per view; status / inliers / iterations: per view; rvec / tvec (and the nullable _ransac, _refit pairs): 3 doubles per
  * view, zero without a model; mask (nullable): 1 byte per correspondence, the best model's inliers.  Views are
@@ -340,7 +361,9 @@ int sfmhip_pnp_ransac(sfmhip_ctx* ctx, int n_views, const int32_t* offsets, cons
                       int32_t* iterations /* nullable */);
 /* The EPnP solve of rule 3 alone for explicit point sets of any size >= 5 (xy_normalised: 2 doubles per point, already
  * undistorted and normalised): R 9 doubles (row-major), t 3 doubles per problem, zero for a set rule 4c refuses.  What
- * the RANSAC runs per sample and the refit per view, exposed for sample-level checks. */
+ * the RANSAC runs per sample and the refit per view, exposed for sample-level checks.  SFMHIP_ERR_ARG, with nothing
+ * written: ctx, offsets, R or t NULL; n_problems < 0; offsets[0] != 0 or decreasing offsets; xyz or xy_normalised NULL; a
+ * problem of fewer than 5 points.  n_problems == 0 is SFMHIP_OK and writes nothing. */
 int sfmhip_pnp_epnp(sfmhip_ctx* ctx, int n_problems, const int32_t* offsets, const double* xyz,
                     const double* xy_normalised, double* R, double* t);
 /* OR over the solves of the last sfmhip_pnp_ransac / sfmhip_pnp_epnp call: bit 0 = a rank-deficient control-point

@@ -140,6 +140,75 @@ def scene(seed, n, dist=DIST0, noise=0.0, outliers=0.0, outlier_shift=0.0):
     return dict(R=R, t=t, X=X, xy=xy, truth=truth)
 
 
+def posed_scene(seed, n, R=None, tz=6.0, scale=(0.6, 0.6, 0.6), dist=DIST0, noise=0.0):
+    """scene with the rotation (None: scene's own draw), the depth and the per-axis half extent of the cloud as arguments;
+    the camera's shift grows with the depth (tz / 6 of scene's), so a near camera keeps the cloud in front of it.  With the
+    defaults it is scene(seed, n, dist, noise) bit for bit (test_pnp_cpu.py asserts it)."""
+    g = np.random.default_rng(seed)
+    own = rot(g.normal(0, 0.4, 3))
+    R = own if R is None else np.asarray(R, np.float64)
+    t = np.array([0.0, 0.0, tz]) + (tz / 6.0) * g.normal(0, 0.5, 3)
+    half = np.asarray(scale, np.float64)
+    X = g.uniform(-half, half, (n, 3))
+    xy = project(X, R, t, K, dist)
+    if noise:
+        xy = xy + g.normal(0, noise, xy.shape)
+    return dict(R=R, t=t, X=X, xy=xy, truth=np.ones(n, np.uint8))
+
+
+def axis_rotation(axis, angle):
+    """the rotation by angle about axis (any length), from rot"""
+    a = np.asarray(axis, np.float64)
+    return rot(a / np.linalg.norm(a) * angle)
+
+
+def _random_axis(seed):
+    a = np.random.default_rng(90000 + seed).normal(0, 1, 3)
+    return a / np.linalg.norm(a)
+
+
+def slab(ratio):
+    """the family of clouds whose z extent is `ratio` of the other two"""
+    return lambda seed, n, dist=DIST0, noise=0.0: posed_scene(seed, n, scale=(0.6, 0.6, 0.6 * ratio), dist=dist, noise=noise)
+
+
+# geometry off scene's default: name -> f(seed, n, dist, noise)
+FAMILIES = {
+    "half_turn": lambda seed, n, dist=DIST0, noise=0.0: posed_scene(seed, n, R=axis_rotation(_random_axis(seed), np.pi), dist=dist, noise=noise),
+    "half_turn_1e-7": lambda seed, n, dist=DIST0, noise=0.0: posed_scene(seed, n, R=axis_rotation(_random_axis(seed), np.pi - 1e-7), dist=dist,
+                                                                         noise=noise),
+    "identity": lambda seed, n, dist=DIST0, noise=0.0: posed_scene(seed, n, R=np.eye(3), dist=dist, noise=noise),
+    "near": lambda seed, n, dist=DIST0, noise=0.0: posed_scene(seed, n, tz=1.5, scale=(0.3, 0.3, 0.3), dist=dist, noise=noise),
+    "far60": lambda seed, n, dist=DIST0, noise=0.0: posed_scene(seed, n, tz=60.0, dist=dist, noise=noise),
+    "far150": lambda seed, n, dist=DIST0, noise=0.0: posed_scene(seed, n, tz=150.0, scale=(15.0, 15.0, 15.0), dist=dist, noise=noise),
+    "slab_1e-1": slab(1e-1), "slab_1e-2": slab(1e-2), "slab_1e-3": slab(1e-3), "slab_1e-4": slab(1e-4), "slab_1e-5": slab(1e-5),
+}
+
+
+def outlier_scene(seed, n, frac, dist=DIST0):
+    """ransac_scene with the outlier share as an argument: frac of the points displaced by >= 20 thresholds, 0.5 px
+    inlier noise, the reference's threshold"""
+    base = scene(seed, n, dist, noise=0.5)
+    thr = 0.006 * float(base["xy"].max())
+    sc = scene(seed, n, dist, noise=0.5, outliers=frac, outlier_shift=30 * thr)
+    sc["thr"] = 0.006 * float(sc["xy"].max())
+    return sc
+
+
+def nonfinite_scene(L, bad):
+    """ransac_scene(3, 300, DIST1) with `bad` in one coordinate of the 3-D point that the first sample draws first and in
+    one of the 2-D point that the second sample draws first, so that solves meet them.  Returns (scene, the two rows)."""
+    sc = ransac_scene(3, 300, DIST1)
+    samp = np.zeros(10, np.int32)
+    L.pnp_samples(300, 2, samp.ctypes.data)
+    i, j = int(samp[0]), int(samp[5])
+    assert i != j
+    X, xy = sc["X"].copy(), sc["xy"].copy()
+    X[i, 1] = bad
+    xy[j, 0] = bad
+    return dict(sc, X=X, xy=xy), (i, j)
+
+
 def ransac_scene(seed, n, dist=DIST0):
     """30 % outliers displaced by >= 20 thresholds, 0.5 px inlier noise, the reference's threshold"""
     base = scene(seed, n, dist, noise=0.5)

@@ -96,6 +96,34 @@ def _f32(a):
     return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
 
 
+def _replay(L, sc, dist, thr, its, confidence=0.99, max_iters=1000):
+    """ptsetreg.cpp's loop over the first `its` iterations of a view (its None: until its own limit ends it): per-iteration
+    counts from the stub's sample solver, the limit from the oracle.  Returns (the limit it ends with, the best count, the
+    best model), and with its None the number of iterations run as a fourth."""
+    n = len(sc["X"])
+    free = its is None
+    samp = np.zeros(5 * max(max_iters if free else its, 1), np.int32)
+    L.pnp_samples(n, len(samp) // 5, samp.ctypes.data)
+    fx, fy = sc["X"].astype(np.float32), sc["xy"].astype(np.float32)
+    Kc, dc = np.ascontiguousarray(S.K.reshape(9)), np.ascontiguousarray(dist)
+    best, niters, best_model = 0, max_iters, None
+    it = -1
+    while it + 1 < (niters if free else its):
+        it += 1
+        assert it < niters, "the loop ran past its own limit"
+        s = samp[5 * it:5 * it + 5]
+        a, b = np.ascontiguousarray(fx[s]), np.ascontiguousarray(fy[s])
+        model = np.zeros(6)
+        ok = L.pnp_sample(a.ctypes.data, b.ctypes.data, Kc.ctypes.data, dc.ctypes.data, model.ctypes.data)
+        if ok & 0xff == 0:
+            continue
+        cnt = L.pnp_count(n, fx.ctypes.data, fy.ctypes.data, Kc.ctypes.data, dc.ctypes.data, model.ctypes.data, thr, None)
+        if cnt > max(best, 4):
+            best, best_model = cnt, model.copy()
+            niters = orc_score.ransac_update_num_iters(confidence, (n - cnt) / n, 5, niters)
+    return (niters, best, best_model, it + 1) if free else (niters, best, best_model)
+
+
 @pytest.mark.parametrize("dist", [S.DIST0, S.DIST1], ids=["nodist", "dist"])
 def test_ransac_masks_outliers_and_stops_by_the_rule(L, dist):
     """30 % outliers displaced by >= 20 thresholds, 0.5 px inlier noise, the reference's threshold, 20 scenes"""
@@ -119,23 +147,7 @@ def test_ransac_masks_outliers_and_stops_by_the_rule(L, dist):
         # the stopping rule, replayed: per-iteration counts from the stub's sample solver, the limit from the oracle
         its = int(r["iterations"][0])
         assert 0 < its <= 1000
-        samp = np.zeros(5 * its, np.int32)
-        L.pnp_samples(n, its, samp.ctypes.data)
-        fx, fy = sc["X"].astype(np.float32), sc["xy"].astype(np.float32)
-        Kc, dc = np.ascontiguousarray(S.K.reshape(9)), np.ascontiguousarray(dist)
-        best, niters, best_model = 0, 1000, None
-        for it in range(its):
-            assert it < niters, "the loop ran past its own limit"
-            s = samp[5 * it:5 * it + 5]
-            a, b = np.ascontiguousarray(fx[s]), np.ascontiguousarray(fy[s])
-            model = np.zeros(6)
-            ok = L.pnp_sample(a.ctypes.data, b.ctypes.data, Kc.ctypes.data, dc.ctypes.data, model.ctypes.data)
-            if ok & 0xff == 0:
-                continue
-            cnt = L.pnp_count(n, fx.ctypes.data, fy.ctypes.data, Kc.ctypes.data, dc.ctypes.data, model.ctypes.data, thr, None)
-            if cnt > max(best, 4):
-                best, best_model = cnt, model.copy()
-                niters = orc_score.ransac_update_num_iters(0.99, (n - cnt) / n, 5, niters)
+        niters, best, best_model = _replay(L, sc, dist, thr, its)
         assert its == niters and best == int(r["inliers"][0])
         assert np.array_equal(best_model[:3], r["rvec_ransac"][0]) and np.array_equal(best_model[3:], r["tvec_ransac"][0])
         # the returned pose is the RANSAC model; both it and the refit are close to ground truth
@@ -218,3 +230,298 @@ def test_find_camera_pose_pnp_wrapper_rules(L):
     assert pnp.accept_pose(10, 10, ok, to_matrix=lambda r: np.diag([1.0, 1.0, 0.5]) @ pnp.rodrigues(r)) is not None
     assert pnp.accept_pose(10, 10, ok, to_matrix=lambda r: (1 + 1e-9) * pnp.rodrigues(r)) is not None
     assert pnp.reference_threshold(sc["xy"]) == 0.006 * sc["xy"].max()
+
+
+# ---------------------------------------------------------------- the branches, options and geometry off the default scene
+HALF_TURN_EPS = (0.0, 1e-12, 1e-9, 1e-7, 5e-6, 2e-5, 1e-3)
+RODRIGUES_AXES = [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1), (0, 1, -1), (1, 0, -1), (1, -1, 0), (-1, -1, -1),
+                  (1e-4, 1, -1), (0.3, -0.5, 0.8), (-0.7, 0.2, 0.1), (-0.2, -0.9, 0.4)]
+# measured worst |rot(rv) - R|max outside the s < 1e-5 branch (half turn: eps 2e-5, 1e-3; identity: 1.1e-5, 1e-4) and at
+# eps <= 1e-12 of a half turn (see test_rodrigues_near_a_half_turn / _near_the_identity); asserted at 10 x
+RODRIGUES_WORST = 1.57e-11
+RODRIGUES_BOUND = 10 * RODRIGUES_WORST
+
+
+def _exact_rotation(axis, angle):
+    """Rodrigues' formula in 80-bit arithmetic, rounded once to f64: the input matrices are the rotations themselves to
+    half an ulp per entry, not a product that carries its own rounding"""
+    assert np.finfo(np.longdouble).eps < 1e-18
+    k = np.asarray(axis, np.longdouble)
+    k = k / np.sqrt(np.sum(k * k))
+    th = np.longdouble(angle)
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]], np.longdouble)
+    return (np.eye(3, dtype=np.longdouble) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx)).astype(np.float64)
+
+
+def _to_vector(L, R):
+    rv = np.full(3, 7.0)
+    fl = L.pnp_rodrigues_to_vector(np.ascontiguousarray(R, np.float64).reshape(9).ctypes.data, rv.ctypes.data)
+    return rv, fl
+
+
+def test_rodrigues_near_a_half_turn(L):
+    """rodrigues_to_vector's s < 1e-5, c <= 0 branch (the axis from the diagonal, the signs from R[1], R[2], the zero-rx
+    sign fix by R[5]): angles pi - eps about 14 axes (+-x, +-y, +-z, axes with one zero or one tiny component, with
+    negative R[1] / R[2], three generic ones), the matrix from 80-bit arithmetic rounded once, |rot(rv) - R|max with
+    numpy's rot.  Inside the branch (eps < 1e-5) the library takes rx >= 0, i.e. the half turn's other sense: its error is
+    up to 2 eps, the angle defect counted twice.  Measured worst: eps 0: 5.4e-14; 1e-12: 1.0e-12; 1e-9: 1.0e-9; 1e-7:
+    2.0e-7; 5e-6: 1.0e-5 (= 2 eps + 1.3e-12); outside the branch 2e-5: 6.0e-12 (1.08e-11 on rot's and scipy's matrices);
+    1e-3: 8.6e-14 (3.9e-13).  Asserted: 10 x the
+    worst outside the branch (RODRIGUES_BOUND = 1.57e-10, set by the identity side's 1.57e-11) there and at eps <= 1e-12,
+    2 eps + that bound inside.
+    The same rotations as numpy's rot and scipy's Rotation build them (a few roundings per entry: within 4 ulp of 1 of the
+    exact matrix, asserted; measured d <= 5.6e-16) go through the branch too: the diagonal formula takes the square root
+    of (R[ii] + 1) / 2, so an input error d in a diagonal entry of -1 turns up to sqrt(d / 2) of a zero axis component,
+    in two components at most, and the rotation moves by up to 2 sqrt(d) (4.7e-8 at d = 5.6e-16).  Measured worst 1.42e-8
+    (eps = 1e-9, axes (0,1,-1), (1,0,-1), (1,-1,0) as rot builds them); asserted at 2 eps + 2 sqrt(d) + RODRIGUES_BOUND
+    inside the branch with d measured per matrix, at RODRIGUES_BOUND outside it.  That is the library's conditioning at a
+    half turn, restated, not corrected."""
+    from scipy.spatial.transform import Rotation
+    for eps in HALF_TURN_EPS:
+        inside = eps < 1e-5
+        worst = worst_noisy = 0.0
+        for axis in RODRIGUES_AXES:
+            a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+            R = _exact_rotation(axis, math.pi - eps)
+            rv, fl = _to_vector(L, R)
+            assert fl == 0 and np.all(np.isfinite(rv))
+            err = float(np.abs(S.rot(rv) - R).max())
+            worst = max(worst, err)
+            assert err <= (2 * eps if inside and eps > 1e-12 else 0.0) + RODRIGUES_BOUND, (eps, axis, err)
+            for Rn in (S.rot(a * (math.pi - eps)), Rotation.from_rotvec(a * (math.pi - eps)).as_matrix()):
+                d = float(np.abs(Rn - R).max())
+                assert d <= 4 * 2.0 ** -52, "the references disagree"
+                rv, fl = _to_vector(L, Rn)
+                err = float(np.abs(S.rot(rv) - Rn).max())
+                worst_noisy = max(worst_noisy, err)
+                assert fl == 0 and err <= (2 * eps + 2 * math.sqrt(d) if inside else 0.0) + RODRIGUES_BOUND, (eps, axis, err, d)
+        print(f"MEASURE rodrigues half turn eps={eps:g} exact-input worst {worst:.3e} rot/scipy-input worst {worst_noisy:.3e}")
+
+
+def test_rodrigues_near_the_identity(L):
+    """rodrigues_to_vector's s < 1e-5, c > 0 branch: angles 0, 1e-12, 1e-7 and 9e-6 about the same axes give exactly the
+    zero vector (the identity is the first camera); 1.1e-5 and 1e-4, just outside it, give the rotation back.  Measured
+    worst outside: 1.57e-11 at 1.1e-5 (acos next to 1), 2.4e-12 at 1e-4; asserted at 10 x: RODRIGUES_BOUND.  An entry >= 100
+    or not a number gives the zero vector and no flag."""
+    for ang in (0.0, 1e-12, 1e-7, 9e-6):
+        for axis in RODRIGUES_AXES:
+            for R in (_exact_rotation(axis, ang), S.axis_rotation(axis, ang) if ang else np.eye(3)):
+                rv, fl = _to_vector(L, R)
+                assert fl == 0 and np.array_equal(rv, np.zeros(3)), (ang, axis)
+    for ang in (1.1e-5, 1e-4):
+        worst = 0.0
+        for axis in RODRIGUES_AXES:
+            for R in (_exact_rotation(axis, ang), S.axis_rotation(axis, ang)):
+                rv, fl = _to_vector(L, R)
+                worst = max(worst, float(np.abs(S.rot(rv) - R).max()))
+                assert fl == 0
+        print(f"MEASURE rodrigues identity side angle={ang:g} worst {worst:.3e}")
+        assert worst <= RODRIGUES_BOUND
+    base = S.axis_rotation((0.3, -0.5, 0.8), 0.7)
+    for k in range(9):
+        for bad in (100.0, 1e300, np.nan, np.inf, -np.inf, -100.5):
+            R = base.copy().reshape(9)
+            R[k] = bad
+            rv, fl = _to_vector(L, R)
+            assert fl == 0 and np.array_equal(rv, np.zeros(3)), (k, bad)
+    R = base.copy().reshape(9)
+    R[4] = -100.0                                                           # (the interval is [-100, 100): -100 goes on to the SVD)
+    rv, fl = _to_vector(L, R)
+    assert np.all(np.isfinite(rv)) and np.any(rv)
+
+
+def test_posed_and_outlier_scenes_restate_the_default_ones():
+    """posed_scene / outlier_scene with the defaults are scene / ransac_scene bit for bit (measured constants hang on them)"""
+    for seed in range(5):
+        for a, b in ((S.scene(seed, 50, S.DIST1, noise=0.3), S.posed_scene(seed, 50, dist=S.DIST1, noise=0.3)),
+                     (S.ransac_scene(seed, 50, S.DIST1), S.outlier_scene(seed, 50, 0.3, S.DIST1))):
+            assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+
+
+# measured worst (rotation angle, relative translation error) per family over SEEDS x both distortions x n in (5, 6, 10, 100,
+# 2000) (see test_epnp_noise_free_off_the_default_geometry); asserted at 10 x
+FAMILY_WORST = {
+    "half_turn": (1.80e-13, 6.53e-14), "half_turn_1e-7": (1.58e-13, 4.04e-14), "identity": (1.72e-13, 6.59e-14),
+    "near": (7.80e-14, 2.89e-14), "far60": (1.42e-11, 3.37e-12), "far150": (1.20e-13, 4.52e-14),
+    "slab_1e-1": (6.91e-13, 7.41e-14), "slab_1e-2": (1.47e-12, 8.09e-14), "slab_1e-3": (1.08e-12, 7.76e-14),
+    "slab_1e-4": (1.40e-12, 1.68e-13), "slab_1e-5": (6.26e-13, 9.48e-14),
+}
+
+
+@pytest.mark.parametrize("family", list(FAMILY_WORST))
+def test_epnp_noise_free_off_the_default_geometry(L, family):
+    """EPnP on exact correspondences against ground truth where scene never goes: a rotation of exactly pi and of
+    pi - 1e-7 about a random axis (the refit's Rodrigues is then in its half-turn branch), R = I, a camera 1.5 units from a
+    cloud of half extent 0.3, 60 units from the default cloud, 150 units from one of half extent 15, and slabs whose z
+    extent is 1e-1 ... 1e-5 of the others (1e-5: solved, four decades of the covariance's condition from the rank limit).
+    20 seeds, both distortions, n in (5, 6, 10, 100, 2000).  Measured worst (angle rad, relative translation): half_turn
+    1.80e-13 6.53e-14; half_turn_1e-7 1.58e-13 4.04e-14; identity 1.72e-13 6.59e-14; near 7.80e-14 2.89e-14; far60
+    1.42e-11 3.37e-12; far150 1.20e-13 4.52e-14; slabs 1e-1 ... 1e-5: 6.91e-13 7.41e-14, 1.47e-12 8.09e-14, 1.08e-12
+    7.76e-14, 1.40e-12 1.68e-13, 6.26e-13 9.48e-14.  Asserted at 10 x, per family."""
+    worst_a = worst_t = 0.0
+    for dist in (S.DIST0, S.DIST1):
+        for n in (5, 6, 10, 100, 2000):
+            for seed in SEEDS:
+                sc = S.FAMILIES[family](seed, n, dist)
+                R, t, fl = S.stub_epnp(L, [sc["X"]], [S.normalise(sc["xy"], S.K, dist)])
+                assert fl == 0, (n, seed)
+                worst_a = max(worst_a, S.rot_angle(R[0], sc["R"]))
+                worst_t = max(worst_t, float(np.linalg.norm(t[0] - sc["t"]) / np.linalg.norm(sc["t"])))
+    print(f"MEASURE epnp family={family} angle {worst_a:.3e} trans {worst_t:.3e}")
+    assert worst_a <= 10 * FAMILY_WORST[family][0] and worst_t <= 10 * FAMILY_WORST[family][1]
+
+
+def _rank_ratio(X):
+    """third over first singular value of the centred cloud's covariance, in 80-bit sums"""
+    Xl = np.asarray(X, np.longdouble)
+    d = Xl - Xl.mean(0)
+    return np.linalg.svd((d.T @ d).astype(np.float64), compute_uv=False)[[2, 0]]
+
+
+def test_epnp_slabs_at_the_rank_limit(L):
+    """FLAG_RANK_DEFICIENT is D[2] <= 1e-12 D[0] on the covariance's singular values, i.e. a thickness ratio of 1e-6 times
+    the ratio of the sample spreads.  Over 20 seeds, both distortions, n in (5, 6, 10, 100, 2000): no 1e-5 slab flags, every
+    1e-7 slab flags and returns zeros, and 1e-6 is the first ratio of the ladder at which a set flags: it sits on the limit,
+    and which side a set falls on follows its own z spread against its widest (measured: 174 of 200 flag, most of the
+    others at n <= 10).  Every 1e-6 set must fall on the side numpy's singular values of the same covariance put it on,
+    unless they are within 1e-6 of the limit (measured: none is); a flagged set returns zeros, an unflagged one the pose
+    (measured worst angle 1.34e-13; asserted at the 1e-5 slab's bound)."""
+    flagged = 0
+    for dist in (S.DIST0, S.DIST1):
+        for n in (5, 6, 10, 100, 2000):
+            for seed in SEEDS:
+                for ratio, want in ((1e-5, 0), (1e-6, None), (1e-7, 1)):
+                    sc = S.slab(ratio)(seed, n, dist)
+                    R, t, fl = S.stub_epnp(L, [sc["X"]], [S.normalise(sc["xy"], S.K, dist)])
+                    assert fl in (0, pnp.FLAG_RANK_DEFICIENT)
+                    if want is None:
+                        d2, d0 = _rank_ratio(sc["X"])
+                        if abs(d2 / (1e-12 * d0) - 1) > 1e-6:
+                            assert fl == (1 if d2 <= 1e-12 * d0 else 0), (n, seed)
+                        flagged += fl
+                    else:
+                        assert fl == want, (ratio, n, seed)
+                    if fl:
+                        assert not np.any(R) and not np.any(t)
+                    else:
+                        assert S.rot_angle(R[0], sc["R"]) <= 10 * FAMILY_WORST["slab_1e-5"][0]
+    print(f"MEASURE slabs of ratio 1e-6 flagged: {flagged} of 200")
+    assert 0 < flagged < 200
+
+
+RANSAC_SHARES = (0.45, 0.5, 0.55, 0.6, 0.65)
+
+
+@pytest.mark.parametrize("frac", RANSAC_SHARES)
+def test_ransac_at_higher_outlier_shares(L, frac):
+    """outlier_scene(seed, 200, frac, DIST1), seeds 0-5: the stopping rule lets these run 89, 145, 247, 447 and 875
+    iterations (measured, the same for every seed), i.e. through the chunks of 64, 128 and 256 of ransac_replay (cumulative
+    edges 32, 96, 224, 480, 736, 992) where the default 30 % never leave the first.  Status 1, the mask holds exactly the
+    true inliers (110, 100, 90, 80, 70), and the iteration count is the oracle's RANSACUpdateNumIters for the final inlier
+    share, both in closed form and replayed sample by sample."""
+    n = 200
+    for seed in range(6):
+        sc = S.outlier_scene(seed, n, frac, S.DIST1)
+        clean = S.project(sc["X"], sc["R"], sc["t"], S.K, S.DIST1)
+        assert np.all(np.linalg.norm(sc["xy"] - clean, axis=1)[sc["truth"] == 0] >= 20 * sc["thr"])
+        r = S.stub_ransac(L, [sc["X"]], [sc["xy"]], S.K, S.DIST1, thresholds=[sc["thr"]])
+        mask, inl, its = r["masks"][0], int(r["inliers"][0]), int(r["iterations"][0])
+        assert r["status"][0] == 1
+        assert not np.any(mask[sc["truth"] == 0]), "a true outlier is in the mask"
+        assert inl == int(mask.sum()) == int(sc["truth"].sum())
+        assert its == orc_score.ransac_update_num_iters(0.99, 1 - inl / n, 5, 1000)
+        niters, best, best_model = _replay(L, sc, S.DIST1, sc["thr"], its)
+        assert its == niters and best == inl
+        assert np.array_equal(best_model[:3], r["rvec_ransac"][0]) and np.array_equal(best_model[3:], r["tvec_ransac"][0])
+        print(f"MEASURE ransac share={frac} seed={seed} iterations {its} inliers {inl}")
+        assert its > 32, "the scene no longer leaves the first chunk"
+
+
+@pytest.mark.parametrize("frac", [0.8, 0.9])
+def test_ransac_reaches_the_iteration_cap(L, frac):
+    """80 % and 90 % outliers: the limit never drops below 1000, so the loop ends at the cap, past the last full chunk
+    (992 -> 1248 drawn, 1000 used).  Either no sample ever gave more than four inliers (status 0, no inliers) or a pose
+    whose mask holds no true outlier; both occur (measured at 0.8: seed 1 finds the 40 inliers, seeds 0, 2-5 find nothing;
+    at 0.9 nothing)."""
+    seen = set()
+    for seed in range(6):
+        sc = S.outlier_scene(seed, 200, frac, S.DIST1)
+        r = S.stub_ransac(L, [sc["X"]], [sc["xy"]], S.K, S.DIST1, thresholds=[sc["thr"]])
+        assert r["iterations"][0] == 1000
+        seen.add(int(r["status"][0]))
+        if r["status"][0] == 0:
+            assert r["inliers"][0] == 0 and not np.any(r["masks"][0]) and not np.any(r["rvec"][0]) and not np.any(r["tvec"][0])
+        else:
+            assert r["status"][0] == 1 and not np.any(r["masks"][0][sc["truth"] == 0])
+            assert int(r["inliers"][0]) == int(r["masks"][0].sum())
+    print(f"MEASURE ransac share={frac} statuses {sorted(seen)}")
+    assert 0 in seen
+
+
+def _one(L, sc, dist=S.DIST1, **k):
+    r = S.stub_ransac(L, [sc["X"]], [sc["xy"]], S.K, dist, thresholds=[k.pop("thr", sc["thr"])], **k)
+    return int(r["status"][0]), int(r["inliers"][0]), int(r["iterations"][0])
+
+
+def test_options_off_their_defaults(L):
+    """max_iters 0, 1, 2 (the loop ends before a model can reach five inliers here), max_iters inside and at the edges of
+    the first chunks (31, 32, 33, 96, 97: the stopping rule's 25 iterations, as with 1000); the confidence clamp of
+    RANSACUpdateNumIters (<= 0, even negative, counts as 0; >= 1 as 1, where the limit never drops) and 0.5, 0.9, 0.999
+    (measured: 6, 6, 6, 13, 38 iterations, 1000 at >= 1) with the counts derived from the oracle; thresholds 0 and 1e-6 (no
+    model in 1000 iterations) and 1e6 (every point an inlier at the first iteration)."""
+    sc = S.ransac_scene(3, 300, S.DIST1)
+    n = 300
+    ref = _one(L, sc)
+    assert ref[0] == 1 and ref[2] == orc_score.ransac_update_num_iters(0.99, 1 - ref[1] / n, 5, 1000)
+    for mi in (0, 1, 2):
+        assert _one(L, sc, max_iters=mi) == (0, 0, mi)
+    for mi in (31, 32, 33, 96, 97):
+        assert _one(L, sc, max_iters=mi) == ref
+    for conf in (-1.0, 0.0, 0.5, 0.9, 0.999, 1.0, 2.0):
+        got = _one(L, sc, confidence=conf)
+        # the loop replayed until its own limit ends it; that limit is the closed form for the final inlier share unless the
+        # first model arrives later than it (confidence <= 0.5: limits 0, 0 and 4, the first model at iteration 6)
+        niters, best, _, ran = _replay(L, sc, S.DIST1, sc["thr"], None, confidence=conf)
+        closed = orc_score.ransac_update_num_iters(conf, 1 - ref[1] / n, 5, 1000)
+        print(f"MEASURE confidence={conf} iterations {got[2]} closed form {closed}")
+        assert got == (1, ref[1], ran) and best == ref[1] and niters == closed, conf
+        assert ran == closed if conf >= 0.9 else ran > closed
+    assert _one(L, sc, confidence=-1.0)[2] == _one(L, sc, confidence=0.5)[2] < _one(L, sc, confidence=0.9)[2] < ref[2]
+    assert _one(L, sc, confidence=1.0)[2] == _one(L, sc, confidence=2.0)[2] == 1000
+    for thr in (0.0, 1e-6):
+        assert _one(L, sc, thr=thr) == (0, 0, 1000)
+    assert _one(L, sc, thr=1e6) == (1, n, 1)
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf], ids=["nan", "inf", "-inf"])
+def test_nonfinite_points_stay_outside_the_model(L, bad):
+    """one non-finite coordinate in a 3-D point and one in a 2-D point, both in rows the first two samples draw: the call
+    returns, those samples are refused as rank-deficient (flags 3: the covariance's SVD meets NaN, bit 1, and its rank
+    test fails, bit 0), the two rows are outside the mask and the pose and the refit are finite and as close to ground
+    truth as on the clean scene (5e-3, the existing test's bound)."""
+    sc, rows = S.nonfinite_scene(L, bad)
+    r = S.stub_ransac(L, [sc["X"]], [sc["xy"]], S.K, S.DIST1, thresholds=[sc["thr"]])
+    print(f"MEASURE nonfinite {bad}: status {r['status'][0]} inliers {r['inliers'][0]} iterations {r['iterations'][0]} flags {r['flags']}")
+    assert r["status"][0] == 1 and r["flags"] == pnp.FLAG_RANK_DEFICIENT | pnp.FLAG_SVD_RANDOM
+    mask = r["masks"][0]
+    assert not mask[rows[0]] and not mask[rows[1]] and not np.any(mask[sc["truth"] == 0])
+    assert int(r["inliers"][0]) == int(mask.sum()) >= 200
+    for k in ("rvec", "tvec", "rvec_refit", "tvec_refit"):
+        assert np.all(np.isfinite(r[k]))
+    for rk, tk in (("rvec", "tvec"), ("rvec_refit", "tvec_refit")):
+        assert S.rot_angle(S.rot(r[rk][0]), sc["R"]) < 5e-3
+        assert np.linalg.norm(r[tk][0] - sc["t"]) / np.linalg.norm(sc["t"]) < 5e-3
+
+
+def test_a_view_of_nothing_but_nan_ends_at_the_cap(L):
+    """every hypothesis is refused: status 0, 1000 iterations, zero outputs, flags 3; a good view next to it is untouched"""
+    sc = S.ransac_scene(3, 300, S.DIST1)
+    X = [np.full((300, 3), np.nan), sc["X"]]
+    xy = [np.full((300, 2), np.nan), sc["xy"]]
+    r = S.stub_ransac(L, X, xy, S.K, S.DIST1, thresholds=[3.0, sc["thr"]])
+    assert (r["status"][0], r["inliers"][0], r["iterations"][0]) == (0, 0, 1000) and not np.any(r["masks"][0])
+    assert r["flags"] == pnp.FLAG_RANK_DEFICIENT | pnp.FLAG_SVD_RANDOM
+    for k in ("rvec", "tvec", "rvec_refit", "tvec_refit"):
+        assert not np.any(r[k][0])
+    alone = S.stub_ransac(L, [sc["X"]], [sc["xy"]], S.K, S.DIST1, thresholds=[sc["thr"]])
+    assert _bits(alone, 0) == _bits(r, 1)
