@@ -5,8 +5,11 @@ file's header), sfmhip_score_homography against the numpy restatement in oracle/
 import numpy as np
 import pytest
 
+from oracle import orc
 from oracle import sfm_oracle_score as S
 from sfm_danpipeline_amd import scoring, synth
+from sfm_danpipeline_amd._lib import lib
+from tests import score_scenes as Z
 
 pytestmark = pytest.mark.gpu
 K = np.array([[1520.0, 0, 302.2], [0, 1520.0, 246.87], [0, 0, 1]])
@@ -166,3 +169,246 @@ def test_homography_degenerate_inputs(ctx):
     cnt, mask, it = S.find_homography_ransac(p[:5], q[:5], 0.004 * float(np.max(p[:5])))
     assert (int(inl[3]), int(its[3])) == (cnt, it)
     assert inl[4] == 0 and its[4] == 0                        # run() returns false at iteration 0
+
+
+# ================================================================ off the defaults, at chunk and batch edges
+# (tables and generators: tests/score_scenes.py; tests/test_oracle_score.py holds the CPU guard of the tables)
+ERR_ARG = -3
+
+
+def _against_essential_oracle(pairs, Kc, got, prob=0.999, threshold=1.0, expect=None):
+    """every pair's count, iteration number and mask against the oracle; all disagreements are listed"""
+    inl, masks, its = got
+    bad = []
+    for i, (a, b) in enumerate(pairs):
+        cnt, mask, E, it = S.find_essential_mat_ransac(a, b, Kc, prob, threshold)
+        if expect is not None:
+            assert (cnt, it) == expect[i], (i, (cnt, it), expect[i])       # the case is the one the table promises
+        print(f"pair {i}: n {len(a)} device {(int(inl[i]), int(its[i]))} oracle {(cnt, it)}")
+        if (int(inl[i]), int(its[i])) != (cnt, it) or not np.array_equal(masks[i], mask):
+            bad.append((i, len(a), (int(inl[i]), int(its[i])), (cnt, it), int((masks[i] != mask).sum())))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("Kc, table", [(Z.K_TALL, Z.OPTIONS_TALL), (Z.K_WIDE, Z.OPTIONS_WIDE)], ids=["fx<fy", "fx>fy"])
+def test_essential_options_and_unequal_focal_lengths(ctx, Kc, table):
+    """prob and threshold off 0.999 / 1.0 on a calibration with fx != fy (x is scaled by 1 / fx, y by 1 / fy, the
+    threshold by 2 / (fx + fy)): the oracle's count, iteration number and mask for every option pair"""
+    a, b = Z.options_scene(Kc)
+    for (prob, thr), want in table:
+        got = scoring.score_essential([(a, b)], Kc, prob=prob, threshold=thr, want_mask=True, ctx=ctx)
+        _against_essential_oracle([(a, b)], Kc, got, prob, thr, expect=[want])
+        assert scoring.last_flags(ctx) == 0
+
+
+def test_runs_that_end_on_and_just_after_every_chunk_end(ctx):
+    """one batch of runs that end at 32 | 33, 96 | 97, 224 | 225, 480 | 481, 736 | 737, 992 | 993 and at the cap: pairs
+    finish in different chunks while the others go on, and a best model of an early chunk is kept through later ones"""
+    pairs = Z.chunk_pairs()
+    got = scoring.score_essential(pairs, K, want_mask=True, ctx=ctx)
+    assert [int(x) for x in got[2]] == [it for _, _, _, it in Z.CHUNK_TABLE]
+    _against_essential_oracle(pairs, K, got)
+
+
+def test_small_counts_with_tied_models_keep_the_oracles_model(ctx):
+    """counts 6 to 24: few matches, many models with the same count (tests/score_scenes.py names the tied ones) -- the
+    strict `>` and the order of a sample's models decide which is kept, and the mask shows it"""
+    pairs = Z.small_pairs()
+    half = len(pairs) // 2
+    for part in (pairs[:half], pairs[half:]):
+        _against_essential_oracle(part, K, scoring.score_essential(part, K, want_mask=True, ctx=ctx))
+
+
+STRIDE_COUNTS = (63, 64, 65, 255, 256, 257, 511, 512, 513)      # one wave, the 256-thread stride and twice that, +-1
+
+
+def test_match_counts_around_the_wave_and_block_strides(ctx):
+    pairs = [_scene(n, 900 + n, outliers=0.3) for n in STRIDE_COUNTS]
+    _against_essential_oracle(pairs, K, scoring.score_essential(pairs, K, want_mask=True, ctx=ctx))
+    hp = [Z.planar(n, 900 + n, 0.5) for n in STRIDE_COUNTS]
+    inl, masks, its = scoring.score_homography(hp, want_mask=True, ctx=ctx)
+    for i, (p, q) in enumerate(hp):
+        cnt, mask, it = S.find_homography_ransac(p, q, 0.004 * float(np.max(p)))
+        assert (int(inl[i]), int(its[i])) == (cnt, it), (i, len(p))
+        assert np.array_equal(masks[i], mask), (i, len(p))
+
+
+def _raw_essential(ctx, pairs, Kc=K, prob=0.999, threshold=1.0, mask=True, iterations=True, n_pairs=None, offsets=None,
+                   inliers=True, left=True, right=True):
+    """sfmhip_score_essential through the C ABI, any pointer optional: (status, inliers, mask, iterations), the outputs
+    pre-filled with -7 / 7"""
+    counts = [len(a) for a, _ in pairs]
+    off = np.asarray(offsets if offsets is not None else np.concatenate([[0], np.cumsum(counts)]), np.int32)
+    L = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float64).reshape(-1, 2) for a, _ in pairs] + [np.zeros((1, 2))]))
+    R = np.ascontiguousarray(np.concatenate([np.asarray(b, np.float64).reshape(-1, 2) for _, b in pairs] + [np.zeros((1, 2))]))
+    inl = np.full(len(pairs) + 1, -7, np.int32)
+    its = np.full(len(pairs) + 1, -7, np.int32)
+    mk = np.full(sum(counts) + 1, 7, np.uint8)
+    rc = lib().sfmhip_score_essential(ctx.h, len(pairs) if n_pairs is None else n_pairs, off.ctypes.data,
+                                      L.ctypes.data if left else None, R.ctypes.data if right else None, float(Kc[0, 0]),
+                                      float(Kc[1, 1]), float(Kc[0, 2]), float(Kc[1, 2]), float(prob), float(threshold),
+                                      inl.ctypes.data if inliers else None, mk.ctypes.data if mask else None,
+                                      its.ctypes.data if iterations else None)
+    return rc, inl, mk, its
+
+
+def _raw_homography(ctx, pairs, thresholds=True, confidence=0.995, max_iters=2000, mask=True, iterations=True, n_pairs=None,
+                    offsets=None, inliers=True, left=True, right=True):
+    counts = [len(a) for a, _ in pairs]
+    off = np.asarray(offsets if offsets is not None else np.concatenate([[0], np.cumsum(counts)]), np.int32)
+    L = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float64).reshape(-1, 2) for a, _ in pairs] + [np.zeros((1, 2))]))
+    R = np.ascontiguousarray(np.concatenate([np.asarray(b, np.float64).reshape(-1, 2) for _, b in pairs] + [np.zeros((1, 2))]))
+    thr = np.array([0.004 * float(np.max(a)) for a, _ in pairs] + [0.0])
+    inl = np.full(len(pairs) + 1, -7, np.int32)
+    its = np.full(len(pairs) + 1, -7, np.int32)
+    mk = np.full(sum(counts) + 1, 7, np.uint8)
+    rc = lib().sfmhip_score_homography(ctx.h, len(pairs) if n_pairs is None else n_pairs, off.ctypes.data,
+                                       L.ctypes.data if left else None, R.ctypes.data if right else None,
+                                       thr.ctypes.data if thresholds else None, float(confidence), int(max_iters),
+                                       inl.ctypes.data if inliers else None, mk.ctypes.data if mask else None,
+                                       its.ctypes.data if iterations else None)
+    return rc, inl, mk, its
+
+
+def test_a_pairs_result_does_not_depend_on_its_batch(ctx):
+    """pairs of one match count share a sample stream: the same pair twice, two more pairs of that count and one of
+    another -- in this order, reversed, each alone, and without masks; device against device is the claim here, and
+    the first pair is also the oracle's.  Then the C entry with iterations = NULL and with mask = NULL."""
+    A, B, Cc, D = _scene(400, 41, outliers=0.45), _scene(400, 42, outliers=0.3), _scene(400, 43, outliers=0.55), _scene(257, 44, outliers=0.4)
+    batch = [A, A, B, Cc, D]
+    inl, masks, its = scoring.score_essential(batch, K, want_mask=True, ctx=ctx)
+    _against_essential_oracle([A], K, (inl[:1], masks[:1], its[:1]))
+    assert (inl[0], its[0]) == (inl[1], its[1]) and np.array_equal(masks[0], masks[1])
+    assert len({int(x) for x in its}) >= 3                                   # (the pairs do finish at different times)
+    rinl, rmasks, rits = scoring.score_essential(batch[::-1], K, want_mask=True, ctx=ctx)
+    assert np.array_equal(rinl[::-1], inl) and np.array_equal(rits[::-1], its)
+    assert all(np.array_equal(x, y) for x, y in zip(rmasks[::-1], masks))
+    for i, pr in enumerate(batch):
+        sinl, smasks, sits = scoring.score_essential([pr], K, want_mask=True, ctx=ctx)
+        assert (int(sinl[0]), int(sits[0])) == (int(inl[i]), int(its[i])) and np.array_equal(smasks[0], masks[i]), i
+    ninl, nmasks, nits = scoring.score_essential(batch, K, want_mask=False, ctx=ctx)
+    assert nmasks is None and np.array_equal(ninl, inl) and np.array_equal(nits, its)
+    rc, cinl, cmk, cits = _raw_essential(ctx, batch, iterations=False)
+    assert rc == 0 and np.array_equal(cinl[:-1], inl) and np.array_equal(cmk[:-1], np.concatenate(masks))
+    assert (cits == -7).all() and cinl[-1] == -7 and cmk[-1] == 7            # nothing written where nothing was asked for
+    rc, cinl, cmk, cits = _raw_essential(ctx, batch, mask=False)
+    assert rc == 0 and np.array_equal(cinl[:-1], inl) and np.array_equal(cits[:-1], its) and (cmk == 7).all()
+    # the homography entry: its streams are per pair, its thresholds too
+    hb = [Z.planar(300, 23, 0.8), Z.planar(300, 23, 0.8), Z.planar(300, 22, 0.8), Z.planar(150, 1, 0.6)]
+    hinl, hmasks, hits = scoring.score_homography(hb, want_mask=True, ctx=ctx)
+    cnt, mask, it = S.find_homography_ransac(hb[0][0], hb[0][1], 0.004 * float(np.max(hb[0][0])))
+    assert (int(hinl[0]), int(hits[0])) == (cnt, it) and np.array_equal(hmasks[0], mask)
+    assert (hinl[0], hits[0]) == (hinl[1], hits[1]) and np.array_equal(hmasks[0], hmasks[1])
+    rinl, rmasks, rits = scoring.score_homography(hb[::-1], want_mask=True, ctx=ctx)
+    assert np.array_equal(rinl[::-1], hinl) and np.array_equal(rits[::-1], hits)
+    assert all(np.array_equal(x, y) for x, y in zip(rmasks[::-1], hmasks))
+    for i, pr in enumerate(hb):
+        sinl, smasks, sits = scoring.score_homography([pr], want_mask=True, ctx=ctx)
+        assert (int(sinl[0]), int(sits[0])) == (int(hinl[i]), int(hits[i])) and np.array_equal(smasks[0], hmasks[i]), i
+    rc, cinl, cmk, cits = _raw_homography(ctx, hb, iterations=False)
+    assert rc == 0 and np.array_equal(cinl[:-1], hinl) and np.array_equal(cmk[:-1], np.concatenate(hmasks)) and (cits == -7).all()
+    rc, cinl, cmk, cits = _raw_homography(ctx, hb, mask=False)
+    assert rc == 0 and np.array_equal(cinl[:-1], hinl) and np.array_equal(cits[:-1], hits) and (cmk == 7).all()
+
+
+H_OPTIONS = [(1.0, 0.9, 2000), (2.0, 0.9999, 5000), (2.0, 0.995, 1), (2.0, 0.995, 32), (2.0, 0.995, 33)]
+
+
+def test_homography_options_default_threshold_and_per_pair_thresholds(ctx):
+    """threshold, confidence and max_iters off their defaults on 300 points with 80 % outliers (seed 23: all 5000
+    iterations of the second option run; seed 22: the 33rd iteration raises the best count, the 32nd does not);
+    thresholds 0 and -1 mean 3; a batch whose pairs have different thresholds"""
+    for seed in (23, 22):
+        p, q = Z.planar(300, seed, 0.8)
+        for thr, conf, mi in H_OPTIONS:
+            inl, masks, its = scoring.score_homography([(p, q)], [thr], conf, mi, want_mask=True, ctx=ctx)
+            cnt, mask, it = S.find_homography_ransac(p, q, thr, conf, mi)
+            print(f"seed {seed} {(thr, conf, mi)}: device {(int(inl[0]), int(its[0]))} oracle {(cnt, it)}")
+            assert (int(inl[0]), int(its[0])) == (cnt, it), (seed, thr, conf, mi)
+            assert np.array_equal(masks[0], mask), (seed, thr, conf, mi)
+            if (seed, mi) == (23, 5000):
+                assert it == 5000                                             # (chunks of 256 to the very end)
+        cnt, mask, it = S.find_homography_ransac(p, q, 3.0)
+        for thr in (0.0, -1.0):
+            inl, masks, its = scoring.score_homography([(p, q)], [thr], want_mask=True, ctx=ctx)
+            assert (int(inl[0]), int(its[0])) == (cnt, it) and np.array_equal(masks[0], mask), thr
+    pairs = [Z.planar(300, 23, 0.8), Z.planar(300, 23, 0.8), Z.planar(300, 22, 0.8), Z.planar(300, 22, 0.8), Z.planar(200, 24, 0.7)]
+    thrs = [0.7, 3.5, 0.0, 1.5, 2.5]
+    inl, masks, its = scoring.score_homography(pairs, thrs, want_mask=True, ctx=ctx)
+    for i, (p, q) in enumerate(pairs):
+        cnt, mask, it = S.find_homography_ransac(p, q, thrs[i] if thrs[i] > 0 else 3.0)
+        assert (int(inl[i]), int(its[i])) == (cnt, it) and np.array_equal(masks[i], mask), i
+    assert len({int(x) for x in inl}) == len(pairs)                           # (the thresholds do tell the pairs apart)
+
+
+def test_homography_rejection_sampling_consumes_the_rng_as_the_library_does(ctx):
+    """40 collinear points and 2, 3, 4 or 6 off the line: checkSubset rejects most samples, every redraw consumes
+    cv::RNG, and the accepted samples decide count, iteration number and mask -- the oracle's, for runs of 20 to 249
+    iterations"""
+    pairs = [Z.line_scene(n_off, seed, Z.LINE_NOISE) for n_off, seed, _ in Z.LINE_TABLE]
+    inl, masks, its = scoring.score_homography(pairs, want_mask=True, ctx=ctx)
+    for i, (p, q) in enumerate(pairs):
+        cnt, mask, it = S.find_homography_ransac(p, q, 0.004 * float(np.max(p)))
+        assert (cnt, it) == Z.LINE_TABLE[i][2] and it >= 20
+        print(f"line set {i}: device {(int(inl[i]), int(its[i]))} oracle {(cnt, it)}")
+        assert (int(inl[i]), int(its[i])) == (cnt, it), i
+        assert np.array_equal(masks[i], mask), i
+
+
+def test_staged_entries_at_the_edges_of_their_64_sample_blocks(ctx):
+    a, b = _scene(400, 703, outliers=0.4, noise=0.5)
+    n1, n2 = orc.em_normalize(a, K), orc.em_normalize(b, K)
+    rng = np.random.default_rng(8)
+    idx = np.array([rng.choice(400, 5, replace=False) for _ in range(65)])
+    q1, q2 = n1[idx], n2[idx]
+    want = [orc.five_point(q1[i], q2[i]) for i in range(65)]
+    M = rng.uniform(0, 640, (65, 4, 2)).astype(np.float32)
+    m = (M @ np.array([[1.02, 0.05], [-0.03, 0.98]], np.float32) + rng.normal(0, 3.0, M.shape)).astype(np.float32)
+    wantH = [orc.homography_kernel(M[i], m[i]) for i in range(65)]
+    assert all(h is not None for h in wantH)
+    for n in (1, 63, 64, 65):
+        models, counts, flags = scoring.five_point(q1[:n], q2[:n], ctx=ctx)
+        assert len(models) == n
+        for i in range(n):
+            E, fl = want[i]
+            assert counts[i] == len(E) and flags[i] == fl, (n, i)
+            assert all(np.array_equal(models[i, k].view(np.uint64), E[k].view(np.uint64)) for k in range(len(E))), (n, i)
+        H, ok = scoring.homography_kernel(M[:n], m[:n], ctx=ctx)
+        assert len(H) == n and ok.all()
+        assert all(np.array_equal(H[i].view(np.uint64), wantH[i].view(np.uint64)) for i in range(n)), n
+
+
+def test_find_best_pair_cuts_below_120_matches(ctx):
+    a, b = _scene(300, 2)
+    c, d = _scene(200, 4, outliers=0.4)
+    ids = [(0, 1), (0, 2)]
+    pts = [(a[:119], b[:119]), (c[:120], d[:120])]
+    got = scoring.find_best_pair(ids, pts, K, ctx=ctx)
+    want = S.find_best_pair_scores([(ids[i], pts[i][0], pts[i][1]) for i in range(2)], K)
+    assert [(float(k), v) for k, v in got] == [(float(k), v) for k, v in want]
+    assert [v for _, v in got] == [(0, 2)]
+
+
+def test_refusals(ctx):
+    """what both entries refuse on the host before anything is launched: SFMHIP_ERR_ARG, every output untouched, and
+    the context as good as before"""
+    pairs = [_scene(40, 5), _scene(30, 6)]
+    untouched = lambda r: (r[1] == -7).all() and (r[2] == 7).all() and (r[3] == -7).all()
+    hip_error = lib().sfmhip_last_hip_error()
+    for kw in (dict(prob=0.0), dict(prob=1.0), dict(prob=-0.5), dict(prob=float("nan")), dict(offsets=[0, 40, 30]),
+               dict(offsets=[40, 0, 70]), dict(n_pairs=-1), dict(inliers=False), dict(left=False), dict(right=False)):
+        r = _raw_essential(ctx, pairs, **kw)
+        assert r[0] == ERR_ARG and untouched(r), kw
+    hp = [Z.planar(40, 3, 0.0), Z.planar(30, 4, 0.0)]
+    for kw in (dict(confidence=0.0), dict(confidence=1.0), dict(confidence=float("nan")), dict(offsets=[0, 40, 30]),
+               dict(offsets=[40, 0, 70]), dict(n_pairs=-1), dict(inliers=False), dict(thresholds=False), dict(left=False),
+               dict(right=False)):
+        r = _raw_homography(ctx, hp, **kw)
+        assert r[0] == ERR_ARG and untouched(r), kw
+    assert lib().sfmhip_last_hip_error() == hip_error
+    r = _raw_essential(ctx, pairs)                                            # and the same arguments, whole, are fine
+    cnt, mask, E, it = S.find_essential_mat_ransac(pairs[0][0], pairs[0][1], K)
+    assert r[0] == 0 and (int(r[1][0]), int(r[3][0])) == (cnt, it) and np.array_equal(r[2][:40], mask)
+    r = _raw_homography(ctx, hp)
+    cnt, mask, it = S.find_homography_ransac(hp[0][0], hp[0][1], 0.004 * float(np.max(hp[0][0])))
+    assert r[0] == 0 and (int(r[1][0]), int(r[3][0])) == (cnt, it) and np.array_equal(r[2][:40], mask)

@@ -7,6 +7,7 @@ import numpy as np
 from oracle import np_check, orc
 from oracle import sfm_oracle_score as S
 from sfm_danpipeline_amd import synth
+from tests import score_scenes as Z
 
 K = np.array([[1520.0, 0, 302.2], [0, 1520.0, 246.87], [0, 0, 1]])
 
@@ -139,3 +140,44 @@ def test_homography_restatement_against_the_independent_numpy_route():
         c2, mask2, it2 = np_check.find_homography_ransac_np(p, q, thr)
         assert (c, it) == (c2, it2) and np.array_equal(mask, mask2), (n, o)
         assert S.find_homography_inliers(p, q) == c
+
+
+# ---------------------------------------------------------------- the guard of tests/score_scenes.py
+# The device tests of tests/test_gpu_score.py are only as sharp as these tables: a change to synth.two_view_scene, to
+# numpy's generators or to the oracle that moves a run off its chunk end fails here, on the CPU.
+def test_chunk_table_still_ends_where_it_says():
+    its = [it for _, _, _, it in Z.CHUNK_TABLE]
+    assert 32 in its and 33 in its and 1000 in its
+    for end in Z.CHUNK_ENDS[1:]:
+        assert end in its or end + 1 in its, end
+    for (m, o, seed, want), (a, b) in zip(Z.CHUNK_TABLE, Z.chunk_pairs()):
+        assert len(a) == m
+        assert S.find_essential_mat_ransac(a, b, Z.K)[3] == want, (m, o, seed)
+
+
+def test_option_tables_still_hold():
+    for Kc, table in ((Z.K_TALL, Z.OPTIONS_TALL), (Z.K_WIDE, Z.OPTIONS_WIDE)):
+        a, b = Z.options_scene(Kc)
+        for (prob, thr), want in table:
+            cnt, mask, E, it = S.find_essential_mat_ransac(a, b, Kc, prob, thr)
+            assert (cnt, it) == want, (prob, thr)
+    assert Z.K_TALL[0, 0] < Z.K_TALL[1, 1] and Z.K_WIDE[0, 0] > Z.K_WIDE[1, 1]
+
+
+def test_small_table_has_its_ties():
+    """at least MIN_TIES of the small pairs have more than one (iteration, model) at the final best count: there the
+    mask, and only the mask, shows which of the tied models a RANSAC kept"""
+    pairs = Z.small_pairs()
+    assert sorted({len(a) for a, _ in pairs}) == list(range(6, 25)) and len(pairs) <= 60
+    tied = [seed for (count, seed, o), (a, b) in zip(Z.SMALL_TABLE, pairs) if Z.tie_census(a, b)[2] > 1]
+    assert len(tied) >= Z.MIN_TIES, tied
+    assert tied == [602, 701, 702, 802, 1102, 1201, 1202, 1301, 1303, 1502, 1701, 1702, 1703, 2001, 2102, 2201, 2202]
+
+
+def test_line_table_still_rejects_and_lasts():
+    for n_off, seed, want in Z.LINE_TABLE:
+        p, q = Z.line_scene(n_off, seed, Z.LINE_NOISE)
+        assert len(p) == 40 + n_off
+        cnt, mask, it = S.find_homography_ransac(p, q, 0.004 * float(p.max()))
+        assert (cnt, it) == want and it >= 20, (n_off, seed)
+    assert {n for n, _, _ in Z.LINE_TABLE} == {2, 3, 4, 6}
