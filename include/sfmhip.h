@@ -1053,6 +1053,64 @@ int sfmhip_mvs_create_distorted(sfmhip_ctx* ctx, int n_views, int rows, int cols
  * sfmhip_mvs_create. */
 int sfmhip_mvs_valid(sfmhip_mvs* h, uint8_t* valid);
 
+/* ---- multi-view feature tracks and their N-view triangulation (PARITY UNPINNED: the reference links a point
+ * to the two views it was triangulated from and never merges) ----
+ * A handle holds, on the device, the tracks of one set of pair lists as the CSR sfmhip_find_2d3d takes.
+ *   T1. A node is (image, feature), id = base[image] + feature, base = the exclusive scan of n_feat.  An edge is one match of
+ *       one pair (match_q in the pair's first image, match_t in its second).  A match index < 0 or >= that image's n_feat, a
+ *       pair that names an image outside [0, n_images) or the same image twice, a negative count or n_feat, or more than
+ *       2^31 - 2 nodes or edges refuse the whole call with SFMHIP_ERR_ARG (the matches are checked on the device, by a flag,
+ *       before anything is made; *out is not written).  Duplicate edges and duplicate pairs are allowed.
+ *   T2. Components of that graph by a union-find whose roots only fall (atomicMin): a component's root is its least node id,
+ *       whatever the order of the edges.
+ *   T3. A component is conflicting when two of its nodes lie in one image.  (Nodes ascend by (image, feature); a stable sort
+ *       by root leaves every component in that order, and a conflict is two neighbours of one image.)
+ *   T4. A component is kept when it is not conflicting and has >= max(2, min_len) nodes.  A conflicting one is dropped whole.
+ *   T5. Tracks are numbered by ascending root; inside a track the nodes ascend by (view, feature).  trk_ptr[n_tracks + 1],
+ *       trk_view / trk_feat[n_obs], node_track[nodes] (-1: in no track).  The bytes depend on the edge SET alone.
+ *   n_pairs = 0, counts all 0, images without features: SFMHIP_OK, 0 tracks.
+ * stats: nodes; edges (with duplicates); components of >= 2 nodes; of those the conflicting ones; the non-conflicting ones
+ * shorter than min_len; n_tracks; n_obs.
+ * N-view triangulation of every track (sfmhip_tracks_triangulate):
+ *   R1. The used observations of a track are those in views with has_pose != 0, ascending view; m of them.  m < 2: keep = 0,
+ *       X = NaN.  err (n_obs, aligned with trk_view) is -1.0f at every unused observation.
+ *   R2. Each used pixel goes through cv::undistortPoints' five iterations and gives the rows x P[2,:] - P[0,:] and
+ *       y P[2,:] - P[1,:] (as sfmhip_triangulate forms them); X is the smallest right singular vector of the 2m x 4 system by
+ *       OpenCV's one-sided Jacobi (sums over rows ascending, max(2m, 30) sweeps, descending selection sort, last row),
+ *       divided by its fourth entry when that is not 0.
+ *   R3. err = (float)sqrt(dx^2 + dy^2) of cv::projectPoints in every used view.
+ *   R4. keep = m >= max(2, min_views) && !(any max_err < err), so a NaN error keeps its point as sfmhip_triangulate does; with
+ *       front_only also P[2,:] (X, 1) > 0 in every used view.
+ *   R5. A track with two used observations gives the bits sfmhip_triangulate gives for those two views.
+ * poses: 12 doubles per image ([R|t], read only where has_pose); xy: pixel pairs, image v's feature f at
+ * xy[2 (xy_ptr[v] + f)]; a posed view with fewer than n_feat[v] pixels, or a decreasing xy_ptr, is SFMHIP_ERR_ARG.  Every
+ * output may be NULL: X 3 n_tracks, err n_obs, n_used and keep n_tracks. */
+#define SFMHIP_TRACKS_STAGES 6
+typedef struct sfmhip_tracks sfmhip_tracks;
+typedef struct sfmhip_tracks_opts {
+  int32_t min_len;     /* 2 */
+  int32_t front_only;  /* 0: the reference has no cheirality test */
+} sfmhip_tracks_opts;
+typedef struct sfmhip_tracks_stats {
+  int64_t nodes, edges, components, conflicting, short_tracks, n_tracks, n_obs;
+} sfmhip_tracks_stats;
+void sfmhip_tracks_default_opts(sfmhip_tracks_opts* opts);
+/* host lists in sfmhip_matchplan_fetch's layout: counts[n_pairs], match_q / match_t packed pair after pair.  opts: NULL = defaults */
+int sfmhip_tracks_build(sfmhip_ctx* ctx, int n_images, const int32_t* n_feat, int n_pairs, const int32_t* pairs, const int32_t* counts,
+                        const int32_t* match_q, const int32_t* match_t, const sfmhip_tracks_opts* opts, sfmhip_tracks** out);
+/* the lists of the plan's last run, read where they lie on the device; n_feat = the image set's row counts.  The same bytes as
+ * sfmhip_tracks_build on the fetched lists. */
+int sfmhip_tracks_build_from_plan(sfmhip_matchplan* plan, const sfmhip_tracks_opts* opts, sfmhip_tracks** out);
+int sfmhip_tracks_counts(const sfmhip_tracks* tracks, sfmhip_tracks_stats* stats);
+int sfmhip_tracks_download(const sfmhip_tracks* tracks, int32_t* trk_ptr, int32_t* trk_view, int32_t* trk_feat, int32_t* node_track);
+int sfmhip_tracks_triangulate(sfmhip_tracks* tracks, const double* poses, const uint8_t* has_pose, const double K[9], const double dist[5],
+                              const int32_t* xy_ptr, const double* xy, float max_err, int min_views, double* X, float* err,
+                              int32_t* n_used, uint8_t* keep);
+/* With sfmhip_set_timing on, seconds by events on the context's stream: check, hook + flatten, sort by root, numbering + CSR,
+ * length buckets (the build), and the kernel of the last sfmhip_tracks_triangulate. */
+int sfmhip_tracks_last_timing(const sfmhip_tracks* tracks, double seconds[SFMHIP_TRACKS_STAGES]);
+void sfmhip_tracks_destroy(sfmhip_tracks* tracks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ SO = os.path.join(HERE, "libsfmhip.so")
 # and want v_fma_f64 -- "fast-honor-pragmas", not "fast": the one function that must NOT contract, the trust-region decision
 # lm_decide (the same bits on the host and on the device), says so with a pragma, which plain "fast" ignores
 SOURCES = {"context.hip": "off", "match.hip": "off", "triangulate.hip": "off", "incremental.hip": "off",
-           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "cloud_filter.hip": "off", "segment.hip": "off", "poisson.hip": "off", "dendro.hip": "off", "ground.hip": "off", "trees.hip": "off", "mvs.hip": "off", "undistort.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
+           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "cloud_filter.hip": "off", "segment.hip": "off", "poisson.hip": "off", "dendro.hip": "off", "ground.hip": "off", "trees.hip": "off", "tracks.hip": "off", "mvs.hip": "off", "undistort.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -123,6 +123,15 @@ def build_incr_demo(force=False):
     return _build_host_exe(os.path.join(HERE, "sfm_incr_selftest"),
                            ("Sfm.cpp", "SfmIO.cpp", "SfmPose.cpp", "SfmIncremental.cpp", "BundleAdjustment.cpp", "incr_selftest.cpp"),
                            force, std="c++17")
+
+
+def build_tracks_demo(force=False):
+    """The track consolidation of the host mirror: baseReconstruction, addMoreViews, then consolidateTracks (sfmhip_tracks_build /
+    sfmhip_tracks_triangulate over all pairs of the registered views) and one more adjustBundle, on incr_selftest's inputs; writes
+    the cloud before and after the consolidation (needs the GPU)."""
+    return _build_host_exe(os.path.join(HERE, "sfm_tracks_selftest"),
+                           ("Sfm.cpp", "SfmIO.cpp", "SfmPose.cpp", "SfmIncremental.cpp", "SfmTracks.cpp", "BundleAdjustment.cpp",
+                            "tracks_selftest.cpp"), force, std="c++17")
 
 
 def build_cloud_demo(force=False):

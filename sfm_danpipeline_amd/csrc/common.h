@@ -122,6 +122,17 @@ int sfm_undistort_apply(hipStream_t st, int n, int rows, int cols, int ch, const
 int sfm_undistort_level_mask(hipStream_t st, int rows, int cols, int level, const uint8_t* valid0, uint8_t* out);
 int sfm_undistort_seam(hipStream_t st, int rows, int cols, int window, const uint8_t* valid, int32_t* idx, float* depth, float* score);
 
+// The ratio-test lists of a match plan's last run where they lie in HBM (match.hip), for tracks.hip: pair p's matches are
+// q[p * stride + k], t[p * stride + k] with k < counts[p]; pairs, counts, q and t are device pointers, n_rows is the host's
+// row count per image.  Valid until the plan's next run or set_pairs; work on them is ordered by the context's stream.
+struct sfm_matchplan_lists {
+  sfmhip_ctx* ctx;
+  int n_images, n_pairs, stride;
+  const int* n_rows;
+  const int *pairs, *counts, *q, *t;
+};
+int sfm_matchplan_device_lists(sfmhip_matchplan* pl, sfm_matchplan_lists* out);
+
 static inline double sfm_now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }

@@ -136,6 +136,13 @@ class StructFromMotion {
   // DEVIATIONS: a proposed view outside [0, nImages.size()) is dropped (the reference would throw in .at()); the loop also
   // ends when a round proposes no new view (the reference would spin when a view can never be reached).
   bool addMoreViews();
+  // ---- multi-view tracks (csrc/host/SfmTracks.cpp; sfmhip_tracks_*; no counterpart in the reference, whose
+  // points keep the two views they were triangulated from).  One match plan over all pairs of nGoodViews -- on the resident
+  // image set where the descriptors are there, else the pair cache / getMatching's lists --, the tracks of those lists with
+  // >= max(2, minViews) views, one DLT point per track over nCameraPoses (6 px, as triangulateViews).  REPLACES
+  // nReconstructionCloud by one Point3D per kept track with every view in idxImage / pt2D and returns the number of points;
+  // on a device error the cloud stays as it is.  Nothing calls it by default.
+  size_t consolidateTracks(int minViews = 2);
   // the inlier list of the last findCameraPosePNP (the reference computes it and reads it nowhere)
   const std::vector<int>& lastPnpInliers() const { return pnpInliers; }
   const std::set<int>& doneViews() const { return nDoneViews; }

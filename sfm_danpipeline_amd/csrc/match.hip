@@ -2289,6 +2289,22 @@ extern "C" int sfmhip_matchplan_fetch_knn(sfmhip_matchplan* pl, int pair, int32_
   return SFMHIP_OK;
 }
 
+// (common.h) where the last run's lists lie on the device, for tracks.hip: nothing is launched, copied or changed
+int sfm_matchplan_device_lists(sfmhip_matchplan* pl, sfm_matchplan_lists* out) {
+  if (!pl || !out) return SFMHIP_ERR_ARG;
+  if (pl->pipe_st) SFM_HIP_TRY(hipStreamSynchronize(pl->pipe_st));  // (the reader runs on the context's stream)
+  out->ctx = pl->set->ctx;
+  out->n_images = pl->set->n_images;
+  out->n_rows = pl->set->n_rows.data();
+  out->n_pairs = pl->n_pairs;
+  out->pairs = (const int*)pl->d_pairs;
+  out->counts = pl->d_counts;
+  out->q = pl->d_out_q;
+  out->t = pl->d_out_t;
+  out->stride = pl->maxq;
+  return SFMHIP_OK;
+}
+
 extern "C" int sfmhip_matchplan_last_timing(sfmhip_matchplan* pl, double seconds[3]) {
   if (!pl || !seconds) return SFMHIP_ERR_ARG;
   seconds[0] = seconds[1] = seconds[2] = 0;

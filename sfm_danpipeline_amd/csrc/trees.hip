@@ -21,6 +21,7 @@
 #include "common.h"
 #include "cloud_grid.h"
 #include "trees.h"
+#include "union_find.h"
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -175,30 +176,8 @@ __global__ __launch_bounds__(256) void trs_cells(const int* count, int ncell, in
   occupied[q] = occ ? 1 : 0;
 }
 
-__device__ __forceinline__ int root_of(int* parent, int x) {
-  for (;;) {  // (parent[x] <= x and a root is its own parent: the walk ends)
-    const int up = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (up == x) return x;
-    x = up;
-  }
-}
-// joins the sets of a and b: the larger root is hooked under the smaller with atomicMin; when another thread hooked it first,
-// that thread's (smaller) target is joined instead.  Every step lowers a root, so the loop ends without waiting for anybody.
-__device__ __forceinline__ void unite(int* parent, int a, int b) {
-  for (;;) {
-    a = root_of(parent, a);
-    b = root_of(parent, b);
-    if (a == b) return;
-    if (a < b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = atomicMin(parent + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
+using sfmuf::root_of;  // (union_find.h: shared with tracks.hip)
+using sfmuf::unite;
 
 __global__ __launch_bounds__(256) void trs_hook(int* parent, int De, int Dn) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
