@@ -1,6 +1,15 @@
 """GPU: the dense multi-view stereo (sfmhip_mvs_*, csrc/mvs.hip) against the g++ build of the same header
 (tests/stub/mvs_capi.cpp), compared as bytes: pyramid, index map, depth, score, point count, xyz, normals, rgb; then the
-fusion cases and the analytic assertions of tests/test_mvs_cpu.py on the device's output.  No test provokes a fault."""
+fusion cases and the analytic assertions of tests/test_mvs_cpu.py on the device's output.
+
+The second half runs the cases S1 - S14 of tests/test_mvs_reference_cpu.py (its docstring has the table and the measured
+figures; the preconditions that keep a case from going vacuous are asserted there, on the CPU): rotated views (a vertical
+weight on 97 % of S1's samples, c <= 0 and all four borders in S4, a source that looks away), exact ties, the u32 ceiling of the LDS sums, a tile
+that leaves early beside one that does not, images smaller than a tile or a window, 256 planes with 8 sources, pyramid
+levels 2 and 3, a short source choice, per-view ranges, one handle at 9, 256 and 9 planes, and the fusion under rotation,
+at half-pixel projections and on non-finite depths.  Each is compared as bytes with the stub and with the numpy reference
+of tests/mvs_reference.py, which shares no code with either (a NaN must meet a NaN: the host's and the device's differ in
+sign).  No test provokes a fault: every input is one the ABI accepts."""
 import os
 import struct
 import subprocess
@@ -10,10 +19,13 @@ import numpy as np
 import pytest
 
 from sfm_danpipeline_amd import build, mvs
+from tests import mvs_reference as R
 from tests.test_gpu_incr_views import _read_out
 from tests.test_host_io import TEMPLE, _png_bytes
 from tests.test_mvs_cpu import (D, DMAX, DMIN, K0, SLANT_BOUND, SPHERE_BOUND, StubMvs, build_stub, check_edge, check_fronto,
                                 check_fusion, check_refusals, check_surface, hit_depth, opts, plane_inv, scene, timing_scene)
+from tests.test_mvs_reference_cpu import (check_s3, check_s11_pyramid, check_s11_tiny, check_s12_reuse, check_s13,
+                                          check_s14_half_pixel, check_s14_odd_depths)
 
 pytestmark = pytest.mark.gpu
 
@@ -42,25 +54,27 @@ def _both(ms, o):
     return mvs.default_opts(**kw), opts(ms, **kw)
 
 
-def _compare(ctx, ms, gray, K, P, level, kw, src=(1, 3, 0, 4), bgr=None, ref=2):
+def _compare(ctx, ms, gray, K, P, level, kw, src=(1, 3, 0, 4), bgr=None, ref=2, dmin=DMIN, dmax=DMAX, maps=False):
+    """device against stub, bytes; dmin / dmax: one range or one per view; maps: return the whole (index, depth, score)"""
     od, oh = _both(ms, opts(ms, **kw))
+    zlo, zhi = (float(np.broadcast_to(a, (len(gray),))[ref]) for a in (dmin, dmax))     # the reference view's range
     with mvs.Mvs(gray, K, P, bgr=bgr, level=level, ctx=ctx) as G, StubMvs(ms, gray, K, P, bgr, level) as H:
         assert (G.rows, G.cols) == (H.rows, H.cols) and _same(G.K, H.K)
         for v in range(len(gray)):
             assert all(a is None and b is None or _same(a, b) for a, b in zip(G.level_image(v), H.level_image(v)))
         src = list(src)[:od.n_src]
-        gi, gd, gs = G.depthmap(ref, src, DMIN, DMAX, od)
-        hi, hd, hs = H.depthmap(ref, src, DMIN, DMAX, oh)
+        gi, gd, gs = G.depthmap(ref, src, zlo, zhi, od)
+        hi, hd, hs = H.depthmap(ref, src, zlo, zhi, oh)
         print(f"{G.cols} x {G.rows}, {kw}: {int((gi >= 0).sum())} pixels with depth; index / depth / score differ at "
               f"{int((gi != hi).sum())} / {int((gd != hd).sum())} / {int((gs != hs).sum())}")
         assert _same(gi, hi) and _same(gd, hd) and _same(gs, hs)
-        gi2, gd2, gs2 = G.depthmap(ref, src, DMIN, DMAX, od)                     # a repeat on the handle: the same bytes
+        gi2, gd2, gs2 = G.depthmap(ref, src, zlo, zhi, od)                     # a repeat on the handle: the same bytes
         assert _same(gi, gi2) and _same(gd, gd2) and _same(gs, gs2)
-        g, h = G.run(DMIN, DMAX, od), H.run(DMIN, DMAX, oh)
+        g, h = G.run(dmin, dmax, od), H.run(dmin, dmax, oh)
         print(f"    run: {len(g[0])} points on the device, {len(h[0])} with the host build")
         assert all(_same(a, b) for a, b in zip(g, h))
-        assert all(_same(a, b) for a, b in zip(g, G.run(DMIN, DMAX, od)))
-        return gi, g
+        assert all(_same(a, b) for a, b in zip(g, G.run(dmin, dmax, od)))
+        return ((gi, gd, gs) if maps else gi), g
 
 
 CASES = [  # every path of the sweep kernel: edge tiles in both directions, D, n_src, window, n_best, level
@@ -131,6 +145,49 @@ def test_run_is_faster_than_the_host_build_on_16_threads(ctx, ms):
         print(f"10 x 640 x 480 at level 1: {len(g[0])} points; device {gpu_s:.3f} s {G.last_timing()}, host build {cpu_s:.3f} s")
         assert len(g[0]) > 10000 and all(_same(a, b) for a, b in zip(g, h)) and all(_same(a, b) for a, b in zip(g, g2))
         assert gpu_s < cpu_s, "the device call is slower than the header's host build on 16 threads"
+
+
+# ---------------------------------------------------------------- the cases of tests/test_mvs_reference_cpu.py
+def _device(ctx):
+    return lambda g, K, P, b, level: mvs.Mvs(g, K, P, bgr=b, level=level, ctx=ctx)
+
+
+@pytest.mark.parametrize("name", sorted(R.CASES))
+def test_case_equals_the_header_build_and_the_reference(ctx, ms, name):
+    c, r = R.case(name), R.reference(name)
+    (gi, gd, gs), pts = _compare(ctx, ms, c.gray, c.K, c.poses, c.level, c.kw, src=c.src, bgr=c.bgr, ref=c.ref, dmin=c.dmin,
+                                 dmax=c.dmax, maps=True)
+    assert _same(gi, r.idx) and _same(gd, r.depth) and _same(gs, r.score)
+    if r.points is not None:
+        assert all(_same(a, b) for a, b in zip(pts, r.points))
+
+
+def test_s3_rendered_scene_under_rotation(ctx):
+    check_s3(_device(ctx), mvs.default_opts)
+
+
+def test_s11_pyramid_levels_two_and_three(ctx):
+    check_s11_pyramid(_device(ctx))
+
+
+def test_s11_images_of_one_and_two_pixels(ctx):
+    check_s11_tiny(_device(ctx), mvs.default_opts)
+
+
+def test_s12_one_handle_at_9_256_and_9_planes(ctx):
+    check_s12_reuse(_device(ctx), mvs.default_opts)
+
+
+def test_s13_fusion_under_rotation(ctx):
+    check_s13(_device(ctx), mvs.default_opts)
+
+
+def test_s14_fusion_where_the_rounding_decides(ctx):
+    check_s14_half_pixel(_device(ctx), mvs.default_opts)
+
+
+def test_s14_fusion_of_odd_depths(ctx):
+    check_s14_odd_depths(_device(ctx), mvs.default_opts)
 
 
 # ---------------------------------------------------------------- the host mirror: densify and its driver

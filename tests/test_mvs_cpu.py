@@ -7,7 +7,10 @@ surface, seen by five cameras on a line with one orientation, so that every pixe
 
 Measured with this header, refined inverse depth against the analytic value over the accepted interior pixels, in
 hypothesis steps (median / 95th percentile): slanted plane (30 degrees) 0.0421 / 0.1162, sphere 0.0218 / 0.0697.  The
-tests assert twice these figures; the margin covers the texture's phase, not the platform (the device is bit-equal)."""
+tests assert twice these figures; the margin covers the texture's phase, not the platform (the device is bit-equal).
+
+Every scene of this file has identity rotations (v == y, no vertical weight, c == 1).  Rotated views, the option ceilings,
+tiny images and an independent numpy reference of the rule list are tests/test_mvs_reference_cpu.py."""
 import ctypes as C
 import os
 import subprocess
