@@ -1,7 +1,7 @@
 // pnp.h -- the numerics of findCameraPosePNP's cv::solvePnPRansac(..., CV_EPNP) (reference src/Sfm.cpp:1153) as
 // __host__ __device__ code that hipcc and a plain g++ both compile: EPnP for n >= 5 points (OpenCV 3.4.1 calib3d/epnp.cpp),
-// Rodrigues in both directions, PnPRansacCallback::computeError's per-point error, and (host only) the replay of
-// ptsetreg.cpp's RANSAC loop over per-iteration inlier counts.  The device code (pnp.hip) and the CPU test stub
+// Rodrigues in both directions and PnPRansacCallback::computeError's per-point error.  (The replay of ptsetreg.cpp's RANSAC
+// loop over per-iteration inlier counts is ransac_host.h's ransac_replay; the end of this file states how PnP calls it.)  The device code (pnp.hip) and the CPU test stub
 // (tests/stub/pnp_capi.cpp) share these bodies, so the device result is checked bit for bit against a CPU build of the
 // same operations.  The rule list is in include/sfmhip.h (sfmhip_pnp_ransac).  Compile with -ffp-contract=off.
 // PARITY UNPINNED: OpenCV is not in the image; the operation order is recalled from its 3.4.1 sources.
@@ -705,120 +705,25 @@ SFM_PNP_HD inline int solve_sample(const float xyz[5][3], const float xy[5][2], 
 
 }  // namespace sfmpnp
 
-// ==================================================================== host only: ptsetreg.cpp's loop, replayed
+// ==================================================================== host only: how PnP calls ptsetreg.cpp's loop
 #include <algorithm>
-#include <map>
 #include <vector>
 #include "ransac_host.h"
 
 namespace sfmpnp {
 
-struct ViewState {
-  int count, niters, iter, best, best_it;
-  bool done;
-  int status;  // 1: a model; 0: none; -1: fewer than five correspondences
-};
-struct Job {  // one active view of a chunk
-  int view;
-  int off;    // first correspondence of the view in the point arrays
-  int count;  // correspondences
-  int samp;   // first row of its sample table (5 indices per iteration) for this chunk
-};
-struct Keep {  // the model of slot `slot` of the last chunk becomes view `view`'s best
-  int slot, view;
-};
+using sfmransac::Job;
+using sfmransac::Keep;
+using sfmransac::ViewState;
 
-// RANSACPointSetRegistrator::run per view, in chunks of iterations: the backend solves and scores every (view, iteration)
-// sample of a chunk -- be.run_chunk(jobs, chunk, samples, ok, counts): ok[slot] = models (0 / 1) | flags << 8, counts[slot] =
-// the model's inliers, slot = job * chunk + iteration -- and keeps the models named by be.keep_best(keeps) before the
-// next chunk overwrites them.  The rule: a model replaces the best when its count exceeds max(best, 4); the iteration
-// limit is then RANSACUpdateNumIters(confidence, (count - good) / count, 5, limit).  A view of exactly five correspondences
-// is its one sample (every point an inlier when it gives a model).  Returns the backend's first non-zero status.
+// sfmransac::ransac_replay as solvePnPRansac runs it: five points and one model per sample, the per-count sample streams,
+// the limit max_iters (none: a view of more than five correspondences is not looked at).  pnp.hip and the CPU test stub
+// both call this, each with its backend.
 template <class Backend>
 int ransac_replay(Backend& be, int n_views, const int32_t* offsets, double confidence, int max_iters, std::vector<ViewState>& vs,
                   int& flags_any) {
-  using sfmransac::SampleStream;
-  vs.resize((size_t)n_views);
-  for (int v = 0; v < n_views; ++v) {
-    ViewState& s = vs[v];
-    s.count = offsets[v + 1] - offsets[v];
-    s.niters = std::max(max_iters, 0);
-    s.iter = 0;
-    s.best = 0;
-    s.best_it = -1;
-    s.status = s.count < MODEL_POINTS ? -1 : 0;
-    s.done = s.count < MODEL_POINTS || (s.count > MODEL_POINTS && s.niters == 0);
-  }
-  std::map<int, SampleStream> streams;
-  std::vector<Job> jobs;
-  std::vector<int> samples, ok, counts;
-  std::vector<Keep> keeps;
-  int chunk = 32;
-  for (;;) {
-    jobs.clear();
-    samples.clear();
-    for (int v = 0; v < n_views; ++v) {
-      ViewState& s = vs[v];
-      if (s.done) continue;
-      Job jb;
-      jb.view = v;
-      jb.off = offsets[v];
-      jb.count = s.count;
-      jb.samp = (int)(samples.size() / 5);
-      if (s.count == MODEL_POINTS) {
-        for (int it = 0; it < chunk; ++it)
-          for (int k = 0; k < 5; ++k) samples.push_back(k);
-      } else {
-        SampleStream& ss = streams[s.count];
-        ss.extend(s.count, s.iter + chunk);
-        samples.insert(samples.end(), ss.idx.begin() + 5 * (size_t)s.iter, ss.idx.begin() + 5 * (size_t)(s.iter + chunk));
-      }
-      jobs.push_back(jb);
-    }
-    if (jobs.empty()) break;
-    const size_t slots = jobs.size() * (size_t)chunk;
-    ok.assign(slots, 0);
-    counts.assign(slots, 0);
-    const int rc = be.run_chunk(jobs, chunk, samples, ok, counts);
-    if (rc) return rc;
-    keeps.clear();
-    for (size_t j = 0; j < jobs.size(); ++j) {
-      ViewState& s = vs[jobs[j].view];
-      if (s.count == MODEL_POINTS) {
-        const size_t slot = j * chunk;
-        flags_any |= ok[slot] >> 8;
-        if ((ok[slot] & 0xff) > 0) {
-          s.best = MODEL_POINTS;
-          s.status = 1;
-          keeps.push_back(Keep{(int)slot, jobs[j].view});
-        }
-        s.done = true;
-        continue;
-      }
-      long long keep = -1;
-      for (int it = 0; it < chunk && s.iter < s.niters; ++it, ++s.iter) {
-        const size_t slot = j * chunk + it;
-        flags_any |= ok[slot] >> 8;
-        if ((ok[slot] & 0xff) == 0) continue;
-        const int good = counts[slot];
-        if (good > std::max(s.best, MODEL_POINTS - 1)) {
-          s.best = good;
-          s.best_it = s.iter;
-          s.status = 1;
-          keep = (long long)slot;
-          s.niters = sfmransac::ransac_update_num_iters(confidence, (double)(s.count - good) / s.count, MODEL_POINTS, s.niters);
-        }
-      }
-      if (keep >= 0) keeps.push_back(Keep{(int)keep, jobs[j].view});
-      if (s.iter >= s.niters) s.done = true;
-    }
-    if (!keeps.empty()) {
-      const int rk = be.keep_best(keeps);
-      if (rk) return rk;
-    }
-    chunk = std::min(2 * chunk, 256);
-  }
-  return 0;
+  sfmransac::CountSamples draw;
+  return sfmransac::ransac_replay(be, draw, MODEL_POINTS, 1, n_views, offsets, confidence, std::max(max_iters, 0), vs, flags_any);
 }
 
 }  // namespace sfmpnp

@@ -1,7 +1,7 @@
 // pnp.hip -- findCameraPosePNP's cv::solvePnPRansac(..., CV_EPNP) (reference src/Sfm.cpp:1137-1210) on gfx950, batched over
 // views and over RANSAC iterations the way score.hip batches findEssentialMat: the host draws the sample tables, the
 // device solves every (view, iteration) sample of a chunk and counts its model's inliers, and the host replays
-// ptsetreg.cpp's update rule over the counts (pnp.h: ransac_replay, shared with the CPU test stub).
+// ptsetreg.cpp's update rule over the counts (ransac_host.h: ransac_replay, shared with score.hip and the CPU test stubs; pnp.h states how PnP calls it).
 //
 // Kernels.  pnp_solve: one thread per (view, iteration): five float correspondences -> undistortPoints -> EPnP -> Rodrigues;
 // the 714 doubles a solve works on (the 12 x 12 system, its V^T, the 6 x 10 matrix, the small solves) live in a global
@@ -494,7 +494,7 @@ extern "C" int sfmhip_pnp_ransac(sfmhip_ctx* ctx, int n_views, const int32_t* of
   SFM_TRY(ransac_replay(be, n_views, offsets, confidence, max_iters, vs, flags_any));
   // the best model's mask and inlier list, then the refit on the inliers
   std::vector<unsigned char> has((size_t)n_views);
-  for (int v = 0; v < n_views; ++v) has[v] = vs[v].status == 1 ? (vs[v].count == MODEL_POINTS ? 2 : 1) : 0;
+  for (int v = 0; v < n_views; ++v) has[v] = sfmransac::has_code(vs[v].status, vs[v].count, MODEL_POINTS);
   SFM_TRY(bufs.alloc(&d_has, (size_t)n_views));
   SFM_TRY(bufs.alloc(&d_mask, total + 1));
   SFM_TRY(bufs.alloc(&d_inl, total + 1));

@@ -7,7 +7,8 @@
 // sample table per distinct match count, the device solves every (pair, iteration) sample (five-point problem, one
 // thread each) and counts the inliers of every model (one workgroup per (pair, iteration)), in chunks of iterations,
 // and the host replays ptsetreg's update rule over the counts in order -- with the host's libm, as the reference
-// does -- until every pair has reached its own iteration limit.
+// does -- until every pair has reached its own iteration limit.  That loop is ransac_host.h's ransac_replay (shared with
+// pnp.hip and the CPU test stubs); here are its two device backends, EssentialBackend and HomographyBackend.
 //
 // The five-point solver follows OpenCV 3.4.1's EMEstimatorCallback::runKernel step by step (round 3; rounds 1-2 took
 // another route to the same matrices): the null space from the library's one-sided Jacobi SVD with its RNG-filled
@@ -21,15 +22,16 @@
 #include "essential_dev.h"
 #include "hypot_glibc.h"
 #include "jacobi.h"
-#include "ransac_host.h"
+#include "score_host.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <map>
 #include <type_traits>
 #include <vector>
 
 namespace {
+
+using namespace sfmransac;  // (ransac_host.h, score_host.h: the sample streams, Job / Keep, ransac_replay)
 
 using sfmjacobi::DevRng;  // (jacobi.h)
 using sfmjacobi::jacobi_svd;
@@ -326,21 +328,15 @@ __global__ void score_normalize(const double* __restrict__ xy, double* __restric
   out[i] = (i & 1) ? xy[i] * ay + by : xy[i] * ax + bx;
 }
 
-struct ScoreJob {  // one active pair of a chunk
-  int off;         // first match of the pair in the point arrays
-  int count;       // matches
-  int samp;        // first row of its sample table (5 indices per iteration) for this chunk
-};
-
 // thread (job, iteration of the chunk): part 1 of the sample's solve -> work (FP_WORK doubles per sample, sample-major
 // in blocks of 64 so that a wave's stores and loads are coalesced: work[(t / 64) * 64 * FP_WORK + k * 64 + t % 64])
-__global__ __launch_bounds__(64) void score_setup(const ScoreJob* __restrict__ jobs, int n_jobs, int chunk,
+__global__ __launch_bounds__(64) void score_setup(const Job* __restrict__ jobs, int n_jobs, int chunk,
                                                   const int* __restrict__ samples, const double* __restrict__ p1,
                                                   const double* __restrict__ p2, double* __restrict__ work) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_jobs * chunk) return;
   const int j = t / chunk, it = t - j * chunk;
-  const ScoreJob jb = jobs[j];
+  const Job jb = jobs[j];
   const int* s = samples + ((size_t)jb.samp + it) * 5;
   double q1[5][2], q2[5][2];
   for (int k = 0; k < 5; ++k) {
@@ -380,14 +376,14 @@ __device__ __forceinline__ bool is_inlier(const double* E, double x1, double y1,
 }
 
 // workgroup (job, iteration): inlier count of every model of the sample
-__global__ __launch_bounds__(256) void score_count(const ScoreJob* __restrict__ jobs, int chunk, const double* __restrict__ p1,
+__global__ __launch_bounds__(256) void score_count(const Job* __restrict__ jobs, int chunk, const double* __restrict__ p1,
                                                    const double* __restrict__ p2, const double* __restrict__ models,
                                                    const int* __restrict__ n_models, float t, int* __restrict__ counts) {
   __shared__ double sE[MAX_MODELS * 9];
   __shared__ int s_cnt[MAX_MODELS];
   const int j = blockIdx.x / chunk;
   const int slot = blockIdx.x;
-  const ScoreJob jb = jobs[j];
+  const Job jb = jobs[j];
   const int nm = n_models[slot] & 0xff;
   if (threadIdx.x < MAX_MODELS) s_cnt[threadIdx.x] = 0;
   if ((int)threadIdx.x < nm * 9) sE[threadIdx.x] = models[(size_t)slot * (MAX_MODELS * 9) + threadIdx.x];
@@ -426,14 +422,9 @@ __global__ __launch_bounds__(256) void score_mask(const int* __restrict__ offset
   }
 }
 
-// ---------------------------------------------------------------- host: cv::RNG, the sample tables, the update rule
-// (cv::RNG, the distinct-index subset draw and RANSACUpdateNumIters are in ransac_host.h, shared with the PnP RANSAC)
-using namespace sfmransac;
-
-
 // ================================================================ homography (findHomographyInliers, src/Sfm.cpp:667-689)
 // cv::findHomography(query, train, RANSAC, threshold, mask) as OpenCV 3.4.1 (calib3d/fundam.cpp) runs it: FLOAT
-// points; 4-point samples, a sample drawn again when checkSubset rejects it (host, below); model = normalised DLT,
+// points; 4-point samples, a sample drawn again when checkSubset rejects it (host: score_host.h); model = normalised DLT,
 // the eigenvector of the smallest eigenvalue of L^T L (cv::eigen's Jacobi, restated) scaled to H[2][2] = 1; the error and the
 // threshold test in float arithmetic; the mask is the RANSAC mask (the refit + LM refinement change H only).
 __device__ int homography_kernel(const float (*M)[2], const float (*m)[2], double* H) {
@@ -577,19 +568,14 @@ __device__ int homography_kernel(const float (*M)[2], const float (*m)[2], doubl
   return 1;
 }
 
-struct HJob {
-  int off, count, samp;
-  float t;  // (float)(threshold * threshold) of the pair
-};
-
-__global__ __launch_bounds__(64) void homog_solve(const HJob* __restrict__ jobs, int n_jobs, int chunk,
+__global__ __launch_bounds__(64) void homog_solve(const Job* __restrict__ jobs, int n_jobs, int chunk,
                                                   const int* __restrict__ samples, const float* __restrict__ p1,
                                                   const float* __restrict__ p2, double* __restrict__ models,
                                                   int* __restrict__ n_models) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_jobs * chunk) return;
   const int j = t / chunk, it = t - j * chunk;
-  const HJob jb = jobs[j];
+  const Job jb = jobs[j];
   const int* s = samples + ((size_t)jb.samp + it) * 4;
   float M[4][2], m[4][2];
   bool ok = true;
@@ -617,22 +603,24 @@ __device__ __forceinline__ bool homog_inlier(const float* Hf, float Mx, float My
   return dx * dx + dy * dy <= t;
 }
 
-__global__ __launch_bounds__(256) void homog_count(const HJob* __restrict__ jobs, int chunk, const float* __restrict__ p1,
+__global__ __launch_bounds__(256) void homog_count(const Job* __restrict__ jobs, int chunk, const float* __restrict__ p1,
                                                    const float* __restrict__ p2, const double* __restrict__ models,
-                                                   const int* __restrict__ n_models, int* __restrict__ counts) {
+                                                   const int* __restrict__ n_models, const float* __restrict__ tt,
+                                                   int* __restrict__ counts) {
   __shared__ float sH[8];
   __shared__ int s_cnt;
   const int slot = blockIdx.x;
-  const HJob jb = jobs[slot / chunk];
+  const Job jb = jobs[slot / chunk];
   const int nm = n_models[slot];
   if (threadIdx.x == 0) s_cnt = 0;
   if (threadIdx.x < 8 && nm) sH[threadIdx.x] = (float)models[(size_t)slot * 9 + threadIdx.x];
   __syncthreads();
   if (nm) {
+    const float t = tt[jb.view];  // (float)(threshold * threshold) of the pair
     int cnt = 0;
     for (int i = threadIdx.x; i < jb.count; i += 256) {
       const size_t k = (size_t)jb.off + i;
-      cnt += homog_inlier(sH, p1[2 * k], p1[2 * k + 1], p2[2 * k], p2[2 * k + 1], jb.t) ? 1 : 0;
+      cnt += homog_inlier(sH, p1[2 * k], p1[2 * k + 1], p2[2 * k], p2[2 * k + 1], t) ? 1 : 0;
     }
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&s_cnt, cnt);
@@ -657,69 +645,6 @@ __global__ __launch_bounds__(256) void homog_mask(const int* __restrict__ offset
   }
 }
 
-// ---- host: HomographyEstimatorCallback::checkSubset and the per-pair sample stream
-static bool have_collinear(const float (*p)[2], int count) {
-  const int i = count - 1;
-  for (int j = 0; j < i; ++j) {
-    const double dx1 = p[j][0] - p[i][0], dy1 = p[j][1] - p[i][1];
-    for (int k = 0; k < j; ++k) {
-      const double dx2 = p[k][0] - p[i][0], dy2 = p[k][1] - p[i][1];
-      if (std::fabs(dx2 * dy1 - dy2 * dx1) <= FLT_EPSILON * (std::fabs(dx1) + std::fabs(dy1) + std::fabs(dx2) + std::fabs(dy2))) return true;
-    }
-  }
-  return false;
-}
-static double det3(const double* m) {
-  return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-}
-static bool homography_check_subset(const float (*s1)[2], const float (*s2)[2]) {
-  if (have_collinear(s1, 4) || have_collinear(s2, 4)) return false;
-  static const int tt[4][3] = {{0, 1, 2}, {1, 2, 3}, {0, 2, 3}, {0, 1, 3}};
-  int negative = 0;
-  for (int i = 0; i < 4; ++i) {
-    const int* t = tt[i];
-    const double A[9] = {s1[t[0]][0], s1[t[0]][1], 1., s1[t[1]][0], s1[t[1]][1], 1., s1[t[2]][0], s1[t[2]][1], 1.};
-    const double B[9] = {s2[t[0]][0], s2[t[0]][1], 1., s2[t[1]][0], s2[t[1]][1], 1., s2[t[2]][0], s2[t[2]][1], 1.};
-    negative += det3(A) * det3(B) < 0;
-  }
-  return negative == 0 || negative == 4;
-}
-struct HSampleStream {  // per pair: the accepted 4-point samples in order (-1: getSubset gave up after 10000 attempts)
-  CvRng rng;
-  std::vector<int> idx;
-  bool dead = false;
-  void extend(const float* m1, const float* m2, int count, int n_iters) {
-    while ((int)idx.size() < 4 * n_iters) {
-      int s[4] = {-1, -1, -1, -1};
-      bool found = false;
-      for (int attempt = 0; attempt < 10000 && !dead; ++attempt) {
-        for (int i = 0; i < 4;) {
-          const int v = rng.uniform(0, count);
-          int j = 0;
-          for (; j < i; ++j)
-            if (s[j] == v) break;
-          if (j < i) continue;
-          s[i++] = v;
-        }
-        float a[4][2], b[4][2];
-        for (int k = 0; k < 4; ++k) {
-          a[k][0] = m1[2 * s[k]]; a[k][1] = m1[2 * s[k] + 1];
-          b[k][0] = m2[2 * s[k]]; b[k][1] = m2[2 * s[k] + 1];
-        }
-        if (homography_check_subset(a, b)) {
-          found = true;
-          break;
-        }
-      }
-      if (!found) {
-        dead = true;
-        s[0] = s[1] = s[2] = s[3] = -1;
-      }
-      idx.insert(idx.end(), s, s + 4);
-    }
-  }
-};
-
 // The model of a RANSAC iteration that raised a pair's best count stays on the device: (index of the model in the
 // chunk's model array, pair) -> best[pair].  (Downloading every model of every iteration for the host to pick from
 // moved 720 bytes per iteration: 0.9 GB for 1225 pairs x 1000 iterations.)
@@ -729,6 +654,87 @@ __global__ void score_keep_best(const int2* __restrict__ upd, int n, const doubl
   const int2 u = upd[i / 9];
   best[(size_t)u.y * 9 + i % 9] = models[(size_t)u.x * 9 + i % 9];
 }
+static_assert(sizeof(Keep) == sizeof(int2) && offsetof(Keep, slot) == 0, "score_keep_best reads a Keep as (model, pair)");
+
+// what the two device sides of ransac_replay share: the chunk's grow-only buffers, its uploads and downloads, the keep-list
+struct ChunkBufs {
+  hipStream_t st;
+  DevBufs& bufs;
+  double* d_best;  // 9 per pair
+  Keep* d_upd;     // n_pairs
+  Job* d_jobs = nullptr;
+  int *d_samples = nullptr, *d_nm = nullptr, *d_counts = nullptr;
+  double* d_models = nullptr;
+  size_t cap_jobs = 0, cap_slots = 0, cap_samples = 0;
+
+  // M models of 9 doubles per slot; grew = the slot buffers were reallocated (the caller's own per-slot buffers follow)
+  int upload(const std::vector<Job>& jobs, size_t slots, int M, const std::vector<int>& samples, bool& grew) {
+    if (jobs.size() > cap_jobs) {
+      SFM_TRY(bufs.alloc(&d_jobs, jobs.size()));
+      cap_jobs = jobs.size();
+    }
+    grew = slots > cap_slots;
+    if (grew) {
+      SFM_TRY(bufs.alloc(&d_nm, slots));
+      SFM_TRY(bufs.alloc(&d_counts, slots * M));
+      SFM_TRY(bufs.alloc(&d_models, slots * M * 9));
+      cap_slots = slots;
+    }
+    if (samples.size() > cap_samples) {
+      SFM_TRY(bufs.alloc(&d_samples, samples.size()));
+      cap_samples = samples.size();
+    }
+    SFM_HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice, st));
+    SFM_HIP_TRY(hipMemcpyAsync(d_samples, samples.data(), sizeof(int) * samples.size(), hipMemcpyHostToDevice, st));
+    return SFMHIP_OK;
+  }
+  int download(std::vector<int>& ok, std::vector<int>& counts) {
+    SFM_HIP_TRY(hipGetLastError());
+    SFM_HIP_TRY(hipMemcpyAsync(ok.data(), d_nm, sizeof(int) * ok.size(), hipMemcpyDeviceToHost, st));
+    SFM_HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, sizeof(int) * counts.size(), hipMemcpyDeviceToHost, st));
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+    return SFMHIP_OK;
+  }
+  int keep_best(const std::vector<Keep>& keeps) {  // (before the next chunk's solve overwrites the models; same stream)
+    SFM_HIP_TRY(hipMemcpyAsync(d_upd, keeps.data(), sizeof(Keep) * keeps.size(), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(score_keep_best, dim3((unsigned)((9 * keeps.size() + 255) / 256)), dim3(256), 0, st, (const int2*)d_upd,
+                       (int)keeps.size(), (const double*)d_models, d_best);
+    return SFMHIP_OK;
+  }
+};
+
+struct EssentialBackend : ChunkBufs {
+  const double *d_p1, *d_p2;
+  float t;
+  double* d_work = nullptr;
+  int run_chunk(const std::vector<Job>& jobs, int chunk, const std::vector<int>& samples, std::vector<int>& ok, std::vector<int>& counts) {
+    const size_t slots = ok.size();
+    bool grew;
+    SFM_TRY(upload(jobs, slots, MAX_MODELS, samples, grew));
+    if (grew) SFM_TRY(bufs.alloc(&d_work, (slots + 63) / 64 * 64 * FP_WORK));
+    hipLaunchKernelGGL(score_setup, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, st, (const Job*)d_jobs, (int)jobs.size(), chunk,
+                       (const int*)d_samples, d_p1, d_p2, d_work);
+    hipLaunchKernelGGL(score_roots, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (int)slots, (const double*)d_work, d_models,
+                       d_nm);
+    hipLaunchKernelGGL(score_count, dim3((unsigned)slots), dim3(256), 0, st, (const Job*)d_jobs, chunk, d_p1, d_p2,
+                       (const double*)d_models, (const int*)d_nm, t, d_counts);
+    return download(ok, counts);
+  }
+};
+
+struct HomographyBackend : ChunkBufs {
+  const float *d_p1, *d_p2, *d_tt;
+  int run_chunk(const std::vector<Job>& jobs, int chunk, const std::vector<int>& samples, std::vector<int>& ok, std::vector<int>& counts) {
+    const size_t slots = ok.size();
+    bool grew;
+    SFM_TRY(upload(jobs, slots, 1, samples, grew));
+    hipLaunchKernelGGL(homog_solve, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, st, (const Job*)d_jobs, (int)jobs.size(), chunk,
+                       (const int*)d_samples, d_p1, d_p2, d_models, d_nm);
+    hipLaunchKernelGGL(homog_count, dim3((unsigned)slots), dim3(256), 0, st, (const Job*)d_jobs, chunk, d_p1, d_p2,
+                       (const double*)d_models, (const int*)d_nm, d_tt, d_counts);
+    return download(ok, counts);
+  }
+};
 
 }  // namespace
 
@@ -759,132 +765,21 @@ int sfm_essential_ransac(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, c
     SFM_HIP_TRY(hipMemcpyAsync(dev.d_right, right_xy, sizeof(double) * 2 * total, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(score_normalize, dim3(nb), dim3(256), 0, st, dev.d_right, d_p2, 2 * total, ax, bx, ay, by);
   }
-  // per pair: the state of ptsetreg's loop
-  struct PairState {
-    int count, niters, iter, best, best_it, best_m;
-    bool done;
-  };
-  std::vector<PairState> ps(n_pairs);
-  std::vector<unsigned char> has(n_pairs, 0);
-  std::map<int, SampleStream> streams;
   double* d_bestE = nullptr;
-  int2* d_upd = nullptr;
-  std::vector<int2> upd;
+  Keep* d_upd = nullptr;
   SFM_TRY(dev.bufs.alloc(&d_bestE, 9 * (size_t)n_pairs));
   dev.d_bestE = d_bestE;
   SFM_TRY(bufs.alloc(&d_upd, (size_t)n_pairs));
   SFM_HIP_TRY(hipMemsetAsync(d_bestE, 0, sizeof(double) * 9 * n_pairs, st));
-  for (int p = 0; p < n_pairs; ++p) {
-    PairState& s = ps[p];
-    s.count = offsets[p + 1] - offsets[p];
-    s.niters = MAX_ITERS;
-    s.iter = 0;
-    s.best = 0;
-    s.best_it = s.best_m = -1;
-    s.done = s.count < MODEL_POINTS;  // (run() returns false: no model, empty mask)
-  }
-  int chunk = 32;
-  std::vector<ScoreJob> jobs;
-  std::vector<int> job_pair, h_samples, h_nm, h_counts;
-  ScoreJob* d_jobs = nullptr;
-  int *d_samples = nullptr, *d_nm = nullptr, *d_counts = nullptr;
-  double *d_models = nullptr, *d_work = nullptr;
-  size_t cap_jobs = 0, cap_slots = 0, cap_samples = 0;
-  for (;;) {
-    jobs.clear();
-    job_pair.clear();
-    h_samples.clear();
-    for (int p = 0; p < n_pairs; ++p) {
-      PairState& s = ps[p];
-      if (s.done) continue;
-      ScoreJob jb;
-      jb.off = offsets[p];
-      jb.count = s.count;
-      jb.samp = (int)(h_samples.size() / 5);
-      if (s.count == MODEL_POINTS) {
-        // run(): count == modelPoints -> runKernel on the five, every match an inlier if there is a model
-        for (int it = 0; it < chunk; ++it)
-          for (int k = 0; k < 5; ++k) h_samples.push_back(k);
-      } else {
-        SampleStream& ss = streams[s.count];
-        ss.extend(s.count, s.iter + chunk);
-        h_samples.insert(h_samples.end(), ss.idx.begin() + 5 * (size_t)s.iter, ss.idx.begin() + 5 * (size_t)(s.iter + chunk));
-      }
-      jobs.push_back(jb);
-      job_pair.push_back(p);
-    }
-    if (jobs.empty()) break;
-    const size_t nj = jobs.size(), slots = nj * (size_t)chunk;
-    if (nj > cap_jobs) {
-      SFM_TRY(bufs.alloc(&d_jobs, nj));
-      cap_jobs = nj;
-    }
-    if (slots > cap_slots) {
-      SFM_TRY(bufs.alloc(&d_nm, slots));
-      SFM_TRY(bufs.alloc(&d_counts, slots * MAX_MODELS));
-      SFM_TRY(bufs.alloc(&d_models, slots * MAX_MODELS * 9));
-      SFM_TRY(bufs.alloc(&d_work, (slots + 63) / 64 * 64 * FP_WORK));
-      cap_slots = slots;
-    }
-    if (h_samples.size() > cap_samples) {
-      SFM_TRY(bufs.alloc(&d_samples, h_samples.size()));
-      cap_samples = h_samples.size();
-    }
-    SFM_HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(ScoreJob) * nj, hipMemcpyHostToDevice, st));
-    SFM_HIP_TRY(hipMemcpyAsync(d_samples, h_samples.data(), sizeof(int) * h_samples.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(score_setup, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, st, d_jobs, (int)nj, chunk, d_samples, d_p1,
-                       d_p2, d_work);
-    hipLaunchKernelGGL(score_roots, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (int)slots, (const double*)d_work, d_models,
-                       d_nm);
-    hipLaunchKernelGGL(score_count, dim3((unsigned)slots), dim3(256), 0, st, d_jobs, chunk, d_p1, d_p2, d_models, d_nm, t, d_counts);
-    SFM_HIP_TRY(hipGetLastError());
-    h_nm.resize(slots);
-    h_counts.resize(slots * MAX_MODELS);
-    SFM_HIP_TRY(hipMemcpyAsync(h_nm.data(), d_nm, sizeof(int) * slots, hipMemcpyDeviceToHost, st));
-    SFM_HIP_TRY(hipMemcpyAsync(h_counts.data(), d_counts, sizeof(int) * slots * MAX_MODELS, hipMemcpyDeviceToHost, st));
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-    upd.clear();
-    // ---- ptsetreg.cpp run(): the models of a sample in order, the iteration limit from the best count so far
-    for (size_t j = 0; j < nj; ++j) {
-      PairState& s = ps[job_pair[j]];
-      if (s.count == MODEL_POINTS) {
-        const size_t slot = j * chunk;
-        flags_any |= h_nm[slot] >> 8;
-        if ((h_nm[slot] & 0xff) > 0) {
-          s.best = MODEL_POINTS;
-          has[job_pair[j]] = 2;
-          upd.push_back(int2{(int)(slot * MAX_MODELS), job_pair[j]});
-        }
-        s.done = true;
-        continue;
-      }
-      long long keep = -1;  // the last model of this chunk that raised the best count
-      for (int it = 0; it < chunk && s.iter < s.niters; ++it, ++s.iter) {
-        const size_t slot = j * chunk + it;
-        flags_any |= h_nm[slot] >> 8;
-        for (int m = 0; m < (h_nm[slot] & 0xff); ++m) {
-          const int good = h_counts[slot * MAX_MODELS + m];
-          if (good > std::max(s.best, MODEL_POINTS - 1)) {
-            s.best = good;
-            has[job_pair[j]] = 1;
-            keep = (long long)(slot * MAX_MODELS + m);
-            s.niters = ransac_update_num_iters(prob, (double)(s.count - good) / s.count, MODEL_POINTS, s.niters);
-          }
-        }
-      }
-      if (keep >= 0) upd.push_back(int2{(int)keep, job_pair[j]});
-      if (s.iter >= s.niters) s.done = true;
-    }
-    if (!upd.empty()) {  // (before the next chunk's solve overwrites the models; same stream)
-      SFM_HIP_TRY(hipMemcpyAsync(d_upd, upd.data(), sizeof(int2) * upd.size(), hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(score_keep_best, dim3((unsigned)((9 * upd.size() + 255) / 256)), dim3(256), 0, st, (const int2*)d_upd,
-                         (int)upd.size(), (const double*)d_models, d_bestE);
-    }
-    chunk = std::min(2 * chunk, 256);
-  }
+  EssentialBackend be{{st, bufs, d_bestE, d_upd}, d_p1, d_p2, t};
+  CountSamples draw;
+  std::vector<ViewState> ps;
+  SFM_TRY(ransac_replay(be, draw, MODEL_POINTS, MAX_MODELS, n_pairs, offsets, prob, MAX_ITERS, ps, flags_any));
+  std::vector<unsigned char> has(n_pairs);
   for (int p = 0; p < n_pairs; ++p) {
     inliers[p] = ps[p].best;
     if (iterations) iterations[p] = ps[p].iter;
+    has[p] = has_code(ps[p].status, ps[p].count, MODEL_POINTS);
   }
   ctx->score_flags = flags_any;
   dev.has = has;
@@ -1036,140 +931,38 @@ extern "C" int sfmhip_score_homography(sfmhip_ctx* ctx, int n_pairs, const int32
   SFM_TRY(bufs.alloc(&d_p2, h2.size()));
   SFM_HIP_TRY(hipMemcpyAsync(d_p1, h1.data(), sizeof(float) * h1.size(), hipMemcpyHostToDevice, st));
   SFM_HIP_TRY(hipMemcpyAsync(d_p2, h2.data(), sizeof(float) * h2.size(), hipMemcpyHostToDevice, st));
-  struct PairState {
-    int count, niters, iter, best;
-    float t;
-    bool done;
-  };
-  std::vector<PairState> ps(n_pairs);
-  std::vector<HSampleStream> streams(n_pairs);
-  std::vector<unsigned char> has(n_pairs, 0);
-  std::vector<float> tts(n_pairs);
-  double* d_bestH = nullptr;
-  int2* d_upd = nullptr;
-  std::vector<int2> upd;
-  SFM_TRY(bufs.alloc(&d_bestH, 9 * (size_t)n_pairs));
-  SFM_TRY(bufs.alloc(&d_upd, (size_t)n_pairs));
-  SFM_HIP_TRY(hipMemsetAsync(d_bestH, 0, sizeof(double) * 9 * n_pairs, st));
+  std::vector<float> tts(n_pairs);  // (float)(threshold * threshold) per pair: homog_count and homog_mask read it
   for (int p = 0; p < n_pairs; ++p) {
-    PairState& s = ps[p];
-    s.count = offsets[p + 1] - offsets[p];
     double thr = thresholds[p];
     if (thr <= 0) thr = 3;  // defaultRANSACReprojThreshold
-    s.t = tts[p] = (float)(thr * thr);
-    s.niters = MAX_ITERS;
-    s.iter = s.best = 0;
-    s.done = s.count < MODEL_POINTS;
+    tts[p] = (float)(thr * thr);
   }
-  int chunk = 32;
-  std::vector<HJob> jobs;
-  std::vector<int> job_pair, h_samples, h_nm, h_counts;
-  HJob* d_jobs = nullptr;
-  int *d_samples = nullptr, *d_nm = nullptr, *d_counts = nullptr;
-  double* d_models = nullptr;
-  size_t cap_jobs = 0, cap_slots = 0, cap_samples = 0;
-  for (;;) {
-    jobs.clear();
-    job_pair.clear();
-    h_samples.clear();
-    for (int p = 0; p < n_pairs; ++p) {
-      PairState& s = ps[p];
-      if (s.done) continue;
-      HJob jb;
-      jb.off = offsets[p];
-      jb.count = s.count;
-      jb.t = s.t;
-      jb.samp = (int)(h_samples.size() / 4);
-      if (s.count == MODEL_POINTS) {  // method == 0 || npoints == 4: runKernel on the four, the mask all ones
-        for (int it = 0; it < chunk; ++it)
-          for (int k = 0; k < 4; ++k) h_samples.push_back(k);
-      } else {
-        HSampleStream& ss = streams[p];
-        ss.extend(h1.data() + 2 * (size_t)offsets[p], h2.data() + 2 * (size_t)offsets[p], s.count, s.iter + chunk);
-        h_samples.insert(h_samples.end(), ss.idx.begin() + 4 * (size_t)s.iter, ss.idx.begin() + 4 * (size_t)(s.iter + chunk));
-      }
-      jobs.push_back(jb);
-      job_pair.push_back(p);
-    }
-    if (jobs.empty()) break;
-    const size_t nj = jobs.size(), slots = nj * (size_t)chunk;
-    if (nj > cap_jobs) {
-      SFM_TRY(bufs.alloc(&d_jobs, nj));
-      cap_jobs = nj;
-    }
-    if (slots > cap_slots) {
-      SFM_TRY(bufs.alloc(&d_nm, slots));
-      SFM_TRY(bufs.alloc(&d_counts, slots));
-      SFM_TRY(bufs.alloc(&d_models, slots * 9));
-      cap_slots = slots;
-    }
-    if (h_samples.size() > cap_samples) {
-      SFM_TRY(bufs.alloc(&d_samples, h_samples.size()));
-      cap_samples = h_samples.size();
-    }
-    SFM_HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(HJob) * nj, hipMemcpyHostToDevice, st));
-    SFM_HIP_TRY(hipMemcpyAsync(d_samples, h_samples.data(), sizeof(int) * h_samples.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(homog_solve, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, st, d_jobs, (int)nj, chunk, d_samples, d_p1,
-                       d_p2, d_models, d_nm);
-    hipLaunchKernelGGL(homog_count, dim3((unsigned)slots), dim3(256), 0, st, d_jobs, chunk, d_p1, d_p2, d_models, d_nm, d_counts);
-    SFM_HIP_TRY(hipGetLastError());
-    h_nm.resize(slots);
-    h_counts.resize(slots);
-    SFM_HIP_TRY(hipMemcpyAsync(h_nm.data(), d_nm, sizeof(int) * slots, hipMemcpyDeviceToHost, st));
-    SFM_HIP_TRY(hipMemcpyAsync(h_counts.data(), d_counts, sizeof(int) * slots, hipMemcpyDeviceToHost, st));
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-    upd.clear();
-    for (size_t j = 0; j < nj; ++j) {
-      const int p = job_pair[j];
-      PairState& s = ps[p];
-      if (s.count == MODEL_POINTS) {
-        if (h_nm[j * chunk] > 0) {
-          s.best = MODEL_POINTS;
-          has[p] = 2;
-        }
-        s.done = true;
-        continue;
-      }
-      long long keep = -1;
-      for (int it = 0; it < chunk && s.iter < s.niters; ++it, ++s.iter) {
-        const size_t slot = j * chunk + it;
-        if (streams[p].idx[4 * (size_t)s.iter] < 0) {  // getSubset failed: run() leaves the loop (iter 0: no model at all)
-          s.niters = s.iter;
-          break;
-        }
-        if (h_nm[slot] <= 0) continue;
-        const int good = h_counts[slot];
-        if (good > std::max(s.best, MODEL_POINTS - 1)) {
-          s.best = good;
-          has[p] = 1;
-          keep = (long long)slot;
-          s.niters = ransac_update_num_iters(confidence, (double)(s.count - good) / s.count, MODEL_POINTS, s.niters);
-        }
-      }
-      if (keep >= 0) upd.push_back(int2{(int)keep, p});
-      if (s.iter >= s.niters) s.done = true;
-    }
-    if (!upd.empty()) {
-      SFM_HIP_TRY(hipMemcpyAsync(d_upd, upd.data(), sizeof(int2) * upd.size(), hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(score_keep_best, dim3((unsigned)((9 * upd.size() + 255) / 256)), dim3(256), 0, st, (const int2*)d_upd,
-                         (int)upd.size(), (const double*)d_models, d_bestH);
-    }
-    chunk = std::min(2 * chunk, 256);
-  }
+  double* d_bestH = nullptr;
+  Keep* d_upd = nullptr;
+  float* d_tt = nullptr;
+  SFM_TRY(bufs.alloc(&d_bestH, 9 * (size_t)n_pairs));
+  SFM_TRY(bufs.alloc(&d_upd, (size_t)n_pairs));
+  SFM_TRY(bufs.alloc(&d_tt, (size_t)n_pairs));
+  SFM_HIP_TRY(hipMemsetAsync(d_bestH, 0, sizeof(double) * 9 * n_pairs, st));
+  SFM_HIP_TRY(hipMemcpyAsync(d_tt, tts.data(), sizeof(float) * n_pairs, hipMemcpyHostToDevice, st));
+  HomographyBackend be{{st, bufs, d_bestH, d_upd}, d_p1, d_p2, d_tt};
+  PairSamples draw{h1.data(), h2.data(), offsets, std::vector<HSampleStream>(n_pairs)};
+  std::vector<ViewState> ps;
+  int flags_any = 0;  // (homog_solve reports none)
+  SFM_TRY(ransac_replay(be, draw, MODEL_POINTS, 1, n_pairs, offsets, confidence, MAX_ITERS, ps, flags_any));
+  std::vector<unsigned char> has(n_pairs);
   for (int p = 0; p < n_pairs; ++p) {
     inliers[p] = ps[p].best;
     if (iterations) iterations[p] = ps[p].iter;
+    has[p] = has_code(ps[p].status, ps[p].count, MODEL_POINTS);
   }
   if (mask && total > 0) {
     int* d_off = nullptr;
-    float* d_tt = nullptr;
     unsigned char *d_has = nullptr, *d_mask = nullptr;
     SFM_TRY(bufs.alloc(&d_off, (size_t)n_pairs + 1));
-    SFM_TRY(bufs.alloc(&d_tt, (size_t)n_pairs));
     SFM_TRY(bufs.alloc(&d_has, (size_t)n_pairs));
     SFM_TRY(bufs.alloc(&d_mask, (size_t)total));
     SFM_HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int) * (n_pairs + 1), hipMemcpyHostToDevice, st));
-    SFM_HIP_TRY(hipMemcpyAsync(d_tt, tts.data(), sizeof(float) * n_pairs, hipMemcpyHostToDevice, st));
     SFM_HIP_TRY(hipMemcpyAsync(d_has, has.data(), n_pairs, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(homog_mask, dim3(n_pairs), dim3(256), 0, st, d_off, d_p1, d_p2, d_bestH, d_has, d_tt, d_mask);
     SFM_HIP_TRY(hipGetLastError());
