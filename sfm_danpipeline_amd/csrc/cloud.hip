@@ -36,22 +36,14 @@ constexpr double KNN_OCCUPANCY = 16.0;    // points per occupied cell the k-NN g
 
 }  // namespace
 
-int sfmgrid::grow_tmp(sfmhip_cloud* c, size_t bytes) {
-  if (bytes <= c->tmp_bytes) return SFMHIP_OK;
-  hipFree(c->tmp);
-  c->tmp = nullptr;
-  c->tmp_bytes = 0;
-  SFM_TRY(sfm_dev_alloc((unsigned char**)&c->tmp, bytes));
-  c->tmp_bytes = bytes;
-  return SFMHIP_OK;
-}
+int sfmgrid::grow_tmp(sfmhip_cloud* c, size_t bytes) { return c->tmp.need(bytes); }
 
 int sfmgrid::scan(sfmhip_cloud* c, const int* in, int* out, size_t n, int* total) {
   size_t need = 0;
   long long t = 0;
   SFM_TRY(sfm_scan_bytes(n, c->ctx->stream, &need));
   SFM_TRY(grow_tmp(c, need));
-  SFM_TRY(sfm_exclusive_scan(c->tmp, c->tmp_bytes, in, out, n, c->ctx->stream, total ? &t : nullptr));
+  SFM_TRY(sfm_exclusive_scan(c->tmp.p, c->tmp.cap, in, out, n, c->ctx->stream, total ? &t : nullptr));
   if (total) *total = (int)t;
   return SFMHIP_OK;
 }
@@ -62,7 +54,7 @@ int sfmgrid::cell_sort(sfmhip_cloud* c, long long ncell, int* keys_in, int* keys
   size_t need = 0;
   SFM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, keys_in, keys_out, vals_in, vals_out, (unsigned)n, 0u, bits, c->ctx->stream));
   SFM_TRY(grow_tmp(c, need));
-  SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp, need, keys_in, keys_out, vals_in, vals_out, (unsigned)n, 0u, bits, c->ctx->stream));
+  SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp.p, need, keys_in, keys_out, vals_in, vals_out, (unsigned)n, 0u, bits, c->ctx->stream));
   return SFMHIP_OK;
 }
 
@@ -296,16 +288,9 @@ int sfmgrid::grid_build(sfmhip_cloud* c, const GridSrc& src, Grid& g, double cel
   }
   SFM_HIP_TRY(hipMemcpyAsync(&g.nonempty, nonempty, sizeof(int), hipMemcpyDeviceToHost, st));
   if (chunks && src.n_valid > 0) {
-    if (c->cbuf_n < g.ncell) {
-      hipFree(c->cbuf[0]);
-      hipFree(c->cbuf[1]);
-      c->cbuf[0] = c->cbuf[1] = nullptr;
-      c->cbuf_n = 0;
-      SFM_TRY(sfm_dev_alloc(&c->cbuf[0], (size_t)g.ncell));
-      SFM_TRY(sfm_dev_alloc(&c->cbuf[1], (size_t)g.ncell));
-      c->cbuf_n = g.ncell;
-    }
-    int *nch = c->cbuf[0], *off = c->cbuf[1];
+    SFM_TRY(c->cbuf[0].need((size_t)g.ncell));
+    SFM_TRY(c->cbuf[1].need((size_t)g.ncell));
+    int *nch = c->cbuf[0].p, *off = c->cbuf[1].p;
     hipLaunchKernelGGL(cloud_chunk_counts, dim3(blocks(g.ncell, 256)), dim3(256), 0, st, g.start, g.end, g.ncell, nch);
     SFM_HIP_TRY(hipGetLastError());
     SFM_TRY(scan(c, nch, off, (size_t)g.ncell, &g.n_chunks));
@@ -411,17 +396,10 @@ int out_buffer(sfmhip_cloud* c, size_t bytes, void** p) { return sfm_ctx_dev_scr
 namespace {
 
 int box_of(sfmhip_cloud* c) {
-  hipStream_t st = c->ctx->stream;
-  unsigned mm[7] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u};
+  unsigned mm[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
   if (c->n > 0) {
-    DevBufs B;
-    unsigned* d = nullptr;
-    SFM_TRY(B.alloc(&d, 7));
-    SFM_HIP_TRY(hipMemcpyAsync(d, mm, sizeof mm, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(cloud_minmax<FinitePoint>, dim3(std::min(blocks(c->n, 256), 1024u)), dim3(256), 0, st, c->xyz, c->n, FinitePoint(), d);
-    SFM_HIP_TRY(hipGetLastError());
-    SFM_HIP_TRY(hipMemcpyAsync(mm, d, sizeof mm, hipMemcpyDeviceToHost, st));
-    SFM_HIP_TRY(hipStreamSynchronize(st));
+    SFM_TRY(minmax(c, c->xyz, c->n, FinitePoint(), mm));
+    SFM_HIP_TRY(hipStreamSynchronize(c->ctx->stream));
   }
   c->n_valid = (int)mm[6];
   for (int a = 0; a < 3; ++a) {
@@ -438,7 +416,8 @@ int sfmgrid::adopt_device(sfmhip_ctx* ctx, float* d_xyz, int n, sfmhip_cloud** o
   c->ctx = ctx;
   c->n = n;
   c->xyz = d_xyz;
-  const int rc = box_of(c);
+  int rc = sfm_dev_alloc(&c->mm, (size_t)7);
+  if (rc == SFMHIP_OK) rc = box_of(c);
   if (rc != SFMHIP_OK) {
     sfmhip_cloud_destroy(c);
     return rc;
@@ -469,19 +448,12 @@ extern "C" void sfmhip_cloud_destroy(sfmhip_cloud* c) {
   if (!c) return;
   hipSetDevice(c->ctx->device);
   hipStreamSynchronize(c->ctx->stream);
-  c->rg.release();
-  c->kg.release();
-  if (c->seg && c->seg_free) c->seg_free(c->seg);
-  if (c->psn && c->psn_free) c->psn_free(c->psn);
-  if (c->dnd && c->dnd_free) c->dnd_free(c->dnd);
-  if (c->gnd && c->gnd_free) c->gnd_free(c->gnd);
-  if (c->trs && c->trs_free) c->trs_free(c->trs);
-  if (c->flt && c->flt_free) c->flt_free(c->flt);
+  for (StageSlot& s : c->stage)
+    if (s.p) s.free(s.p);
   hipFree(c->xyz);
-  hipFree(c->tmp);
+  hipFree(c->mm);
   for (int b = 0; b < 4; ++b) hipFree(c->ibuf[b]);
-  for (int b = 0; b < 2; ++b) hipFree(c->cbuf[b]);
-  delete c;
+  delete c;  // (the two grids, tmp and cbuf release themselves)
 }
 
 extern "C" int sfmhip_cloud_passthrough(sfmhip_cloud* c, int axis, float lo, float hi, int negative, int32_t* idx_out, int32_t* n_out) {

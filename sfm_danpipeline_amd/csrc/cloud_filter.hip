@@ -30,42 +30,14 @@ namespace {
 
 constexpr int RED_BLOCK = 256;  // runs per vg_reduce workgroup (4 waves)
 
-template <typename T>
-struct Grow {  // a grow-only device array
-  T* p = nullptr;
-  size_t cap = 0;
-  int need(size_t n) {
-    if (n <= cap && p) return SFMHIP_OK;
-    hipFree(p);
-    p = nullptr;
-    cap = 0;
-    SFM_TRY(sfm_dev_alloc(&p, n));
-    cap = std::max(n, (size_t)1);
-    return SFMHIP_OK;
-  }
-};
-
-struct FltState {
+struct FltState {  // on the cloud handle, freed with it: run tables, attributes, mean distances
+  static constexpr sfmgrid::Stage slot = sfmgrid::FILTER;  // (its slot on the handle: stage<FltState>(cloud))
   Grow<int> run_start, emit, row, voxel_of, sel;
   Grow<uint32_t> rgb_in, rgb_out;
   Grow<float> nrm_in, nrm_out, md;
   Grow<double> part;
+  double ms[4] = {0, 0, 0, 0};  // key + sort, voxel reduce (last voxel grid); neighbour means, threshold + compaction (last outlier call)
 };
-
-void flt_state_free(void* p) {
-  FltState* s = (FltState*)p;
-  hipFree(s->run_start.p), hipFree(s->emit.p), hipFree(s->row.p), hipFree(s->voxel_of.p), hipFree(s->sel.p);
-  hipFree(s->rgb_in.p), hipFree(s->rgb_out.p), hipFree(s->nrm_in.p), hipFree(s->nrm_out.p), hipFree(s->md.p), hipFree(s->part.p);
-  delete s;
-}
-
-FltState* flt_state(sfmhip_cloud* c) {
-  if (!c->flt) {
-    c->flt = new FltState();
-    c->flt_free = flt_state_free;
-  }
-  return (FltState*)c->flt;
-}
 
 // ---- voxel grid
 
@@ -322,11 +294,11 @@ extern "C" int sfmhip_cloud_voxel_grid(sfmhip_cloud* c, const float leaf[3], int
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
   hipStream_t st = c->ctx->stream;
   const bool timing = c->ctx->timing;
-  c->flt_ms[0] = c->flt_ms[1] = 0;
+  FltState* s = stage<FltState>(c);
+  s->ms[0] = s->ms[1] = 0;
   const int n = c->n, nv = c->n_valid;
   int n_runs = 0, m = 0;
   float* d_out = nullptr;
-  FltState* s = flt_state(c);
   if (nv > 0) {
     SFM_TRY(ensure_ibuf(c));
     SFM_TRY(s->run_start.need(n));
@@ -384,8 +356,8 @@ extern "C" int sfmhip_cloud_voxel_grid(sfmhip_cloud* c, const float leaf[3], int
       return rc;
     }
     if (timing) {
-      c->flt_ms[0] = t1 - t0;
-      c->flt_ms[1] = sfm_now_ms() - t1;
+      s->ms[0] = t1 - t0;
+      s->ms[1] = sfm_now_ms() - t1;
     }
   } else {
     for (int i = 0; voxel_of && i < n; ++i) voxel_of[i] = -1;
@@ -403,7 +375,8 @@ extern "C" int sfmhip_cloud_statistical_outlier(sfmhip_cloud* c, int mean_k, dou
     return SFMHIP_ERR_ARG;
   const int n = c->n, nv = c->n_valid;
   if (nv > 0 && nv <= mean_k) return SFMHIP_ERR_ARG;  // S5
-  c->flt_ms[2] = c->flt_ms[3] = 0;
+  FltState* s = stage<FltState>(c);
+  s->ms[2] = s->ms[3] = 0;
   *n_out = 0;
   if (threshold) *threshold = 0.0;
   if (nv == 0) {
@@ -413,7 +386,6 @@ extern "C" int sfmhip_cloud_statistical_outlier(sfmhip_cloud* c, int mean_k, dou
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
   hipStream_t st = c->ctx->stream;
   const bool timing = c->ctx->timing;
-  FltState* s = flt_state(c);
   SFM_TRY(ensure_ibuf(c));
   SFM_TRY(knn_grid(c));
   const long long n_part = (n + (long long)sfmfilter::SUM_BLOCK - 1) / sfmfilter::SUM_BLOCK;
@@ -437,8 +409,8 @@ extern "C" int sfmhip_cloud_statistical_outlier(sfmhip_cloud* c, int mean_k, dou
   SFM_TRY(compact(c, idx_out, n_out));
   if (threshold) *threshold = thr;
   if (timing) {
-    c->flt_ms[2] = t1 - t0;
-    c->flt_ms[3] = sfm_now_ms() - t1;
+    s->ms[2] = t1 - t0;
+    s->ms[3] = sfm_now_ms() - t1;
   }
   return SFMHIP_OK;
 }
@@ -450,7 +422,7 @@ extern "C" int sfmhip_cloud_select(sfmhip_cloud* c, const int32_t* indices, int 
   *out = nullptr;
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
   hipStream_t st = c->ctx->stream;
-  FltState* s = flt_state(c);
+  FltState* s = stage<FltState>(c);
   float* d = nullptr;
   SFM_TRY(sfm_dev_alloc(&d, (size_t)3 * std::max(n_idx, 1)));
   if (n_idx > 0) {
@@ -486,6 +458,7 @@ extern "C" int sfmhip_cloud_download(sfmhip_cloud* c, float* xyz) {
 
 extern "C" int sfmhip_cloud_filter_last_timing(sfmhip_cloud* c, double ms4[4]) {
   if (!c || !ms4) return SFMHIP_ERR_ARG;
-  for (int i = 0; i < 4; ++i) ms4[i] = c->flt_ms[i];
+  const FltState* s = stage<FltState>(c);
+  for (int i = 0; i < 4; ++i) ms4[i] = s->ms[i];
   return SFMHIP_OK;
 }

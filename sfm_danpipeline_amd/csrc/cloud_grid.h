@@ -1,7 +1,13 @@
-// cloud_grid.h -- the device-resident cloud (sfmhip_cloud), its uniform grids and the primitives the cloud family shares:
-// cloud.hip (map3D's step 10), segment.hip (the colour region growing after it), poisson.hip (create_mesh), dendro.hip
-// (the dendrometry after the segmentation), ground.hip (the ground plane that gives it its vertical), trees.hip (the trees of a plot) and, for blocks(), mvs.hip.  The bodies of the host functions declared here (grid builds, the handle's scan and cell sort) live
-// in cloud.hip; the device helpers (cell_of, block_bound, row_span, the min / max kernel) are inline.
+// cloud_grid.h -- the device-resident cloud (sfmhip_cloud), its uniform grids and everything the cloud family shares:
+// cloud.hip (map3D's step 10), cloud_filter.hip (the voxel grid and the statistical outlier removal), segment.hip (the colour
+// region growing after it), poisson.hip (create_mesh), dendro.hip (the dendrometry after the segmentation), ground.hip (the
+// ground plane that gives it its vertical), trees.hip (the trees of a plot) and, for blocks(), mvs.hip.
+// The handle plumbing is here once: a stage keeps its state in its slot of the handle's table (stage<S>(): made on first use,
+// deleted with the handle, so a state owns its device memory through members with destructors -- DevBufs, Grow, Grid), a
+// grow-only device array is a Grow<T>, and a min / max over points is minmax() into the handle's 7-word record.  A stage added
+// to the family names itself in Stage, gives its state `static constexpr Stage slot`, and edits nothing else here.  The bodies of the host functions declared here (grid
+// builds, the handle's scan and cell sort) live in cloud.hip; the device helpers (cell_of, block_bound, row_span, the min /
+// max kernel) are inline.  The fixed-order block sum of f-9, f-11 and f-12 is block_sum.h's.
 //
 // Spatial index: cell coordinates floor((x - lo) / cell) in double, clamped to the grid (a far outlier lands in a
 // border cell instead of stretching the grid: clamping keeps two points whose true cells are adjacent in adjacent
@@ -11,7 +17,9 @@
 #pragma once
 #include "common.h"
 #include "cloud.h"
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 
 namespace sfmgrid {
 
@@ -42,6 +50,10 @@ struct Grid {
   float4* pts = nullptr;
   int4* chunks = nullptr;
   int n_chunks = 0;
+  Grid() = default;
+  Grid(const Grid&) = delete;
+  Grid& operator=(const Grid&) = delete;
+  ~Grid() { release(); }
   void release() {
     hipFree(start);
     hipFree(end);
@@ -78,6 +90,35 @@ struct GridSrc {
   double lo[3], hi[3];  // box of the finite points
 };
 
+// a grow-only device array: need(n) keeps the block when it holds n elements, else frees it and takes a new one from
+// sfm_dev_alloc (so SFMHIP_POISON applies); old contents are never carried over.  Freed with its owner.
+template <typename T>
+struct Grow {
+  T* p = nullptr;
+  size_t cap = 0;
+  Grow() = default;
+  Grow(const Grow&) = delete;
+  Grow& operator=(const Grow&) = delete;
+  Grow(Grow&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }  // (for a std::vector of them)
+  ~Grow() { hipFree(p); }
+  int need(size_t n) {
+    if (n <= cap && p) return SFMHIP_OK;
+    hipFree(p);  // (synchronises: no launch of an earlier call still reads it)
+    p = nullptr;
+    cap = 0;
+    SFM_TRY(sfm_dev_alloc(&p, n));
+    cap = std::max(n, (size_t)1);
+    return SFMHIP_OK;
+  }
+};
+
+// the stages that keep state on the handle, and a stage's slot: the state and what deletes it
+enum Stage { SEGMENT, POISSON, DENDRO, GROUND, TREES, FILTER, N_STAGES };
+struct StageSlot {
+  void* p = nullptr;
+  void (*free)(void*) = nullptr;
+};
+
 }  // namespace sfmgrid
 
 struct sfmhip_cloud {
@@ -86,25 +127,11 @@ struct sfmhip_cloud {
   float* xyz = nullptr;          // 3 n, as given
   double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // box of the finite points
   sfmgrid::Grid rg, kg;          // radius grid, k-NN grid
-  void* tmp = nullptr;           // rocPRIM temporary storage (grow-only)
-  size_t tmp_bytes = 0;
+  sfmgrid::Grow<unsigned char> tmp;  // rocPRIM temporary storage
   int* ibuf[4] = {nullptr, nullptr, nullptr, nullptr};  // 4 int scratch arrays of max(n, 1) (keys / values in, flags, scan)
-  int* cbuf[2] = {nullptr, nullptr};                    // 2 int scratch arrays of ncell (chunk counts and offsets)
-  long long cbuf_n = 0;
-  void* seg = nullptr;           // segment.hip's state on this handle (the subset grid and its buffers), freed with it
-  void (*seg_free)(void*) = nullptr;
-  double psn_ms[4] = {0, 0, 0, 0};  // poisson.hip: stage times of the last sfmhip_cloud_poisson call on this handle
-  void* psn = nullptr;           // poisson.hip's grow-only device blocks on this handle, freed with it
-  void (*psn_free)(void*) = nullptr;
-  void* dnd = nullptr;           // dendro.hip's state on this handle (frame, slice tables, stage times), freed with it
-  void (*dnd_free)(void*) = nullptr;
-  void* gnd = nullptr;           // ground.hip's state on this handle (selection list, hypotheses, counts, stage times), freed with it
-  void (*gnd_free)(void*) = nullptr;
-  void* trs = nullptr;           // trees.hip's state on this handle (frame coordinates, cell and voxel tables, keys, stage times), freed with it
-  void (*trs_free)(void*) = nullptr;
-  void* flt = nullptr;           // cloud_filter.hip's grow-only device blocks on this handle (run tables, attributes, mean distances), freed with it
-  void (*flt_free)(void*) = nullptr;
-  double flt_ms[4] = {0, 0, 0, 0};  // cloud_filter.hip: key + sort, voxel reduce (last voxel grid); neighbour means, threshold + compaction (last outlier call)
+  sfmgrid::Grow<int> cbuf[2];                           // 2 int scratch arrays of ncell (chunk counts and offsets)
+  unsigned* mm = nullptr;        // 7 words: minmax()'s record, made and freed with the handle
+  sfmgrid::StageSlot stage[sfmgrid::N_STAGES];  // the stages' state on this handle (stage<S>()), deleted with it
 };
 
 namespace sfmgrid {
@@ -133,6 +160,27 @@ int compact(sfmhip_cloud* c, int32_t* idx_out, int32_t* n_out);
 // a handle over n points that are on the device already (d_xyz: 3 max(n, 1) floats from sfm_dev_alloc; the handle owns
 // it from here on, also when the call fails): the box by cloud_minmax, then n_valid
 int adopt_device(sfmhip_ctx* ctx, float* d_xyz, int n, sfmhip_cloud** out);
+
+// a struct of the C ABI and the header's struct it mirrors field for field: one as the other
+template <class To, class From>
+To mirror(const From& f) {
+  static_assert(sizeof(To) == sizeof(From), "a struct of the C ABI mirrors the header's");
+  To t;
+  memcpy(&t, &f, sizeof t);
+  return t;
+}
+
+// a stage's state on the handle, in the slot the state names (S::slot, so a state cannot be read out of another stage's
+// slot): an S made on first use (stage times start at zero), deleted with the handle
+template <class S>
+S* stage(sfmhip_cloud* c) {
+  StageSlot& s = c->stage[S::slot];
+  if (!s.p) {
+    s.p = new S();
+    s.free = [](void* p) { delete (S*)p; };
+  }
+  return (S*)s.p;
+}
 
 #ifdef __HIPCC__
 __device__ __forceinline__ int cell_of(double v, double o, double cell, int D) {
@@ -200,6 +248,20 @@ __global__ __launch_bounds__(256) void cloud_minmax(const float* xyz, int n, Ok 
     }
     atomicAdd(out + 6, cnt);
   }
+}
+
+// the one min / max call: the start values into the handle's record, cloud_minmax<Ok> over the n points of xyz, the record
+// into out[0..6], all on the handle's stream.  Does not wait: out is valid after the caller's next wait on the stream.  With
+// no accepted point out[6] is 0 and out[0..5] are the start values, the keys of no float.
+template <class Ok>
+int minmax(sfmhip_cloud* c, const float* xyz, int n, Ok ok, unsigned out[7]) {
+  static const unsigned init[7] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u};
+  hipStream_t st = c->ctx->stream;
+  SFM_HIP_TRY(hipMemcpyAsync(c->mm, init, sizeof init, hipMemcpyHostToDevice, st));
+  if (n > 0) hipLaunchKernelGGL(cloud_minmax<Ok>, dim3(std::min(blocks(n, 256), 1024u)), dim3(256), 0, st, xyz, n, ok, c->mm);
+  SFM_HIP_TRY(hipGetLastError());
+  SFM_HIP_TRY(hipMemcpyAsync(out, c->mm, sizeof init, hipMemcpyDeviceToHost, st));
+  return SFMHIP_OK;
 }
 #endif
 

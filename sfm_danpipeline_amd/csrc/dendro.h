@@ -10,6 +10,7 @@
 #include <cstring>
 #include <thread>
 #include <vector>
+#include "block_sum.h"
 #include "cloud.h"
 #include "draw_hash.h"
 
@@ -301,12 +302,7 @@ SFM_DND_INLINE int extent_need(double q, int nk) {
 
 // ------------------------------------------------------------------------------------------------ host: the whole call
 // the fixed-order sum: slot i mod 256 in ascending i, then four 64-entry trees (strides 32 .. 1), then (w0 + w1) + (w2 + w3)
-inline double chunk_tree(double v[CHUNK]) {
-  for (int w = 0; w < 4; ++w)
-    for (int off = 32; off >= 1; off >>= 1)
-      for (int t = 0; t < off; ++t) v[64 * w + t] = v[64 * w + t] + v[64 * w + t + off];
-  return (v[0] + v[64]) + (v[128] + v[192]);
-}
+using sfmsum::chunk_tree;  // (block_sum.h)
 
 template <typename F>
 inline void parallel_for(int n, int threads, F f) {

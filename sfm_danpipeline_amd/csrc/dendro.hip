@@ -25,10 +25,9 @@
 
 using namespace sfmdendro;
 using sfmgrid::blocks;
+using sfmgrid::mirror;  // (the options in, the defaults and the result out: size-checked)
 
-static_assert(sizeof(sfmhip_dendro_opts) == sizeof(Opts), "sfmhip_dendro_opts mirrors sfmdendro::Opts");
 static_assert(sizeof(sfmhip_dendro_slice) == sizeof(Slice), "sfmhip_dendro_slice mirrors sfmdendro::Slice");
-static_assert(sizeof(sfmhip_dendro_result) == sizeof(Result), "sfmhip_dendro_result mirrors sfmdendro::Result");
 
 namespace {
 
@@ -38,6 +37,7 @@ constexpr int HPB = RW * HPW;    // hypotheses of a workgroup
 constexpr int STAGE = 1024;      // (e, n) pairs of one LDS chunk
 
 struct DndState {  // on the cloud handle, freed with it; the cloud's size never changes, so the blocks are made once
+  static constexpr sfmgrid::Stage slot = sfmgrid::DENDRO;  // (its slot on the handle: stage<DndState>(cloud))
   DevBufs B;
   bool ready = false;
   float* frame = nullptr;               // 3 n
@@ -47,19 +47,8 @@ struct DndState {  // on the cloud handle, freed with it; the cloud's size never
   int* start = nullptr;                 // MAX_SLICES + 1
   unsigned long long* keys = nullptr;   // MAX_SLICES winners
   Slice* table = nullptr;               // MAX_SLICES rows
-  unsigned* mm = nullptr;               // 7: cloud_minmax's record
   double ms[6] = {0, 0, 0, 0, 0, 0};
 };
-
-void dnd_state_free(void* p) { delete (DndState*)p; }
-
-DndState* dnd_state(sfmhip_cloud* c) {
-  if (!c->dnd) {
-    c->dnd = new DndState();
-    c->dnd_free = dnd_state_free;
-  }
-  return (DndState*)c->dnd;
-}
 
 int dnd_alloc(sfmhip_cloud* c, DndState* s) {
   if (s->ready) return SFMHIP_OK;
@@ -71,7 +60,6 @@ int dnd_alloc(sfmhip_cloud* c, DndState* s) {
   SFM_TRY(s->B.alloc(&s->start, (size_t)MAX_SLICES + 1));
   SFM_TRY(s->B.alloc(&s->keys, (size_t)MAX_SLICES));
   SFM_TRY(s->B.alloc(&s->table, (size_t)MAX_SLICES));
-  SFM_TRY(s->B.alloc(&s->mm, 7));
   s->ready = true;
   return SFMHIP_OK;
 }
@@ -182,18 +170,6 @@ struct RefitArgs {
   uint32_t seed;
 };
 
-// dendro.h's chunk_tree over the 256 threads of a workgroup, eight sums at once; every thread gets the values
-__device__ __forceinline__ void block_tree8(double v[8], int nq, double (*sh)[4]) {
-  for (int q = 0; q < nq; ++q) {
-    double x = v[q];
-    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off);
-    if ((threadIdx.x & 63) == 0) sh[q][threadIdx.x >> 6] = x;
-  }
-  __syncthreads();
-  for (int q = 0; q < nq; ++q) v[q] = (sh[q][0] + sh[q][1]) + (sh[q][2] + sh[q][3]);
-  __syncthreads();
-}
-
 __global__ __launch_bounds__(CHUNK) void dnd_refit(const P2* __restrict__ pts, const int* __restrict__ start, const int* __restrict__ cnt,
                                                    const unsigned long long* __restrict__ keys, RefitArgs a, Slice* table) {
   __shared__ double sh[8][4];
@@ -230,7 +206,7 @@ __global__ __launch_bounds__(CHUNK) void dnd_refit(const P2* __restrict__ pts, c
         term[0] = res2_term(dx, dy, fa, fb, fr);
       for (int q = 0; q < nq; ++q) acc[q] = acc[q] + term[q];
     }
-    block_tree8(acc, nq, sh);
+    sfmsum::block_tree<8>(acc, sh, nq);
     if (pass == 0)
       kasa_solve(acc, N, fa, fb, fr);
     else if (pass <= GN_STEPS)
@@ -271,31 +247,13 @@ __global__ __launch_bounds__(256) void dnd_extent(const P2* __restrict__ pts, co
   }
 }
 
-template <class Ok>
-int minmax7(sfmhip_cloud* c, DndState* s, Ok ok, unsigned out[7]) {
-  hipStream_t st = c->ctx->stream;
-  const unsigned init[7] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u};
-  SFM_HIP_TRY(hipMemcpyAsync(s->mm, init, sizeof init, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(sfmgrid::cloud_minmax<Ok>, dim3(std::min(blocks(c->n, 256), 1024u)), dim3(256), 0, st, s->frame, c->n, ok, s->mm);
-  SFM_HIP_TRY(hipGetLastError());
-  SFM_HIP_TRY(hipMemcpyAsync(out, s->mm, sizeof init, hipMemcpyDeviceToHost, st));
-  SFM_HIP_TRY(hipStreamSynchronize(st));
-  return SFMHIP_OK;
-}
-
-Opts to_opts(const sfmhip_dendro_opts* o) {
-  Opts r;
-  memcpy(&r, o, sizeof r);
-  return r;
-}
-
 // the whole call; `slices` gets the S rows (cloud units)
 int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, Result& res, std::vector<Slice>& slices) {
   Frame f;
   if (!make_frame(o, f)) return SFMHIP_ERR_ARG;
   slices.clear();
   empty_result(res);
-  DndState* s = dnd_state(c);
+  DndState* s = sfmgrid::stage<DndState>(c);
   for (double& m : s->ms) m = 0;
   if (c->n <= 0) return SFMHIP_OK;
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
@@ -310,7 +268,8 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, Re
   hipLaunchKernelGGL(dnd_frame, dim3(blocks(n, 256)), dim3(256), 0, st, c->xyz, labels ? s->labels : nullptr, label, n, f, s->frame);
   SFM_HIP_TRY(hipGetLastError());
   unsigned mm[7];
-  SFM_TRY(minmax7(c, s, Selected(), mm));
+  SFM_TRY(sfmgrid::minmax(c, s->frame, n, Selected(), mm));
+  SFM_HIP_TRY(hipStreamSynchronize(st));
   const double t1 = sfm_now_ms();
   s->ms[0] = t1 - t0;
   s->ms[5] = t1 - t0;
@@ -363,7 +322,8 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, Re
   if (cb >= 0) {
     AtOrAbove ok;
     ok.hb = h0 + (double)cb * f.t;
-    SFM_TRY(minmax7(c, s, ok, mm));
+    SFM_TRY(sfmgrid::minmax(c, s->frame, n, ok, mm));
+    SFM_HIP_TRY(hipStreamSynchronize(st));
     for (int a = 0; a < 2; ++a) {
       mn[a] = sfmcloud::ord_val(mm[a]);
       mx[a] = sfmcloud::ord_val(mm[3 + a]);
@@ -383,8 +343,7 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, Re
 
 extern "C" void sfmhip_dendro_default_opts(sfmhip_dendro_opts* o) {
   if (!o) return;
-  const Opts r = default_opts();
-  memcpy(o, &r, sizeof r);
+  *o = mirror<sfmhip_dendro_opts>(default_opts());
 }
 
 extern "C" int sfmhip_cloud_dendrometry(sfmhip_cloud* c, const int32_t* labels, int32_t label, const sfmhip_dendro_opts* opts,
@@ -392,8 +351,8 @@ extern "C" int sfmhip_cloud_dendrometry(sfmhip_cloud* c, const int32_t* labels, 
   if (!c || !opts || !out) return SFMHIP_ERR_ARG;
   Result res;
   std::vector<Slice> slices;
-  SFM_TRY(run(c, labels, label, to_opts(opts), res, slices));
-  memcpy(out, &res, sizeof res);
+  SFM_TRY(run(c, labels, label, mirror<Opts>(*opts), res, slices));
+  *out = mirror<sfmhip_dendro_result>(res);
   return SFMHIP_OK;
 }
 
@@ -402,9 +361,9 @@ extern "C" int sfmhip_cloud_dendro_profile(sfmhip_cloud* c, const int32_t* label
   if (!c || !opts || !n_slices || cap < 0 || (cap > 0 && !slices)) return SFMHIP_ERR_ARG;
   Result res;
   std::vector<Slice> rows;
-  SFM_TRY(run(c, labels, label, to_opts(opts), res, rows));
+  SFM_TRY(run(c, labels, label, mirror<Opts>(*opts), res, rows));
   *n_slices = (int32_t)rows.size();
-  if (out) memcpy(out, &res, sizeof res);
+  if (out) *out = mirror<sfmhip_dendro_result>(res);
   const size_t m = std::min(rows.size(), (size_t)cap);
   if (m) memcpy(slices, rows.data(), sizeof(Slice) * m);
   return SFMHIP_OK;
@@ -412,7 +371,7 @@ extern "C" int sfmhip_cloud_dendro_profile(sfmhip_cloud* c, const int32_t* label
 
 extern "C" int sfmhip_cloud_dendro_last_timing(sfmhip_cloud* c, double ms6[6]) {
   if (!c || !ms6) return SFMHIP_ERR_ARG;
-  const DndState* s = dnd_state(c);
+  const DndState* s = sfmgrid::stage<DndState>(c);
   for (int i = 0; i < 6; ++i) ms6[i] = s->ms[i];
   return SFMHIP_OK;
 }

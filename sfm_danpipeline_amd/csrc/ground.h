@@ -10,8 +10,9 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
+#include "block_sum.h"  // chunk_tree (f-11 rule 6's fixed-order sum)
 #include "cloud.h"
-#include "dendro.h"  // dnan, finite_d, chunk_tree (f-11 rule 6's fixed-order sum), parallel_for
+#include "dendro.h"  // dnan, finite_d, parallel_for
 #include "draw_hash.h"
 #include "jacobi.h"
 
@@ -23,7 +24,7 @@
 
 namespace sfmground {
 
-using sfmdendro::chunk_tree;
+using sfmsum::chunk_tree;
 using sfmdendro::dnan;
 using sfmdendro::finite_d;
 

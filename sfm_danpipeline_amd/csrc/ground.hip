@@ -22,10 +22,9 @@
 
 using namespace sfmground;
 using sfmgrid::blocks;
-
-static_assert(sizeof(sfmhip_ground_opts) == sizeof(Opts), "sfmhip_ground_opts mirrors sfmground::Opts");
-static_assert(sizeof(sfmhip_ground_result) == sizeof(Result), "sfmhip_ground_result mirrors sfmground::Result");
-static_assert(sizeof(sfmhip_dendro_opts) == sizeof(sfmdendro::Opts), "sfmhip_dendro_opts mirrors sfmdendro::Opts");
+using sfmgrid::mirror;  // (the options in, the defaults and the result out: size-checked)
+using sfmsum::block_count;  // (block_sum.h: rule 7's fixed-order sums over the 256 threads of a workgroup)
+using sfmsum::block_tree;
 
 namespace {
 
@@ -41,6 +40,7 @@ struct Last {  // the final plane's counts and the fixed-order sum of s^2 over i
 };
 
 struct GndState {  // on the cloud handle, freed with it; the cloud's size never changes, so the blocks are made once
+  static constexpr sfmgrid::Stage slot = sfmgrid::GROUND;  // (its slot on the handle: stage<GndState>(cloud))
   DevBufs B;
   bool ready = false;
   int* labels = nullptr;     // n
@@ -49,25 +49,9 @@ struct GndState {  // on the cloud handle, freed with it; the cloud's size never
   Counts* cnt = nullptr;     // MAX_ITERS
   Plane* plane = nullptr;    // 1
   Last* last = nullptr;      // 1
-  unsigned* mm = nullptr;    // 7: cloud_minmax's record
-  double* cams = nullptr;    // 3 cams_cap, grow-only
-  int cams_cap = 0;
+  sfmgrid::Grow<double> cams;  // 3 per camera centre
   double ms[4] = {0, 0, 0, 0};
 };
-
-void gnd_state_free(void* p) {
-  GndState* s = (GndState*)p;
-  hipFree(s->cams);
-  delete s;
-}
-
-GndState* gnd_state(sfmhip_cloud* c) {
-  if (!c->gnd) {
-    c->gnd = new GndState();
-    c->gnd_free = gnd_state_free;
-  }
-  return (GndState*)c->gnd;
-}
 
 int gnd_alloc(sfmhip_cloud* c, GndState* s, int n_cam) {
   if (!s->ready) {
@@ -78,16 +62,9 @@ int gnd_alloc(sfmhip_cloud* c, GndState* s, int n_cam) {
     SFM_TRY(s->B.alloc(&s->cnt, (size_t)MAX_ITERS));
     SFM_TRY(s->B.alloc(&s->plane, 1));
     SFM_TRY(s->B.alloc(&s->last, 1));
-    SFM_TRY(s->B.alloc(&s->mm, 7));
     s->ready = true;
   }
-  if (n_cam > s->cams_cap) {
-    hipFree(s->cams);
-    s->cams = nullptr;
-    s->cams_cap = 0;
-    SFM_TRY(sfm_dev_alloc(&s->cams, 3 * (size_t)n_cam));
-    s->cams_cap = n_cam;
-  }
+  if (n_cam) SFM_TRY(s->cams.need(3 * (size_t)n_cam));
   return SFMHIP_OK;
 }
 
@@ -229,29 +206,6 @@ __global__ __launch_bounds__(CHUNK) void gnd_pick(const Hyp* __restrict__ hyp, c
   }
 }
 
-// dendro.h's chunk_tree over the 256 threads of a workgroup, nq sums at once; every thread gets the values
-template <int Q>
-__device__ __forceinline__ void block_tree(double v[Q], double (*sh)[4]) {
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    double x = v[q];
-    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off);
-    if ((threadIdx.x & 63) == 0) sh[q][threadIdx.x >> 6] = x;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < Q; ++q) v[q] = (sh[q][0] + sh[q][1]) + (sh[q][2] + sh[q][3]);
-  __syncthreads();
-}
-__device__ __forceinline__ uint32_t block_count(uint32_t v, uint32_t* sh) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return v;
-}
-
 // f(i, point) for the points i = threadIdx.x, threadIdx.x + 256, ... of the list in ascending i: rule 7's order.  The loads
 // of RB points are issued together and consumed in order, so a thread waits for memory once per RB points, not once per point.
 constexpr int RB = 8;
@@ -330,16 +284,10 @@ __global__ __launch_bounds__(CHUNK) void gnd_refit(const P3* __restrict__ pts, i
   }
 }
 
-Opts to_opts(const sfmhip_ground_opts* o) {
-  Opts r;
-  memcpy(&r, o, sizeof r);
-  return r;
-}
-
 int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, const double* cams, int n_cam, Result& res) {
   Prep pr;
   if (!prepare(o, pr) || n_cam < 0 || (n_cam > 0 && !cams)) return SFMHIP_ERR_ARG;
-  GndState* s = gnd_state(c);
+  GndState* s = sfmgrid::stage<GndState>(c);
   for (double& m : s->ms) m = 0;
   empty_result(res, 0, dnan(), F_FEW);
   if (c->n <= 0) return SFMHIP_OK;
@@ -352,19 +300,15 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, co
   const double t0 = sfm_now_ms();
   // rules 1, 2: the list, its length and its box
   if (labels) SFM_HIP_TRY(hipMemcpyAsync(s->labels, labels, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-  if (n_cam) SFM_HIP_TRY(hipMemcpyAsync(s->cams, cams, sizeof(double) * 3 * (size_t)n_cam, hipMemcpyHostToDevice, st));
+  if (n_cam) SFM_HIP_TRY(hipMemcpyAsync(s->cams.p, cams, sizeof(double) * 3 * (size_t)n_cam, hipMemcpyHostToDevice, st));
   Selected sel;
   sel.labels = labels ? s->labels : nullptr;
   sel.label = label;
   int *flag = c->ibuf[2], *at = c->ibuf[3];
   hipLaunchKernelGGL(gnd_flag, dim3(blocks(n, 256)), dim3(256), 0, st, c->xyz, n, sel, flag);
   SFM_HIP_TRY(hipGetLastError());
-  const unsigned init[7] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u};
   unsigned mm[7];
-  SFM_HIP_TRY(hipMemcpyAsync(s->mm, init, sizeof init, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(sfmgrid::cloud_minmax<Selected>, dim3(std::min(blocks(n, 256), 1024u)), dim3(256), 0, st, c->xyz, n, sel, s->mm);
-  SFM_HIP_TRY(hipGetLastError());
-  SFM_HIP_TRY(hipMemcpyAsync(mm, s->mm, sizeof mm, hipMemcpyDeviceToHost, st));
+  SFM_TRY(sfmgrid::minmax(c, c->xyz, n, sel, mm));
   int n_sel = 0;
   SFM_TRY(sfmgrid::scan(c, flag, at, (size_t)n, &n_sel));  // (waits for the stream: mm has arrived too)
   const double t1 = sfm_now_ms();
@@ -392,7 +336,7 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, co
   if (timing) SFM_HIP_TRY(hipStreamSynchronize(st));
   const double t3 = sfm_now_ms();
   // rules 5 - 7
-  hipLaunchKernelGGL(gnd_pick, dim3(1), dim3(CHUNK), 0, st, s->hyp, s->cnt, o.ransac_iters, s->cams, n_cam, o.min_inliers,
+  hipLaunchKernelGGL(gnd_pick, dim3(1), dim3(CHUNK), 0, st, s->hyp, s->cnt, o.ransac_iters, s->cams.p, n_cam, o.min_inliers,
                      below_cap(o.below_max, n_sel), s->plane);
   SFM_HIP_TRY(hipGetLastError());
   for (int r = 0; r <= o.refit_rounds; ++r) {
@@ -421,33 +365,29 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, co
 
 extern "C" void sfmhip_ground_default_opts(sfmhip_ground_opts* o) {
   if (!o) return;
-  const Opts r = default_opts();
-  memcpy(o, &r, sizeof r);
+  *o = mirror<sfmhip_ground_opts>(default_opts());
 }
 
 extern "C" int sfmhip_cloud_ground_plane(sfmhip_cloud* c, const int32_t* labels, int32_t label, const sfmhip_ground_opts* opts,
                                          const double* cam_centres, int n_cam, sfmhip_ground_result* out) {
   if (!c || !opts || !out) return SFMHIP_ERR_ARG;
   Result res;
-  SFM_TRY(run(c, labels, label, to_opts(opts), cam_centres, n_cam, res));
-  memcpy(out, &res, sizeof res);
+  SFM_TRY(run(c, labels, label, mirror<Opts>(*opts), cam_centres, n_cam, res));
+  *out = mirror<sfmhip_ground_result>(res);
   return SFMHIP_OK;
 }
 
 extern "C" int sfmhip_dendro_opts_from_ground(const sfmhip_ground_result* g, sfmhip_dendro_opts* io) {
   if (!g || !io) return SFMHIP_ERR_ARG;
-  Result r;
-  sfmdendro::Opts d;
-  memcpy(&r, g, sizeof r);
-  memcpy(&d, io, sizeof d);
-  if (!opts_from_ground(r, d)) return SFMHIP_ERR_ARG;
-  memcpy(io, &d, sizeof d);
+  sfmdendro::Opts d = mirror<sfmdendro::Opts>(*io);
+  if (!opts_from_ground(mirror<Result>(*g), d)) return SFMHIP_ERR_ARG;
+  *io = mirror<sfmhip_dendro_opts>(d);
   return SFMHIP_OK;
 }
 
 extern "C" int sfmhip_cloud_ground_last_timing(sfmhip_cloud* c, double ms4[4]) {
   if (!c || !ms4) return SFMHIP_ERR_ARG;
-  const GndState* s = gnd_state(c);
+  const GndState* s = sfmgrid::stage<GndState>(c);
   for (int i = 0; i < 4; ++i) ms4[i] = s->ms[i];
   return SFMHIP_OK;
 }

@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include "block_sum.h"
 #include "cloud.h"
 #ifndef __HIPCC__
 #include <algorithm>
@@ -181,13 +182,7 @@ SFM_PSN_INLINE bool brick_cell(const Brick& b, int id, int t, int& x, int& y, in
   return lz < b.bz;
 }
 
-// the tree of one chunk (v is overwritten)
-inline double chunk_tree(double v[CHUNK]) {
-  for (int w = 0; w < 4; ++w)
-    for (int off = 32; off >= 1; off >>= 1)
-      for (int t = 0; t < off; ++t) v[64 * w + t] = v[64 * w + t] + v[64 * w + t + off];
-  return (v[0] + v[64]) + (v[128] + v[192]);
-}
+using sfmsum::chunk_tree;  // block_sum.h: the tree of one chunk (v is overwritten)
 // chunk results -> the sum
 inline double sum_partials(const double* part, size_t n) {
   double v[CHUNK];

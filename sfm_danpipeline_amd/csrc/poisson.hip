@@ -23,6 +23,7 @@
 
 using namespace sfmpoisson;
 using sfmgrid::blocks;
+using sfmsum::block_tree;  // (block_sum.h: the chunk tree over the 256 threads of a workgroup)
 
 struct sfmhip_mesh {
   std::vector<float> verts;
@@ -44,24 +45,11 @@ struct Ctl {
 // depth 7).  The requests of sfmhip_cloud_poisson and sfmhip_cloud_poisson_splat come in the same order, so a block keeps
 // its role.  Without a pool (the staged entries on a bare context) a block lives until the call ends.  Nothing relies on
 // what a block holds when it is handed out.
-struct Pool {
-  std::vector<void*> p;
-  std::vector<size_t> bytes;
+struct Pool {  // on the cloud handle, freed with it
+  static constexpr sfmgrid::Stage slot = sfmgrid::POISSON;  // (its slot on the handle: stage<Pool>(cloud))
+  std::vector<sfmgrid::Grow<unsigned char>> blk;
+  double ms[4] = {0, 0, 0, 0};  // stage times of the last sfmhip_cloud_poisson call on the handle
 };
-
-void pool_free(void* q) {
-  Pool* pool = (Pool*)q;
-  for (void* b : pool->p) hipFree(b);
-  delete pool;
-}
-
-Pool* pool_of(sfmhip_cloud* c) {
-  if (!c->psn) {
-    c->psn = new Pool();
-    c->psn_free = pool_free;
-  }
-  return (Pool*)c->psn;
-}
 
 struct Bufs {
   Pool* pool;
@@ -72,34 +60,12 @@ struct Bufs {
   int get(T** out, size_t n) {
     n = std::max(n, (size_t)1);
     if (!pool) return own.alloc(out, n);
-    if (k == pool->p.size()) {
-      pool->p.push_back(nullptr);
-      pool->bytes.push_back(0);
-    }
-    const size_t need = n * sizeof(T);
-    if (pool->bytes[k] < need) {
-      hipFree(pool->p[k]);  // (synchronises: no launch of an earlier call still reads it)
-      pool->p[k] = nullptr;
-      pool->bytes[k] = 0;
-      unsigned char* v = nullptr;
-      SFM_TRY(sfm_dev_alloc(&v, need));
-      pool->p[k] = v;
-      pool->bytes[k] = need;
-    }
-    *out = (T*)pool->p[k++];
+    if (k == pool->blk.size()) pool->blk.emplace_back();
+    SFM_TRY(pool->blk[k].need(n * sizeof(T)));
+    *out = (T*)pool->blk[k++].p;
     return SFMHIP_OK;
   }
 };
-
-// the chunk tree of poisson.h over the 256 threads of a workgroup; every thread gets the value
-__device__ __forceinline__ double block_tree(double v, double* sh4) {
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
-  __syncthreads();
-  return r;
-}
 
 // ---------------------------------------------------------------------------------------------- samples
 struct UsableSample {  // cloud_minmax's predicate: the points that are samples (rule 1)
@@ -171,8 +137,8 @@ __global__ __launch_bounds__(256) void psn_dot_rr(const double* r, int N, Brick 
     const double rv = r[((size_t)z * N + y) * N + x];
     v = rv * rv;
   }
-  const double s = block_tree(v, sh4);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
+  block_tree<1>(&v, &sh4);
+  if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
 
 // mode 0: r.r of the start (bb, the threshold, beta = 0); 1: p.q -> alpha; 2: r.r -> beta, the count, the decision; 3: a sum
@@ -181,7 +147,8 @@ __global__ __launch_bounds__(256) void psn_reduce(const double* part, int n, Ctl
   if ((mode == 1 || mode == 2) && ctl->done) return;
   double a = 0.0;
   for (int j = threadIdx.x; j < n; j += CHUNK) a = a + part[j];
-  const double s = block_tree(a, sh4);
+  block_tree<1>(&a, &sh4);
+  const double s = a;
   if (threadIdx.x != 0) return;
   if (mode == 0) {
     ctl->rr = s;
@@ -240,8 +207,8 @@ __global__ __launch_bounds__(256) void psn_apply(const double* __restrict__ r, c
     q[c] = qv;
     v = pc * qv;
   }
-  const double s = block_tree(v, sh4);
-  if (threadIdx.x == 0) part[id] = s;
+  block_tree<1>(&v, &sh4);
+  if (threadIdx.x == 0) part[id] = v;
 }
 
 __global__ __launch_bounds__(256) void psn_update(double* __restrict__ chi, double* __restrict__ r, const double* __restrict__ p,
@@ -258,17 +225,17 @@ __global__ __launch_bounds__(256) void psn_update(double* __restrict__ chi, doub
     r[c] = rv;
     v = rv * rv;
   }
-  const double s = block_tree(v, sh4);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
+  block_tree<1>(&v, &sh4);
+  if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
 
 // ---------------------------------------------------------------------------------------------- iso-value
 __global__ __launch_bounds__(256) void psn_iso_vals(const double* chi, Cube g, const float* pts4, int m, double* part) {
   __shared__ double sh4[4];
   const size_t s = (size_t)blockIdx.x * CHUNK + threadIdx.x;
-  const double v = s < (size_t)m ? trilinear(chi, g, pts4 + 4 * s) : 0.0;
-  const double t = block_tree(v, sh4);
-  if (threadIdx.x == 0) part[blockIdx.x] = t;
+  double v = s < (size_t)m ? trilinear(chi, g, pts4 + 4 * s) : 0.0;
+  block_tree<1>(&v, &sh4);
+  if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
 
 // ---------------------------------------------------------------------------------------------- extraction
@@ -342,21 +309,10 @@ int make_samples(sfmhip_cloud* c, const float* normals, int stride, const Opts& 
   hipStream_t st = c->ctx->stream;
   const int n = c->n;
   float* d_nrm = nullptr;
-  unsigned* d_mm = nullptr;
   SFM_TRY(B.get(&d_nrm, (size_t)stride * n));
-  SFM_TRY(B.get(&d_mm, 7));
   unsigned mm[7];
-  for (int a = 0; a < 3; ++a) mm[a] = 0xFFFFFFFFu, mm[3 + a] = 0u;
-  mm[6] = 0;
-  SFM_HIP_TRY(hipMemcpyAsync(d_mm, mm, sizeof mm, hipMemcpyHostToDevice, st));
-  if (n > 0) {
-    SFM_HIP_TRY(hipMemcpyAsync(d_nrm, normals, sizeof(float) * (size_t)stride * n, hipMemcpyHostToDevice, st));
-    const UsableSample ok{d_nrm, stride};
-    hipLaunchKernelGGL(sfmgrid::cloud_minmax<UsableSample>, dim3(std::min(blocks(n, 256), 1024u)), dim3(256), 0, st, c->xyz, n, ok,
-                       d_mm);
-    SFM_HIP_TRY(hipGetLastError());
-  }
-  SFM_HIP_TRY(hipMemcpyAsync(mm, d_mm, sizeof mm, hipMemcpyDeviceToHost, st));
+  if (n > 0) SFM_HIP_TRY(hipMemcpyAsync(d_nrm, normals, sizeof(float) * (size_t)stride * n, hipMemcpyHostToDevice, st));
+  SFM_TRY(sfmgrid::minmax(c, c->xyz, n, UsableSample{d_nrm, stride}, mm));
   SFM_HIP_TRY(hipStreamSynchronize(st));
   S.m = (int)mm[6];
   if (S.m < 0 || S.m > n) return SFMHIP_ERR_STATE;
@@ -531,7 +487,8 @@ extern "C" int sfmhip_cloud_poisson(sfmhip_cloud* c, const float* normals, const
   const Opts o = to_opts(opts);
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
   hipStream_t st = c->ctx->stream;
-  Bufs B(pool_of(c));
+  Pool* pool = sfmgrid::stage<Pool>(c);
+  Bufs B(pool);
   Samp S;
   Ctl h = {};
   double iso = 0.0;
@@ -559,10 +516,10 @@ extern "C" int sfmhip_cloud_poisson(sfmhip_cloud* c, const float* normals, const
     delete mesh;
     return rc;
   }
-  c->psn_ms[0] = t1 - t0;
-  c->psn_ms[1] = t2 - t1;
-  c->psn_ms[2] = t3 - t2;
-  c->psn_ms[3] = t3 - t0;
+  pool->ms[0] = t1 - t0;
+  pool->ms[1] = t2 - t1;
+  pool->ms[2] = t3 - t2;
+  pool->ms[3] = t3 - t0;
   fill_summary(summary, S, h, iso, mesh);
   *out = mesh;
   return SFMHIP_OK;
@@ -590,7 +547,7 @@ extern "C" int sfmhip_cloud_poisson_splat(sfmhip_cloud* c, const float* normals,
   const Opts o = to_opts(opts);
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
   hipStream_t st = c->ctx->stream;
-  Bufs B(pool_of(c));
+  Bufs B(sfmgrid::stage<Pool>(c));
   Samp S;
   SFM_TRY(make_samples(c, normals, opts->normal_stride, o, B, S));
   const size_t nc = (size_t)S.g.N * S.g.N * S.g.N;
@@ -667,6 +624,7 @@ extern "C" int sfmhip_poisson_extract(sfmhip_ctx* ctx, int n, const double* chi,
 
 extern "C" int sfmhip_cloud_poisson_last_timing(sfmhip_cloud* c, double* ms4) {
   if (!c || !ms4) return SFMHIP_ERR_ARG;
-  for (int i = 0; i < 4; ++i) ms4[i] = c->psn_ms[i];
+  const Pool* pool = sfmgrid::stage<Pool>(c);
+  for (int i = 0; i < 4; ++i) ms4[i] = pool->ms[i];
   return SFMHIP_OK;
 }

@@ -32,24 +32,11 @@ namespace {
 
 constexpr int WAVES = 4;  // points (waves) per seg_knn workgroup
 
-struct SegState {
-  Grid g;                             // the grid of the indexed points of the call in progress
+struct SegState {  // on the cloud handle, freed with it
+  static constexpr sfmgrid::Stage slot = sfmgrid::SEGMENT;  // (its slot on the handle: stage<SegState>(cloud))
+  Grid g;                             // the grid of the indexed points of the call in progress (releases itself)
   double ms[5] = {0, 0, 0, 0, 0};     // subset k-NN, growth, segment statistics, host region step, whole call
 };
-
-void seg_state_free(void* p) {
-  SegState* s = (SegState*)p;
-  s->g.release();
-  delete s;
-}
-
-SegState* seg_state(sfmhip_cloud* c) {
-  if (!c->seg) {
-    c->seg = new SegState();
-    c->seg_free = seg_state_free;
-  }
-  return (SegState*)c->seg;
-}
 
 __global__ void seg_gather(const float* xyz, const int* ind, int m, float* out) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -259,28 +246,6 @@ __global__ void seg_nbr_write(const unsigned long long* keys, const int* b, int 
   nbr_d2[o] = __int_as_float((int)(unsigned)(keys[e] & 0xFFFFFFFFull));
 }
 
-int minmax_dev(sfmhip_cloud* c, const float* d_xyz, int n, unsigned* d_out7, float mn[3], float mx[3], int* count) {
-  hipStream_t st = c->ctx->stream;
-  unsigned init[7];
-  for (int a = 0; a < 3; ++a) {
-    init[a] = sfmcloud::ord_key(FLT_MAX);
-    init[3 + a] = sfmcloud::ord_key(-FLT_MAX);
-  }
-  init[6] = 0;
-  SFM_HIP_TRY(hipMemcpyAsync(d_out7, init, sizeof init, hipMemcpyHostToDevice, st));
-  if (n > 0) hipLaunchKernelGGL(cloud_minmax<FinitePoint>, dim3(std::min(blocks(n, 256), 1024u)), dim3(256), 0, st, d_xyz, n, FinitePoint(),
-                                d_out7);
-  SFM_HIP_TRY(hipGetLastError());
-  SFM_HIP_TRY(hipMemcpyAsync(init, d_out7, sizeof init, hipMemcpyDeviceToHost, st));
-  SFM_HIP_TRY(hipStreamSynchronize(st));
-  for (int a = 0; a < 3; ++a) {
-    mn[a] = sfmcloud::ord_val(init[a]);
-    mx[a] = sfmcloud::ord_val(init[3 + a]);
-  }
-  *count = (int)init[6];
-  return SFMHIP_OK;
-}
-
 // the index list: strictly ascending indices of the cloud (what PassThrough writes)
 bool indices_valid(const sfmhip_cloud* c, const int32_t* ind, int m) {
   if (!ind || m < 1 || m > c->n) return false;
@@ -311,19 +276,19 @@ int subset_knn(sfmhip_cloud* c, SegState* s, DevBufs& B, const int32_t* indices,
   SFM_TRY(B.alloc(&w.xyz, (size_t)3 * m));
   SFM_TRY(B.alloc(&w.knn_idx, (size_t)m * k));
   SFM_TRY(B.alloc(&w.knn_d2, (size_t)m * k));
-  unsigned* mm = nullptr;
-  SFM_TRY(B.alloc(&mm, 7));
   SFM_HIP_TRY(hipMemcpyAsync(w.ind, indices, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(seg_gather, dim3(blocks(m, 256)), dim3(256), 0, st, c->xyz, w.ind, m, w.xyz);
   SFM_HIP_TRY(hipGetLastError());
   GridSrc src;
   src.xyz = w.xyz;
   src.n = m;
-  float mn[3], mx[3];
-  SFM_TRY(minmax_dev(c, w.xyz, m, mm, mn, mx, &src.n_valid));
+  unsigned mm[7];
+  SFM_TRY(minmax(c, w.xyz, m, FinitePoint(), mm));
+  SFM_HIP_TRY(hipStreamSynchronize(st));
+  src.n_valid = (int)mm[6];
   for (int a = 0; a < 3; ++a) {
-    src.lo[a] = src.n_valid ? (double)mn[a] : 0.0;
-    src.hi[a] = src.n_valid ? (double)mx[a] : 0.0;
+    src.lo[a] = src.n_valid ? (double)sfmcloud::ord_val(mm[a]) : 0.0;
+    src.hi[a] = src.n_valid ? (double)sfmcloud::ord_val(mm[3 + a]) : 0.0;
   }
   w.n_valid = src.n_valid;
   SFM_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)w.knn_idx, -1, (size_t)m * k, st));  // points with no list: -1 / +inf
@@ -435,15 +400,15 @@ int segment_tables(sfmhip_cloud* c, DevBufs& B, const sfmseg::Opts& o, Work& w, 
   size_t need = 0;
   SFM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, k0, k1, v0, v1, (size_t)ne, 0u, std::min(64u, 2 * sbits + 1), st));
   SFM_TRY(grow_tmp(c, need));
-  need = c->tmp_bytes;
-  SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp, need, k0, k1, v0, v1, (size_t)ne, 0u, std::min(64u, 2 * sbits + 1), st));
+  need = c->tmp.cap;
+  SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp.p, need, k0, k1, v0, v1, (size_t)ne, 0u, std::min(64u, 2 * sbits + 1), st));
   // the minimum d2 of every (a, b): the unique keys into k0, the minima into v0, their number into cnt[0]
   need = 0;
   SFM_HIP_TRY(rocprim::reduce_by_key(nullptr, need, k1, v1, (size_t)ne, k0, v0, cnt, rocprim::minimum<float>(),
                                      rocprim::equal_to<unsigned long long>(), st));
   SFM_TRY(grow_tmp(c, need));
-  need = c->tmp_bytes;
-  SFM_HIP_TRY(rocprim::reduce_by_key(c->tmp, need, k1, v1, (size_t)ne, k0, v0, cnt, rocprim::minimum<float>(),
+  need = c->tmp.cap;
+  SFM_HIP_TRY(rocprim::reduce_by_key(c->tmp.p, need, k1, v1, (size_t)ne, k0, v0, cnt, rocprim::minimum<float>(),
                                      rocprim::equal_to<unsigned long long>(), st));
   int np = 0;
   SFM_HIP_TRY(hipMemcpyAsync(&np, cnt, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -458,8 +423,8 @@ int segment_tables(sfmhip_cloud* c, DevBufs& B, const sfmseg::Opts& o, Work& w, 
   need = 0;
   SFM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, k1, k0, b0, b1, (size_t)np, 0u, 32u + sbits, st));
   SFM_TRY(grow_tmp(c, need));
-  need = c->tmp_bytes;
-  SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp, need, k1, k0, b0, b1, (size_t)np, 0u, 32u + sbits, st));
+  need = c->tmp.cap;
+  SFM_HIP_TRY(rocprim::radix_sort_pairs(c->tmp.p, need, k1, k0, b0, b1, (size_t)np, 0u, 32u + sbits, st));
   int *start = nullptr, *end = nullptr, *ncnt = nullptr, *noff = nullptr, *nseg = nullptr;
   float* nd2 = nullptr;
   SFM_TRY(B.alloc(&start, (size_t)S));
@@ -517,11 +482,13 @@ extern "C" void sfmhip_segment_default_opts(sfmhip_segment_opts* o) {
 extern "C" int sfmhip_cloud_minmax(sfmhip_cloud* c, float* mn, float* mx, double* height) {
   if (!c || !mn || !mx) return SFMHIP_ERR_ARG;
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
-  DevBufs B;
-  unsigned* d = nullptr;
-  SFM_TRY(B.alloc(&d, 7));
-  int count = 0;
-  SFM_TRY(minmax_dev(c, c->xyz, c->n, d, mn, mx, &count));
+  unsigned mm[7];
+  SFM_TRY(minmax(c, c->xyz, c->n, FinitePoint(), mm));
+  SFM_HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+  for (int a = 0; a < 3; ++a) {  // (pcl::getMinMax3D starts at FLT_MAX / -FLT_MAX: what a cloud with no finite point keeps)
+    mn[a] = mm[6] ? sfmcloud::ord_val(mm[a]) : FLT_MAX;
+    mx[a] = mm[6] ? sfmcloud::ord_val(mm[3 + a]) : -FLT_MAX;
+  }
   if (height) *height = sfmseg::height(mn, mx);
   return SFMHIP_OK;
 }
@@ -531,7 +498,7 @@ extern "C" int sfmhip_cloud_subset_knn(sfmhip_cloud* c, const int32_t* indices, 
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
   DevBufs B;
   Work w;
-  SFM_TRY(subset_knn(c, seg_state(c), B, indices, n_idx, k, w));
+  SFM_TRY(subset_knn(c, stage<SegState>(c), B, indices, n_idx, k, w));
   const size_t e = (size_t)n_idx * k;
   hipStream_t st = c->ctx->stream;
   SFM_HIP_TRY(hipMemcpyAsync(idx, w.knn_idx, e * 4, hipMemcpyDeviceToHost, st));
@@ -551,7 +518,7 @@ extern "C" int sfmhip_cloud_segment_grow(sfmhip_cloud* c, const uint32_t* rgb, c
   DevBufs B;
   Work w;
   DevTables d;
-  SFM_TRY(subset_knn(c, seg_state(c), B, indices, n_idx, o.region_neighbour_number, w));
+  SFM_TRY(subset_knn(c, stage<SegState>(c), B, indices, n_idx, o.region_neighbour_number, w));
   SFM_TRY(grow(c, B, rgb, indices, o, w));
   SFM_TRY(number_segments(c, B, w, d));
   std::vector<int> seg((size_t)n_idx);
@@ -571,7 +538,7 @@ extern "C" int sfmhip_cloud_segment_rgb(sfmhip_cloud* c, const uint32_t* rgb, co
   const sfmseg::Opts o = to_opts(opts);
   if (!sfmseg::opts_valid(o)) return SFMHIP_ERR_ARG;
   SFM_HIP_TRY(hipSetDevice(c->ctx->device));
-  SegState* s = seg_state(c);
+  SegState* s = stage<SegState>(c);
   DevBufs B;
   Work w;
   DevTables d;
@@ -610,7 +577,7 @@ extern "C" int sfmhip_cloud_segment_rgb(sfmhip_cloud* c, const uint32_t* rgb, co
 
 extern "C" int sfmhip_cloud_segment_last_timing(sfmhip_cloud* c, double* ms5) {
   if (!c || !ms5) return SFMHIP_ERR_ARG;
-  const SegState* s = seg_state(c);
+  const SegState* s = stage<SegState>(c);
   for (int i = 0; i < 5; ++i) ms5[i] = s->ms[i];
   return SFMHIP_OK;
 }

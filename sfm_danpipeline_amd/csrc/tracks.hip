@@ -27,7 +27,9 @@ static_assert(sizeof(sfmhip_tracks_stats) == sizeof(Stats), "sfmhip_tracks_stats
 
 struct sfmhip_tracks {
   sfmhip_ctx* ctx = nullptr;
-  sfmhip_cloud scratch;  // (only its rocPRIM temporary storage: what sfmgrid::scan and sfmgrid::cell_sort work through)
+  // (only its rocPRIM temporary storage, which frees itself with this struct: what sfmgrid::scan and sfmgrid::cell_sort work
+  // through.  It is no handle of adopt_device: it has no min / max record (mm is null), so sfmgrid::minmax must not be called on it)
+  sfmhip_cloud scratch;
   DevBufs B;
   int n_images = 0, n_nodes = 0, n_tracks = 0, n_obs = 0, n_waves = 0;
   long long slab_len = 0;  // sum over the waves of their longest track: the slab is 512 doubles per unit
@@ -487,6 +489,5 @@ extern "C" int sfmhip_tracks_last_timing(const sfmhip_tracks* tr, double seconds
 extern "C" void sfmhip_tracks_destroy(sfmhip_tracks* tr) {
   if (!tr) return;
   hipSetDevice(tr->ctx->device);
-  hipFree(tr->scratch.tmp);
-  delete tr;
+  delete tr;  // (the scratch handle's temporary storage frees itself)
 }

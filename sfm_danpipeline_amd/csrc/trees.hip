@@ -28,11 +28,9 @@
 
 using namespace sfmtrees;
 using sfmgrid::blocks;
+using sfmgrid::mirror;  // (the options in, the defaults and the result out: size-checked)
 
-static_assert(sizeof(sfmhip_trees_opts) == sizeof(Opts), "sfmhip_trees_opts mirrors sfmtrees::Opts");
 static_assert(sizeof(sfmhip_tree_stem) == sizeof(Stem), "sfmhip_tree_stem mirrors sfmtrees::Stem");
-static_assert(sizeof(sfmhip_trees_result) == sizeof(Result), "sfmhip_trees_result mirrors sfmtrees::Result");
-static_assert(sizeof(sfmhip_ground_result) == sizeof(sfmground::Result), "sfmhip_ground_result mirrors sfmground::Result");
 
 namespace {
 
@@ -46,6 +44,7 @@ struct Totals {  // trs_frame's and trs_vlabel's counts
 };
 
 struct TrsState {  // on the cloud handle, freed with it; the cloud's size never changes, so the blocks sized by it are made once
+  static constexpr sfmgrid::Stage slot = sfmgrid::TREES;  // (its slot on the handle: stage<TrsState>(cloud))
   DevBufs B;
   bool ready = false;
   int* labels = nullptr;    // n
@@ -67,29 +66,11 @@ struct TrsState {  // on the cloud handle, freed with it; the cloud's size never
   int* pts = nullptr;       // MAX_TREES
   Totals* tot = nullptr;    // 1
   unsigned* changed = nullptr;  // 1
-  unsigned* mm = nullptr;   // 7: cloud_minmax's record
-  int* cells = nullptr;     // 4 cells_cap, grow-only: count, parent, occupied, slot
-  long long cells_cap = 0;
-  int* adj = nullptr;       // 26 adj_cap, grow-only: adj[k nv + v]
-  long long adj_cap = 0;
+  sfmgrid::Grow<int> cells;  // 4 per stem cell: count, parent, occupied, slot
+  sfmgrid::Grow<int> adj;    // 26 per voxel: adj[k nv + v]
   double ms[6] = {0, 0, 0, 0, 0, 0};
   int sweeps = 0;
 };
-
-void trs_state_free(void* p) {
-  TrsState* s = (TrsState*)p;
-  hipFree(s->cells);
-  hipFree(s->adj);
-  delete s;
-}
-
-TrsState* trs_state(sfmhip_cloud* c) {
-  if (!c->trs) {
-    c->trs = new TrsState();
-    c->trs_free = trs_state_free;
-  }
-  return (TrsState*)c->trs;
-}
 
 int trs_alloc(sfmhip_cloud* c, TrsState* s) {
   if (s->ready) return SFMHIP_OK;
@@ -113,19 +94,7 @@ int trs_alloc(sfmhip_cloud* c, TrsState* s) {
   SFM_TRY(s->B.alloc(&s->pts, (size_t)MAX_TREES));
   SFM_TRY(s->B.alloc(&s->tot, 1));
   SFM_TRY(s->B.alloc(&s->changed, 1));
-  SFM_TRY(s->B.alloc(&s->mm, 7));
   s->ready = true;
-  return SFMHIP_OK;
-}
-
-template <typename T>
-int grow(T** p, long long* cap, long long need, int per) {
-  if (need <= *cap) return SFMHIP_OK;
-  hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  SFM_TRY(sfm_dev_alloc(p, (size_t)per * (size_t)need));
-  *cap = need;
   return SFMHIP_OK;
 }
 
@@ -359,12 +328,6 @@ __global__ __launch_bounds__(256) void trs_plabel(const int* pvox, const int* vl
   tree_of[i] = v >= 0 && v < nv ? vlabel[v] : -1;
 }
 
-Opts to_opts(const sfmhip_trees_opts* o) {
-  Opts r;
-  memcpy(&r, o, sizeof r);
-  return r;
-}
-
 #define TRS_LAUNCH(kernel, grid, ...)                                              \
   do {                                                                             \
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, __VA_ARGS__);               \
@@ -374,7 +337,7 @@ Opts to_opts(const sfmhip_trees_opts* o) {
 int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, int32_t* tree_of, int cap, Stem* stems, Result& res) {
   Prep p;
   if (!prepare(o, p)) return SFMHIP_ERR_ARG;
-  TrsState* s = trs_state(c);
+  TrsState* s = sfmgrid::stage<TrsState>(c);
   for (double& m : s->ms) m = 0;
   s->sweeps = 0;
   empty_result(res, F_NONE_ABOVE);
@@ -395,12 +358,9 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, in
   if (labels) SFM_HIP_TRY(hipMemcpyAsync(s->labels, labels, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
   SFM_HIP_TRY(hipMemsetAsync(s->tot, 0, sizeof(Totals), st));
   TRS_LAUNCH(trs_frame, gn, c->xyz, labels ? s->labels : nullptr, label, n, p, s->enh, s->tot);
-  const unsigned init[7] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u};
   unsigned mm[7];
   Totals tot;
-  SFM_HIP_TRY(hipMemcpyAsync(s->mm, init, sizeof init, hipMemcpyHostToDevice, st));
-  TRS_LAUNCH(sfmgrid::cloud_minmax<InA>, dim3(std::min(blocks(n, 256), 1024u)), s->enh, n, InA(), s->mm);
-  SFM_HIP_TRY(hipMemcpyAsync(mm, s->mm, sizeof mm, hipMemcpyDeviceToHost, st));
+  SFM_TRY(sfmgrid::minmax(c, s->enh, n, InA(), mm));
   SFM_HIP_TRY(hipMemcpyAsync(&tot, s->tot, sizeof tot, hipMemcpyDeviceToHost, st));
   SFM_HIP_TRY(hipStreamSynchronize(st));
   res.n_selected = (int32_t)tot.selected;
@@ -416,8 +376,8 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, in
   if (!make_dims(p, lo, hi, d)) return SFMHIP_ERR_ARG;
   // rules 4, 5: the band histogram, the components, the stems
   const int ncell = d.De * d.Dn;
-  SFM_TRY(grow(&s->cells, &s->cells_cap, (long long)ncell, 4));
-  int *count = s->cells, *parent = count + s->cells_cap, *occupied = parent + s->cells_cap, *slot = occupied + s->cells_cap;
+  SFM_TRY(s->cells.need(4 * (size_t)ncell));
+  int *count = s->cells.p, *parent = count + ncell, *occupied = parent + ncell, *slot = occupied + ncell;
   const dim3 gc(blocks(ncell, 256));
   SFM_HIP_TRY(hipMemsetAsync(count, 0, sizeof(int) * (size_t)ncell, st));
   TRS_LAUNCH(trs_hist, gn, s->enh, n, p, d, ncell, count);
@@ -456,13 +416,13 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, in
   SFM_TRY(sfmgrid::scan(c, s->head, s->hx, (size_t)n, &nv));
   if (nv < 1 || nv > res.n_above) return SFMHIP_ERR_STATE;  // (never)
   res.n_voxels = nv;
-  SFM_TRY(grow(&s->adj, &s->adj_cap, (long long)nv, STEPS));
+  SFM_TRY(s->adj.need((size_t)STEPS * nv));
   SFM_HIP_TRY(hipMemsetAsync(s->key, 0xFF, sizeof(u64) * (size_t)nv, st));
   SFM_HIP_TRY(hipMemsetAsync(s->pvox, 0xFF, sizeof(int) * (size_t)n, st));
   TRS_LAUNCH(trs_vox_emit, gn, keys_out, vals_out, s->head, s->hx, n, res.n_above, nvox, nv, s->enh, p, d, ncell, parent, slot, n_occ,
              s->stem_of, s->pvox, s->ukey, s->vstart, s->key);
   const dim3 gv(blocks(nv, 256));
-  TRS_LAUNCH(trs_adj, dim3(gv.x, STEPS), s->ukey, nv, d, s->adj);
+  TRS_LAUNCH(trs_adj, dim3(gv.x, STEPS), s->ukey, nv, d, s->adj.p);
   if (c->ctx->timing) SFM_HIP_TRY(hipStreamSynchronize(st));
   t3 = t4 = sfm_now_ms();
   // rule 8: sweeps in batches, until a batch changes no key.  A sweep that changes a key settles at least one more voxel
@@ -470,7 +430,7 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, in
   for (;;) {
     unsigned changed = 0;
     SFM_HIP_TRY(hipMemsetAsync(s->changed, 0, sizeof(unsigned), st));
-    for (int b = 0; b < BATCH; ++b) TRS_LAUNCH(trs_sweep, gv, s->key, s->adj, nv, s->changed);
+    for (int b = 0; b < BATCH; ++b) TRS_LAUNCH(trs_sweep, gv, s->key, s->adj.p, nv, s->changed);
     SFM_HIP_TRY(hipMemcpyAsync(&changed, s->changed, sizeof changed, hipMemcpyDeviceToHost, st));
     SFM_HIP_TRY(hipStreamSynchronize(st));
     s->sweeps += BATCH;
@@ -502,18 +462,14 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, in
 
 extern "C" void sfmhip_trees_default_opts(sfmhip_trees_opts* o) {
   if (!o) return;
-  const Opts r = default_opts();
-  memcpy(o, &r, sizeof r);
+  *o = mirror<sfmhip_trees_opts>(default_opts());
 }
 
 extern "C" int sfmhip_trees_opts_from_ground(const sfmhip_ground_result* g, sfmhip_trees_opts* io) {
   if (!g || !io) return SFMHIP_ERR_ARG;
-  sfmground::Result r;
-  Opts t;
-  memcpy(&r, g, sizeof r);
-  memcpy(&t, io, sizeof t);
-  if (!opts_from_ground(r, t)) return SFMHIP_ERR_ARG;
-  memcpy(io, &t, sizeof t);
+  Opts t = mirror<Opts>(*io);
+  if (!opts_from_ground(mirror<sfmground::Result>(*g), t)) return SFMHIP_ERR_ARG;
+  *io = mirror<sfmhip_trees_opts>(t);
   return SFMHIP_OK;
 }
 
@@ -521,14 +477,14 @@ extern "C" int sfmhip_cloud_trees(sfmhip_cloud* c, const int32_t* labels_in, int
                                   int cap, sfmhip_tree_stem* stems, sfmhip_trees_result* out) {
   if (!c || !opts || !out || cap < 0 || (cap > 0 && !stems) || (c->n > 0 && !tree_of)) return SFMHIP_ERR_ARG;
   Result res;
-  SFM_TRY(run(c, labels_in, label, to_opts(opts), tree_of, cap, (Stem*)stems, res));
-  memcpy(out, &res, sizeof res);
+  SFM_TRY(run(c, labels_in, label, mirror<Opts>(*opts), tree_of, cap, (Stem*)stems, res));
+  *out = mirror<sfmhip_trees_result>(res);
   return SFMHIP_OK;
 }
 
 extern "C" int sfmhip_cloud_trees_last_timing(sfmhip_cloud* c, double ms6[6], int32_t* sweeps) {
   if (!c || !ms6) return SFMHIP_ERR_ARG;
-  const TrsState* s = trs_state(c);
+  const TrsState* s = sfmgrid::stage<TrsState>(c);
   for (int i = 0; i < 6; ++i) ms6[i] = s->ms[i];
   if (sweeps) *sweeps = s->sweeps;
   return SFMHIP_OK;
