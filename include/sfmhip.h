@@ -603,7 +603,8 @@ int sfmhip_cloud_dendro_last_timing(sfmhip_cloud* cloud, double ms6[6]);
  * A structure-from-motion cloud stands in the first camera's frame: gravity points anywhere and the lowest point along z is
  * no ground.  This call finds the dominant ground plane of the cloud by RANSAC, refits it and orients it so that the trees
  * stand on it; sfmhip_dendro_opts_from_ground hands it to the dendrometry as up, north and ground.  Metric scale cannot
- * come from the cloud: it stays the caller's `scale`.  The arithmetic is csrc/ground.h (compiled by g++ and hipcc without
+ * come from the cloud: it stays the caller's `scale` (a similarity registration against a metric cloud gives it:
+ * sfmhip_cloud_register below).  The arithmetic is csrc/ground.h (compiled by g++ and hipcc without
  * contraction; the device equals the host build bit for bit).  The rules:
  *  1 selection: the finite points (with labels: those with labels[i] == label), listed in ascending input index (flag, the
  *    handle's scan, emit).  Fewer than 3: status OK, flag bit 0, every double NaN, winner -1.  SFMHIP_ERR_ARG: ransac_iters
@@ -746,6 +747,72 @@ int sfmhip_cloud_trees(sfmhip_cloud* cloud, const int32_t* labels_in, int32_t la
  * the whole call; with sweeps not NULL, the sweeps it enqueued (a multiple of 16).  The voxel stage and the sweeps are timed
  * apart only under sfmhip_set_timing (a stream synchronisation); without it the voxel stage's device time shows in the sweeps'. */
 int sfmhip_cloud_trees_last_timing(sfmhip_cloud* cloud, double ms6[6], int32_t* sweeps);
+
+/* ---- two clouds meet: nearest points, rigid and similarity ICP ----
+ * What pcl::IterativeClosestPoint with TransformationEstimationSVD / ...SVDScale computes, and pcl::transformPointCloud, on
+ * two device-resident clouds of one context.  A similarity registration against a metric cloud is where the `scale` of the
+ * dendrometry comes from.  The arithmetic is csrc/register.h (compiled by g++ and hipcc without contraction; the device equals
+ * the host build bit for bit).  PCL parity is UNPINNED (PCL is not in the image); + marks a reading of PCL from memory.
+ *  1 refusals: SFMHIP_ERR_ARG for handles of different contexts, a transform with a non-finite entry or scale not > 0,
+ *    max_dist NaN or <= 0, eps < 0 or NaN, max_iters < 0, min_pairs < 3.  source == target is allowed.  An empty source or a
+ *    target without a finite point: status OK, no pairs, mse NaN, flag FEW.
+ *  2 moving a point, in f64: y_r = scale * ((R[3r] x + R[3r+1] y) + R[3r+2] z) + t_r, q = (float)y.  A source point that is
+ *    non-finite before or after has no pair: idx -1, d2 +inf.  Every iteration moves the ORIGINAL floats by the current
+ *    transform: the source is never changed and no product of increments accumulates.
+ *  3 a pair: the finite target point of least (d2, index), d2 the family's float ((dx dx) + dy dy) + dz dz of q - target;
+ *    duplicates resolve to the lower index.  Kept iff d2 <= (float)(max_dist * max_dist), squared in f64 +; +inf keeps all.
+ *  4 sums, all f64, over source indices in consecutive blocks of 256: each block by the fixed-order tree of f-9 (a point
+ *    without a pair adds +0.0), the block partials added sequentially in ascending order.  Pass 1: N, sum p, sum m (p the
+ *    source float, m the matched target float, widened); mu_p = sum p / N, mu_m = sum m / N.  Pass 2: H[r][c] = sum (m_r -
+ *    mu_m_r)(p_c - mu_p_c), sigma = sum ((dx dx + dy dy) + dz dz) of p - mu_p, and sum (double)d2.
+ *  5 the estimate (Umeyama / Horn +): svd3(H) -> U, W, Vt (the 3 x 3 Jacobi of the pose step); d = +1 when det(U) det(Vt)
+ *    >= 0, else -1; R[r][c] = (U[r][0] Vt[0][c] + U[r][1] Vt[1][c]) + (d U[r][2]) Vt[2][c]; scale = with_scale ? ((W0 + W1) +
+ *    d W2) / sigma : the initial scale; t_r = mu_m_r - scale ((R[r][0] mu_p_0 + R[r][1] mu_p_1) + R[r][2] mu_p_2).
+ *    DEGENERATE when svd3 raises its flag, sigma == 0, W1 <= 1e-12 W0 (pairs on a line), or the new scale or any entry of
+ *    the new transform is not finite or the scale not > 0: the loop stops and the current transform is returned.
+ *  6 the loop: T_0 = init.  For k = 0, 1, ...: C_k = the pairs under T_k (the idx array, -1 included).  pairs < min_pairs:
+ *    flag FEW, stop (so FEW says of every returned transform that it has too few pairs, also with max_iters 0).  Else if
+ *    k > 0 and C_k == C_{k-1}: converged 1, stop (the estimate would reproduce T_k).  Else if k > 0, eps > 0 and no entry
+ *    of scale R and of t differs between T_k and T_{k-1} by more than eps: converged 2, stop.  Else if k == max_iters:
+ *    converged 0, stop.  Else T_{k+1} = rule 5 on C_k, or stop with DEGENERATE.  iterations = k; pairs, mse (the mean of
+ *    (double)d2 over the pairs; NaN without) and idx always describe the returned transform.
+ *  7 sfmhip_cloud_nearest is rules 2 + 3 once, per source point.  A rejected pair reports idx -1 and keeps the d2 of its
+ *    nearest point, so a cloud-to-cloud distance map is max_dist = +inf and sqrt(d2).  (Inside sfmhip_cloud_register the
+ *    search of a point with nothing within max_dist ends there; its d2 is not reported.)
+ *  8 sfmhip_cloud_transform writes q of rule 2 for every point (a non-finite point stays as it is) into a new handle born on
+ *    the device; sfmhip_cloud_concat copies a's points, then b's, device to device.  Both keep the input order. */
+typedef struct sfmhip_transform {
+  double R[9];
+  double t[3];
+  double scale;
+} sfmhip_transform; /* x -> scale R x + t, R row-major */
+typedef struct sfmhip_register_opts {
+  int32_t max_iters;  /* 50; 0: evaluate the initial transform only */
+  int32_t with_scale; /* 0: rigid, the scale stays the initial one; 1: similarity */
+  int32_t min_pairs;  /* 3 */
+  int32_t reserved;
+  double max_dist; /* +inf: every pair kept; else target cloud units, > 0 */
+  double eps;      /* 0: off; else stop when no entry of scale R and t moved by more than eps */
+} sfmhip_register_opts;
+typedef struct sfmhip_register_result {
+  sfmhip_transform T;
+  int32_t iterations, pairs;
+  int32_t converged; /* 0 limit (or a flag), 1 fixed point, 2 eps */
+  int32_t flags;     /* 1 FEW, 2 DEGENERATE */
+  double mse;        /* mean of (double)d2 over the pairs under T; NaN without pairs */
+} sfmhip_register_result;
+void sfmhip_register_default_opts(sfmhip_register_opts* opts);
+/* T: NULL for the identity; idx / d2: one entry per source point */
+int sfmhip_cloud_nearest(sfmhip_cloud* target, sfmhip_cloud* source, const sfmhip_transform* T, double max_dist, int32_t* idx,
+                         float* d2);
+/* opts: NULL for the defaults; init: NULL for the identity; idx: NULL or one entry per source point, the pairs under out->T */
+int sfmhip_cloud_register(sfmhip_cloud* target, sfmhip_cloud* source, const sfmhip_register_opts* opts, const sfmhip_transform* init,
+                          sfmhip_register_result* out, int32_t* idx);
+int sfmhip_cloud_transform(sfmhip_cloud* cloud, const sfmhip_transform* T, sfmhip_cloud** out);
+int sfmhip_cloud_concat(sfmhip_cloud* a, sfmhip_cloud* b, sfmhip_cloud** out);
+/* With sfmhip_set_timing on (zeros while it is off): host-clock ms of the last sfmhip_cloud_register call with this target,
+ * summed over its iterations -- search, sums, update + the record's read -- and the iterations it ran. */
+int sfmhip_cloud_register_last_timing(sfmhip_cloud* target, double ms3[3], int32_t* iterations);
 
 /* ---- the second half of create_mesh: Poisson surface reconstruction (reference src/Sfm.cpp:1365-1381) ----
  * pcl::Poisson at depth 7 on the cloud and its flipped normals, as a screened Poisson solve on the same device-resident

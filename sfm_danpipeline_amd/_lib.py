@@ -78,6 +78,8 @@ SYMBOLS = [
     "sfmhip_ba_iterate", "sfmhip_ba_reduced_system", "sfmhip_ba_linearize_obs", "sfmhip_ba_last_timing", "sfmhip_ba_reduced_layout", "sfmhip_ba_reduced_tree", "sfmhip_probe_i8_mfma_peak", "sfmhip_probe_clock_start", "sfmhip_probe_clock_read", "sfmhip_ba_reduced_step", "sfmhip_ba_lm_decide", "sfmhip_score_essential", "sfmhip_score_last_flags", "sfmhip_score_five_point", "sfmhip_score_homography_kernel", "sfmhip_score_homography", "sfmhip_recover_pose", "sfmhip_essential_pose", "sfmhip_pose_last_flags", "sfmhip_pnp_ransac", "sfmhip_pnp_epnp", "sfmhip_pnp_last_flags", "sfmhip_pnp_last_timing", "sfmhip_cloud_create", "sfmhip_cloud_destroy", "sfmhip_cloud_passthrough", "sfmhip_cloud_radius_count", "sfmhip_cloud_radius_outlier", "sfmhip_cloud_knn", "sfmhip_cloud_normals", "sfmhip_cloud_voxel_grid", "sfmhip_cloud_statistical_outlier", "sfmhip_cloud_select", "sfmhip_cloud_size", "sfmhip_cloud_download", "sfmhip_cloud_filter_last_timing", "sfmhip_segment_default_opts", "sfmhip_cloud_segment_rgb", "sfmhip_cloud_subset_knn", "sfmhip_cloud_segment_grow", "sfmhip_cloud_segment_last_timing", "sfmhip_cloud_minmax", "sfmhip_dendro_default_opts", "sfmhip_cloud_dendrometry", "sfmhip_cloud_dendro_profile", "sfmhip_cloud_dendro_last_timing", "sfmhip_ground_default_opts", "sfmhip_cloud_ground_plane", "sfmhip_dendro_opts_from_ground", "sfmhip_cloud_ground_last_timing", "sfmhip_trees_default_opts", "sfmhip_trees_opts_from_ground", "sfmhip_cloud_trees", "sfmhip_cloud_trees_last_timing", "sfmhip_poisson_default_opts", "sfmhip_cloud_poisson", "sfmhip_mesh_counts", "sfmhip_mesh_download", "sfmhip_mesh_destroy", "sfmhip_cloud_poisson_splat", "sfmhip_poisson_solve", "sfmhip_poisson_extract", "sfmhip_cloud_poisson_last_timing", "sfmhip_mvs_default_opts", "sfmhip_mvs_create", "sfmhip_mvs_destroy", "sfmhip_mvs_level", "sfmhip_mvs_depthmap", "sfmhip_mvs_set_depthmap", "sfmhip_mvs_fuse", "sfmhip_mvs_run", "sfmhip_mvs_download", "sfmhip_mvs_last_timing", "sfmhip_image_undistort", "sfmhip_image_undistort_last_timing", "sfmhip_mvs_create_distorted", "sfmhip_mvs_valid", "sfmhip_sift_detect_and_compute", "sfmhip_sift_detect_and_compute_device", "sfmhip_sift_batch", "sfmhip_device_free", "sfmhip_host_free", "sfmhip_device_download", "sfmhip_ba_destroy", "sfmhip_ba_last_solve_profile", "sfmhip_host_parallel_for",
     "sfmhip_tracks_default_opts", "sfmhip_tracks_build", "sfmhip_tracks_build_from_plan", "sfmhip_tracks_counts", "sfmhip_tracks_download",
     "sfmhip_tracks_triangulate", "sfmhip_tracks_last_timing", "sfmhip_tracks_destroy",
+    "sfmhip_register_default_opts", "sfmhip_cloud_nearest", "sfmhip_cloud_register", "sfmhip_cloud_transform", "sfmhip_cloud_concat",
+    "sfmhip_cloud_register_last_timing",
 ]
 
 _lib = None
@@ -238,6 +240,13 @@ def lib():
         L.sfmhip_tracks_last_timing.argtypes = [vp, vp]
         L.sfmhip_tracks_destroy.argtypes = [vp]
         L.sfmhip_tracks_destroy.restype = None
+        L.sfmhip_register_default_opts.argtypes = [vp]
+        L.sfmhip_register_default_opts.restype = None
+        L.sfmhip_cloud_nearest.argtypes = [vp, vp, vp, f64, vp, vp]
+        L.sfmhip_cloud_register.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.sfmhip_cloud_transform.argtypes = [vp, vp, C.POINTER(vp)]
+        L.sfmhip_cloud_concat.argtypes = [vp, vp, C.POINTER(vp)]
+        L.sfmhip_cloud_register_last_timing.argtypes = [vp, vp, vp]
         if hasattr(L, "sfmhip_ba_last_solve_profile"):  # (diagnostic builds of older revisions lack it)
             L.sfmhip_ba_last_solve_profile.argtypes = [vp, C.POINTER(BaSolveProfile)]
     _lib = L

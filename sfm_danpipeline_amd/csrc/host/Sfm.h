@@ -235,6 +235,13 @@ class StructFromMotion {
   // reported on stderr with its residual.  mesh.cloud takes the vertices, mesh.polygons the triangles.  vizualizeMesh is
   // not built (GUI).
   void create_mesh(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PolygonMesh& mesh);
+  // (ours) the similarity ICP that brings `cloud` onto `reference`, a cloud of the same scene in metres (a
+  // terrestrial scan, last year's reconstruction, a surveyed subset): sfmhip_cloud_register with the scale estimated, from
+  // `guess` (NULL: the identity; a large motion needs one).  Returns the metres per cloud unit that Dendrometry takes as
+  // `scale` (also in *scale_out), 0 when the registration has too few pairs or is degenerate; `result` receives the whole
+  // record.  max_dist: reference units, +inf keeps every pair.  Nothing calls it by default.
+  double registerCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, const pcl::PointCloud<pcl::PointXYZ>& reference, double* scale_out = nullptr,
+                       double max_dist = INFINITY, const sfmhip_transform* guess = nullptr, sfmhip_register_result* result = nullptr);
 
   const std::vector<cv::Mat>& colorImages() const { return mColorImages; }
   const std::vector<cv::Mat>& grayImages() const { return mGrayImages; }

@@ -138,3 +138,22 @@ void StructFromMotion::create_mesh(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, p
   for (int i = 0; i < s.n_triangles; ++i)
     mesh.polygons[i].vertices = {(uint32_t)t[3 * i], (uint32_t)t[3 * i + 1], (uint32_t)t[3 * i + 2]};
 }
+
+double StructFromMotion::registerCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, const pcl::PointCloud<pcl::PointXYZ>& reference,
+                                       double* scale_out, double max_dist, const sfmhip_transform* guess, sfmhip_register_result* result) {
+  sfmhip_cloud* ref = nullptr;
+  check(sfmhip_cloud_create(sfm_hip_context(), (int)reference.size(), reference.size() ? &reference.points[0].x : nullptr, &ref),
+        "sfmhip_cloud_create");
+  sfmhip_register_opts o;
+  sfmhip_register_default_opts(&o);
+  o.with_scale = 1;
+  o.max_dist = max_dist;
+  sfmhip_register_result res;
+  const int rc = sfmhip_cloud_register(ref, device_cloud(*cloud), &o, guess, &res, nullptr);
+  sfmhip_cloud_destroy(ref);
+  check(rc, "sfmhip_cloud_register");
+  const double scale = res.flags == 0 ? res.T.scale : 0.0;
+  if (scale_out) *scale_out = scale;
+  if (result) *result = res;
+  return scale;
+}

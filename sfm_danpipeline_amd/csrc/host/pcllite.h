@@ -1,7 +1,8 @@
 // pcllite.h -- the few PCL 1.8.1 types map3D's step 10 passes around (reference src/Sfm.cpp:94-102, include/Sfm.h:182-186),
 // as plain stand-ins next to cvlite.h (PCL is not a dependency of this build), and the PCD reader that loads MAP3D.pcd
-// into them (pcl::io::loadPCDFile for PointXYZ and PointXYZRGB), and pcl::VoxelGrid / pcl::StatisticalOutlierRemoval over the C
-// ABI.  Header-only and C++14: the host mirror and the CPU tests include it.
+// into them (pcl::io::loadPCDFile for PointXYZ and PointXYZRGB), and pcl::VoxelGrid / pcl::StatisticalOutlierRemoval /
+// pcl::IterativeClosestPoint / pcl::transformPointCloud over the C ABI.  Header-only and C++14: the host mirror and the CPU
+// tests include it.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -437,6 +438,119 @@ class StatisticalOutlierRemoval {
   int mean_k_ = 1;          // PCL's defaults
   double std_mul_ = 0.0;
   bool negative_ = false;
+};
+
+// ---- pcl::IterativeClosestPoint, its similarity form and pcl::transformPointCloud with PCL's setters, forwarding to
+// sfmhip_cloud_register / sfmhip_cloud_transform (include/sfmhip.h, DESIGN.md f-17 rules 1-8).  The matrix is the 4 x 4 float
+// one PCL code reads the result from.  Not mirrored: reciprocal correspondences, RANSAC rejection, the Euclidean fitness epsilon.
+}  // namespace pcl
+
+namespace Eigen {
+struct Matrix4f {
+  float m[16];
+  Matrix4f() {
+    for (int i = 0; i < 16; ++i) m[i] = 0.0f;
+  }
+  static Matrix4f Identity() {
+    Matrix4f M;
+    M.m[0] = M.m[5] = M.m[10] = M.m[15] = 1.0f;
+    return M;
+  }
+  float& operator()(int r, int c) { return m[4 * r + c]; }
+  float operator()(int r, int c) const { return m[4 * r + c]; }
+};
+}  // namespace Eigen
+
+namespace pcl {
+namespace detail {
+
+// the similarity of a 4 x 4 [s R | t]: s = cbrt(det), R = the block / s (the library wants finite entries and s > 0)
+inline sfmhip_transform to_transform(const Eigen::Matrix4f& M) {
+  const double a[9] = {M(0, 0), M(0, 1), M(0, 2), M(1, 0), M(1, 1), M(1, 2), M(2, 0), M(2, 1), M(2, 2)};
+  const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
+  sfmhip_transform T;
+  T.scale = std::cbrt(det);
+  for (int i = 0; i < 9; ++i) T.R[i] = a[i] / T.scale;
+  for (int r = 0; r < 3; ++r) T.t[r] = M(r, 3);
+  return T;
+}
+inline Eigen::Matrix4f to_matrix(const sfmhip_transform& T) {
+  Eigen::Matrix4f M = Eigen::Matrix4f::Identity();
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) M(r, c) = (float)(T.scale * T.R[3 * r + c]);
+    M(r, 3) = (float)T.t[r];
+  }
+  return M;
+}
+template <typename T>
+inline void download_into(sfmhip_cloud* h, const PointCloud<T>& in, PointCloud<T>& out) {
+  std::vector<float> xyz(3 * in.size() + 3);
+  filter_check(sfmhip_cloud_download(h, xyz.data()), "sfmhip_cloud_download");
+  PointCloud<T> r = in;  // (every other field rides along)
+  for (size_t i = 0; i < in.size(); ++i) r.points[i].x = xyz[3 * i], r.points[i].y = xyz[3 * i + 1], r.points[i].z = xyz[3 * i + 2];
+  out = r;
+}
+
+}  // namespace detail
+
+// x -> M x for every point (rule 2: f64, rounded once; a non-finite point stays), on the device
+template <typename PointT>
+inline void transformPointCloud(const PointCloud<PointT>& in, PointCloud<PointT>& out, const Eigen::Matrix4f& M) {
+  const sfmhip_transform T = detail::to_transform(M);
+  sfmhip_cloud *h = detail::upload(in), *moved = nullptr;
+  const int rc = sfmhip_cloud_transform(h, &T, &moved);
+  sfmhip_cloud_destroy(h);
+  detail::filter_check(rc, "sfmhip_cloud_transform");
+  detail::download_into(moved, in, out);
+  sfmhip_cloud_destroy(moved);
+}
+
+template <typename PointSource, typename PointTarget>
+class IterativeClosestPoint {
+ public:
+  void setInputSource(const typename PointCloud<PointSource>::Ptr& cloud) { source_ = cloud; }
+  void setInputTarget(const typename PointCloud<PointTarget>::Ptr& cloud) { target_ = cloud; }
+  void setMaxCorrespondenceDistance(double d) { max_dist_ = d; }
+  void setMaximumIterations(int n) { max_iters_ = n; }
+  void setTransformationEpsilon(double e) { eps_ = e; }
+  void setEstimateScale(bool on) { with_scale_ = on; }  // (ours: TransformationEstimationSVDScale in place of ...SVD)
+  void align(PointCloud<PointSource>& output) { align(output, Eigen::Matrix4f::Identity()); }
+  // the source under the final transformation; a guess must be a similarity with finite entries
+  void align(PointCloud<PointSource>& output, const Eigen::Matrix4f& guess) {
+    const PointCloud<PointSource> src = source_ ? *source_ : PointCloud<PointSource>();
+    const PointCloud<PointTarget> tgt = target_ ? *target_ : PointCloud<PointTarget>();
+    sfmhip_register_opts o;
+    sfmhip_register_default_opts(&o);
+    o.max_iters = max_iters_, o.with_scale = with_scale_ ? 1 : 0, o.max_dist = max_dist_, o.eps = eps_;
+    const sfmhip_transform init = detail::to_transform(guess);
+    sfmhip_cloud *hs = detail::upload(src), *ht = detail::upload(tgt), *moved = nullptr;
+    int rc = sfmhip_cloud_register(ht, hs, &o, &init, &result_, nullptr);
+    if (rc == SFMHIP_OK) rc = sfmhip_cloud_transform(hs, &result_.T, &moved);
+    sfmhip_cloud_destroy(hs);
+    sfmhip_cloud_destroy(ht);
+    detail::filter_check(rc, "sfmhip_cloud_register");
+    detail::download_into(moved, src, output);
+    sfmhip_cloud_destroy(moved);
+  }
+  bool hasConverged() const { return result_.flags == 0; }  // (PCL counts the iteration limit as a criterion met)
+  double getFitnessScore() const { return result_.mse; }
+  Eigen::Matrix4f getFinalTransformation() const { return detail::to_matrix(result_.T); }
+  const sfmhip_register_result& result() const { return result_; }  // (ours: the f64 transform, the counts and the flags)
+
+ protected:
+  typename PointCloud<PointSource>::Ptr source_;
+  typename PointCloud<PointTarget>::Ptr target_;
+  double max_dist_ = INFINITY, eps_ = 0.0;  // PCL: sqrt(DBL_MAX) and 0
+  int max_iters_ = 10;                      // PCL's default
+  bool with_scale_ = false;
+  sfmhip_register_result result_ = sfmhip_register_result();
+};
+
+// (ours) the similarity form under a name of its own
+template <typename PointSource, typename PointTarget>
+class IterativeClosestPointWithScale : public IterativeClosestPoint<PointSource, PointTarget> {
+ public:
+  IterativeClosestPointWithScale() { this->with_scale_ = true; }
 };
 
 }  // namespace pcl

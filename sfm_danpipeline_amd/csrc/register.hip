@@ -1,0 +1,390 @@
+// register.hip -- two clouds meet: the nearest target point of every source point, rigid and similarity
+// ICP around it, and the two calls that keep the result on the device (transform, concat).  The rules are register.h's,
+// which the CPU test stub compiles too.
+//
+// reg_nearest: a lane per source point; a source of at least SORT_MIN points is walked in the order of the target cells of its
+// images under the call's first transform (reg_keys + the handle's cell_sort, once per call), so that the lanes of a wave
+// walk the same rows; results do not depend on the order.  The point is moved by the current transform (read from the loop's
+// record on the device), its cell in the TARGET's k-NN grid is cell_of clamped to the grid, and the rings grow as in cloud_knn with one
+// best slot.  block_bound stays a lower bound for a point outside the grid's box: it only counts faces that have cells
+// beyond them, the clamped cell is the border cell on every axis on which the point is outside, so the face the point is
+// beyond is never counted, and the distance to every counted face is taken from the point's own coordinate.  The slack
+// adds the point's magnitude, since a source point can lie far from the box the grid's knn_abs_eps was sized for.
+// reg_sums1 / reg_sums2: 256 source points per workgroup through block_tree; reg_means and reg_update (one wave each)
+// fold the partials in ascending order, a lane per sum; reg_update's lane 0 then takes rule 6's decision (loop_step) and
+// writes the next transform.  The host reads the loop's record once per iteration; no n-sized array crosses the bus
+// inside the loop.  No atomics, no spins, no hand-offs between workgroups: the "pairs changed" flag is a plain store of 1.
+#include "common.h"
+#include "cloud.h"
+#include "cloud_grid.h"
+#include "block_sum.h"
+#include "register.h"
+#include <algorithm>
+#include <cmath>
+
+using namespace sfmgrid;
+using sfmreg::Loop;
+using sfmreg::N1;
+using sfmreg::N2;
+using sfmreg::Opts;
+using sfmreg::Result;
+using sfmreg::Transform;
+
+namespace {
+
+constexpr int SUM_BLOCK = sfmsum::CHUNK;  // rule 4's block: 256 source points, one workgroup
+constexpr int NEAR_BLOCK = 128;
+constexpr int SORT_MIN = 8192;  // sources of at least this many points are searched in the order of the target's cells
+
+struct DevLoop {  // the loop's record on the device
+  Loop L;
+  int32_t changed, pad;
+  double s1[N1], mu_p[3], mu_m[3];
+};
+
+struct RegState {  // on the TARGET handle, freed with it
+  static constexpr sfmgrid::Stage slot = sfmgrid::REGISTER;
+  Grow<int> idx, kin, kout, vin, order;
+  Grow<float> d2;
+  Grow<double> part1, part2;
+  Grow<DevLoop> rec;
+  double ms[3] = {0, 0, 0};  // search, sums, update of the last register call
+  int iterations = 0;
+};
+
+__device__ __forceinline__ void scan_best(const GridDev& g, int row, int xa, int xb, const float4& q, float& bd, int& bi) {
+  int s, e;
+  row_span(g, row, xa, xb, &s, &e);
+  for (int j = s; j < e; ++j) {
+    const float4 t = g.pts[j];
+    const float dd = sfmcloud::dist2(q.x, q.y, q.z, t.x, t.y, t.z);
+    const int ti = __float_as_int(t.w);
+    if (sfmcloud::knn_less(dd, ti, bd, bi)) bd = dd, bi = ti;
+  }
+}
+
+// the target cell of every source point's image (a point without one: `invalid`, behind every cell) and its index: what
+// the handle's cell_sort turns into the order reg_nearest walks the source in, so that the lanes of a wave walk the same rows
+__global__ void reg_keys(GridDev g, const float* src, int n_src, const Transform* Tp, int invalid, int* keys, int* vals) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_src) return;
+  const Transform T = *Tp;
+  float q[3];
+  int key = invalid;
+  if (sfmreg::move(T, src[3 * (size_t)i], src[3 * (size_t)i + 1], src[3 * (size_t)i + 2], q))
+    key = (cell_of((double)q[2], g.o[2], g.cell, g.D[2]) * g.D[1] + cell_of((double)q[1], g.o[1], g.cell, g.D[1])) * g.D[0] +
+          cell_of((double)q[0], g.o[0], g.cell, g.D[0]);
+  keys[i] = key;
+  vals[i] = i;
+}
+
+// rules 2 + 3.  order: NULL, or the source index of every lane (results do not depend on it).  T: the transform (the loop's
+// record, or one uploaded for sfmhip_cloud_nearest).  exact: search until the nearest is known also beyond md2 (sfmhip_cloud_nearest: a rejected pair keeps its d2); else a lane with nothing within
+// md2 in reach leaves once the bound exceeds max_dist.  changed: raised when an index differs from the array's old entry.
+__global__ __launch_bounds__(NEAR_BLOCK) void reg_nearest(GridDev g, double abs_eps, const float* src, int n_src, const int* order,
+                                                         const Transform* Tp, float md2, int exact, int* idx, float* d2, int32_t* changed) {
+  const int l = blockIdx.x * NEAR_BLOCK + threadIdx.x;
+  if (l >= n_src) return;
+  const int i = order ? order[l] : l;
+  const Transform T = *Tp;
+  float qv[3];
+  const bool ok = sfmreg::move(T, src[3 * (size_t)i], src[3 * (size_t)i + 1], src[3 * (size_t)i + 2], qv);
+  float bd = sfmcloud::bits_f(0x7F800000u);
+  int bi = INT_MAX;
+  if (ok && g.n_valid > 0) {
+    const float4 q = make_float4(qv[0], qv[1], qv[2], 0.0f);
+    const int c[3] = {cell_of((double)q.x, g.o[0], g.cell, g.D[0]), cell_of((double)q.y, g.o[1], g.cell, g.D[1]),
+                      cell_of((double)q.z, g.o[2], g.cell, g.D[2])};
+    const double eps = abs_eps + 1e-12 * ((fabs((double)q.x) + fabs((double)q.y)) + fabs((double)q.z));
+    for (int R = 0;; ++R) {
+      for (int z = max(c[2] - R, 0); z <= min(c[2] + R, g.D[2] - 1); ++z)
+        for (int y = max(c[1] - R, 0); y <= min(c[1] + R, g.D[1] - 1); ++y) {
+          const int row = (z * g.D[1] + y) * g.D[0];
+          if (abs(z - c[2]) == R || abs(y - c[1]) == R) {
+            scan_best(g, row, max(c[0] - R, 0), min(c[0] + R, g.D[0] - 1), q, bd, bi);
+          } else {
+            if (c[0] - R >= 0) scan_best(g, row, c[0] - R, c[0] - R, q, bd, bi);
+            if (c[0] + R <= g.D[0] - 1) scan_best(g, row, c[0] + R, c[0] + R, q, bd, bi);
+          }
+        }
+      const double b = block_bound(g, q, c, R);
+      if (b == INFINITY) break;  // the block covers the grid
+      const double bs = b * (1.0 - 1.0 / 65536.0) - eps;
+      if (bs > 0.0) {
+        if (bi != INT_MAX && bs * bs > (double)bd) break;  // every unsearched point is strictly farther than the best
+        if (!exact && bs * bs > (double)md2) break;        // ... or than max_dist
+      }
+    }
+  }
+  const bool got = bi != INT_MAX;
+  const int out = got && sfmreg::keep(bd, md2) ? bi : -1;
+  if (changed && idx[i] != out) *changed = 1;
+  idx[i] = out;
+  d2[i] = got ? bd : sfmcloud::bits_f(0x7F800000u);
+}
+
+__device__ __forceinline__ bool load_pair(const float* src, const float* tgt, const int* idx, int i, int n_src, float p[3], float m[3]) {
+  bool paired = false;
+  for (int a = 0; a < 3; ++a) p[a] = m[a] = 0.0f;
+  if (i < n_src) {
+    const int j = idx[i];
+    paired = j >= 0;
+    for (int a = 0; a < 3; ++a) p[a] = src[3 * (size_t)i + a];
+    if (paired)
+      for (int a = 0; a < 3; ++a) m[a] = tgt[3 * (size_t)j + a];
+  }
+  return paired;
+}
+
+__global__ __launch_bounds__(SUM_BLOCK) void reg_sums1(const float* src, const float* tgt, const int* idx, int n_src, double* part) {
+  __shared__ double sh[N1][4];
+  const int i = blockIdx.x * SUM_BLOCK + threadIdx.x;
+  float p[3], m[3];
+  const bool paired = load_pair(src, tgt, idx, i, n_src, p, m);
+  double v[N1];
+  sfmreg::terms1(paired, p, m, v);
+  sfmsum::block_tree<N1>(v, sh);
+  if (threadIdx.x < N1) {
+    double w = v[0];
+    for (int k = 1; k < N1; ++k) w = threadIdx.x == k ? v[k] : w;
+    part[(size_t)blockIdx.x * N1 + threadIdx.x] = w;
+  }
+}
+
+// the partials of pass 1 in ascending block order, a lane per sum; then the means
+__global__ __launch_bounds__(64) void reg_means(const double* part, int n_blocks, DevLoop* rec) {
+  const int k = threadIdx.x;
+  if (k < N1) {
+    double s = 0.0;
+    for (int b = 0; b < n_blocks; ++b) s = s + part[(size_t)b * N1 + k];
+    rec->s1[k] = s;
+  }
+  __syncthreads();
+  if (k == 0) sfmreg::means(rec->s1, rec->mu_p, rec->mu_m);
+}
+
+__global__ __launch_bounds__(SUM_BLOCK) void reg_sums2(const float* src, const float* tgt, const int* idx, const float* d2, int n_src,
+                                                      const DevLoop* rec, double* part) {
+  __shared__ double sh[N2][4];
+  const int i = blockIdx.x * SUM_BLOCK + threadIdx.x;
+  float p[3], m[3];
+  const bool paired = load_pair(src, tgt, idx, i, n_src, p, m);
+  double mu_p[3], mu_m[3];
+  for (int a = 0; a < 3; ++a) mu_p[a] = rec->mu_p[a], mu_m[a] = rec->mu_m[a];
+  double v[N2];
+  sfmreg::terms2(paired, p, m, paired ? d2[i] : 0.0f, mu_p, mu_m, v);
+  sfmsum::block_tree<N2>(v, sh);
+  if (threadIdx.x < N2) {
+    double w = v[0];
+    for (int k = 1; k < N2; ++k) w = threadIdx.x == k ? v[k] : w;
+    part[(size_t)blockIdx.x * N2 + threadIdx.x] = w;
+  }
+}
+
+// pass 2's partials folded as pass 1's, then rule 6's step on lane 0: the stop decision or the next transform
+__global__ __launch_bounds__(64) void reg_update(const double* part, int n_blocks, Opts o, DevLoop* rec) {
+  __shared__ double s2[N2];
+  const int k = threadIdx.x;
+  if (k < N2) {
+    double s = 0.0;
+    for (int b = 0; b < n_blocks; ++b) s = s + part[(size_t)b * N2 + k];
+    s2[k] = s;
+  }
+  __syncthreads();
+  if (k == 0) {
+    double t2[N2];
+    for (int q = 0; q < N2; ++q) t2[q] = s2[q];
+    sfmreg::loop_step(rec->L, o, rec->changed != 0, rec->s1, t2);
+    rec->changed = 0;
+  }
+}
+
+__global__ void reg_transform(const float* xyz, int n, Transform T, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+  float q[3];
+  sfmreg::move(T, x, y, z, q);
+  const bool f = sfmcloud::finite3(x, y, z);  // rule 8: a non-finite point stays as it is
+  out[3 * (size_t)i] = f ? q[0] : x;
+  out[3 * (size_t)i + 1] = f ? q[1] : y;
+  out[3 * (size_t)i + 2] = f ? q[2] : z;
+}
+
+int prepare(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState** state) {
+  SFM_HIP_TRY(hipSetDevice(tgt->ctx->device));
+  RegState* s = stage<RegState>(tgt);
+  const size_t n1 = (size_t)std::max(src->n, 1), nb = blocks(n1, SUM_BLOCK);
+  SFM_TRY(s->idx.need(n1));
+  SFM_TRY(s->d2.need(n1));
+  SFM_TRY(s->part1.need(nb * N1));
+  SFM_TRY(s->part2.need(nb * N2));
+  SFM_TRY(s->rec.need(1));
+  if (tgt->n_valid > 0) SFM_TRY(knn_grid(tgt));
+  *state = s;
+  return SFMHIP_OK;
+}
+
+// the source's order by target cell under the transform at d_T (once per call: the loop moves the points little); *order
+// stays NULL for a small source or a target without a finite point
+int sort_source(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, const Transform* d_T, const int** order) {
+  *order = nullptr;
+  const int n = src->n;
+  if (n < SORT_MIN || tgt->n_valid == 0) return SFMHIP_OK;
+  SFM_TRY(s->kin.need(n));
+  SFM_TRY(s->kout.need(n));
+  SFM_TRY(s->vin.need(n));
+  SFM_TRY(s->order.need(n));
+  const long long ncell = tgt->kg.ncell;
+  hipLaunchKernelGGL(reg_keys, dim3(blocks(n, 256)), dim3(256), 0, tgt->ctx->stream, tgt->kg.dev(tgt->n_valid), src->xyz, n, d_T, (int)ncell,
+                     s->kin.p, s->vin.p);
+  SFM_HIP_TRY(hipGetLastError());
+  SFM_TRY(cell_sort(tgt, ncell, s->kin.p, s->kout.p, s->vin.p, s->order.p, n));
+  *order = s->order.p;
+  return SFMHIP_OK;
+}
+
+void launch_nearest(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, const int* order, const Transform* d_T, float md2, bool exact,
+                    int32_t* d_changed) {
+  if (src->n == 0) return;
+  GridDev g = tgt->kg.dev(tgt->n_valid);  // (never dereferenced without a finite target point)
+  const double eps = tgt->n_valid > 0 ? knn_abs_eps(tgt) : 0.0;
+  hipLaunchKernelGGL(reg_nearest, dim3(blocks(src->n, NEAR_BLOCK)), dim3(NEAR_BLOCK), 0, tgt->ctx->stream, g, eps, src->xyz, src->n, order,
+                     d_T, md2, exact ? 1 : 0, s->idx.p, s->d2.p, d_changed);
+}
+
+}  // namespace
+
+extern "C" void sfmhip_register_default_opts(sfmhip_register_opts* o) {
+  if (o) *o = mirror<sfmhip_register_opts>(sfmreg::default_opts());
+}
+
+extern "C" int sfmhip_cloud_nearest(sfmhip_cloud* tgt, sfmhip_cloud* src, const sfmhip_transform* T, double max_dist, int32_t* idx, float* d2) {
+  if (!tgt || !src || tgt->ctx != src->ctx || !sfmreg::valid_max_dist(max_dist) || (src->n > 0 && (!idx || !d2))) return SFMHIP_ERR_ARG;
+  const Transform T0 = T ? mirror<Transform>(*T) : sfmreg::identity();
+  if (!sfmreg::valid_transform(T0)) return SFMHIP_ERR_ARG;
+  if (src->n == 0) return SFMHIP_OK;
+  RegState* s = nullptr;
+  SFM_TRY(prepare(tgt, src, &s));
+  hipStream_t st = tgt->ctx->stream;
+  Loop L;
+  sfmreg::loop_init(L, T0);
+  SFM_HIP_TRY(hipMemcpyAsync(&s->rec.p->L, &L, sizeof L, hipMemcpyHostToDevice, st));
+  const int* order = nullptr;
+  SFM_TRY(sort_source(tgt, src, s, &s->rec.p->L.T, &order));
+  launch_nearest(tgt, src, s, order, &s->rec.p->L.T, sfmreg::max_d2(max_dist), true, nullptr);
+  SFM_HIP_TRY(hipGetLastError());
+  SFM_HIP_TRY(hipMemcpyAsync(idx, s->idx.p, sizeof(int) * (size_t)src->n, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipMemcpyAsync(d2, s->d2.p, sizeof(float) * (size_t)src->n, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipStreamSynchronize(st));
+  return SFMHIP_OK;
+}
+
+extern "C" int sfmhip_cloud_register(sfmhip_cloud* tgt, sfmhip_cloud* src, const sfmhip_register_opts* opts, const sfmhip_transform* init,
+                                     sfmhip_register_result* out, int32_t* idx) {
+  if (!tgt || !src || !out || tgt->ctx != src->ctx) return SFMHIP_ERR_ARG;
+  const Opts o = opts ? mirror<Opts>(*opts) : sfmreg::default_opts();
+  const Transform T0 = init ? mirror<Transform>(*init) : sfmreg::identity();
+  if (!sfmreg::valid_opts(o) || !sfmreg::valid_transform(T0)) return SFMHIP_ERR_ARG;
+  RegState* s = nullptr;
+  SFM_TRY(prepare(tgt, src, &s));
+  hipStream_t st = tgt->ctx->stream;
+  const bool timing = tgt->ctx->timing;
+  const int n = src->n, nb = (int)blocks(n, SUM_BLOCK);
+  const float md2 = sfmreg::max_d2(o.max_dist);
+  s->ms[0] = s->ms[1] = s->ms[2] = 0;
+  s->iterations = 0;
+  DevLoop h;
+  memset(&h, 0, sizeof h);
+  sfmreg::loop_init(h.L, T0);
+  DevLoop* rec = s->rec.p;
+  SFM_HIP_TRY(hipMemcpyAsync(rec, &h, sizeof h, hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemsetAsync(s->idx.p, 0xFE, sizeof(int) * (size_t)std::max(n, 1), st));  // (no index: C_0 differs from it)
+  const int* order = nullptr;
+  const double ts = timing ? sfm_now_ms() : 0.0;
+  SFM_TRY(sort_source(tgt, src, s, &rec->L.T, &order));
+  if (timing) {
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+    s->ms[0] = sfm_now_ms() - ts;  // (the source's cell order counts as search)
+  }
+  for (;;) {
+    double t0 = 0, t1 = 0, t2 = 0;
+    if (timing) t0 = sfm_now_ms();
+    launch_nearest(tgt, src, s, order, &rec->L.T, md2, false, &rec->changed);
+    SFM_HIP_TRY(hipGetLastError());
+    if (timing) {
+      SFM_HIP_TRY(hipStreamSynchronize(st));
+      t1 = sfm_now_ms();
+    }
+    if (nb > 0) hipLaunchKernelGGL(reg_sums1, dim3(nb), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, s->idx.p, n, s->part1.p);
+    hipLaunchKernelGGL(reg_means, dim3(1), dim3(64), 0, st, s->part1.p, nb, rec);
+    if (nb > 0) hipLaunchKernelGGL(reg_sums2, dim3(nb), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, s->idx.p, s->d2.p, n, rec, s->part2.p);
+    SFM_HIP_TRY(hipGetLastError());
+    if (timing) {
+      SFM_HIP_TRY(hipStreamSynchronize(st));
+      t2 = sfm_now_ms();
+    }
+    hipLaunchKernelGGL(reg_update, dim3(1), dim3(64), 0, st, s->part2.p, nb, o, rec);
+    SFM_HIP_TRY(hipGetLastError());
+    SFM_HIP_TRY(hipMemcpyAsync(&h.L, &rec->L, sizeof h.L, hipMemcpyDeviceToHost, st));  // the one small record of the iteration
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+    if (timing) s->ms[0] += t1 - t0, s->ms[1] += t2 - t1, s->ms[2] += sfm_now_ms() - t2;
+    if (h.L.stop) break;
+    if (h.L.k < 0 || h.L.k > o.max_iters) return SFMHIP_ERR_STATE;
+  }
+  s->iterations = h.L.res.iterations;
+  *out = mirror<sfmhip_register_result>(h.L.res);
+  if (idx && n > 0) {
+    SFM_HIP_TRY(hipMemcpyAsync(idx, s->idx.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+  }
+  return SFMHIP_OK;
+}
+
+extern "C" int sfmhip_cloud_transform(sfmhip_cloud* c, const sfmhip_transform* T, sfmhip_cloud** out) {
+  if (!c || !T || !out) return SFMHIP_ERR_ARG;
+  const Transform T0 = mirror<Transform>(*T);
+  if (!sfmreg::valid_transform(T0)) return SFMHIP_ERR_ARG;
+  *out = nullptr;
+  SFM_HIP_TRY(hipSetDevice(c->ctx->device));
+  hipStream_t st = c->ctx->stream;
+  float* d = nullptr;
+  SFM_TRY(sfm_dev_alloc(&d, (size_t)3 * std::max(c->n, 1)));
+  if (c->n > 0) {
+    hipLaunchKernelGGL(reg_transform, dim3(blocks(c->n, 256)), dim3(256), 0, st, c->xyz, c->n, T0, d);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+      hipFree(d);
+      return SFMHIP_ERR_HIP;
+    }
+  }
+  return adopt_device(c->ctx, d, c->n, out);
+}
+
+extern "C" int sfmhip_cloud_concat(sfmhip_cloud* a, sfmhip_cloud* b, sfmhip_cloud** out) {
+  if (!a || !b || !out || a->ctx != b->ctx) return SFMHIP_ERR_ARG;
+  if ((long long)a->n + b->n > INT_MAX) return SFMHIP_ERR_UNSUPPORTED;
+  *out = nullptr;
+  SFM_HIP_TRY(hipSetDevice(a->ctx->device));
+  hipStream_t st = a->ctx->stream;
+  const int n = a->n + b->n;
+  float* d = nullptr;
+  SFM_TRY(sfm_dev_alloc(&d, (size_t)3 * std::max(n, 1)));
+  hipError_t e = hipSuccess;
+  if (a->n > 0) e = hipMemcpyAsync(d, a->xyz, sizeof(float) * 3 * (size_t)a->n, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess && b->n > 0) e = hipMemcpyAsync(d + 3 * (size_t)a->n, b->xyz, sizeof(float) * 3 * (size_t)b->n, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    g_sfmhip_last_hip_error = (int)e;
+    hipFree(d);
+    return SFMHIP_ERR_HIP;
+  }
+  return adopt_device(a->ctx, d, n, out);
+}
+
+extern "C" int sfmhip_cloud_register_last_timing(sfmhip_cloud* tgt, double ms3[3], int32_t* iterations) {
+  if (!tgt || !ms3) return SFMHIP_ERR_ARG;
+  const RegState* s = stage<RegState>(tgt);
+  for (int i = 0; i < 3; ++i) ms3[i] = s->ms[i];
+  if (iterations) *iterations = s->iterations;
+  return SFMHIP_OK;
+}
