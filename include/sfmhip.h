@@ -814,6 +814,94 @@ int sfmhip_cloud_concat(sfmhip_cloud* a, sfmhip_cloud* b, sfmhip_cloud** out);
  * summed over its iterations -- search, sums, update + the record's read -- and the iterations it ran. */
 int sfmhip_cloud_register_last_timing(sfmhip_cloud* target, double ms3[3], int32_t* iterations);
 
+/* ---- coarse plot alignment: height-keyed pose voting and multi-start ICP ----
+ * sfmhip_cloud_register needs `init` within a few degrees.  Two reconstructions of one plot differ by an arbitrary rotation,
+ * translation and scale; once each is levelled by its ground plane, what is left is a scale, a yaw about the vertical and a
+ * horizontal shift.  The points above the ground vote for those by their heights, ICP runs from every candidate at once, and
+ * the start that pairs most wins.  The arithmetic is csrc/align.h (compiled by g++ and hipcc without contraction; integer
+ * counts, f64 expressions in one written order: the device equals the host build byte for byte).
+ * Entry 1, sfmhip_cloud_register_batch: n_init starts in one lock-step loop.  results[b] and row b of idx are byte-equal to
+ *    what sfmhip_cloud_register(target, source, opts, &inits[b], ...) returns.  SFMHIP_ERR_ARG, nothing written: whatever
+ *    f-17 rule 1 refuses for any one init, inits NULL, n_init outside 1..1024.  The launches per iteration do not depend on
+ *    n_init; a large source is not walked in cell order (results do not depend on it).
+ * Entry 2, sfmhip_cloud_align_vote, the rules:
+ *  V1 SFMHIP_ERR_ARG: a frame f-11 rule 1 refuses (|up| not 1 within 1e-6, north parallel to up) or with a non-finite offset,
+ *     an option outside its range below or non-finite, handles of different contexts, one handle given twice.
+ *  V2 (e, n, h) per cloud by f-11 rules 2 and 3, float32; d = (f64)h - offset; hmax the largest d over the finite points; a
+ *     point is above the ground iff d >= clear_rel hmax.  A side without an above point or with hmax <= 0: status OK, flag
+ *     bit 0, no candidates.
+ *  V3 the above points in ascending input index, every stride-th kept: stride = ceil(N_above / K).
+ *  V4 tables, by the host: s_k = scale_lo (scale_hi / scale_lo)^(k / (n_scale - 1)), s_0 = scale_lo; cos and sin of 2 pi m / n_yaw.
+ *  V5 hypothesis (k, m) moves source sample i to qe = s (c e - sn n), qn = s (sn e + c n), hq = s d.
+ *  V6 W = window_rel max(e extent, n extent) of the target sample; centre = the midpoint 0.5 (min + max) of the target
+ *     sample's (e, n) box minus that of q's box; lo = centre - W; w = 2 W / bins.
+ *  V7 pair (i, j) votes iff |d_j - hq_i| <= h_tol, in bin floor(((e_j - qe_i) - lo_e) / w) and likewise for n, iff both lie
+ *     in [0, bins).
+ *  V8 a hypothesis's peak: its largest count, the lowest bin id by bins + bx on a tie; without a vote it is dropped.  The
+ *     translation is lo + (b + 0.5) w per axis.
+ *  V9 candidates by (votes descending, k ascending, m ascending), the first n_cand.  In cloud coordinates R = E_t^T (Rz E_s),
+ *     t = E_t^T (te, tn, offset_t - s offset_s), scale = s, E's rows east, north, up; every entry (a0 b0 + a1 b1) + a2 b2.
+ * Entry 3, sfmhip_cloud_align: V1 - V9; the source sample gathered by sfmhip_cloud_select (ground points are left out: a
+ *    plane sliding on a plane pairs everything); entry 1 from the candidates against the whole target with with_scale =
+ *    (n_scale > 1), max_iters = icp_max_iters, max_dist = icp_dist_bins w; the winner is the result with flags == 0 first by
+ *    (pairs descending, mse ascending, candidate index ascending).  None: flag bit 1, the identity.  The caller hands the
+ *    winner's T to sfmhip_cloud_register on the full clouds as init.
+ * Limits: both clouds must be levelled (one dominant ground plane each); near-symmetric plots can tie; the scale range is
+ * the caller's (the ratio of the two hmax is a guess when both clouds show the same tallest tree). */
+typedef struct sfmhip_frame {
+  double up[3], north[3]; /* as sfmhip_ground_result's */
+  double offset;          /* up . p = offset on the ground, cloud units */
+} sfmhip_frame;
+typedef struct sfmhip_align_opts {
+  double scale_lo, scale_hi; /* required: 0 < scale_lo <= scale_hi */
+  double clear_rel;          /* 0.1; 0 <= value < 1 */
+  double h_tol;              /* required: target units, > 0 */
+  double window_rel;         /* 1; > 0 */
+  double icp_dist_bins;      /* 1.25; > 0: entry 3's max_dist in vote bins */
+  int32_t n_scale;           /* 15; 1 ... 64, 1 means scale_lo only */
+  int32_t n_yaw;             /* 72; 1 ... 720 */
+  int32_t bins;              /* 64; 4 ... 128 */
+  int32_t src_samples;       /* 2048; 1 ... 8192 */
+  int32_t tgt_samples;       /* 2048; 1 ... 8192 */
+  int32_t n_cand;            /* 64; 1 ... 1024 */
+  int32_t icp_max_iters;     /* 30; >= 0 */
+  int32_t reserved;
+} sfmhip_align_opts;
+typedef struct sfmhip_align_candidate {
+  sfmhip_transform T; /* source cloud -> target cloud */
+  int32_t votes, k, m, bin;
+} sfmhip_align_candidate;
+typedef struct sfmhip_align_stats {
+  double hmax_src, hmax_tgt; /* NaN for a cloud without a finite point */
+  double w, window;          /* the bin width and W; NaN when flag bit 0 is set */
+  int32_t n_above_src, n_above_tgt, n_src, n_tgt /* sample sizes */, n_hyp /* hypotheses with votes */;
+  int32_t flags; /* 1 EMPTY */
+} sfmhip_align_stats;
+typedef struct sfmhip_align_result {
+  sfmhip_register_result reg;  /* the winner's */
+  sfmhip_align_candidate cand; /* the candidate it started from */
+  int32_t cand_index;          /* its row, -1 none */
+  int32_t n_same;              /* candidates whose ICP reached the winner's transform, byte for byte */
+  int32_t n_cand;
+  int32_t flags; /* 1 EMPTY, 2 NO_WINNER */
+  sfmhip_align_stats stats;
+} sfmhip_align_result;
+void sfmhip_align_default_opts(sfmhip_align_opts* opts);
+/* host only: up, north and offset of a ground result that has a plane (SFMHIP_ERR_ARG otherwise) */
+int sfmhip_frame_from_ground(const sfmhip_ground_result* ground, sfmhip_frame* out);
+/* opts: NULL for the defaults; results: n_init entries; idx: NULL or n_init rows of one entry per source point */
+int sfmhip_cloud_register_batch(sfmhip_cloud* target, sfmhip_cloud* source, const sfmhip_register_opts* opts, const sfmhip_transform* inits,
+                                int n_init, sfmhip_register_result* results, int32_t* idx);
+/* as sfmhip_cloud_register_last_timing, of the last batch with this target; iterations: those of its longest problem */
+int sfmhip_cloud_register_batch_last_timing(sfmhip_cloud* target, double ms3[3], int32_t* iterations);
+/* candidates: room for opts->n_cand; n_out: how many were written */
+int sfmhip_cloud_align_vote(sfmhip_cloud* target, sfmhip_cloud* source, const sfmhip_frame* target_frame, const sfmhip_frame* source_frame,
+                            const sfmhip_align_opts* opts, sfmhip_align_candidate* candidates, int32_t* n_out, sfmhip_align_stats* stats);
+int sfmhip_cloud_align(sfmhip_cloud* target, sfmhip_cloud* source, const sfmhip_frame* target_frame, const sfmhip_frame* source_frame,
+                       const sfmhip_align_opts* opts, sfmhip_align_result* out);
+/* host-clock ms of the last vote or alignment with this target: the vote, the batch ICP (0 after a vote alone), the whole call */
+int sfmhip_cloud_align_last_timing(sfmhip_cloud* target, double ms3[3]);
+
 /* ---- the second half of create_mesh: Poisson surface reconstruction (reference src/Sfm.cpp:1365-1381) ----
  * pcl::Poisson at depth 7 on the cloud and its flipped normals, as a screened Poisson solve on the same device-resident
  * cloud.  The rules (PCL 1.8.1 parity is UNPINNED -- PCL is absent and its solver is an adaptive octree):

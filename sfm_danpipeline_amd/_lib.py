@@ -80,6 +80,8 @@ SYMBOLS = [
     "sfmhip_tracks_triangulate", "sfmhip_tracks_last_timing", "sfmhip_tracks_destroy",
     "sfmhip_register_default_opts", "sfmhip_cloud_nearest", "sfmhip_cloud_register", "sfmhip_cloud_transform", "sfmhip_cloud_concat",
     "sfmhip_cloud_register_last_timing",
+    "sfmhip_align_default_opts", "sfmhip_frame_from_ground", "sfmhip_cloud_register_batch", "sfmhip_cloud_register_batch_last_timing",
+    "sfmhip_cloud_align_vote", "sfmhip_cloud_align", "sfmhip_cloud_align_last_timing",
 ]
 
 _lib = None
@@ -247,6 +249,14 @@ def lib():
         L.sfmhip_cloud_transform.argtypes = [vp, vp, C.POINTER(vp)]
         L.sfmhip_cloud_concat.argtypes = [vp, vp, C.POINTER(vp)]
         L.sfmhip_cloud_register_last_timing.argtypes = [vp, vp, vp]
+        L.sfmhip_align_default_opts.argtypes = [vp]
+        L.sfmhip_align_default_opts.restype = None
+        L.sfmhip_frame_from_ground.argtypes = [vp, vp]
+        L.sfmhip_cloud_register_batch.argtypes = [vp, vp, vp, vp, cint, vp, vp]
+        L.sfmhip_cloud_register_batch_last_timing.argtypes = [vp, vp, vp]
+        L.sfmhip_cloud_align_vote.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+        L.sfmhip_cloud_align.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.sfmhip_cloud_align_last_timing.argtypes = [vp, vp]
         if hasattr(L, "sfmhip_ba_last_solve_profile"):  # (diagnostic builds of older revisions lack it)
             L.sfmhip_ba_last_solve_profile.argtypes = [vp, C.POINTER(BaSolveProfile)]
     _lib = L

@@ -15,7 +15,7 @@ SO = os.path.join(HERE, "libsfmhip.so")
 # and want v_fma_f64 -- "fast-honor-pragmas", not "fast": the one function that must NOT contract, the trust-region decision
 # lm_decide (the same bits on the host and on the device), says so with a pragma, which plain "fast" ignores
 SOURCES = {"context.hip": "off", "match.hip": "off", "triangulate.hip": "off", "incremental.hip": "off",
-           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "cloud_filter.hip": "off", "register.hip": "off", "segment.hip": "off", "poisson.hip": "off", "dendro.hip": "off", "ground.hip": "off", "trees.hip": "off", "tracks.hip": "off", "mvs.hip": "off", "undistort.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
+           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "cloud_filter.hip": "off", "register.hip": "off", "align.hip": "off", "segment.hip": "off", "poisson.hip": "off", "dendro.hip": "off", "ground.hip": "off", "trees.hip": "off", "tracks.hip": "off", "mvs.hip": "off", "undistort.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -185,6 +185,15 @@ def build_registration_demo(force=False):
     return _build_host_exe(os.path.join(HERE, "sfm_registration_selftest"),
                            ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "Segmentation.cpp", "DendrometryE.cpp",
                             "registration_selftest.cpp"), force)
+
+
+def build_align_demo(force=False):
+    """Two reconstructions of one plot in unrelated gauges brought together without a starting guess in the host mirror
+    (computeGroundPlane on each, StructFromMotion::alignPlots, then registerCloud from its result); makes its own plots
+    (needs the GPU)."""
+    return _build_host_exe(os.path.join(HERE, "sfm_align_selftest"),
+                           ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "Segmentation.cpp", "DendrometryE.cpp",
+                            "align_selftest.cpp"), force)
 
 
 def _build_host_exe(exe, files, force, std="c++14"):

@@ -243,6 +243,14 @@ class StructFromMotion {
   double registerCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, const pcl::PointCloud<pcl::PointXYZ>& reference, double* scale_out = nullptr,
                        double max_dist = INFINITY, const sfmhip_transform* guess = nullptr, sfmhip_register_result* result = nullptr);
 
+  // (ours) the starting guess registerCloud needs when `cloud` and `reference` stand in unrelated gauges (two
+  // reconstructions of one plot): each cloud is levelled by its own ground plane (sfmhip_cloud_ground_plane with `ground`, NULL:
+  // the defaults), then sfmhip_cloud_align votes for scale, yaw and shift and runs ICP from every candidate.  `opts` needs
+  // scale_lo, scale_hi and h_tol (sfmhip_align_default_opts sets the rest).  Returns the result's flags (0: result->reg.T is
+  // the `guess` for registerCloud), or -1 when one of the clouds has no ground plane.  Nothing calls it by default.
+  int alignPlots(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, const pcl::PointCloud<pcl::PointXYZ>& reference, const sfmhip_align_opts& opts,
+                 sfmhip_align_result* result, const sfmhip_ground_opts* ground = nullptr);
+
   const std::vector<cv::Mat>& colorImages() const { return mColorImages; }
   const std::vector<cv::Mat>& grayImages() const { return mGrayImages; }
   const std::vector<std::string>& imagePaths() const { return nImagesPath; }

@@ -157,3 +157,26 @@ double StructFromMotion::registerCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& clou
   if (result) *result = res;
   return scale;
 }
+
+int StructFromMotion::alignPlots(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, const pcl::PointCloud<pcl::PointXYZ>& reference,
+                                 const sfmhip_align_opts& opts, sfmhip_align_result* result, const sfmhip_ground_opts* ground) {
+  sfmhip_cloud* ref = nullptr;
+  check(sfmhip_cloud_create(sfm_hip_context(), (int)reference.size(), reference.size() ? &reference.points[0].x : nullptr, &ref),
+        "sfmhip_cloud_create");
+  sfmhip_cloud* src = device_cloud(*cloud);
+  sfmhip_ground_result g[2];
+  sfmhip_frame f[2];
+  sfmhip_ground_opts go;
+  sfmhip_ground_default_opts(&go);
+  if (ground) go = *ground;
+  int rc = sfmhip_cloud_ground_plane(ref, nullptr, 0, &go, nullptr, 0, &g[0]);
+  if (rc == SFMHIP_OK) rc = sfmhip_cloud_ground_plane(src, nullptr, 0, &go, nullptr, 0, &g[1]);
+  const bool planes = rc == SFMHIP_OK && sfmhip_frame_from_ground(&g[0], &f[0]) == SFMHIP_OK && sfmhip_frame_from_ground(&g[1], &f[1]) == SFMHIP_OK;
+  sfmhip_align_result res;
+  if (planes) rc = sfmhip_cloud_align(ref, src, &f[0], &f[1], &opts, &res);
+  sfmhip_cloud_destroy(ref);
+  check(rc, planes ? "sfmhip_cloud_align" : "sfmhip_cloud_ground_plane");
+  if (!planes) return -1;
+  if (result) *result = res;
+  return res.flags;
+}

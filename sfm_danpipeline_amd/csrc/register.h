@@ -77,6 +77,14 @@ SFM_REG_INLINE bool valid_max_dist(double md) { return md > 0.0; }  // (NaN fail
 SFM_REG_INLINE bool valid_opts(const Opts& o) {
   return valid_max_dist(o.max_dist) && o.eps >= 0.0 && o.max_iters >= 0 && o.min_pairs >= 3;
 }
+// f-18's batch of starts: rule 1 for every one of them, 1 .. MAX_BATCH starts (host)
+constexpr int MAX_BATCH = 1024;
+inline bool valid_batch(const Opts& o, const Transform* inits, int n_init) {
+  if (!valid_opts(o) || !inits || n_init < 1 || n_init > MAX_BATCH) return false;
+  for (int b = 0; b < n_init; ++b)
+    if (!valid_transform(inits[b])) return false;
+  return true;
+}
 
 // rule 2: q = (float)(scale ((R x + R y) + R z) + t) in f64; false when the point has no image
 SFM_REG_INLINE bool move(const Transform& T, float x, float y, float z, float q[3]) {
@@ -303,6 +311,33 @@ inline void sum_host(int n_src, Terms terms, double out[Q]) {
   }
 }
 
+// one step of rule 6 on the host: C_k under L.T into idx / d2 (prev: scratch for C_{k-1}), the two sums, the decision
+inline bool iterate_host(const HostGrid& g, const float* tgt, int n_src, const float* src, const Opts& o, float md2, Loop& L,
+                         std::vector<int32_t>& idx, std::vector<int32_t>& prev, std::vector<float>& d2) {
+  prev = idx;
+  nearest_host(g, n_src, src, L.T, md2, false, idx.data(), d2.data());
+  bool changed = false;
+  for (int i = 0; i < n_src; ++i) changed = changed || idx[i] != prev[i];
+  double s1[N1], s2[N2], mu_p[3], mu_m[3];
+  auto pm = [&](int i, float p[3], float m[3]) {
+    const bool paired = idx[i] >= 0;
+    for (int a = 0; a < 3; ++a) p[a] = src[3 * i + a], m[a] = paired ? tgt[3 * (size_t)idx[i] + a] : 0.0f;
+    return paired;
+  };
+  sum_host<N1>(n_src, [&](int i, double* v) {
+    float p[3], m[3];
+    const bool paired = pm(i, p, m);
+    terms1(paired, p, m, v);
+  }, s1);
+  means(s1, mu_p, mu_m);
+  sum_host<N2>(n_src, [&](int i, double* v) {
+    float p[3], m[3];
+    const bool paired = pm(i, p, m);
+    terms2(paired, p, m, d2[i], mu_p, mu_m, v);
+  }, s2);
+  return loop_step(L, o, changed, s1, s2);
+}
+
 // the whole of rule 6; idx (n_src, or NULL) receives the pairs under res.T.  false: rule 1 refuses
 inline bool run_host(int n_tgt, const float* tgt, int n_src, const float* src, const Opts& o, const Transform* init, Result& res, int32_t* idx_out) {
   const Transform T0 = init ? *init : identity();
@@ -314,33 +349,40 @@ inline bool run_host(int n_tgt, const float* tgt, int n_src, const float* src, c
   std::vector<float> d2((size_t)std::max(n_src, 1));
   Loop L;
   loop_init(L, T0);
-  for (;;) {
-    prev = idx;
-    nearest_host(g, n_src, src, L.T, md2, false, idx.data(), d2.data());
-    bool changed = false;
-    for (int i = 0; i < n_src; ++i) changed = changed || idx[i] != prev[i];
-    double s1[N1], s2[N2], mu_p[3], mu_m[3];
-    auto pm = [&](int i, float p[3], float m[3]) {
-      const bool paired = idx[i] >= 0;
-      for (int a = 0; a < 3; ++a) p[a] = src[3 * i + a], m[a] = paired ? tgt[3 * (size_t)idx[i] + a] : 0.0f;
-      return paired;
-    };
-    sum_host<N1>(n_src, [&](int i, double* v) {
-      float p[3], m[3];
-      const bool paired = pm(i, p, m);
-      terms1(paired, p, m, v);
-    }, s1);
-    means(s1, mu_p, mu_m);
-    sum_host<N2>(n_src, [&](int i, double* v) {
-      float p[3], m[3];
-      const bool paired = pm(i, p, m);
-      terms2(paired, p, m, d2[i], mu_p, mu_m, v);
-    }, s2);
-    if (loop_step(L, o, changed, s1, s2)) break;
+  while (!iterate_host(g, tgt, n_src, src, o, md2, L, idx, prev, d2)) {
   }
   res = L.res;
   if (idx_out)
     for (int i = 0; i < n_src; ++i) idx_out[i] = idx[i];
+  return true;
+}
+
+// f-18's batch: n_init starts in one lock-step loop over one grid, a record per problem; a problem that has stopped is left
+// alone.  results[b] and row b of idx_out (n_init x n_src, or NULL) are run_host's from inits[b].  false: refused, nothing
+// written.  `longest` (nullable): the iterations of the problem that ran longest.
+inline bool run_host_batch(int n_tgt, const float* tgt, int n_src, const float* src, const Opts& o, const Transform* inits, int n_init,
+                           Result* results, int32_t* idx_out, int* longest = nullptr) {
+  if (!valid_batch(o, inits, n_init)) return false;
+  HostGrid g;
+  g.build(n_tgt, tgt);
+  const float md2 = max_d2(o.max_dist);
+  const size_t n1 = (size_t)std::max(n_src, 1);
+  std::vector<std::vector<int32_t>> idx((size_t)n_init, std::vector<int32_t>(n1, -2));
+  std::vector<int32_t> prev;
+  std::vector<float> d2(n1);  // (a problem's d2 is read only inside its own step)
+  std::vector<Loop> L((size_t)n_init);
+  for (int b = 0; b < n_init; ++b) loop_init(L[b], inits[b]);
+  for (int round = 0, open = n_init; open > 0 && round <= o.max_iters; ++round)
+    for (int b = 0; b < n_init; ++b)
+      if (!L[b].stop && iterate_host(g, tgt, n_src, src, o, md2, L[b], idx[b], prev, d2)) --open;
+  int most = 0;
+  for (int b = 0; b < n_init; ++b) {
+    results[b] = L[b].res;
+    most = std::max(most, (int)L[b].res.iterations);
+    if (idx_out)
+      for (int i = 0; i < n_src; ++i) idx_out[(size_t)b * n_src + i] = idx[b][i];
+  }
+  if (longest) *longest = most;
   return true;
 }
 

@@ -14,6 +14,11 @@
 // fold the partials in ascending order, a lane per sum; reg_update's lane 0 then takes rule 6's decision (loop_step) and
 // writes the next transform.  The host reads the loop's record once per iteration; no n-sized array crosses the bus
 // inside the loop.  No atomics, no spins, no hand-offs between workgroups: the "pairs changed" flag is a plain store of 1.
+//
+// The batch (f-18, sfmhip_cloud_register_batch): the same kernels with the problem as grid dimension y.  Problem b owns record
+// b, row b of idx / d2 and slab b of the partials; a workgroup whose problem has stopped reads the stop flag and returns, so
+// a stopped problem's row stays the pairs under its result.  A single call is a batch of one whose record never reads
+// "stopped" at a launch.  The host reads the block of records once per iteration and leaves when all have stopped.
 #include "common.h"
 #include "cloud.h"
 #include "cloud_grid.h"
@@ -21,6 +26,7 @@
 #include "register.h"
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 using namespace sfmgrid;
 using sfmreg::Loop;
@@ -50,6 +56,8 @@ struct RegState {  // on the TARGET handle, freed with it
   Grow<DevLoop> rec;
   double ms[3] = {0, 0, 0};  // search, sums, update of the last register call
   int iterations = 0;
+  double batch_ms[3] = {0, 0, 0};  // the same of the last batch call
+  int batch_iterations = 0;        // ... of its longest problem
 };
 
 __device__ __forceinline__ void scan_best(const GridDev& g, int row, int xa, int xb, const float4& q, float& bd, int& bi) {
@@ -78,15 +86,21 @@ __global__ void reg_keys(GridDev g, const float* src, int n_src, const Transform
   vals[i] = i;
 }
 
-// rules 2 + 3.  order: NULL, or the source index of every lane (results do not depend on it).  T: the transform (the loop's
-// record, or one uploaded for sfmhip_cloud_nearest).  exact: search until the nearest is known also beyond md2 (sfmhip_cloud_nearest: a rejected pair keeps its d2); else a lane with nothing within
-// md2 in reach leaves once the bound exceeds max_dist.  changed: raised when an index differs from the array's old entry.
+// rules 2 + 3 for problem blockIdx.y.  order: NULL, or the source index of every lane (results do not depend on it).  rec: the
+// records, one per problem; the transform is the record's (the loop's, or the one sfmhip_cloud_nearest uploaded into it), and
+// a problem whose record says "stopped" is left as it is.  row: the length of a problem's row of idx / d2.  exact: search
+// until the nearest is known also beyond md2 (sfmhip_cloud_nearest: a rejected pair keeps its d2); else a lane with nothing
+// within md2 in reach leaves once the bound exceeds max_dist.  track: raise the record's "changed" when an index differs from
+// the row's old entry.
 __global__ __launch_bounds__(NEAR_BLOCK) void reg_nearest(GridDev g, double abs_eps, const float* src, int n_src, const int* order,
-                                                         const Transform* Tp, float md2, int exact, int* idx, float* d2, int32_t* changed) {
+                                                         DevLoop* rec, size_t row, float md2, int exact, int* idx, float* d2, int track) {
   const int l = blockIdx.x * NEAR_BLOCK + threadIdx.x;
-  if (l >= n_src) return;
+  rec += blockIdx.y;
+  if (l >= n_src || rec->L.stop) return;
+  idx += row * blockIdx.y, d2 += row * blockIdx.y;
+  int32_t* changed = track ? &rec->changed : nullptr;
   const int i = order ? order[l] : l;
-  const Transform T = *Tp;
+  const Transform T = rec->L.T;
   float qv[3];
   const bool ok = sfmreg::move(T, src[3 * (size_t)i], src[3 * (size_t)i + 1], src[3 * (size_t)i + 2], qv);
   float bd = sfmcloud::bits_f(0x7F800000u);
@@ -136,8 +150,11 @@ __device__ __forceinline__ bool load_pair(const float* src, const float* tgt, co
   return paired;
 }
 
-__global__ __launch_bounds__(SUM_BLOCK) void reg_sums1(const float* src, const float* tgt, const int* idx, int n_src, double* part) {
+__global__ __launch_bounds__(SUM_BLOCK) void reg_sums1(const float* src, const float* tgt, const int* idx, int n_src, const DevLoop* rec,
+                                                      size_t row, double* part) {
   __shared__ double sh[N1][4];
+  if (rec[blockIdx.y].L.stop) return;  // (uniform over the workgroup)
+  idx += row * blockIdx.y, part += (size_t)gridDim.x * N1 * blockIdx.y;
   const int i = blockIdx.x * SUM_BLOCK + threadIdx.x;
   float p[3], m[3];
   const bool paired = load_pair(src, tgt, idx, i, n_src, p, m);
@@ -154,6 +171,8 @@ __global__ __launch_bounds__(SUM_BLOCK) void reg_sums1(const float* src, const f
 // the partials of pass 1 in ascending block order, a lane per sum; then the means
 __global__ __launch_bounds__(64) void reg_means(const double* part, int n_blocks, DevLoop* rec) {
   const int k = threadIdx.x;
+  rec += blockIdx.x, part += (size_t)n_blocks * N1 * blockIdx.x;
+  if (rec->L.stop) return;
   if (k < N1) {
     double s = 0.0;
     for (int b = 0; b < n_blocks; ++b) s = s + part[(size_t)b * N1 + k];
@@ -164,8 +183,11 @@ __global__ __launch_bounds__(64) void reg_means(const double* part, int n_blocks
 }
 
 __global__ __launch_bounds__(SUM_BLOCK) void reg_sums2(const float* src, const float* tgt, const int* idx, const float* d2, int n_src,
-                                                      const DevLoop* rec, double* part) {
+                                                      const DevLoop* rec, size_t row, double* part) {
   __shared__ double sh[N2][4];
+  rec += blockIdx.y;
+  if (rec->L.stop) return;  // (uniform over the workgroup)
+  idx += row * blockIdx.y, d2 += row * blockIdx.y, part += (size_t)gridDim.x * N2 * blockIdx.y;
   const int i = blockIdx.x * SUM_BLOCK + threadIdx.x;
   float p[3], m[3];
   const bool paired = load_pair(src, tgt, idx, i, n_src, p, m);
@@ -185,6 +207,8 @@ __global__ __launch_bounds__(SUM_BLOCK) void reg_sums2(const float* src, const f
 __global__ __launch_bounds__(64) void reg_update(const double* part, int n_blocks, Opts o, DevLoop* rec) {
   __shared__ double s2[N2];
   const int k = threadIdx.x;
+  rec += blockIdx.x, part += (size_t)n_blocks * N2 * blockIdx.x;
+  if (rec->L.stop) return;
   if (k < N2) {
     double s = 0.0;
     for (int b = 0; b < n_blocks; ++b) s = s + part[(size_t)b * N2 + k];
@@ -211,15 +235,15 @@ __global__ void reg_transform(const float* xyz, int n, Transform T, float* out) 
   out[3 * (size_t)i + 2] = f ? q[2] : z;
 }
 
-int prepare(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState** state) {
+int prepare(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState** state, int n_init = 1) {
   SFM_HIP_TRY(hipSetDevice(tgt->ctx->device));
   RegState* s = stage<RegState>(tgt);
-  const size_t n1 = (size_t)std::max(src->n, 1), nb = blocks(n1, SUM_BLOCK);
-  SFM_TRY(s->idx.need(n1));
-  SFM_TRY(s->d2.need(n1));
-  SFM_TRY(s->part1.need(nb * N1));
-  SFM_TRY(s->part2.need(nb * N2));
-  SFM_TRY(s->rec.need(1));
+  const size_t n1 = (size_t)std::max(src->n, 1), nb = blocks(n1, SUM_BLOCK), B = (size_t)n_init;
+  SFM_TRY(s->idx.need(B * n1));
+  SFM_TRY(s->d2.need(B * n1));
+  SFM_TRY(s->part1.need(B * nb * N1));
+  SFM_TRY(s->part2.need(B * nb * N2));
+  SFM_TRY(s->rec.need(B));
   if (tgt->n_valid > 0) SFM_TRY(knn_grid(tgt));
   *state = s;
   return SFMHIP_OK;
@@ -244,13 +268,42 @@ int sort_source(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, const Transfo
   return SFMHIP_OK;
 }
 
-void launch_nearest(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, const int* order, const Transform* d_T, float md2, bool exact,
-                    int32_t* d_changed) {
+void launch_nearest(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, const int* order, float md2, bool exact, bool track, int n_init = 1) {
   if (src->n == 0) return;
   GridDev g = tgt->kg.dev(tgt->n_valid);  // (never dereferenced without a finite target point)
   const double eps = tgt->n_valid > 0 ? knn_abs_eps(tgt) : 0.0;
-  hipLaunchKernelGGL(reg_nearest, dim3(blocks(src->n, NEAR_BLOCK)), dim3(NEAR_BLOCK), 0, tgt->ctx->stream, g, eps, src->xyz, src->n, order,
-                     d_T, md2, exact ? 1 : 0, s->idx.p, s->d2.p, d_changed);
+  hipLaunchKernelGGL(reg_nearest, dim3(blocks(src->n, NEAR_BLOCK), n_init), dim3(NEAR_BLOCK), 0, tgt->ctx->stream, g, eps, src->xyz, src->n,
+                     order, s->rec.p, (size_t)src->n, md2, exact ? 1 : 0, s->idx.p, s->d2.p, track ? 1 : 0);
+}
+
+// one iteration of rule 6 for n_init problems: the search, the two sums, the step.  t (nullable): host-clock ms added to
+// search / sums / update, a stream synchronisation between them; else the launches only
+int launch_iteration(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, const int* order, const Opts& o, float md2, int n_init, double* t) {
+  hipStream_t st = tgt->ctx->stream;
+  const int n = src->n, nb = (int)blocks(n, SUM_BLOCK);
+  const size_t row = (size_t)n;
+  DevLoop* rec = s->rec.p;
+  double t0 = 0, t1 = 0, t2 = 0;
+  if (t) t0 = sfm_now_ms();
+  launch_nearest(tgt, src, s, order, md2, false, true, n_init);
+  SFM_HIP_TRY(hipGetLastError());
+  if (t) {
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+    t1 = sfm_now_ms();
+  }
+  if (nb > 0) hipLaunchKernelGGL(reg_sums1, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, s->idx.p, n, rec, row, s->part1.p);
+  hipLaunchKernelGGL(reg_means, dim3(n_init), dim3(64), 0, st, s->part1.p, nb, rec);
+  if (nb > 0)
+    hipLaunchKernelGGL(reg_sums2, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, s->idx.p, s->d2.p, n, rec, row, s->part2.p);
+  SFM_HIP_TRY(hipGetLastError());
+  if (t) {
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+    t2 = sfm_now_ms();
+  }
+  hipLaunchKernelGGL(reg_update, dim3(n_init), dim3(64), 0, st, s->part2.p, nb, o, rec);
+  SFM_HIP_TRY(hipGetLastError());
+  if (t) t[0] += t1 - t0, t[1] += t2 - t1, t[2] -= t2;  // (the caller adds the clock after the record's read)
+  return SFMHIP_OK;
 }
 
 }  // namespace
@@ -272,7 +325,7 @@ extern "C" int sfmhip_cloud_nearest(sfmhip_cloud* tgt, sfmhip_cloud* src, const 
   SFM_HIP_TRY(hipMemcpyAsync(&s->rec.p->L, &L, sizeof L, hipMemcpyHostToDevice, st));
   const int* order = nullptr;
   SFM_TRY(sort_source(tgt, src, s, &s->rec.p->L.T, &order));
-  launch_nearest(tgt, src, s, order, &s->rec.p->L.T, sfmreg::max_d2(max_dist), true, nullptr);
+  launch_nearest(tgt, src, s, order, sfmreg::max_d2(max_dist), true, false);
   SFM_HIP_TRY(hipGetLastError());
   SFM_HIP_TRY(hipMemcpyAsync(idx, s->idx.p, sizeof(int) * (size_t)src->n, hipMemcpyDeviceToHost, st));
   SFM_HIP_TRY(hipMemcpyAsync(d2, s->d2.p, sizeof(float) * (size_t)src->n, hipMemcpyDeviceToHost, st));
@@ -290,7 +343,7 @@ extern "C" int sfmhip_cloud_register(sfmhip_cloud* tgt, sfmhip_cloud* src, const
   SFM_TRY(prepare(tgt, src, &s));
   hipStream_t st = tgt->ctx->stream;
   const bool timing = tgt->ctx->timing;
-  const int n = src->n, nb = (int)blocks(n, SUM_BLOCK);
+  const int n = src->n;
   const float md2 = sfmreg::max_d2(o.max_dist);
   s->ms[0] = s->ms[1] = s->ms[2] = 0;
   s->iterations = 0;
@@ -308,27 +361,10 @@ extern "C" int sfmhip_cloud_register(sfmhip_cloud* tgt, sfmhip_cloud* src, const
     s->ms[0] = sfm_now_ms() - ts;  // (the source's cell order counts as search)
   }
   for (;;) {
-    double t0 = 0, t1 = 0, t2 = 0;
-    if (timing) t0 = sfm_now_ms();
-    launch_nearest(tgt, src, s, order, &rec->L.T, md2, false, &rec->changed);
-    SFM_HIP_TRY(hipGetLastError());
-    if (timing) {
-      SFM_HIP_TRY(hipStreamSynchronize(st));
-      t1 = sfm_now_ms();
-    }
-    if (nb > 0) hipLaunchKernelGGL(reg_sums1, dim3(nb), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, s->idx.p, n, s->part1.p);
-    hipLaunchKernelGGL(reg_means, dim3(1), dim3(64), 0, st, s->part1.p, nb, rec);
-    if (nb > 0) hipLaunchKernelGGL(reg_sums2, dim3(nb), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, s->idx.p, s->d2.p, n, rec, s->part2.p);
-    SFM_HIP_TRY(hipGetLastError());
-    if (timing) {
-      SFM_HIP_TRY(hipStreamSynchronize(st));
-      t2 = sfm_now_ms();
-    }
-    hipLaunchKernelGGL(reg_update, dim3(1), dim3(64), 0, st, s->part2.p, nb, o, rec);
-    SFM_HIP_TRY(hipGetLastError());
+    SFM_TRY(launch_iteration(tgt, src, s, order, o, md2, 1, timing ? s->ms : nullptr));
     SFM_HIP_TRY(hipMemcpyAsync(&h.L, &rec->L, sizeof h.L, hipMemcpyDeviceToHost, st));  // the one small record of the iteration
     SFM_HIP_TRY(hipStreamSynchronize(st));
-    if (timing) s->ms[0] += t1 - t0, s->ms[1] += t2 - t1, s->ms[2] += sfm_now_ms() - t2;
+    if (timing) s->ms[2] += sfm_now_ms();
     if (h.L.stop) break;
     if (h.L.k < 0 || h.L.k > o.max_iters) return SFMHIP_ERR_STATE;
   }
@@ -337,6 +373,51 @@ extern "C" int sfmhip_cloud_register(sfmhip_cloud* tgt, sfmhip_cloud* src, const
   if (idx && n > 0) {
     SFM_HIP_TRY(hipMemcpyAsync(idx, s->idx.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
     SFM_HIP_TRY(hipStreamSynchronize(st));
+  }
+  return SFMHIP_OK;
+}
+
+extern "C" int sfmhip_cloud_register_batch(sfmhip_cloud* tgt, sfmhip_cloud* src, const sfmhip_register_opts* opts, const sfmhip_transform* inits,
+                                           int n_init, sfmhip_register_result* out, int32_t* idx) {
+  if (!tgt || !src || !out || !inits || tgt->ctx != src->ctx) return SFMHIP_ERR_ARG;
+  const Opts o = opts ? mirror<Opts>(*opts) : sfmreg::default_opts();
+  static_assert(sizeof(sfmhip_transform) == sizeof(Transform) && sizeof(sfmhip_register_result) == sizeof(Result), "the C ABI mirrors register.h");
+  if (!sfmreg::valid_batch(o, (const Transform*)inits, n_init)) return SFMHIP_ERR_ARG;
+  RegState* s = nullptr;
+  SFM_TRY(prepare(tgt, src, &s, n_init));
+  hipStream_t st = tgt->ctx->stream;
+  const bool timing = tgt->ctx->timing;
+  const int n = src->n;
+  const float md2 = sfmreg::max_d2(o.max_dist);
+  s->batch_ms[0] = s->batch_ms[1] = s->batch_ms[2] = 0;
+  s->batch_iterations = 0;
+  std::vector<DevLoop> h((size_t)n_init);
+  memset(h.data(), 0, sizeof(DevLoop) * h.size());
+  for (int b = 0; b < n_init; ++b) sfmreg::loop_init(h[b].L, mirror<Transform>(inits[b]));
+  DevLoop* rec = s->rec.p;
+  SFM_HIP_TRY(hipMemcpyAsync(rec, h.data(), sizeof(DevLoop) * h.size(), hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemsetAsync(s->idx.p, 0xFE, sizeof(int) * (size_t)n_init * std::max(n, 1), st));  // (no index: C_0 differs from it)
+  // (no cell order per problem: each start would need a sort of its own, and results do not depend on it)
+  for (int round = 0;; ++round) {
+    SFM_TRY(launch_iteration(tgt, src, s, nullptr, o, md2, n_init, timing ? s->batch_ms : nullptr));
+    SFM_HIP_TRY(hipMemcpyAsync(h.data(), rec, sizeof(DevLoop) * h.size(), hipMemcpyDeviceToHost, st));  // the block of records, once
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+    if (timing) s->batch_ms[2] += sfm_now_ms();
+    bool all = true;
+    for (int b = 0; b < n_init; ++b) {
+      if (h[b].L.k < 0 || h[b].L.k > o.max_iters) return SFMHIP_ERR_STATE;
+      all = all && h[b].L.stop;
+    }
+    if (all) break;
+    if (round >= o.max_iters) return SFMHIP_ERR_STATE;  // (a problem stops at k == max_iters at the latest)
+  }
+  if (idx && n > 0) {  // (n > 0: the rows are n apart on the device too)
+    SFM_HIP_TRY(hipMemcpyAsync(idx, s->idx.p, sizeof(int) * (size_t)n_init * n, hipMemcpyDeviceToHost, st));
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+  }
+  for (int b = 0; b < n_init; ++b) {
+    out[b] = mirror<sfmhip_register_result>(h[b].L.res);
+    s->batch_iterations = std::max(s->batch_iterations, (int)h[b].L.res.iterations);
   }
   return SFMHIP_OK;
 }
@@ -386,5 +467,13 @@ extern "C" int sfmhip_cloud_register_last_timing(sfmhip_cloud* tgt, double ms3[3
   const RegState* s = stage<RegState>(tgt);
   for (int i = 0; i < 3; ++i) ms3[i] = s->ms[i];
   if (iterations) *iterations = s->iterations;
+  return SFMHIP_OK;
+}
+
+extern "C" int sfmhip_cloud_register_batch_last_timing(sfmhip_cloud* tgt, double ms3[3], int32_t* iterations) {
+  if (!tgt || !ms3) return SFMHIP_ERR_ARG;
+  const RegState* s = stage<RegState>(tgt);
+  for (int i = 0; i < 3; ++i) ms3[i] = s->batch_ms[i];
+  if (iterations) *iterations = s->batch_iterations;
   return SFMHIP_OK;
 }

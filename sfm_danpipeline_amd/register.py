@@ -6,7 +6,13 @@ dendrometry takes comes from.
 `nearest(target, source, T, max_dist)` returns (idx, d2) per source point; `icp(target, source, init, **opts)` a
 RegisterResult (T, iterations, pairs, converged, flags, mse; with return_pairs also the idx array); `transform(cloud, T)` and
 `concat(a, b)` new Clouds born on the device.  `Transform` carries x -> scale R x + t with host-only helpers (matrix, inverse,
-compose).  Parity with PCL is UNPINNED."""
+compose).  Parity with PCL is UNPINNED.
+
+The coarse alignment needs no `init`: `icp_batch(target, source, inits, **opts)` runs many starts in one
+lock-step loop (each result is `icp`'s from that start, byte for byte), `align_vote(target, source, target_frame,
+source_frame, **opts)` lists candidate poses of two levelled clouds by a height-keyed vote, `align(...)` runs the batch from
+them and returns the winner, whose `.reg.T` is the `init` for `icp` on the full clouds.  `Frame.from_ground(result)` makes
+a frame of a ground-plane result; `scale_guess(stats)` is the ratio of the two clouds' heights."""
 import ctypes as C
 import math
 
@@ -135,6 +141,113 @@ def concat(a, b):
     h = C.c_void_p()
     _lib.check(_lib.lib().sfmhip_cloud_concat(a.h, b.h, C.byref(h)), "sfmhip_cloud_concat")
     return Cloud.from_handle(h, a.ctx)
+
+
+# ---------------------------------------------------------------- the coarse alignment (f-18)
+EMPTY, NO_WINNER = 1, 2                      # bits of AlignResult.flags (AlignStats.flags: EMPTY only)
+
+
+class Frame(C.Structure):
+    """A levelled frame: the ground plane's up, north and offset (up . p = offset on the ground)."""
+    _fields_ = [("up", C.c_double * 3), ("north", C.c_double * 3), ("offset", C.c_double)]
+
+    @classmethod
+    def make(cls, up=(0, 0, 1), north=(0, 1, 0), offset=0.0):
+        f = cls()
+        f.up, f.north, f.offset = (C.c_double * 3)(*up), (C.c_double * 3)(*north), float(offset)
+        return f
+
+    @classmethod
+    def from_ground(cls, ground):
+        """Of a GroundResult that has a plane (sfmhip_frame_from_ground)."""
+        f = cls()
+        _lib.check(_lib.lib().sfmhip_frame_from_ground(C.byref(ground), C.byref(f)), "sfmhip_frame_from_ground")
+        return f
+
+
+class AlignOpts(C.Structure):
+    _fields_ = [("scale_lo", C.c_double), ("scale_hi", C.c_double), ("clear_rel", C.c_double), ("h_tol", C.c_double),
+                ("window_rel", C.c_double), ("icp_dist_bins", C.c_double), ("n_scale", C.c_int32), ("n_yaw", C.c_int32),
+                ("bins", C.c_int32), ("src_samples", C.c_int32), ("tgt_samples", C.c_int32), ("n_cand", C.c_int32),
+                ("icp_max_iters", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AlignCandidate(C.Structure):
+    _fields_ = [("T", Transform), ("votes", C.c_int32), ("k", C.c_int32), ("m", C.c_int32), ("bin", C.c_int32)]
+
+
+class AlignStats(C.Structure):
+    _fields_ = [("hmax_src", C.c_double), ("hmax_tgt", C.c_double), ("w", C.c_double), ("window", C.c_double),
+                ("n_above_src", C.c_int32), ("n_above_tgt", C.c_int32), ("n_src", C.c_int32), ("n_tgt", C.c_int32),
+                ("n_hyp", C.c_int32), ("flags", C.c_int32)]
+
+
+class AlignResult(C.Structure):
+    _fields_ = [("reg", RegisterResult), ("cand", AlignCandidate), ("cand_index", C.c_int32), ("n_same", C.c_int32),
+                ("n_cand", C.c_int32), ("flags", C.c_int32), ("stats", AlignStats)]
+
+
+def align_default_opts(**kw):
+    """The table of f-18 rule V1; scale_lo, scale_hi and h_tol have no default and must be given."""
+    o = AlignOpts()
+    _lib.lib().sfmhip_align_default_opts(C.byref(o))
+    return set_opts(o, **kw)
+
+
+def icp_batch(target, source, inits, return_pairs=False, opts=None, **kw):
+    """A list of RegisterResult, one per Transform of `inits`: what `icp` returns from that start, from one lock-step loop
+    (with return_pairs each carries its idx row)."""
+    o = set_opts(opts, **kw) if opts is not None else default_opts(**kw)
+    n = len(inits)
+    starts = (Transform * max(n, 1))(*inits)
+    res = (RegisterResult * max(n, 1))()
+    idx = np.empty((max(n, 1), max(source.n, 1)), np.int32) if return_pairs else None   # (rows of source.n entries when it is > 0)
+    _lib.check(_lib.lib().sfmhip_cloud_register_batch(target.h, source.h, C.byref(o), starts, n, res,
+                                                      None if idx is None else idx.ctypes.data), "sfmhip_cloud_register_batch")
+    out = []
+    for b in range(n):
+        r = RegisterResult.from_buffer_copy(res[b])
+        if return_pairs:
+            r.idx = idx[b, :source.n].copy()
+        out.append(r)
+    return out
+
+
+def align_vote(target, source, target_frame, source_frame, opts=None, **kw):
+    """(candidates, stats): the first n_cand poses of the vote as AlignCandidate, best first, and the AlignStats."""
+    o = set_opts(opts, **kw) if opts is not None else align_default_opts(**kw)
+    cands, n, stats = (AlignCandidate * max(int(o.n_cand), 1))(), C.c_int32(0), AlignStats()
+    _lib.check(_lib.lib().sfmhip_cloud_align_vote(target.h, source.h, C.byref(target_frame), C.byref(source_frame), C.byref(o), cands,
+                                                  C.byref(n), C.byref(stats)), "sfmhip_cloud_align_vote")
+    return [AlignCandidate.from_buffer_copy(cands[i]) for i in range(n.value)], stats
+
+
+def align(target, source, target_frame, source_frame, opts=None, **kw):
+    """AlignResult: the vote, ICP from every candidate, the winner (reg.T: the `init` for `icp` on the full clouds)."""
+    o = set_opts(opts, **kw) if opts is not None else align_default_opts(**kw)
+    out = AlignResult()
+    _lib.check(_lib.lib().sfmhip_cloud_align(target.h, source.h, C.byref(target_frame), C.byref(source_frame), C.byref(o), C.byref(out)),
+               "sfmhip_cloud_align")
+    return out
+
+
+def scale_guess(stats):
+    """hmax of the target over hmax of the source: the scale when both clouds show the same tallest point above their ground."""
+    return stats.hmax_tgt / stats.hmax_src
+
+
+def align_last_timing(target):
+    """Host-clock ms of the last align_vote / align with this target: vote, batch ICP, the whole call."""
+    ms = (C.c_double * 3)()
+    _lib.check(_lib.lib().sfmhip_cloud_align_last_timing(target.h, ms), "sfmhip_cloud_align_last_timing")
+    return dict(vote=ms[0], icp=ms[1], total=ms[2])
+
+
+def batch_last_timing(target):
+    """As last_timing, of the last icp_batch with this target; iterations: those of its longest problem."""
+    ms, it = (C.c_double * 3)(), C.c_int32(0)
+    _lib.check(_lib.lib().sfmhip_cloud_register_batch_last_timing(target.h, ms, C.byref(it)), "sfmhip_cloud_register_batch_last_timing")
+    return dict(search=ms[0], sums=ms[1], update=ms[2], iterations=it.value)
 
 
 def last_timing(target):
