@@ -1266,6 +1266,59 @@ int sfmhip_tracks_triangulate(sfmhip_tracks* tracks, const double* poses, const 
 int sfmhip_tracks_last_timing(const sfmhip_tracks* tracks, double seconds[SFMHIP_TRACKS_STAGES]);
 void sfmhip_tracks_destroy(sfmhip_tracks* tracks);
 
+/* ---- two-view verification of match lists before the tracks (PARITY UNPINNED, as for the score entries: the
+ * reference hands its ratio-test lists on unfiltered) ----
+ * A handle holds, on the device, one set of pair lists after the verification, in a match plan's layout (`stride` slots per
+ * pair, entries in list order, counts[n_pairs]), so that the tracks builder reads it unchanged.
+ *   V1. For pair p = (a, b), match i has the pixel of image a's feature match_q[i] on the left and of image b's feature
+ *       match_t[i] on the right, in list order; image v's feature f at xy[2 (xy_ptr[v] + f)], as sfmhip_tracks_triangulate
+ *       takes them.  Both are normalised as findEssentialMat does, x * (1 / fx) + (-cx * (1 / fx)) and likewise y, by the kernel
+ *       that gathers them from the lists where they lie; no pixel is stored per match.  xy is uploaded once per call.
+ *   V2. The model of a pair is sfmhip_score_essential's RANSAC, unchanged (sample streams per count, chunks, keep rule,
+ *       iteration limit), started from the gathered points.  The host reads the n_pairs counts once.
+ *   V3. The mask of a match: 0 without a model, 1 for every match of a pair of exactly five with a model, else the RANSAC's
+ *       inlier test under the pair's best E -- the mask sfmhip_score_essential returns.
+ *   V4. kept[p] = the pair has a model and inliers[p] >= min_inliers.  A pair that is not kept has output count 0; inliers,
+ *       iterations and E (9 per pair, zero without a model) are reported for every pair.
+ *   V5. A kept pair's output list is its matches with a non-zero mask in their input order; its count equals inliers[p].  The
+ *       input lists are not written.
+ *   V6. SFMHIP_ERR_ARG, *out not written: a match index < 0 or >= its image's n_feat, or a pair naming an image outside
+ *       [0, n_images) or the same image twice (checked on the device, by a flag, before the RANSAC); a negative count or one
+ *       above the stride; more than 2^31 - 2 matches; a negative xy_ptr[0], a decreasing xy_ptr, an image with
+ *       xy_ptr[v + 1] - xy_ptr[v] < n_feat[v]; prob outside (0, 1); NULL K or xy_ptr; NULL xy with any match present.
+ *       n_pairs = 0, counts all 0, pairs of fewer than five matches: SFMHIP_OK, an empty set.
+ * sfmhip_score_last_flags(ctx) reports the five-point corner flags of the call, as for sfmhip_score_essential.
+ * stats: pairs; of those the kept ones; those without a model; the matches given; the matches kept. */
+typedef struct sfmhip_verified sfmhip_verified;
+typedef struct sfmhip_verify_opts {
+  double prob;         /* 0.999: findEssentialMat's, as findBestPair calls it */
+  double threshold;    /* 1.0 px */
+  int32_t min_inliers; /* 15: a pair with fewer RANSAC inliers keeps no match (policy, the caller's to change) */
+  int32_t reserved;
+} sfmhip_verify_opts;
+typedef struct sfmhip_verify_stats {
+  int64_t pairs, pairs_kept, pairs_no_model, matches_in, matches_out;
+} sfmhip_verify_stats;
+void sfmhip_verify_default_opts(sfmhip_verify_opts* opts);
+/* the lists of the plan's last run, read where they lie on the device; n_feat = the image set's row counts.  opts: NULL = defaults */
+int sfmhip_matchplan_verify(sfmhip_matchplan* plan, const int32_t* xy_ptr, const double* xy, const double K[9],
+                            const sfmhip_verify_opts* opts, sfmhip_verified** out);
+/* host lists in sfmhip_matchplan_fetch's layout.  The same bytes as sfmhip_matchplan_verify on a plan that holds them. */
+int sfmhip_verify_lists(sfmhip_ctx* ctx, int n_images, const int32_t* n_feat, int n_pairs, const int32_t* pairs, const int32_t* counts,
+                        const int32_t* match_q, const int32_t* match_t, const int32_t* xy_ptr, const double* xy, const double K[9],
+                        const sfmhip_verify_opts* opts, sfmhip_verified** out);
+int sfmhip_verified_counts(const sfmhip_verified* verified, sfmhip_verify_stats* stats);
+/* Every output may be NULL: counts, inliers, iterations and kept n_pairs; match_q / match_t packed pair after pair
+ * (stats.matches_out entries); E 9 n_pairs. */
+int sfmhip_verified_download(const sfmhip_verified* verified, int32_t* counts, int32_t* match_q, int32_t* match_t, int32_t* inliers,
+                             int32_t* iterations, double* E, uint8_t* kept);
+/* the tracks of the verified lists, read where they lie on the device: the same bytes as sfmhip_tracks_build on the download */
+int sfmhip_tracks_build_from_verified(const sfmhip_verified* verified, const sfmhip_tracks_opts* opts, sfmhip_tracks** out);
+/* seconds of the call that made the handle, by the host's clock between its stream synchronisations: uploads + gather, the
+ * RANSAC, the compaction, and the whole call */
+int sfmhip_verified_last_timing(const sfmhip_verified* verified, double seconds[4]);
+void sfmhip_verified_destroy(sfmhip_verified* verified);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,8 @@ SYMBOLS = [
     "sfmhip_cloud_register_last_timing",
     "sfmhip_align_default_opts", "sfmhip_frame_from_ground", "sfmhip_cloud_register_batch", "sfmhip_cloud_register_batch_last_timing",
     "sfmhip_cloud_align_vote", "sfmhip_cloud_align", "sfmhip_cloud_align_last_timing",
+    "sfmhip_verify_default_opts", "sfmhip_matchplan_verify", "sfmhip_verify_lists", "sfmhip_verified_counts", "sfmhip_verified_download",
+    "sfmhip_tracks_build_from_verified", "sfmhip_verified_last_timing", "sfmhip_verified_destroy",
 ]
 
 _lib = None
@@ -257,6 +259,16 @@ def lib():
         L.sfmhip_cloud_align_vote.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
         L.sfmhip_cloud_align.argtypes = [vp, vp, vp, vp, vp, vp]
         L.sfmhip_cloud_align_last_timing.argtypes = [vp, vp]
+        L.sfmhip_verify_default_opts.argtypes = [vp]
+        L.sfmhip_verify_default_opts.restype = None
+        L.sfmhip_matchplan_verify.argtypes = [vp, vp, vp, vp, vp, C.POINTER(vp)]
+        L.sfmhip_verify_lists.argtypes = [vp, cint, vp, cint, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+        L.sfmhip_verified_counts.argtypes = [vp, vp]
+        L.sfmhip_verified_download.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+        L.sfmhip_tracks_build_from_verified.argtypes = [vp, vp, C.POINTER(vp)]
+        L.sfmhip_verified_last_timing.argtypes = [vp, vp]
+        L.sfmhip_verified_destroy.argtypes = [vp]
+        L.sfmhip_verified_destroy.restype = None
         if hasattr(L, "sfmhip_ba_last_solve_profile"):  # (diagnostic builds of older revisions lack it)
             L.sfmhip_ba_last_solve_profile.argtypes = [vp, C.POINTER(BaSolveProfile)]
     _lib = L

@@ -132,6 +132,8 @@ struct sfm_matchplan_lists {
   const int *pairs, *counts, *q, *t;
 };
 int sfm_matchplan_device_lists(sfmhip_matchplan* pl, sfm_matchplan_lists* out);
+// The same view of a verified match set (verify.hip): its own lists, valid as long as the handle.
+int sfm_verified_device_lists(const sfmhip_verified* v, sfm_matchplan_lists* out);
 
 static inline double sfm_now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();

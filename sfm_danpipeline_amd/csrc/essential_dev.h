@@ -23,3 +23,9 @@ struct EssentialDev {
 int sfm_essential_ransac(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, const double* left_xy, const double* right_xy,
                          double fx, double fy, double cx, double cy, double prob, double threshold, int32_t* inliers,
                          int32_t* iterations, bool want_mask, EssentialDev& dev);
+
+// The same from normalised points already on the device: the caller has allocated dev.d_p1 / dev.d_p2 from dev.bufs
+// (2 doubles per match, at least one match's worth) and filled them on ctx->stream (verify.hip gathers them from the match
+// lists).  d_left / d_right stay null.  sfm_essential_ransac is its upload and normalisation followed by this.
+int sfm_essential_ransac_points(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, double fx, double fy, double prob,
+                                double threshold, int32_t* inliers, int32_t* iterations, bool want_mask, EssentialDev& dev);

@@ -142,7 +142,11 @@ class StructFromMotion {
   // >= max(2, minViews) views, one DLT point per track over nCameraPoses (6 px, as triangulateViews).  REPLACES
   // nReconstructionCloud by one Point3D per kept track with every view in idxImage / pt2D and returns the number of points;
   // on a device error the cloud stays as it is.  Nothing calls it by default.
-  size_t consolidateTracks(int minViews = 2);
+  // verify: the lists first pass the two-view verification (sfmhip_matchplan_verify on the resident route, sfmhip_verify_lists
+  // on the host-list route) with cameraMatrix.K over imagesPts2D, at its default options, and the tracks are
+  // built from what it keeps; the last call's statistics are lastVerifyStats().  false: the call as it was.
+  size_t consolidateTracks(int minViews = 2, bool verify = false);
+  const sfmhip_verify_stats& lastVerifyStats() const { return verifyStats; }
   // the inlier list of the last findCameraPosePNP (the reference computes it and reads it nowhere)
   const std::vector<int>& lastPnpInliers() const { return pnpInliers; }
   const std::set<int>& doneViews() const { return nDoneViews; }
@@ -150,6 +154,7 @@ class StructFromMotion {
 
  private:
   std::vector<int> pnpInliers;
+  sfmhip_verify_stats verifyStats = {0, 0, 0, 0, 0};
 
  public:
   // what the last baseReconstruction chose (pose_selftest): the pair, E, R, T, recoverPose's count and mask

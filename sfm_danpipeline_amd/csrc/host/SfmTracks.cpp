@@ -1,11 +1,27 @@
 // SfmTracks.cpp -- StructFromMotion::consolidateTracks: the multi-view tracks of the registered views (sfmhip_tracks_*,
 // DESIGN.md f-16) in place of the two-view points triangulateViews and mergeNewPoints leave.  The reference has no
-// counterpart (parity UNPINNED); nothing calls this by default.
+// counterpart (parity UNPINNED); nothing calls this by default.  With `verify` the lists first pass the two-view verification
+// (sfmhip_matchplan_verify / sfmhip_verify_lists) and the tracks are built from what it keeps.
 #include <iostream>
 #include "Sfm.h"
 #include "hip_backend.h"
 
-size_t StructFromMotion::consolidateTracks(int minViews) {
+namespace {
+// every image's pixels one after the other, as sfmhip_tracks_triangulate and the verification take them
+void packPixels(const std::vector<Points2d>& pts, std::vector<int32_t>& xyPtr, std::vector<double>& xy) {
+  xyPtr.assign(pts.size() + 1, 0);
+  xy.clear();
+  for (size_t i = 0; i < pts.size(); ++i) {
+    xyPtr[i + 1] = xyPtr[i] + (int32_t)pts[i].size();
+    for (const cv::Point2d& p : pts[i]) {
+      xy.push_back(p.x);
+      xy.push_back(p.y);
+    }
+  }
+}
+}  // namespace
+
+size_t StructFromMotion::consolidateTracks(int minViews, bool verify) {
   const int nImg = (int)imagesPts2D.size();
   std::vector<int32_t> good(nGoodViews.begin(), nGoodViews.end()), pairs, nFeat((size_t)nImg);
   for (int i = 0; i < nImg; ++i) nFeat[i] = (int32_t)imagesPts2D[i].size();
@@ -21,6 +37,10 @@ size_t StructFromMotion::consolidateTracks(int minViews) {
   sfmhip_tracks_default_opts(&opts);
   opts.min_len = minViews;
   sfmhip_tracks* tracks = nullptr;
+  sfmhip_verified* verified = nullptr;
+  std::vector<int32_t> xyPtr;
+  std::vector<double> xy;
+  packPixels(imagesPts2D, xyPtr, xy);
   int rc = SFMHIP_OK;
   // descriptors of one kind, one row per 2-D point: the resident image set (made here as getMatching makes it) and one plan
   // over every pair, whose lists are read where they lie on the device
@@ -41,7 +61,8 @@ size_t StructFromMotion::consolidateTracks(int minViews) {
     sfmhip_matchplan* plan = nullptr;
     if (rc == SFMHIP_OK) rc = sfmhip_matchplan_create(devSet, pairs.data(), nPairs, &plan);
     if (rc == SFMHIP_OK) rc = sfmhip_matchplan_run_async(plan, NN_MATCH_RATIO);
-    if (rc == SFMHIP_OK) rc = sfmhip_tracks_build_from_plan(plan, &opts, &tracks);
+    if (rc == SFMHIP_OK && verify) rc = sfmhip_matchplan_verify(plan, xyPtr.data(), xy.data(), cameraMatrix.K.data.data(), nullptr, &verified);
+    if (rc == SFMHIP_OK) rc = verify ? sfmhip_tracks_build_from_verified(verified, &opts, &tracks) : sfmhip_tracks_build_from_plan(plan, &opts, &tracks);
     if (plan) sfmhip_matchplan_destroy(plan);
   } else {  // the pair cache, or one matcher call per pair: host lists
     std::vector<int32_t> counts, q, t;
@@ -54,7 +75,19 @@ size_t StructFromMotion::consolidateTracks(int minViews) {
         t.push_back(d.trainIdx);
       }
     }
-    rc = sfmhip_tracks_build(sfm_hip_context(), nImg, nFeat.data(), nPairs, pairs.data(), counts.data(), q.data(), t.data(), &opts, &tracks);
+    if (verify) {
+      rc = sfmhip_verify_lists(sfm_hip_context(), nImg, nFeat.data(), nPairs, pairs.data(), counts.data(), q.data(), t.data(), xyPtr.data(),
+                               xy.data(), cameraMatrix.K.data.data(), nullptr, &verified);
+      if (rc == SFMHIP_OK) rc = sfmhip_tracks_build_from_verified(verified, &opts, &tracks);
+    } else {
+      rc = sfmhip_tracks_build(sfm_hip_context(), nImg, nFeat.data(), nPairs, pairs.data(), counts.data(), q.data(), t.data(), &opts, &tracks);
+    }
+  }
+  if (verified) {
+    sfmhip_verified_counts(verified, &verifyStats);
+    sfmhip_verified_destroy(verified);
+    std::cout << "verify: " << verifyStats.pairs_kept << " of " << verifyStats.pairs << " pairs kept (" << verifyStats.pairs_no_model
+              << " without a model), " << verifyStats.matches_out << " of " << verifyStats.matches_in << " matches" << std::endl;
   }
   if (rc != SFMHIP_OK) {
     std::cerr << "consolidateTracks: " << sfmhip_error_string(rc) << std::endl;
@@ -62,18 +95,13 @@ size_t StructFromMotion::consolidateTracks(int minViews) {
   }
   sfmhip_tracks_stats st;
   sfmhip_tracks_counts(tracks, &st);
-  std::vector<double> poses(12 * (size_t)nImg, 0.0), xy, X(3 * (size_t)st.n_tracks);
+  std::vector<double> poses(12 * (size_t)nImg, 0.0), X(3 * (size_t)st.n_tracks);
   std::vector<uint8_t> hasPose((size_t)nImg, 0), keep((size_t)st.n_tracks);
-  std::vector<int32_t> xyPtr((size_t)nImg + 1, 0), ptr((size_t)st.n_tracks + 1), view((size_t)st.n_obs), feat((size_t)st.n_obs);
+  std::vector<int32_t> ptr((size_t)st.n_tracks + 1), view((size_t)st.n_obs), feat((size_t)st.n_obs);
   for (int i = 0; i < nImg; ++i) {
     if (nGoodViews.count(i) && (size_t)i < nCameraPoses.size()) {
       hasPose[i] = 1;
       for (int k = 0; k < 12; ++k) poses[12 * (size_t)i + k] = nCameraPoses[i].val[k];
-    }
-    xyPtr[i + 1] = xyPtr[i] + nFeat[i];
-    for (const cv::Point2d& p : imagesPts2D[i]) {
-      xy.push_back(p.x);
-      xy.push_back(p.y);
     }
   }
   double dist[5] = {0, 0, 0, 0, 0};

@@ -2,6 +2,8 @@
 // addMoreViews(), consolidateTracks(minViews), adjustBundle().
 //   tracks_selftest --scene <scene.bin> <out prefix> [minViews]
 //   tracks_selftest --images <image dir> <calibration.xml> <out prefix> [minViews]
+// With --verify among the arguments the lists pass the two-view verification first (consolidateTracks(minViews, true);
+// DESIGN.md f-19), and a line "verified: pairs P kept K no_model N matches A -> B" precedes "consolidated:".
 // The inputs are incr_selftest's.  Writes <out prefix>.before (the state after addMoreViews) and <out prefix>.after (after the
 // consolidation and one more bundle adjustment), both in incr_selftest's out.bin layout.  A line "consolidated: N" goes to
 // stdout and to stderr before that last bundle adjustment, so that its messages can be told from the earlier ones.
@@ -50,6 +52,14 @@ bool write_state(const std::string& path, const StructFromMotion& sfm, int n_img
 }  // namespace
 
 int main(int argc, char** argv) {
+  bool verify = false;  // --verify, wherever it stands, is taken out of the arguments
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == "--verify") {
+      verify = true;
+      for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+      --argc;
+      --i;
+    }
   if (argc < 4) return 2;
   StructFromMotion sfm;
   std::string out;
@@ -104,7 +114,12 @@ int main(int argc, char** argv) {
   const int base_cloud = (int)sfm.nReconstructionCloud.size();
   if (!sfm.addMoreViews()) return 6;
   if (!write_state(out + ".before", sfm, n_img, base_cloud)) return 2;
-  const size_t n = sfm.consolidateTracks(min_views);
+  const size_t n = verify ? sfm.consolidateTracks(min_views, true) : sfm.consolidateTracks(min_views);
+  if (verify) {
+    const sfmhip_verify_stats& vs = sfm.lastVerifyStats();
+    std::cout << "verified: pairs " << vs.pairs << " kept " << vs.pairs_kept << " no_model " << vs.pairs_no_model << " matches " << vs.matches_in
+              << " -> " << vs.matches_out << std::endl;
+  }
   std::cout << "consolidated: " << n << std::endl;
   std::cerr << "consolidated: " << n << std::endl;
   if (n == 0) return 7;

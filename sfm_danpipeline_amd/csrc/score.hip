@@ -23,6 +23,7 @@
 #include "hypot_glibc.h"
 #include "jacobi.h"
 #include "score_host.h"
+#include "verify.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -362,18 +363,9 @@ __global__ __launch_bounds__(256, 4) void score_roots(int n_samples, const doubl
   n_models[t] = n | (flags << 8);
 }
 
-// EMEstimatorCallback::computeError + findInliers for one correspondence
-__device__ __forceinline__ bool is_inlier(const double* E, double x1, double y1, double x2, double y2, float t) {
-  const double ex0 = E[0] * x1 + E[1] * y1 + E[2] * 1.0;
-  const double ex1 = E[3] * x1 + E[4] * y1 + E[5] * 1.0;
-  const double ex2 = E[6] * x1 + E[7] * y1 + E[8] * 1.0;
-  const double et0 = E[0] * x2 + E[3] * y2 + E[6] * 1.0;
-  const double et1 = E[1] * x2 + E[4] * y2 + E[7] * 1.0;
-  const double x2tEx1 = x2 * ex0 + y2 * ex1 + 1.0 * ex2;
-  const double a = ex0 * ex0, b = ex1 * ex1, c = et0 * et0, d = et1 * et1;
-  const float err = (float)(x2tEx1 * x2tEx1 / (a + b + c + d));
-  return err <= t;
-}
+// EMEstimatorCallback::computeError + findInliers for one correspondence: verify.h's, which the verification's compaction
+// (verify.hip) and its CPU stub evaluate too
+using sfmverify::is_inlier;
 
 // workgroup (job, iteration): inlier count of every model of the sample
 __global__ __launch_bounds__(256) void score_count(const Job* __restrict__ jobs, int chunk, const double* __restrict__ p1,
@@ -744,27 +736,36 @@ int sfm_essential_ransac(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, c
   const long long total = offsets[n_pairs];
   SFM_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  constexpr int MAX_ITERS = 1000, MODEL_POINTS = 5;
-  const double thr = threshold / ((fx + fy) / 2);
-  const float t = (float)(thr * thr);
   const double ax = 1. / fx, bx = -cx * ax, ay = 1. / fy, by = -cy * ay;
-  int flags_any = 0;
   ctx->score_flags = 0;
 
-  DevBufs bufs;  // the loop's scratch (what the caller reads lives in dev)
   const size_t pts_n = 2 * (size_t)std::max<long long>(total, 1);
   SFM_TRY(dev.bufs.alloc(&dev.d_left, pts_n));
   SFM_TRY(dev.bufs.alloc(&dev.d_right, pts_n));
   SFM_TRY(dev.bufs.alloc(&dev.d_p1, pts_n));
   SFM_TRY(dev.bufs.alloc(&dev.d_p2, pts_n));
-  double *d_p1 = dev.d_p1, *d_p2 = dev.d_p2;
   if (total > 0) {
     const int nb = (int)((2 * total + 255) / 256);
     SFM_HIP_TRY(hipMemcpyAsync(dev.d_left, left_xy, sizeof(double) * 2 * total, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(score_normalize, dim3(nb), dim3(256), 0, st, dev.d_left, d_p1, 2 * total, ax, bx, ay, by);
+    hipLaunchKernelGGL(score_normalize, dim3(nb), dim3(256), 0, st, dev.d_left, dev.d_p1, 2 * total, ax, bx, ay, by);
     SFM_HIP_TRY(hipMemcpyAsync(dev.d_right, right_xy, sizeof(double) * 2 * total, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(score_normalize, dim3(nb), dim3(256), 0, st, dev.d_right, d_p2, 2 * total, ax, bx, ay, by);
+    hipLaunchKernelGGL(score_normalize, dim3(nb), dim3(256), 0, st, dev.d_right, dev.d_p2, 2 * total, ax, bx, ay, by);
   }
+  return sfm_essential_ransac_points(ctx, n_pairs, offsets, fx, fy, prob, threshold, inliers, iterations, want_mask, dev);
+}
+
+int sfm_essential_ransac_points(sfmhip_ctx* ctx, int n_pairs, const int32_t* offsets, double fx, double fy, double prob,
+                                double threshold, int32_t* inliers, int32_t* iterations, bool want_mask, EssentialDev& dev) {
+  const long long total = offsets[n_pairs];
+  SFM_HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  constexpr int MAX_ITERS = 1000, MODEL_POINTS = 5;
+  const float t = sfmverify::error_bound(fx, fy, threshold);
+  int flags_any = 0;
+  ctx->score_flags = 0;
+
+  DevBufs bufs;  // the loop's scratch (what the caller reads lives in dev)
+  double *d_p1 = dev.d_p1, *d_p2 = dev.d_p2;
   double* d_bestE = nullptr;
   Keep* d_upd = nullptr;
   SFM_TRY(dev.bufs.alloc(&d_bestE, 9 * (size_t)n_pairs));

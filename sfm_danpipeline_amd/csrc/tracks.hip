@@ -398,6 +398,17 @@ extern "C" int sfmhip_tracks_build_from_plan(sfmhip_matchplan* plan, const sfmhi
   return build_device(l.ctx, l.n_images, l.n_rows, l.n_pairs, l.pairs, l.counts, nullptr, l.stride, l.q, l.t, o, sp, out);
 }
 
+extern "C" int sfmhip_tracks_build_from_verified(const sfmhip_verified* verified, const sfmhip_tracks_opts* opts, sfmhip_tracks** out) {
+  if (!verified || !out) return SFMHIP_ERR_ARG;
+  sfm_matchplan_lists l;
+  SFM_TRY(sfm_verified_device_lists(verified, &l));
+  Opts o = default_opts();
+  if (opts) o = Opts{opts->min_len, opts->front_only};
+  SFM_HIP_TRY(hipSetDevice(l.ctx->device));
+  Stamps sp(l.ctx->stream, l.ctx->timing);
+  return build_device(l.ctx, l.n_images, l.n_rows, l.n_pairs, l.pairs, l.counts, nullptr, l.stride, l.q, l.t, o, sp, out);
+}
+
 extern "C" int sfmhip_tracks_counts(const sfmhip_tracks* tr, sfmhip_tracks_stats* stats) {
   if (!tr || !stats) return SFMHIP_ERR_ARG;
   stats->nodes = tr->stats.nodes;

@@ -3,7 +3,8 @@ components of the match graph as the CSR `incremental.find_2d3d` takes, numbered
 (two features of one image) dropped, and one DLT point per track over every view that has a pose.
 
 `build(ctx, n_feat, pairs, counts, q, t, **opts)` takes host lists in MatchPlan.fetch's layout, `build_from_plan(plan, **opts)`
-reads the lists of the plan's last run where they lie on the device; both return a `Tracks`, whose `stats`, `download()`,
+reads the lists of the plan's last run where they lie on the device, `build_from_verified(verified, **opts)` those of a
+verify.Verified; all return a `Tracks`, whose `stats`, `download()`,
 `triangulate(...)`, `last_timing()` and `close()` mirror the C entry points."""
 import ctypes as C
 
@@ -105,4 +106,11 @@ def build_from_plan(plan, **opts):
     """The tracks of the lists a matcher.MatchPlan's last run left on the device."""
     o, h = default_opts(**opts), C.c_void_p()
     _lib.check(_lib.lib().sfmhip_tracks_build_from_plan(plan.h, C.byref(o), C.byref(h)), "sfmhip_tracks_build_from_plan")
+    return Tracks(h)
+
+
+def build_from_verified(verified, **opts):
+    """The tracks of a verify.Verified's lists, read where they lie on the device."""
+    o, h = default_opts(**opts), C.c_void_p()
+    _lib.check(_lib.lib().sfmhip_tracks_build_from_verified(verified.h, C.byref(o), C.byref(h)), "sfmhip_tracks_build_from_verified")
     return Tracks(h)
