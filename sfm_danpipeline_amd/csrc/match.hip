@@ -1710,6 +1710,7 @@ struct sfmhip_imageset {
 
 struct sfmhip_matchplan {
   sfmhip_imageset* set;
+  int device = 0;  // (the set's; destroy must not read the set: a garbage collector may have destroyed that first)
   int n_pairs, n_items, maxq;
   int cap_pairs = 0;
   size_t cap_items = 0;
@@ -1988,6 +1989,7 @@ extern "C" int sfmhip_matchplan_create(sfmhip_imageset* s, const int32_t* pairs,
   SFM_TRY(plan_check_pairs(s, pairs, n_pairs));
   sfmhip_matchplan* pl = new sfmhip_matchplan();
   pl->set = s;
+  pl->device = s->ctx->device;
   pl->n_pairs = n_pairs;
   pl->cap_pairs = std::max(n_pairs, 1);
   pl->maxq = std::max(s->maxq, 1);
@@ -2338,7 +2340,7 @@ extern "C" int sfmhip_matchplan_last_knn_kernel_time(sfmhip_matchplan* pl, doubl
 
 extern "C" void sfmhip_matchplan_destroy(sfmhip_matchplan* pl) {
   if (!pl) return;
-  hipSetDevice(pl->set->ctx->device);
+  hipSetDevice(pl->device);
   hipFree(pl->d_pairs);
   hipFree(pl->d_items);
   hipFree(pl->d_knn);

@@ -92,7 +92,11 @@ class ImageSet:
 
 
 class MatchPlan:
-    """A list of (queryImage, trainImage) pairs matched by one batched launch."""
+    """A list of (queryImage, trainImage) pairs matched by one batched launch.
+
+    Lifetime: a plan works on its set's device buffers, so every call on it but close() needs the set open (the object
+    holds a reference to it for that).  close() alone -- sfmhip_matchplan_destroy -- may come after the set's: the cycle
+    collector finalises a set and its plan in either order."""
 
     def __init__(self, image_set, pairs):
         self.set = image_set

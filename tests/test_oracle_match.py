@@ -64,6 +64,27 @@ def test_random_vs_bruteforce_and_threads(orc):
     assert np.all(np.diff(r[0]) > 0)  # ascending queryIdx
 
 
+@pytest.mark.parametrize("norm,width", [("l2", d) for d in (8, 32, 61, 64, 200, 250, 256, 300)] +
+                         [("hamming", b) for b in (1, 8, 16, 31, 32, 33, 61, 64)])
+def test_other_widths_vs_bruteforce(orc, norm, width):
+    """The widths the GPU suite leans on the oracle for (tests/test_gpu_match_widths.py): the 8-lane f32 sums and the
+    8-byte popcount loop with their tails, against numpy.  The second half of the train rows copies the first, so every
+    query's best distance is tied and the lower train index has to come first."""
+    rng = np.random.default_rng(1000 + width)
+    q = rng.integers(0, 256, (60, width), dtype=np.uint8)
+    t = rng.integers(0, 256, (90, width), dtype=np.uint8)
+    t[45:] = t[:45]
+    q[::7] = t[rng.integers(0, 90, len(q[::7]))]          # some exact hits: distance 0, tied as well
+    casts = (np.uint8,) if norm == "hamming" else (np.uint8, np.float32)
+    for cast in casts:
+        qc, tc = q.astype(cast), t.astype(cast)
+        idx, dist = nc.knn2_bruteforce(qc, tc, norm=norm)
+        r = orc.match_knn2(qc, tc, norm=orc.NORM_HAMMING if norm == "hamming" else orc.NORM_L2, want_knn=True)
+        assert np.all(dist[:, 0] == dist[:, 1]) and np.all(idx[:, 0] < idx[:, 1])      # the ties are there
+        assert np.array_equal(r[3], idx)
+        assert np.array_equal(r[4].view(np.uint32), dist.view(np.uint32))
+
+
 def test_non_integer_rows_keep_documented_order(orc):
     rng = np.random.default_rng(0)
     q = rng.random((20, 128), dtype=np.float32) * 255
