@@ -638,7 +638,8 @@ int sfmhip_cloud_dendro_last_timing(sfmhip_cloud* cloud, double ms6[6]);
  *    > 1e-6 (or the hint is 0), h is the coordinate axis with the smallest |up| component (the lowest index on a tie) and
  *    flag bit 3 is set.
  * What the rules do not do: a scene whose largest plane is a wall at the edge of the cloud needs camera centres or an
- * up_hint; sloping ground gives the slope's normal, not gravity; one plane, no terrain. */
+ * up_hint; sloping ground gives the slope's normal, not gravity; one plane: the terrain over it is sfmhip_cloud_terrain's
+ * (f-20, below). */
 typedef struct sfmhip_ground_opts {
   double inlier_tol;      /* 0: use inlier_rel; else cloud units */
   double inlier_rel;      /* 0.005 of the selection's bounding-box diagonal */
@@ -747,6 +748,97 @@ int sfmhip_cloud_trees(sfmhip_cloud* cloud, const int32_t* labels_in, int32_t la
  * the whole call; with sweeps not NULL, the sweeps it enqueued (a multiple of 16).  The voxel stage and the sweeps are timed
  * apart only under sfmhip_set_timing (a stream synchronisation); without it the voxel stage's device time shows in the sweeps'. */
 int sfmhip_cloud_trees_last_timing(sfmhip_cloud* cloud, double ms6[6], int32_t* sweeps);
+
+/* ---- the terrain model: ground points, a DTM raster, height above ground ----
+ * The ground plane is one plane, and the trees and the dendrometry take one scalar `ground` along `up`.  On a plot that
+ * undulates every height is then wrong by the plane's residual.  This call classifies the ground points with a progressive
+ * morphological filter on a raster (Zhang et al. 2003; PCL 1.8.1's ApproximateProgressiveMorphologicalFilter), rasterises
+ * a digital terrain model from them and replaces every point's height by its height above the terrain.  The tree and
+ * dendrometry calls then run unchanged on the normalised cloud with up = +z, ground = 0.  PCL parity is UNPINNED; + marks a
+ * reading of PCL from memory.  The arithmetic is csrc/terrain.h (compiled by g++ and hipcc without contraction): every step
+ * is a min, a max or a comparison of float32 or f64 values, or an f64 expression written in one order, so the device equals
+ * the host build byte for byte.  The rules:
+ *  1 options: the table below; lengths are metres and are divided by `scale` once, in f64.  The frame and its refusals are
+ *    f-11 rule 1's.  SFMHIP_ERR_ARG also: cell, initial_distance or max_distance not > 0 or not finite (in metres or in
+ *    cloud units); max_window or slope negative or not finite; base < 2; fill_rounds outside 0..4096; relax_sweeps outside
+ *    0..1024.
+ *  2 selection and frame: f-13 rule 2's (e, n, h) as float32; selected: finite in both forms, labels == label when labels
+ *    are given.  Nothing selected: status OK, flag bit 0, De = Dn = 0, every per-point output "not ground / NaN".
+ *  3 raster: c = cell / scale; e_min, n_min and the maxima are float32, over the selection; ix = floor(((f64)e - e_min) / c),
+ *    iy likewise with n; De = ix(e_max) + 1, Dn likewise; De Dn > 2^24 (as f64): SFMHIP_ERR_ARG.  Cell id = iy De + ix.
+ *  4 lowest-point raster: Z_0[cell] = the least h of the cell's selected points; a cell without points is empty.
+ *  5 windows +: k_i = base^i when exponential, else (i + 1) base, for i = 0, 1, ... (an integer, held as an f64: exact below
+ *    2^53); window i exists while (f64)(2 k_i + 1) <= (max_window / scale) / c and i < 32.  dh_0 = d0;
+ *    dh_i = min(dmax, slope ((f64)(2 (k_i - k_{i-1})) c) + d0), with d0 and dmax the two distances over scale.  No window:
+ *    flag bit 2, and every selected point is a ground point.
+ *  6 opening of Z_i by window i: E_i[x, y] = the least non-empty Z_i[x', y'] with |x' - x| <= k_i, |y' - y| <= k_i inside
+ *    the raster, empty when there is none; O_i = the largest non-empty E_i over the same window, empty when there is none;
+ *    Z_{i+1} = O_i.
+ *  7 ground points: a selected point in cell q is a ground point iff (f64)h - (f64)O_i[q] <= dh_i for every window i.
+ *  8 terrain raster: for a cell with m > 0 ground points T = float32(S / (f64)m); S is their (f64)h summed in this order:
+ *    the point at position j of the cell's run (its selected points in ascending input index) adds to slot j mod 64 in
+ *    ascending j, points that are not ground add nothing; the 64 slots then fold by strides 32, 16, ..., 1
+ *    (slot[s] += slot[s + stride]).  The cell gets kind 1.
+ *  9 fill: in round r = 1 .. fill_rounds every cell that is empty before the round and has a non-empty 8-neighbour takes
+ *    float32(s / (f64)m), s the f64 sum (from 0) of those neighbours' values before the round in the order (dx, dy) =
+ *    (-1,-1), (0,-1), (1,-1), (-1,0), (1,0), (-1,1), (0,1), (1,1), m their count; it gets kind 2.  The fill stops after a
+ *    round that fills nothing (that round is counted).  Cells still empty: kind 0, value NaN, flag bit 1.
+ * 10 relaxation: relax_sweeps Jacobi sweeps over the kind-2 cells, kind-1 cells fixed: each becomes
+ *    float32(((W + E) + (S + N)) / 4.0) in f64 from the previous sweep's values (W, E: x - 1, x + 1; S, N: y - 1, y + 1);
+ *    a neighbour outside the raster or of kind 0 counts as the cell's own value.
+ * 11 height above ground of a selected point in cell q: NaN when q has kind 0.  Else u = ((f64)e - e_min) / c - 0.5,
+ *    x0 = clamp(floor(u), 0, De - 1), x1 = min(x0 + 1, De - 1), fx = clamp(u - x0, 0, 1); v, y0, y1, fy likewise with n.
+ *    The four corners T[y][x] are read as f64, a corner of kind 0 replaced by T[q];
+ *    g = ((T00 (1 - fx) + T01 fx) (1 - fy)) + ((T10 (1 - fx) + T11 fx) fy); hag = float32((f64)h - g).
+ * 12 canopy raster: chm[cell] = the largest finite hag of the cell's selected points, NaN when there is none.
+ * 13 outputs: per point is_ground (0 / 1; 0 when not selected) and hag (NaN when not selected); the rasters T, kind and
+ *    chm, row-major with ix fastest; the result below.  The normalised cloud has n rows: (e, n, hag) for a selected point
+ *    with finite hag, three NaN otherwise, so a tree_of computed on it indexes the original cloud.
+ * What the rules do not do: the opening's windows are clipped at the raster's edge, so a band of k_i cells along an
+ * upslope edge is flattened (the opening of a plane is the plane only k cells inside); initial_distance must cover the
+ * terrain's height change across one cell plus the noise; trunk points within initial_distance of the terrain are ground
+ * points; with the ground plane's normal as `up` the model describes the undulation over the slope, not gravity. */
+typedef struct sfmhip_terrain_opts {
+  double up[3];            /* (0, 0, 1) */
+  double north[3];         /* (0, 1, 0) */
+  double scale;            /* 1: metres per cloud unit */
+  double cell;             /* 0.5 */
+  double max_window;       /* 9.0: the widest window, 2 k + 1 cells */
+  double slope;            /* 1.0 */
+  double initial_distance; /* 0.15 */
+  double max_distance;     /* 2.5 */
+  int32_t base;            /* 2 */
+  int32_t exponential;     /* 1 */
+  int32_t fill_rounds;     /* 64; 0 ... 4096 */
+  int32_t relax_sweeps;    /* 32; 0 ... 1024 */
+} sfmhip_terrain_opts;
+typedef struct sfmhip_terrain_result {
+  double c;                /* the cell, cloud units */
+  float e_min, n_min;      /* the raster's origin in the frame */
+  float t_min, t_max;      /* the least and largest T (NaN: no cell has a value) */
+  float hag_max;           /* the largest finite hag (NaN: none) */
+  int32_t De, Dn, n_selected, n_ground, n_windows;
+  int32_t n_kind1, n_kind2, n_kind0; /* cells with ground points, filled, still empty */
+  int32_t fill_rounds;     /* the fill rounds run */
+  int32_t flags;           /* bit 0 nothing selected, 1 cells left empty, 2 no window */
+  int32_t pad;
+} sfmhip_terrain_result;
+void sfmhip_terrain_default_opts(sfmhip_terrain_opts* opts);
+/* host only: io->up and io->north from a result that has a plane (SFMHIP_ERR_ARG otherwise) */
+int sfmhip_terrain_opts_from_ground(const sfmhip_ground_result* ground, sfmhip_terrain_opts* io);
+/* labels: NULL (every finite point) or n entries; is_ground, hag: NULL or n entries on the host. */
+int sfmhip_cloud_terrain(sfmhip_cloud* cloud, const int32_t* labels, int32_t label, const sfmhip_terrain_opts* opts,
+                         int32_t* is_ground, float* hag, sfmhip_terrain_result* out);
+/* the rasters of the last sfmhip_cloud_terrain call on the handle (De Dn entries each, any pointer may be NULL);
+ * SFMHIP_ERR_ARG when there was no call. */
+int sfmhip_cloud_terrain_raster(sfmhip_cloud* cloud, float* dtm, uint8_t* kind, float* chm);
+/* the normalised cloud of the last call as a handle born on the device (as sfmhip_cloud_select's): the points never pass
+ * through the host.  SFMHIP_ERR_ARG when there was no call. */
+int sfmhip_cloud_terrain_normalize(sfmhip_cloud* cloud, sfmhip_cloud** out);
+/* host-clock ms of the last sfmhip_cloud_terrain call on the handle: frame + raster, windows, point test + terrain raster,
+ * fill + relax, heights + canopy, the whole call.  The windows and the point test are timed apart only under
+ * sfmhip_set_timing (a stream synchronisation each); without it their device time shows in the fill's figure. */
+int sfmhip_cloud_terrain_last_timing(sfmhip_cloud* cloud, double ms6[6]);
 
 /* ---- two clouds meet: nearest points, rigid and similarity ICP ----
  * What pcl::IterativeClosestPoint with TransformationEstimationSVD / ...SVDScale computes, and pcl::transformPointCloud, on

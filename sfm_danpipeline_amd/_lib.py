@@ -82,6 +82,8 @@ SYMBOLS = [
     "sfmhip_cloud_register_last_timing",
     "sfmhip_align_default_opts", "sfmhip_frame_from_ground", "sfmhip_cloud_register_batch", "sfmhip_cloud_register_batch_last_timing",
     "sfmhip_cloud_align_vote", "sfmhip_cloud_align", "sfmhip_cloud_align_last_timing",
+    "sfmhip_terrain_default_opts", "sfmhip_terrain_opts_from_ground", "sfmhip_cloud_terrain", "sfmhip_cloud_terrain_raster",
+    "sfmhip_cloud_terrain_normalize", "sfmhip_cloud_terrain_last_timing",
     "sfmhip_verify_default_opts", "sfmhip_matchplan_verify", "sfmhip_verify_lists", "sfmhip_verified_counts", "sfmhip_verified_download",
     "sfmhip_tracks_build_from_verified", "sfmhip_verified_last_timing", "sfmhip_verified_destroy",
 ]
@@ -259,6 +261,13 @@ def lib():
         L.sfmhip_cloud_align_vote.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
         L.sfmhip_cloud_align.argtypes = [vp, vp, vp, vp, vp, vp]
         L.sfmhip_cloud_align_last_timing.argtypes = [vp, vp]
+        L.sfmhip_terrain_default_opts.argtypes = [vp]
+        L.sfmhip_terrain_default_opts.restype = None
+        L.sfmhip_terrain_opts_from_ground.argtypes = [vp, vp]
+        L.sfmhip_cloud_terrain.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+        L.sfmhip_cloud_terrain_raster.argtypes = [vp, vp, vp, vp]
+        L.sfmhip_cloud_terrain_normalize.argtypes = [vp, C.POINTER(vp)]
+        L.sfmhip_cloud_terrain_last_timing.argtypes = [vp, vp]
         L.sfmhip_verify_default_opts.argtypes = [vp]
         L.sfmhip_verify_default_opts.restype = None
         L.sfmhip_matchplan_verify.argtypes = [vp, vp, vp, vp, vp, C.POINTER(vp)]

@@ -5,6 +5,8 @@
 // findGround() is the vertical frame they need on a reconstruction's cloud: sfmhip_cloud_ground_plane;
 // the overloads of measure() / estimateTree() that take ground options level first.  findTrees() cuts a levelled plot into
 // trees: sfmhip_cloud_trees; estimatePlot() is the chain ground plane -> trees -> one measurement per tree.
+// findTerrain() is the terrain model of a plot that undulates: sfmhip_cloud_terrain; the estimatePlot()
+// overload that takes terrain options puts it, and the height normalisation, between the ground plane and the trees.
 #pragma once
 #include <vector>
 #include "pcllite.h"
@@ -21,6 +23,12 @@ class Dendrometry {
   std::vector<int> treeOf_;
   std::vector<sfmhip_tree_stem> stems_;
   std::vector<sfmhip_dendro_result> plot_;
+  sfmhip_terrain_result terrain_ = {};
+  std::vector<int> isGround_;
+  std::vector<float> hag_;
+  // sfmhip_cloud_terrain on a handle made from cloudPCL; with `keep`, the handle is handed over instead of destroyed
+  int terrainOn(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_terrain_opts& opts,
+                sfmhip_cloud** keep);
 
  public:
   Dendrometry() {}
@@ -58,6 +66,18 @@ class Dendrometry {
   // SFMHIP_ERR_ARG when no plane was found.
   int estimatePlot(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const sfmhip_ground_opts& ground_opts, const double* cam_centres,
                    int n_cam, const sfmhip_trees_opts* trees_opts = nullptr, const sfmhip_dendro_opts* dendro_opts = nullptr);
+  // the terrain model of the points with labels[i] == label (labels == nullptr: of every finite point) in the frame `opts`
+  // carries (sfmhip_terrain_opts_from_ground): sfmhip_cloud_terrain.  isGround()[i] is 1 for a ground point,
+  // heightAboveGround()[i] point i's height above the terrain in cloud units (NaN: none).
+  int findTerrain(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_terrain_opts& opts);
+  // estimatePlot() over a terrain: findGround(), the terrain in its frame, then the trees and one measurement per tree on the
+  // normalised cloud (up +z, north +y, ground 0), which stays on the device; treeOf() indexes cloudPCL.
+  int estimatePlot(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const sfmhip_ground_opts& ground_opts, const double* cam_centres,
+                   int n_cam, const sfmhip_terrain_opts& terrain_opts, const sfmhip_trees_opts* trees_opts = nullptr,
+                   const sfmhip_dendro_opts* dendro_opts = nullptr);
+  const sfmhip_terrain_result& terrain() const { return terrain_; }
+  const std::vector<int>& isGround() const { return isGround_; }
+  const std::vector<float>& heightAboveGround() const { return hag_; }
   const sfmhip_trees_result& trees() const { return trees_; }
   const std::vector<int>& treeOf() const { return treeOf_; }
   const std::vector<sfmhip_tree_stem>& stems() const { return stems_; }
