@@ -840,6 +840,95 @@ int sfmhip_cloud_terrain_normalize(sfmhip_cloud* cloud, sfmhip_cloud** out);
  * sfmhip_set_timing (a stream synchronisation each); without it their device time shows in the fill's figure. */
 int sfmhip_cloud_terrain_last_timing(sfmhip_cloud* cloud, double ms6[6]);
 
+/* ---- crown delineation: tree tops and crowns from the canopy raster ----
+ * sfmhip_cloud_trees finds a tree by its stem; a cloud taken from above has dense crowns and few stem points.  This call
+ * finds the trees on the canopy height model instead: tree tops as variable-window maxima of the smoothed raster, crowns by
+ * steepest ascent to a summit and window merging of the summits, then a tree number per point in the layout
+ * sfmhip_cloud_dendrometry takes as labels.  The arithmetic is csrc/crowns.h (compiled by g++ and hipcc without
+ * contraction).  Every quantity is a pure function of the raster and no result depends on the order in which cells are
+ * visited, so the device equals the host build byte for byte.  PCL and the reference have nothing comparable: there is no
+ * parity to pin.  The rules:
+ *  1 options: the table below; lengths are metres and are divided by `scale` once, in f64.  SFMHIP_ERR_ARG: any of them not
+ *    finite; scale, min_height, r_min or max_crown_radius not > 0; r_max < r_min; win_b < 0; crown_frac outside [0, 1];
+ *    ground_clear < 0; smooth_passes outside 0..64; max_trees outside 1..65536; the cell c not > 0 or not finite;
+ *    (r_max / scale) / c > 64, the window's cap in cells.
+ *  2 input: a raster Z[Dn][De] of float32, row-major with ix fastest, cell id q = iy De + ix, the cell c in cloud units; NaN
+ *    means empty.  De Dn > 2^24: SFMHIP_ERR_ARG.  De Dn = 0: status OK, flag bit 0.
+ *  3 smoothing: H_0 = Z; pass p gives a non-empty cell H_{p+1} = float32(S / W), S the f64 sum (from 0) of k (f64)H_p and W
+ *    the f64 sum of k over the non-empty cells of the 3 x 3 block inside the raster in the order (dx, dy) = (-1,-1), (0,-1),
+ *    (1,-1), (-1,0), (0,0), (1,0), (-1,1), (0,1), (1,1) with k = 1, 2, 1, 2, 4, 2, 1, 2, 1.  An empty cell stays empty.
+ *    H is the raster after smooth_passes passes.
+ *  4 canopy: a cell is canopy iff H is finite and (f64)H >= min_height / scale.
+ *  5 order: key(q) = (H[q], -q): the greater H wins, at equal H the smaller cell id.  Strict and total.
+ *  6 ascent: up(q) = the canopy cell of greatest key among q and its 8 neighbours inside the raster; a canopy cell with
+ *    up(q) = q is a summit; root(q) = the summit reached by following up (the key rises strictly).
+ *  7 windows: for a summit s, r = min(r_max, max(r_min, win_a + win_b ((f64)H[s] scale))), rc = (r / scale) / c,
+ *    R2 = max(2, (int)floor(rc rc)); dom(s) = the canopy cell of greatest key among the cells inside the raster with
+ *    dx^2 + dy^2 <= R2, s included; parent(s) = root(dom(s)).  s is a top iff dom(s) = s; otherwise parent(s)'s key exceeds
+ *    s's, so following parent ends at a top, top(s).
+ *  8 numbering: tops are numbered 0 .. T - 1 by ascending cell id; beyond max_trees the first max_trees are kept and flag
+ *    bit 2 is set; cells whose top was dropped get -1.
+ *  9 crowns: a canopy cell q with t = top(root(q)) kept as number j has label j iff (f64)H[q] >= crown_frac (f64)H[t] and
+ *    (f64)(dx^2 + dy^2) <= floor(mr mr), mr = (max_crown_radius / scale) / c, (dx, dy) from t to q.  Else -1; a cell that is
+ *    not canopy has -1.
+ * 10 points (cloud entry): tree_of[i] = label(cell of i) when point i was selected by the terrain call, its hag is finite
+ *    and (f64)hag >= ground_clear / scale; else -1.  The cell of i is f-20 rule 3's.
+ * 11 outputs: the top rows and the result below.  A top's e = e_min + ((f64)ix + 0.5) c, n likewise; height = Z[cell], the
+ *    raw canopy in cloud units; height_smooth = H[cell]; cells = the cells with its label; points = the points with its
+ *    number (0 from the raster entry); area = (f64)cells (c c).  max_depth = the most parent steps from a summit to its top.
+ * What the rules do not do: this is a steepest-ascent partition with window merging, not a flooding watershed.  Two crowns
+ * that touch are split along the valley of the smoothed raster.  A minor summit goes to the tree of the highest cell in its
+ * window, which can leave a crown in two pieces.  A tree shorter than a taller neighbour's window away from it is absorbed. */
+typedef struct sfmhip_crowns_opts {
+  double scale;            /* 1: metres per cloud unit */
+  double min_height;       /* 2.0: a cell lower than this is not canopy */
+  double win_a;            /* 0.6: the window radius r = clamp(win_a + win_b * height in metres, r_min, r_max) */
+  double win_b;            /* 0.06 */
+  double r_min;            /* 0.6 */
+  double r_max;            /* 5.0 */
+  double crown_frac;       /* 0.3: a crown cell is at least this share of its top */
+  double max_crown_radius; /* 10.0 */
+  double ground_clear;     /* 0.3: points lower than this belong to no tree */
+  int32_t smooth_passes;   /* 2; 0 ... 64 */
+  int32_t max_trees;       /* 4096; 1 ... 65536 */
+} sfmhip_crowns_opts;
+typedef struct sfmhip_crown_top { /* cloud units */
+  double e, n;             /* the centre of the top's cell in the frame */
+  double area;             /* cells * c * c */
+  float height;            /* Z[cell]: the raw canopy */
+  float height_smooth;     /* H[cell] */
+  int32_t cell_id, ix, iy, R2, cells, points;
+} sfmhip_crown_top;
+typedef struct sfmhip_crowns_result {
+  double c;                /* the cell, cloud units */
+  float e_min, n_min;      /* the raster's origin in the frame */
+  int32_t De, Dn, n_canopy, n_summits;
+  int32_t n_trees;         /* the tops, before the cap */
+  int32_t n_labelled_cells, n_labelled; /* cells and points with a tree */
+  int32_t max_depth;       /* the longest parent chain */
+  int32_t flags;           /* bit 0 no canopy cell, 2 more tops than max_trees */
+  int32_t pad;
+} sfmhip_crowns_result;
+void sfmhip_crowns_default_opts(sfmhip_crowns_opts* opts);
+/* the raster entry: a host raster chm (De Dn floats, NULL when De Dn = 0) of any canopy model, e_min = n_min = 0.  labels,
+ * smooth: NULL or De Dn entries on the host; min(n_trees, max_trees) top rows exist, the first min(cap, that) are written. */
+int sfmhip_chm_crowns(sfmhip_ctx* ctx, const float* chm, int De, int Dn, double c, const sfmhip_crowns_opts* opts, int32_t* labels,
+                      float* smooth, int cap, sfmhip_crown_top* tops, sfmhip_crowns_result* out);
+/* the product: on the canopy raster, the frame coordinates and the heights above ground of the last sfmhip_cloud_terrain call
+ * on the handle, where they lie on the device (SFMHIP_ERR_ARG when there was no such call); c, e_min and n_min are that
+ * call's.  tree_of: NULL or n entries on the host.  Nothing but tree_of, the top rows and the result crosses to the host. */
+int sfmhip_cloud_crowns(sfmhip_cloud* cloud, const sfmhip_crowns_opts* opts, int32_t* tree_of, int cap, sfmhip_crown_top* tops,
+                        sfmhip_crowns_result* out);
+/* the rasters H and label of the last sfmhip_cloud_crowns call on the handle (De Dn entries each, either pointer may be
+ * NULL); SFMHIP_ERR_ARG when there was no call. */
+int sfmhip_cloud_crowns_raster(sfmhip_cloud* cloud, float* smooth, int32_t* labels);
+/* host-clock ms of the last sfmhip_cloud_crowns call on the handle: smoothing, ascent (up, doubling, the summit list),
+ * windows (with the summit forest and the numbering), labels, points, the whole call.  The stages are timed apart only
+ * under sfmhip_set_timing (a stream synchronisation each); without it the smoothing's device time shows in the ascent's. */
+int sfmhip_cloud_crowns_last_timing(sfmhip_cloud* cloud, double ms6[6]);
+/* the doubling rounds the last sfmhip_cloud_crowns call counted until one moved nothing: of rule 6's ascent, of rule 7's parents */
+int sfmhip_cloud_crowns_last_rounds(sfmhip_cloud* cloud, int32_t rounds2[2]);
+
 /* ---- two clouds meet: nearest points, rigid and similarity ICP ----
  * What pcl::IterativeClosestPoint with TransformationEstimationSVD / ...SVDScale computes, and pcl::transformPointCloud, on
  * two device-resident clouds of one context.  A similarity registration against a metric cloud is where the `scale` of the

@@ -84,6 +84,8 @@ SYMBOLS = [
     "sfmhip_cloud_align_vote", "sfmhip_cloud_align", "sfmhip_cloud_align_last_timing",
     "sfmhip_terrain_default_opts", "sfmhip_terrain_opts_from_ground", "sfmhip_cloud_terrain", "sfmhip_cloud_terrain_raster",
     "sfmhip_cloud_terrain_normalize", "sfmhip_cloud_terrain_last_timing",
+    "sfmhip_crowns_default_opts", "sfmhip_chm_crowns", "sfmhip_cloud_crowns", "sfmhip_cloud_crowns_raster",
+    "sfmhip_cloud_crowns_last_timing", "sfmhip_cloud_crowns_last_rounds",
     "sfmhip_verify_default_opts", "sfmhip_matchplan_verify", "sfmhip_verify_lists", "sfmhip_verified_counts", "sfmhip_verified_download",
     "sfmhip_tracks_build_from_verified", "sfmhip_verified_last_timing", "sfmhip_verified_destroy",
 ]
@@ -268,6 +270,13 @@ def lib():
         L.sfmhip_cloud_terrain_raster.argtypes = [vp, vp, vp, vp]
         L.sfmhip_cloud_terrain_normalize.argtypes = [vp, C.POINTER(vp)]
         L.sfmhip_cloud_terrain_last_timing.argtypes = [vp, vp]
+        L.sfmhip_crowns_default_opts.argtypes = [vp]
+        L.sfmhip_crowns_default_opts.restype = None
+        L.sfmhip_chm_crowns.argtypes = [vp, vp, cint, cint, f64, vp, vp, vp, cint, vp, vp]
+        L.sfmhip_cloud_crowns.argtypes = [vp, vp, vp, cint, vp, vp]
+        L.sfmhip_cloud_crowns_raster.argtypes = [vp, vp, vp]
+        L.sfmhip_cloud_crowns_last_timing.argtypes = [vp, vp]
+        L.sfmhip_cloud_crowns_last_rounds.argtypes = [vp, vp]
         L.sfmhip_verify_default_opts.argtypes = [vp]
         L.sfmhip_verify_default_opts.restype = None
         L.sfmhip_matchplan_verify.argtypes = [vp, vp, vp, vp, vp, C.POINTER(vp)]

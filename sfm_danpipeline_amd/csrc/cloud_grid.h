@@ -2,8 +2,8 @@
 // cloud.hip (map3D's step 10), cloud_filter.hip (the voxel grid and the statistical outlier removal), register.hip (two clouds:
 // nearest points and ICP, whose queries are not the grid's own points), align.hip (two levelled clouds: the pose vote), segment.hip (the colour
 // region growing after it), poisson.hip (create_mesh), dendro.hip (the dendrometry after the segmentation), ground.hip (the
-// ground plane that gives it its vertical), trees.hip (the trees of a plot), terrain.hip (the terrain under them) and, for
-// blocks(), mvs.hip.
+// ground plane that gives it its vertical), trees.hip (the trees of a plot), terrain.hip (the terrain under them), crowns.hip (the crowns
+// on its canopy raster) and, for blocks(), mvs.hip.
 // The handle plumbing is here once: a stage keeps its state in its slot of the handle's table (stage<S>(): made on first use,
 // deleted with the handle, so a state owns its device memory through members with destructors -- DevBufs, Grow, Grid), a
 // grow-only device array is a Grow<T>, and a min / max over points is minmax() into the handle's 7-word record.  A stage added
@@ -115,7 +115,7 @@ struct Grow {
 };
 
 // the stages that keep state on the handle, and a stage's slot: the state and what deletes it
-enum Stage { SEGMENT, POISSON, DENDRO, GROUND, TREES, FILTER, REGISTER, ALIGN, TERRAIN, N_STAGES };
+enum Stage { SEGMENT, POISSON, DENDRO, GROUND, TREES, FILTER, REGISTER, ALIGN, TERRAIN, CROWNS, N_STAGES };
 struct StageSlot {
   void* p = nullptr;
   void (*free)(void*) = nullptr;

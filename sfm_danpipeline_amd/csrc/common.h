@@ -60,6 +60,8 @@ struct sfmhip_ctx {
   size_t ba_pinned_bytes = 0;
   void* ba_host_scratch = nullptr;  // (and the host vectors of its set-ups: ba.hip, BaHostScratch)
   void (*ba_host_scratch_free)(void*) = nullptr;
+  void* crowns_state = nullptr;  // the device state of sfmhip_chm_crowns, the raster entry of crowns.hip (grow-only, freed with the context)
+  void (*crowns_state_free)(void*) = nullptr;
 };
 
 int sfm_ctx_pinned(sfmhip_ctx* ctx, size_t bytes, void** out);

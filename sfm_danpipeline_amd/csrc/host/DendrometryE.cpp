@@ -3,7 +3,8 @@
 // estimateTree() fill them (one sfmhip_cloud_dendro_profile call: the scalars and the stem table); findGround() and the
 // levelling overloads put sfmhip_cloud_ground_plane in front of them; findTrees() and estimatePlot() put sfmhip_cloud_trees
 // between the two, for a plot of several trees; findTerrain() and the estimatePlot() overload with terrain options put
-// sfmhip_cloud_terrain and its normalised cloud, which never leaves the device, in front of the trees.
+// sfmhip_cloud_terrain and its normalised cloud, which never leaves the device, in front of the trees; findCrowns() and the
+// estimatePlot() overload with crown options find the trees by sfmhip_cloud_crowns on the terrain's canopy raster instead.
 #include "DendrometryE.h"
 #include <cstdio>
 #include <cstdlib>
@@ -307,6 +308,89 @@ int Dendrometry::estimatePlot(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, 
     std::cout << "Tree " << s << ": Total Height =" << tree_.total_height << " Altura copa viva=" << tree_.live_crown
               << " Altura base de copa=" << tree_.crown_base_height << " Altura DAP=" << d.dbh_height << " DAP=" << tree_.dbh
               << " Amplitud N-S=" << tree_.spread_ns << " Amplitud E-W=" << tree_.spread_ew << std::endl;
+  }
+  sfmhip_cloud_destroy(flat);
+  std::cout << "************************************************" << std::endl;
+  std::cout << "************************************************" << std::endl;
+  return rc;
+}
+
+// sfmhip_cloud_crowns on a handle that holds a terrain call: treeOf_, tops_ and crowns_
+static int crownsOn(sfmhip_cloud* dev, int n, const sfmhip_crowns_opts& opts, std::vector<int>& treeOf, std::vector<sfmhip_crown_top>& tops,
+                    sfmhip_crowns_result& res) {
+  treeOf.assign((size_t)n + 1, -1);
+  tops.assign((size_t)(opts.max_trees > 0 ? opts.max_trees : 1), sfmhip_crown_top());
+  const int rc = sfmhip_cloud_crowns(dev, &opts, treeOf.data(), (int)tops.size(), tops.data(), &res);
+  treeOf.resize((size_t)n);
+  tops.resize(rc == SFMHIP_OK ? (size_t)(res.n_trees < opts.max_trees ? res.n_trees : opts.max_trees) : 0);
+  return rc;
+}
+
+int Dendrometry::findCrowns(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const sfmhip_terrain_opts& terrain_opts,
+                            const sfmhip_crowns_opts& crown_opts) {
+  sfmhip_cloud* dev = nullptr;
+  int rc = terrainOn(cloudPCL, nullptr, 0, terrain_opts, &dev);
+  if (rc != SFMHIP_OK) return rc;
+  rc = crownsOn(dev, (int)cloudPCL->size(), crown_opts, treeOf_, tops_, crowns_);
+  sfmhip_cloud_destroy(dev);
+  return rc;
+}
+
+int Dendrometry::estimatePlot(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const sfmhip_ground_opts& ground_opts,
+                              const double* cam_centres, int n_cam, const sfmhip_terrain_opts& terrain_opts,
+                              const sfmhip_crowns_opts& crown_opts, const sfmhip_dendro_opts* dendro_opts) {
+  sfmhip_dendro_opts d;
+  sfmhip_terrain_opts g = terrain_opts;
+  plot_.clear();
+  if (dendro_opts)
+    d = *dendro_opts;
+  else
+    sfmhip_dendro_default_opts(&d);
+  int rc = findGround(cloudPCL, nullptr, 0, cam_centres, n_cam, &ground_opts);
+  if (rc == SFMHIP_OK) rc = sfmhip_terrain_opts_from_ground(&ground_, &g);
+  if (rc != SFMHIP_OK) {
+    std::fprintf(stderr, "[sfm] sfmhip_cloud_ground_plane: %s\n", sfmhip_error_string(rc));
+    return rc;
+  }
+  sfmhip_cloud *dev = nullptr, *flat = nullptr;  // the plot, and the plot normalised: born on the device
+  rc = terrainOn(cloudPCL, nullptr, 0, g, &dev);
+  if (rc != SFMHIP_OK) {
+    std::fprintf(stderr, "[sfm] sfmhip_cloud_terrain: %s\n", sfmhip_error_string(rc));
+    return rc;
+  }
+  rc = crownsOn(dev, (int)cloudPCL->size(), crown_opts, treeOf_, tops_, crowns_);
+  if (rc != SFMHIP_OK) std::fprintf(stderr, "[sfm] sfmhip_cloud_crowns: %s\n", sfmhip_error_string(rc));
+  if (rc == SFMHIP_OK) {
+    rc = sfmhip_cloud_terrain_normalize(dev, &flat);
+    if (rc != SFMHIP_OK) std::fprintf(stderr, "[sfm] sfmhip_cloud_terrain_normalize: %s\n", sfmhip_error_string(rc));
+  }
+  sfmhip_cloud_destroy(dev);
+  if (rc != SFMHIP_OK) return rc;
+  for (int a = 0; a < 3; ++a) {  // on the normalised cloud up is +z, north +y and the ground is at 0
+    d.up[a] = a == 2 ? 1.0 : 0.0;
+    d.north[a] = a == 1 ? 1.0 : 0.0;
+  }
+  d.ground = 0.0;
+  std::cout << "************************************************" << std::endl;
+  std::cout << "              DENDROMETRY ESTIMATION            " << std::endl;
+  std::cout << "************************************************" << std::endl;
+  std::cout << "Terrain=" << terrain_.De << "x" << terrain_.Dn << " Ground points=" << terrain_.n_ground << std::endl;
+  std::cout << "Crowns=" << tops_.size() << " Summits=" << crowns_.n_summits << std::endl;
+  for (int s = 0; s < (int)tops_.size(); ++s) {
+    int32_t S = 0;
+    profile_.assign(4096, sfmhip_dendro_slice());
+    rc = sfmhip_cloud_dendro_profile(flat, treeOf_.data(), s, &d, (int)profile_.size(), profile_.data(), &S, &tree_);
+    profile_.resize(rc == SFMHIP_OK ? (size_t)S : 0);
+    if (rc != SFMHIP_OK) {
+      std::fprintf(stderr, "[sfm] sfmhip_cloud_dendrometry: %s\n", sfmhip_error_string(rc));
+      sfmhip_cloud_destroy(flat);
+      return rc;
+    }
+    plot_.push_back(tree_);
+    std::cout << "Tree " << s << ": Total Height =" << tree_.total_height << " Altura copa viva=" << tree_.live_crown
+              << " Altura base de copa=" << tree_.crown_base_height << " Altura DAP=" << d.dbh_height << " DAP=" << tree_.dbh
+              << " Amplitud N-S=" << tree_.spread_ns << " Amplitud E-W=" << tree_.spread_ew << " Area de copa=" << tops_[(size_t)s].area
+              << std::endl;
   }
   sfmhip_cloud_destroy(flat);
   std::cout << "************************************************" << std::endl;

@@ -7,6 +7,8 @@
 // trees: sfmhip_cloud_trees; estimatePlot() is the chain ground plane -> trees -> one measurement per tree.
 // findTerrain() is the terrain model of a plot that undulates: sfmhip_cloud_terrain; the estimatePlot()
 // overload that takes terrain options puts it, and the height normalisation, between the ground plane and the trees.
+// findCrowns() finds the trees of a plot seen from above, by their crowns on the terrain's canopy raster: sfmhip_cloud_crowns
+// (DESIGN.md f-21); the estimatePlot() overload that takes crown options uses it where the other uses the stems.
 #pragma once
 #include <vector>
 #include "pcllite.h"
@@ -26,6 +28,8 @@ class Dendrometry {
   sfmhip_terrain_result terrain_ = {};
   std::vector<int> isGround_;
   std::vector<float> hag_;
+  sfmhip_crowns_result crowns_ = {};
+  std::vector<sfmhip_crown_top> tops_;
   // sfmhip_cloud_terrain on a handle made from cloudPCL; with `keep`, the handle is handed over instead of destroyed
   int terrainOn(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const int* labels, int label, const sfmhip_terrain_opts& opts,
                 sfmhip_cloud** keep);
@@ -75,6 +79,16 @@ class Dendrometry {
   int estimatePlot(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const sfmhip_ground_opts& ground_opts, const double* cam_centres,
                    int n_cam, const sfmhip_terrain_opts& terrain_opts, const sfmhip_trees_opts* trees_opts = nullptr,
                    const sfmhip_dendro_opts* dendro_opts = nullptr);
+  // the trees of a plot by their crowns: findTerrain() with `terrain_opts`, then sfmhip_cloud_crowns on its canopy raster
+  // (DESIGN.md f-21).  treeOf()[i] is the tree of point i or -1, tops() one row per tree; no stem point is needed.
+  int findCrowns(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const sfmhip_terrain_opts& terrain_opts, const sfmhip_crowns_opts& crown_opts);
+  // estimatePlot() by crowns: findGround(), the terrain in its frame, the crowns on its canopy raster, then one measurement per
+  // crown on the normalised cloud (up +z, north +y, ground 0), which stays on the device; treeOf() indexes cloudPCL.
+  int estimatePlot(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloudPCL, const sfmhip_ground_opts& ground_opts, const double* cam_centres,
+                   int n_cam, const sfmhip_terrain_opts& terrain_opts, const sfmhip_crowns_opts& crown_opts,
+                   const sfmhip_dendro_opts* dendro_opts = nullptr);
+  const sfmhip_crowns_result& crowns() const { return crowns_; }
+  const std::vector<sfmhip_crown_top>& tops() const { return tops_; }
   const sfmhip_terrain_result& terrain() const { return terrain_; }
   const std::vector<int>& isGround() const { return isGround_; }
   const std::vector<float>& heightAboveGround() const { return hag_; }

@@ -2,6 +2,7 @@
 //   dendro_selftest <MAP3D.pcd> <out.bin> [label] [--level[=inlier_tol]]
 //   dendro_selftest <MAP3D.pcd> <out.bin> --plot[=inlier_tol]
 //   dendro_selftest <MAP3D.pcd> <out.bin> --terrain[=inlier_tol]
+//   dendro_selftest <MAP3D.pcd> <out.bin> --crowns[=inlier_tol]
 // Without a label: Dendrometry::estimateTree() on every point of the PCD.  With one: the colour segmentation first
 // (Segmentation::color_based_growing_segmentation), then estimateTree() on that cluster.  With --level, the ground plane of
 // the whole cloud is found first (Dendrometry::findGround, default options or the given tolerance in cloud units) and the
@@ -11,7 +12,10 @@
 // sfmhip_tree_stem rows, that many sfmhip_dendro_result, then one i32 tree number per point.  With --terrain the plot stands on
 // a terrain: estimatePlot() with default terrain options (ground plane, sfmhip_cloud_terrain in its frame, the trees and the
 // measurements on the normalised cloud); out.bin as with --plot, then the sfmhip_terrain_result, one i32 ground flag and one
-// float height above ground per point.
+// float height above ground per point.  With --crowns the trees are found by their crowns, not their stems: estimatePlot() with
+// default terrain and crown options (ground plane, sfmhip_cloud_terrain, sfmhip_cloud_crowns on its canopy raster, the
+// measurements on the normalised cloud); out.bin: i32 trees, that many sfmhip_crown_top rows, that many sfmhip_dendro_result, one
+// i32 tree number per point, then the sfmhip_crowns_result and the sfmhip_terrain_result.
 // Exit 3: the cloud is empty or no cluster came out; 4: the library refused the call.
 #include <cstdio>
 #include <cstdlib>
@@ -31,6 +35,28 @@ int main(int argc, char** argv) {
   }
   Dendrometry den;
   int rc;
+  if (std::strncmp(argv[argc - 1], "--crowns", 8) == 0) {
+    if (argv[argc - 1][8] == '=') gopts.inlier_tol = std::atof(argv[argc - 1] + 9);
+    pcl::PointCloud<pcl::PointXYZRGB>::Ptr cloud(new pcl::PointCloud<pcl::PointXYZRGB>());
+    pcl::io::loadPCDFile(argv[1], *cloud);
+    if (cloud->size() <= 0) return 3;
+    sfmhip_terrain_opts topts;
+    sfmhip_terrain_default_opts(&topts);
+    sfmhip_crowns_opts copts;
+    sfmhip_crowns_default_opts(&copts);
+    if (den.estimatePlot(cloud, gopts, nullptr, 0, topts, copts) != SFMHIP_OK) return 4;
+    FILE* o = fopen(argv[2], "wb");
+    if (!o) return 2;
+    const int T = (int)den.tops().size();
+    fwrite(&T, 4, 1, o);
+    fwrite(den.tops().data(), sizeof(sfmhip_crown_top), (size_t)T, o);
+    fwrite(den.plot().data(), sizeof(sfmhip_dendro_result), (size_t)T, o);
+    fwrite(den.treeOf().data(), sizeof(int), den.treeOf().size(), o);
+    fwrite(&den.crowns(), sizeof(sfmhip_crowns_result), 1, o);
+    fwrite(&den.terrain(), sizeof(sfmhip_terrain_result), 1, o);
+    fclose(o);
+    return 0;
+  }
   if (std::strncmp(argv[argc - 1], "--terrain", 9) == 0) {
     if (argv[argc - 1][9] == '=') gopts.inlier_tol = std::atof(argv[argc - 1] + 10);
     pcl::PointCloud<pcl::PointXYZRGB>::Ptr cloud(new pcl::PointCloud<pcl::PointXYZRGB>());

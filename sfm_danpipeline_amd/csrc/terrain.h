@@ -220,6 +220,20 @@ inline bool opts_from_ground(const sfmground::Result& g, Opts& io) {
   return true;
 }
 
+// what the last sfmhip_cloud_terrain call left on a handle, for the stages after it (crowns.hip): device pointers to the canopy
+// raster (De Dn cells; null when nothing was selected), the frame coordinates (3 n) and the heights above ground (n), the
+// raster and the cell.  Defined in terrain.hip; false: no call yet (or the last one was refused).
+struct LastCall {
+  const float *chm, *enh, *hag;
+  Dims d;
+  double c;
+  int32_t n;
+};
+}  // namespace sfmterrain
+struct sfmhip_cloud;
+namespace sfmterrain {
+bool last_call(sfmhip_cloud* c, LastCall& out);
+
 // ------------------------------------------------------------------------------------------------ host: the whole call
 // one pass of rule 6 along the lines of a raster (stride `step` between a line's elements): the least (or largest) value within
 // k of each element, the window clipped at the line's ends.  Empty cells are +inf in `in` and in `out`.

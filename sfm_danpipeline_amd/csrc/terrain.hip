@@ -66,6 +66,8 @@ struct TerState {  // on the cloud handle, freed with it
   const unsigned char* K = nullptr;
   const float* chm = nullptr;
   int ncell = 0;
+  Dims d = {0.0f, 0.0f, 0, 0};      // the last call's raster and cell, for last_call()
+  double c = 0;
   double ms[6] = {0, 0, 0, 0, 0, 0};
 };
 
@@ -355,6 +357,7 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, in
   s->has_call = false;
   s->ncell = 0;
   s->T = s->chm = nullptr, s->K = nullptr;
+  s->d = Dims{0.0f, 0.0f, 0, 0}, s->c = p.c;
   empty_result(res, p, F_NONE_SELECTED);
   const int n = c->n;
   if (n <= 0) {
@@ -472,12 +475,22 @@ int run(sfmhip_cloud* c, const int32_t* labels, int32_t label, const Opts& o, in
   if (tot.hagmax) res.hag_max = sfmcloud::ord_val(tot.hagmax);
   s->T = T[cur], s->K = kinds, s->chm = R2;
   s->ncell = ncell;
+  s->d = d;
   s->has_call = true;
   stamp(sfm_now_ms());
   return SFMHIP_OK;
 }
 
 }  // namespace
+
+// (not of the C ABI: crowns.hip reads the last call's rasters and per-point arrays where they lie)
+bool sfmterrain::last_call(sfmhip_cloud* c, LastCall& out) {
+  const TerState* s = sfmgrid::stage<TerState>(c);
+  if (!s->has_call) return false;
+  out.chm = s->chm, out.enh = s->enh, out.hag = s->hag;
+  out.d = s->d, out.c = s->c, out.n = c->n;
+  return true;
+}
 
 extern "C" void sfmhip_terrain_default_opts(sfmhip_terrain_opts* o) {
   if (!o) return;
