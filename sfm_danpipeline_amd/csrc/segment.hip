@@ -354,10 +354,11 @@ int number_segments(sfmhip_cloud* c, DevBufs& B, Work& w, DevTables& d) {
   SFM_HIP_TRY(hipGetLastError());
   SFM_TRY(scan(c, flags, off, (size_t)m, &w.n_seg));  // (m >= 1: indices_valid)
   if (w.n_seg < 0 || w.n_seg > m) return SFMHIP_ERR_STATE;
-  SFM_TRY(B.alloc(&d.acc, (size_t)4 * w.n_seg));
-  SFM_TRY(B.alloc(&d.count, (size_t)w.n_seg));
-  SFM_TRY(B.alloc(&d.colour, (size_t)3 * w.n_seg));
-  SFM_HIP_TRY(hipMemsetAsync(d.acc, 0, sizeof(unsigned) * 4 * (size_t)std::max(w.n_seg, 1), st));
+  const size_t ns = (size_t)std::max(w.n_seg, 1);  // (a list with no finite point has no segment: the tables keep one unused row)
+  SFM_TRY(B.alloc(&d.acc, 4 * ns));
+  SFM_TRY(B.alloc(&d.count, ns));
+  SFM_TRY(B.alloc(&d.colour, 3 * ns));
+  SFM_HIP_TRY(hipMemsetAsync(d.acc, 0, sizeof(unsigned) * 4 * ns, st));
   hipLaunchKernelGGL(seg_assign, dim3(blocks(m, 256)), dim3(256), 0, st, w.lab, off, w.rgb, m, w.seg, d.acc);
   SFM_HIP_TRY(hipGetLastError());
   if (w.n_seg > 0) hipLaunchKernelGGL(seg_colours, dim3(blocks(w.n_seg, 256)), dim3(256), 0, st, d.acc, w.n_seg, d.count, d.colour);

@@ -2,8 +2,9 @@
 src/Segmentation.cpp:3-66) and Dendrometry's bounds (src/DendrometryE.cpp:3-29) on the CPU, through a g++ build of the
 header the device code compiles (tests/stub/segment_capi.cpp): an independent, literal Python transcription of rules
 2-10 of DESIGN.md f-8 (queue growth, plain loops, scipy's neighbours re-ranked in float32) against the stub on seeded
-clouds, a planted scene of colour patches, the rule cases built by hand, the bounds against numpy, the XYZRGB PCD
-reader, and one cloud under ASan / UBSan.  No GPU.  PARITY UNPINNED: PCL is not in the image."""
+clouds, a planted scene of colour patches, the rule cases built by hand, the small scenes of tests/segment_scenes.py
+(the stub against the twin, or against numpy's brute force where distances tie, and the property each scene is named
+for), the bounds against numpy, the XYZRGB PCD reader, and one cloud under ASan / UBSan.  No GPU.  PARITY UNPINNED: PCL is not in the image."""
 import ctypes as C
 import heapq
 import os
@@ -14,6 +15,9 @@ from collections import deque
 import numpy as np
 import pytest
 from scipy.spatial import cKDTree
+
+from tests import segment_scenes as scenes
+from tests.segment_scenes import PATCH_COLOURS, _line, pack, patch_scene  # noqa: F401  (tests/test_gpu_segment.py takes them from here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STUB = os.path.join(ROOT, "tests", "stub", "segment_capi.cpp")
@@ -121,37 +125,9 @@ def stub_regions(sc, o, count, colour, lists, point_seg):
     return sr, int(nr[0]), pc, int(nc[0])
 
 
-def pack(r, g, b):
-    return (np.asarray(r, np.uint32) << 16) | (np.asarray(g, np.uint32) << 8) | np.asarray(b, np.uint32)
-
-
 def passthrough_z(xyz, lo=0.0, hi=14.0):
     xyz = _f(xyz)
     return np.nonzero(np.isfinite(xyz).all(1) & ~((xyz[:, 2] < np.float32(lo)) | (xyz[:, 2] > np.float32(hi))))[0].astype(np.int32)
-
-
-PATCH_COLOURS = [(200, 40, 40), (40, 200, 40), (40, 40, 200), (200, 200, 40), (40, 200, 200), (200, 40, 200)]
-
-
-def patch_scene(n, seed, salt=0.03, scale=1.0, close=False):
-    """Six colour patches and a gradient patch (red 20..200 along x) on unit squares of a slightly wavy sheet at z ~ 1,
-    colour noise of +-1 per channel, and `salt` of the points recoloured at random.  close: patches 1 and 2 get colours
-    within the region threshold of patch 0's (the homogeneous merging joins them).  Returns xyz, rgb, patch id, salt mask."""
-    rng = np.random.default_rng(seed)
-    patch = rng.integers(0, 7, n)
-    u, v = rng.uniform(0, 1, n), rng.uniform(0, 1, n)
-    x, y = (patch % 4) + u, (patch // 4) + v
-    z = 1.0 + 0.05 * np.sin(3 * x) * np.cos(2 * y) + rng.normal(0, 1e-3, n)
-    cols = list(PATCH_COLOURS)
-    if close:
-        cols[1], cols[2] = (202, 42, 41), (198, 38, 42)
-    base = np.array(cols + [(0, 90, 160)])[patch]
-    base[patch == 6, 0] = np.round(20 + 180 * u[patch == 6])
-    rgb = base + rng.integers(-1, 2, (n, 3))
-    is_salt = rng.uniform(size=n) < salt
-    rgb[is_salt] = rng.integers(0, 256, (int(is_salt.sum()), 3))
-    xyz = (np.c_[x, y, z] * [scale, scale, 1.0]).astype(np.float32)
-    return xyz, pack(*rgb.T), patch, is_salt
 
 
 # ---------------------------------------------------------------- the independent twin: rules 2-10, literally
@@ -192,11 +168,36 @@ def twin_knn(xyz, ind, k, check=True):
     return cand[:, :kk], d2[:, :kk]
 
 
-def twin_segment(xyz, rgb, ind, o):
-    """Returns (segment per list position, region per list position, clusters: lists of cloud indices, in order)."""
+def brute_knn(xyz, ind, k):
+    """Positions and float32 d2 of the min(k, finite rows) nearest indexed points by brute force: all pairwise d2 in float32,
+    np.lexsort((position, d2)).  For clouds whose d2 are exact in float32 (the lattice scenes: ties are the rule there, and the
+    order of a list is (d2, index) by definition); rows of non-finite points, and the columns past the list, are -1 / inf."""
+    pts = _f(xyz)[ind]
+    m = len(pts)
+    fin = np.isfinite(pts).all(1)
+    with np.errstate(invalid="ignore"):
+        d = pts[:, None, :] - pts[None, :, :]
+        d2 = ((d[..., 0] * d[..., 0]) + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    assert d2.dtype == np.float32
+    d2[:, ~fin] = np.inf
+    pos = np.broadcast_to(np.arange(m), (m, m))
+    order = np.lexsort((pos, d2), axis=1)
+    kk = min(k, int(fin.sum()))
+    nbr, nd2 = np.full((m, k), -1, np.int64), np.full((m, k), np.inf, np.float32)
+    nbr[:, :kk], nd2[:, :kk] = order[:, :kk], np.take_along_axis(d2, order[:, :kk], 1)
+    nbr[~fin], nd2[~fin] = -1, np.inf
+    return nbr, nd2
+
+
+def twin_segment(xyz, rgb, ind, o, knn=None):
+    """Returns (segment per list position, region per list position, clusters: lists of cloud indices, in order).  knn: the
+    (positions, d2) lists to grow over, for a tied cloud the twin's own search refuses (brute_knn's, all rows finite)."""
     rgb = _u(rgb)[ind]
     m = len(ind)
-    nbr, d2 = twin_knn(xyz, ind, o["region_neighbour_number"])
+    nbr, d2 = knn if knn is not None else twin_knn(xyz, ind, o["region_neighbour_number"])
+    if knn is not None:
+        nbr, d2 = nbr[:, :min(o["region_neighbour_number"], m)], d2[:, :min(o["region_neighbour_number"], m)]
+        assert (nbr >= 0).all()
     ch = np.stack([(rgb >> 16) & 255, (rgb >> 8) & 255, rgb & 255], 1).astype(np.int64)
     p2p = float(np.float32(o["point_color_threshold"]) * np.float32(o["point_color_threshold"]))
     r2r = float(np.float32(o["region_color_threshold"]) * np.float32(o["region_color_threshold"]))
@@ -382,38 +383,27 @@ def test_planted_scene(sc):
     assert np.array_equal(labels[lone], labels[idx[lone, 1]])
 
 
-# ---------------------------------------------------------------- rule cases built by hand
-def _line(xs, cols, order=None):
-    xyz = np.c_[np.asarray(xs, np.float32), np.zeros(len(xs)), np.ones(len(xs))].astype(np.float32)
-    rgb = pack(*np.asarray(cols).T)
-    if order is not None:
-        xyz, rgb = xyz[order], rgb[order]
-    return xyz, rgb
-
-
+# ---------------------------------------------------------------- rule cases built by hand (the scenes: tests/segment_scenes.py)
 def test_neighbour_ranked_beyond_30_does_not_join(sc):
-    A, B = (10, 10, 10), (200, 10, 10)
-    xs = [0.0] + [1.0 + 0.37 * j for j in range(35)] + [40.0]
-    xyz, rgb = _line(xs, [A] + [B] * 35 + [A])
-    ind = np.arange(len(xs), dtype=np.int32)
+    xyz, rgb, ind, kw = scenes.beyond_30()
     idx, _ = stub_subset_knn(sc, xyz, ind, 37)
     assert list(idx[0]).index(36) == 36                                              # rank 37 of 100 searched, beyond the first 30
-    seg, ns = stub_grow(sc, xyz, rgb, ind, ref_opts())
+    seg, ns = stub_grow(sc, xyz, rgb, ind, ref_opts(**kw))
     assert ns == 3 and seg[0] == 0 and seg[36] == 2 and (seg[1:36] == 1).all()
-    seg, ns = stub_grow(sc, xyz, rgb, ind, ref_opts(neighbour_number=40))           # (within the entries looked at: it joins)
-    assert ns == 2 and seg[36] == seg[0] == 0
+    xyz, rgb, ind, kw = scenes.beyond_30(neighbour_number=40)
+    seg, ns = stub_grow(sc, xyz, rgb, ind, ref_opts(**kw))                           # (within the entries looked at: it joins)
+    assert kw == dict(neighbour_number=40) and ns == 2 and seg[36] == seg[0] == 0
 
 
 def test_directed_pair_depends_on_index_order(sc):
-    xs, cols = [0.0, 1.0, 1.5], [(50, 50, 50)] * 3                                    # u, v, w: u -> v, v -> w, w -> v with 2 entries
-    o = ref_opts(neighbour_number=2, region_neighbour_number=2)
-    xyz, rgb = _line(xs, cols)
-    ind = np.arange(3, dtype=np.int32)
+    xyz, rgb, ind, kw = scenes.directed_pair(True)                                   # u, v, w: u -> v, v -> w, w -> v with 2 entries
+    o = ref_opts(**kw)
+    assert kw == dict(neighbour_number=2, region_neighbour_number=2)
     idx, _ = stub_subset_knn(sc, xyz, ind, 2)
     assert idx.tolist() == [[0, 1], [1, 2], [2, 1]]                                  # v is in u's list, u is not in v's
     seg, ns = stub_grow(sc, xyz, rgb, ind, o)
     assert ns == 1 and list(seg) == [0, 0, 0]                                        # u first: u -> v -> w
-    xyz, rgb = _line(xs, cols, order=[1, 2, 0])                                      # v, w, u: v's flood never reaches u
+    xyz, rgb, ind, kw = scenes.directed_pair(False)                                  # v, w, u: v's flood never reaches u
     seg, ns = stub_grow(sc, xyz, rgb, ind, o)
     assert ns == 2 and list(seg) == [0, 0, 1]
 
@@ -421,16 +411,17 @@ def test_directed_pair_depends_on_index_order(sc):
 def test_colour_thresholds_are_inclusive_and_strict(sc):
     assert sc.seg_colour_diff(0x000000, 0x060000) == 36 and sc.seg_colour_diff(0x102030, 0x0F2232) == 9
     assert sc.seg_channel(10, 4) == 2 and sc.seg_channel(255 * 3, 3) == 255
-    ind = np.arange(2, dtype=np.int32)
-    for c, want in (((6, 0, 0), 1), ((6, 1, 0), 2), ((4, 4, 2), 1), ((4, 4, 3), 2)):  # 36 joins, 37 and 41 do not
-        xyz, rgb = _line([0.0, 1.0], [(0, 0, 0), c])
-        assert stub_grow(sc, xyz, rgb, ind, ref_opts())[1] == want
+    assert scenes.POINT_THRESHOLD_PAIRS == (((6, 0, 0), 1), ((6, 1, 0), 2), ((4, 4, 2), 1), ((4, 4, 3), 2))
+    for c, want in scenes.POINT_THRESHOLD_PAIRS:                                     # 36 joins, 37 and 41 do not
+        xyz, rgb, ind, kw = scenes.threshold_pair(c)
+        assert stub_grow(sc, xyz, rgb, ind, ref_opts(**kw))[1] == want and kw == {}
     # region colour: a difference of exactly 25 does not merge, 16 does; d2 == 100 is near enough, the next float is not
     o = ref_opts(min_cluster_size=1)
-    above = float(np.nextafter(np.float32(100), np.float32(200)))
-    for colour, d2, regions in (([(10, 10, 10), (15, 10, 10)], 1.0, 2), ([(10, 10, 10), (14, 10, 10)], 1.0, 1),
-                                ([(10, 10, 10), (13, 14, 10)], 1.0, 2), ([(10, 10, 10), (14, 10, 10)], 100.0, 1),
-                                ([(10, 10, 10), (14, 10, 10)], above, 2)):
+    cases = scenes.region_threshold_cases()
+    assert [(sc.seg_colour_diff(int(pack(*a)), int(pack(*b))), regions) for (a, b), _, regions in cases] == \
+        [(25, 2), (16, 1), (25, 2), (16, 1), (16, 2)]
+    assert [d2 for _, d2, _ in cases][:4] == [1.0, 1.0, 1.0, 100.0] and np.float32(cases[4][1]) == np.nextafter(np.float32(100), np.float32(200))
+    for colour, d2, regions in cases:
         sr, nr, pc, nc = stub_regions(sc, o, [3, 2], colour, [[(1, d2)], [(0, d2)]], [0, 0, 0, 1, 1])
         assert nr == regions and nc == regions and list(pc) == ([0, 0, 0, 0, 0] if regions == 1 else [0, 0, 0, 1, 1])
 
@@ -438,20 +429,279 @@ def test_colour_thresholds_are_inclusive_and_strict(sc):
 def test_small_regions_and_compaction_by_hand(sc):
     # four segments of distinct colours in a row 0 - 1 - 2 - 3, sizes 5, 2, 6, 1; min 4: region 1 moves into its nearest
     # (segment 2, d2 1 against 4), region 3 into region 2; the emptied regions 1 and 3 are compacted away in place
-    col = [(0, 0, 0), (100, 0, 0), (0, 100, 0), (0, 0, 100)]
-    lists = [[(1, 4.0)], [(0, 4.0), (2, 1.0)], [(1, 1.0), (3, 9.0)], [(2, 9.0)]]
-    pts = [0] * 5 + [1] * 2 + [2] * 6 + [3]
-    sr, nr, pc, nc = stub_regions(sc, ref_opts(min_cluster_size=4), [5, 2, 6, 1], col, lists, pts)
+    t = scenes.compaction_tables()
+    kw, count, col, lists, pts, _ = t[0]
+    assert (kw, count, lists) == (dict(min_cluster_size=4), [5, 2, 6, 1], [[(1, 4.0)], [(0, 4.0), (2, 1.0)], [(1, 1.0), (3, 9.0)], [(2, 9.0)]])
+    sr, nr, pc, nc = stub_regions(sc, ref_opts(**kw), count, col, lists, pts)
     assert nr == 4 and list(sr) == [0, 2, 2, 2] and nc == 2
     assert list(pc) == [0] * 5 + [1] * 9
     # an emptied FIRST region takes the last one's place: the cluster order changes (rule 10)
-    sr, nr, pc, nc = stub_regions(sc, ref_opts(min_cluster_size=4), [2, 6, 5], col[:3], [[(1, 1.0)], [(0, 1.0), (2, 4.0)], [(1, 4.0)]],
-                                  [0] * 2 + [1] * 6 + [2] * 5)
+    kw, count, col, lists, pts, _ = t[1]
+    assert (kw, count, lists) == (dict(min_cluster_size=4), [2, 6, 5], [[(1, 1.0)], [(0, 1.0), (2, 4.0)], [(1, 4.0)]])
+    sr, nr, pc, nc = stub_regions(sc, ref_opts(**kw), count, col, lists, pts)
     assert list(sr) == [1, 1, 2] and nc == 2 and list(pc) == [1] * 8 + [0] * 5
     # a region with no list stays and is erased by the size limit; so is one above the maximum
-    sr, nr, pc, nc = stub_regions(sc, ref_opts(min_cluster_size=4, max_cluster_size=5), [2, 6, 5], col[:3], [[], [(2, 4.0)], [(1, 4.0)]],
-                                  [0] * 2 + [1] * 6 + [2] * 5)
+    kw, count, col, lists, pts, _ = t[2]
+    assert (kw, count, lists) == (dict(min_cluster_size=4, max_cluster_size=5), [2, 6, 5], [[], [(2, 4.0)], [(1, 4.0)]])
+    sr, nr, pc, nc = stub_regions(sc, ref_opts(**kw), count, col, lists, pts)
     assert nc == 1 and list(pc) == [-1] * 8 + [0] * 5
+    for kw, count, col, lists, pts, (want_sr, want_nc, want_pc) in t:                # (what the scenes module hands the device tests)
+        sr, nr, pc, nc = stub_regions(sc, ref_opts(**kw), count, col, lists, pts)
+        assert (want_sr is None or list(sr) == want_sr) and nc == want_nc and list(pc) == want_pc
+        assert [tuple(c) for c in col] == scenes.COMPACTION_COLOURS[:len(count)] and pts == [s for s, n in enumerate(count) for _ in range(n)]
+
+
+def check_expectation(want, grow, whole):
+    """A rule scene's expectation (segment_scenes.rule_scenes) against (segment [n], count) and (labels [n], clusters, regions)."""
+    if "segments" in want:
+        assert grow[1] == want["segments"][0] and list(grow[0]) == want["segments"][1]
+    if "clusters" in want:
+        assert whole[1] == want["clusters"][0] and list(whole[0]) == want["clusters"][1]
+    if "regions" in want:
+        assert whole[2] == want["regions"]
+
+
+@pytest.mark.parametrize("name,scene,want", scenes.rule_scenes(), ids=[r[0] for r in scenes.rule_scenes()])
+def test_rule_scenes_as_points(sc, name, scene, want):
+    xyz, rgb, ind, kw = scene
+    o = ref_opts(**kw)
+    labels, nc, stats, _ = stub_segment(sc, xyz, rgb, ind, o)
+    check_expectation(want, stub_grow(sc, xyz, rgb, ind, o), (labels, nc, stats[2]))
+
+
+# ---------------------------------------------------------------- the small scenes: the stub against the twins, and what each is named for
+def finite_rows_knn(xyz, ind, k, knn=twin_knn):
+    """The reference lists of a list with non-finite rows: `knn` over the finite rows, as cloud indices; -1 / inf elsewhere."""
+    ind = np.asarray(ind)
+    fin = np.isfinite(_f(xyz)[ind]).all(1)
+    idx, d2 = np.full((len(ind), k), -1, np.int32), np.full((len(ind), k), np.inf, np.float32)
+    if fin.any():
+        nbr, nd2 = knn(xyz, ind[fin], k)
+        idx[fin, :nbr.shape[1]], d2[fin, :nbr.shape[1]] = np.where(nbr >= 0, ind[fin][np.maximum(nbr, 0)], -1), nd2
+    return idx, d2
+
+
+def ubits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def check_knn(got, xyz, ind, k, knn=twin_knn):
+    idx, d2 = finite_rows_knn(xyz, ind, k, knn)
+    assert np.array_equal(got[0], idx) and np.array_equal(ubits(got[1]), ubits(d2))
+
+
+def reference_segmentation(xyz, rgb, ind, o, tied=False):
+    """(segment [n], segments, labels [n], clusters, final region of every list position) from the literal twin; tied: over
+    brute_knn's lists."""
+    knn = brute_knn(xyz, ind, o["region_neighbour_number"]) if tied else None
+    t_seg, t_reg, t_clusters = twin_segment(xyz, rgb, ind, o, knn=knn)
+    n = len(_f(xyz))
+    seg, labels = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    seg[ind] = t_seg
+    for c, members in enumerate(t_clusters):
+        labels[members] = c
+    return seg, int(t_seg.max()) + 1, labels, len(t_clusters), t_reg
+
+
+def check_stub_against_twin(sc, xyz, rgb, ind, o, tied=False):
+    k = o["region_neighbour_number"]
+    check_knn(stub_subset_knn(sc, xyz, ind, k), xyz, ind, k, brute_knn if tied else twin_knn)
+    ref = reference_segmentation(xyz, rgb, ind, o, tied)
+    seg, ns = stub_grow(sc, xyz, rgb, ind, o)
+    assert ns == ref[1] and np.array_equal(seg, ref[0])
+    labels, nc, stats, reg = stub_segment(sc, xyz, rgb, ind, o)
+    assert nc == ref[3] and np.array_equal(labels, ref[2]) and list(stats[:2]) == [len(ind), ns] and np.array_equal(reg, ref[4])
+    return ref + (int(stats[2]),)                                                    # (and the regions rule 8 opened, from the stub)
+
+
+K_SWEEP = (1, 2, 3, 4, 5, 63, 64, 65, 99, 100, 101, 127, 128)
+K_GROW = (2, 3, 5, 65, 127)
+
+
+def sweep_lengths(k, n=300):
+    return sorted({m for m in (1, 2, k - 1, k, k + 1, n) if 1 <= m <= n})
+
+
+@pytest.mark.parametrize("k", K_SWEEP)
+def test_scene_untied_sheet(sc, k):
+    xyz, rgb, ind, kw = scenes.untied_sheet(300)
+    for m in sweep_lengths(k):
+        check_knn(stub_subset_knn(sc, xyz, ind[:m], k), xyz, ind[:m], k)             # (the twin asserts that no row ties)
+    if k in K_GROW:
+        ref = check_stub_against_twin(sc, xyz, rgb, ind, ref_opts(**dict(kw, region_neighbour_number=k, neighbour_number=min(30, k))))
+        assert ref[1] > 7
+
+
+@pytest.mark.parametrize("k", [3, 27, 64, 101])
+def test_scene_lattice(sc, k):
+    xyz, rgb, ind, kw = scenes.lattice(6, 6, 3)
+    idx, d2 = stub_subset_knn(sc, xyz, ind, k)
+    check_knn((idx, d2), xyz, ind, k, brute_knn)
+    assert set(np.unique(d2)) <= set(np.arange(0, 60, dtype=np.float32))             # small integers: exact in any order
+    ties = np.diff(d2, axis=1) == 0
+    assert ties.any(1).all() and ties.mean() > 0.3                                   # every list has ties, many of them
+    assert (np.diff(idx, axis=1)[ties] > 0).all()                                    # and tied entries ascend by index
+
+
+@pytest.mark.parametrize("k", [5, 100, 127])
+def test_scene_far_clusters(sc, k):
+    xyz, rgb, ind, kw, member = scenes.far_clusters(k)
+    assert kw["region_neighbour_number"] == k and len(ind) >= k
+    nbr, _ = twin_knn(xyz, ind, k)
+    assert ((member[nbr[:, k - 1]] != member) | (member < 0)).all()                  # the k-th neighbour: in another cluster
+    assert (member[nbr[:, 1]] == member)[member >= 0].all()                          # the nearest: in its own
+    sizes = np.bincount(member[member >= 0])
+    assert len(sizes) == 3 and (sizes < k).all() and (member < 0).sum() == 2
+    for sub in (ind, ind[::3]):
+        check_knn(stub_subset_knn(sc, xyz, sub, k), xyz, sub, k)
+    check_stub_against_twin(sc, xyz, rgb, ind, ref_opts(**kw))
+
+
+@pytest.mark.parametrize("k", [3, 100])
+def test_scene_line(sc, k):
+    xyz, rgb, ind, kw = scenes.line(5000)
+    assert len(ind) == 5000 and (xyz[:, 1] == 0).all() and (xyz[:, 2] == 1).all() and (np.diff(xyz[:, 0]) > 0).all()
+    assert np.diff(xyz[:, 0]).max() > 2 * np.diff(xyz[:, 0]).min()                   # unequal spacings
+    for sub in (ind, ind[::3]):
+        check_knn(stub_subset_knn(sc, xyz, sub, k), xyz, sub, k)
+    if k == 100:
+        ref = check_stub_against_twin(sc, xyz, rgb, ind, ref_opts(**kw))
+        assert ref[1] == 10
+
+
+def with_holes(xyz, ind):
+    """The scene with a few indexed rows made non-finite: every 7th gets a NaN, an inf or a -inf in one coordinate."""
+    xyz = xyz.copy()
+    rows = np.asarray(ind)[3::7]
+    for j, r in enumerate(rows):
+        xyz[r, j % 3] = (np.nan, np.inf, -np.inf)[j % 3]
+    return xyz, rows
+
+
+def test_scene_holes_stub_against_twin(sc):
+    for (xyz, _, ind, *_), k in ((scenes.far_clusters(100), 100), (scenes.line(5000), 3)):
+        holed, rows = with_holes(xyz, ind)
+        idx, d2 = stub_subset_knn(sc, holed, ind, k)
+        check_knn((idx, d2), holed, ind, k)
+        assert len(rows) > 3 and not np.isin(idx, rows).any() and (idx[np.isin(ind, rows)] == -1).all()
+
+
+@pytest.mark.parametrize("order", ["ascending", "descending", "shuffled"])
+@pytest.mark.parametrize("nn", [2, 3])
+def test_scene_snake(sc, order, nn):
+    m = 4097
+    xyz, rgb, ind, kw = scenes.snake(m, order)
+    o = ref_opts(**dict(kw, neighbour_number=nn))
+    ref = check_stub_against_twin(sc, xyz, rgb, ind, o)
+    assert ref[1] == 1 and (ref[0] == 0).all() and ref[3] == 1                       # one segment of m points
+    # what the chain is made of: consecutive points within the point threshold, points two apart outside it
+    chain = np.argsort(xyz[:, 0])
+    ch = np.stack([(rgb >> 16) & 255, (rgb >> 8) & 255, rgb & 255], 1).astype(np.int64)[chain]
+    assert (((ch[1:] - ch[:-1]) ** 2).sum(1) <= 36).all() and (((ch[2:] - ch[:-2]) ** 2).sum(1) > 36).all()
+    nbr, _ = twin_knn(xyz, ind, 2)
+    assert np.array_equal(nbr[chain[:-1], 1], chain[1:])                             # every point's nearest: the next of the chain
+    assert chain[0] == 0 and {"ascending": chain[-1] == m - 1, "descending": chain[-1] == 1 and (np.diff(chain[1:]) == -1).all(),
+                              "shuffled": (np.diff(chain) < 0).mean() > 0.4}[order]
+    if nn == 2 and order == "ascending":      # the same chain indexed from its tail (m - 1, .., 1, 0): no seed reaches past its neighbour
+        assert stub_grow(sc, xyz[::-1], rgb[::-1], ind, o)[1] == m - 1
+
+
+@pytest.mark.parametrize("S", scenes.BLOB_SIZES)
+def test_scene_blobs(sc, S):
+    xyz, rgb, ind, kw, which = scenes.blobs(S)
+    ref = check_stub_against_twin(sc, xyz, rgb, ind, ref_opts(**kw))
+    assert ref[1] == S and ref[3] == S and ref[5] == S                               # exactly S segments, clusters, regions
+    first = [int(np.nonzero(which == b)[0][0]) for b in range(S)]
+    assert np.array_equal(ref[0], np.argsort(np.argsort(first))[which])              # numbered by their smallest index
+    if S > 1:
+        nbr, _ = twin_knn(xyz, ind, kw["region_neighbour_number"])
+        assert (which[nbr] != which[:, None]).any(1).all()                           # every point's list reaches another blob
+
+
+def segment_neighbours(xyz, ind, k, seg, a):
+    """Segment a's neighbour segments as (d2, segment), ascending: the minimum over its points' entries (rule 6, uncapped)."""
+    nbr, d2 = brute_knn(xyz, ind, k)
+    best = {}
+    for u in np.nonzero(seg == a)[0]:
+        for v, d in zip(nbr[u], d2[u]):
+            if v >= 0 and seg[v] != a:
+                best[int(seg[v])] = min(best.get(int(seg[v]), np.inf), float(d))
+    return sorted((d, b) for b, d in best.items())
+
+
+@pytest.mark.parametrize("keep", [1, 4, 5])
+def test_scene_hub(sc, keep):
+    n_sat = 12
+    xyz, rgb, ind, kw, n_hub = scenes.hub(n_sat, keep)
+    o = ref_opts(**kw)
+    assert o["region_neighbour_number"] == keep and n_sat > keep
+    ref = check_stub_against_twin(sc, xyz, rgb, ind, o, tied=True)
+    if keep == 1:               # one neighbour searched: the point itself.  No list crosses a segment, so no segment has a neighbour
+        assert ref[1] == len(ind) and ref[5] == len(ind) and segment_neighbours(xyz, ind, keep, ref[0], 0) == []
+        return
+    assert ref[1] == 1 + n_sat and (ref[0][:n_hub] == 0).all() and list(ref[0][n_hub:]) == list(range(1, n_sat + 1))
+    nb = segment_neighbours(xyz, ind, keep, ref[0], 0)
+    assert len(nb) == n_sat > keep                                                   # more neighbour segments than the cap keeps
+    assert sorted(d for d, _ in nb) == [1 / 16] * 2 + [1 / 4] * 4 + [9 / 16] * 6
+    assert nb[keep - 1][0] == nb[keep][0]                                            # the cap cuts between two tied satellites
+    kept = [b for _, b in nb[:keep]]
+    assert nb[keep][1] > nb[keep - 1][1] and kept != sorted(kept) and kept != list(range(1, keep + 1))
+    # rule 8 merges what the hub's list keeps, and nothing else: the clusters show the cap and its tie-break
+    assert ref[5] == 1 + n_sat - keep
+    assert sorted(np.nonzero(ref[2] == ref[2][0])[0][n_hub:] - n_hub + 1) == sorted(kept)
+
+
+def test_scene_thirds(sc):
+    xyz, rgb, ind, kw, run = scenes.thirds()
+    ref = check_stub_against_twin(sc, xyz, rgb, ind, ref_opts(**kw))
+    assert np.array_equal(ref[0], run) and ref[1] == 5 and list(np.bincount(run)) == [3, 7, 5, 5, 5]
+    ch = np.stack([(rgb >> 16) & 255, (rgb >> 8) & 255, rgb & 255], 1).astype(np.int64)
+    for s, c in ((0, 0), (1, 1)):
+        total, n = int(ch[run == s, c].sum()), int((run == s).sum())
+        assert total % n != 0 and sc.seg_channel(total, n) == total // n == int(round(total / n)) - 1   # truncated, not rounded
+    lab = ref[2]
+    A, B, D, E, F = (lab[run == j] for j in range(5))
+    assert ref[5] == 4 and ref[3] == 4
+    assert (A == A[0]).all() and (F == A[0]).all() and (D != A[0]).all() and (E != B[0]).all()           # rounded means: A + D, B + E
+
+
+@pytest.mark.parametrize("m", [257, 1025])
+def test_scene_every_point_its_own_segment(sc, m):
+    xyz, rgb, ind, kw = scenes.untied_sheet(m, seed=m)
+    ref = check_stub_against_twin(sc, xyz, rgb, ind, ref_opts(**dict(kw, neighbour_number=1)))
+    assert ref[1] == m and np.array_equal(ref[0], np.arange(m))
+
+
+def test_scene_clamped_neighbour_number_and_zero_threshold(sc):
+    xyz, rgb, ind, kw = scenes.untied_sheet(300)
+    a = check_stub_against_twin(sc, xyz, rgb, ind, ref_opts(**dict(kw, neighbour_number=200, region_neighbour_number=100)))
+    b = check_stub_against_twin(sc, xyz, rgb, ind, ref_opts(**dict(kw, neighbour_number=100, region_neighbour_number=100)))
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[2], b[2])                 # 200 entries of a list of 100: all of them
+    z = check_stub_against_twin(sc, xyz, rgb, ind, ref_opts(**dict(kw, point_color_threshold=0.0)))
+    seg = z[0]
+    assert z[1] > a[1] and all(len(set(rgb[seg == s])) == 1 for s in range(z[1]))    # only equal colours join
+
+
+def test_all_non_finite_and_single_rows(sc):
+    xyz, rgb, ind, kw = scenes.untied_sheet(300)
+    o = ref_opts(**kw)
+    none = xyz.copy()
+    none[ind[:40], 0] = np.nan
+    labels, nc, stats, _ = stub_segment(sc, none, rgb, ind[:40], o)
+    assert (labels == -1).all() and nc == 0 and list(stats) == [0, 0, 0, 0]
+    seg, ns = stub_grow(sc, none, rgb, ind[:40], o)
+    assert (seg == -1).all() and ns == 0
+    idx, d2 = stub_subset_knn(sc, none, ind[:40], 5)
+    assert (idx == -1).all() and np.isinf(d2).all()
+    one = none.copy()
+    one[17] = xyz[17]
+    labels, nc, stats, _ = stub_segment(sc, one, rgb, ind[:40], ref_opts(min_cluster_size=1))
+    assert nc == 1 and list(np.nonzero(labels == 0)[0]) == [17] and list(stats[:3]) == [1, 1, 1]
+    seg, ns = stub_grow(sc, one, rgb, ind[:40], o)
+    assert ns == 1 and list(np.nonzero(seg == 0)[0]) == [17] and (np.delete(seg, 17) == -1).all()
+    check_knn(stub_subset_knn(sc, one, ind[:40], 3), one, ind[:40], 3)
+    labels, nc, stats, _ = stub_segment(sc, xyz[:1], rgb[:1], ind[:1], ref_opts(min_cluster_size=1))    # a cloud of one point
+    assert list(labels) == [0] and nc == 1 and list(stats[:3]) == [1, 1, 1]
 
 
 def test_points_outside_the_limits_and_short_lists(sc):
