@@ -1083,6 +1083,63 @@ int sfmhip_cloud_align(sfmhip_cloud* target, sfmhip_cloud* source, const sfmhip_
 /* host-clock ms of the last vote or alignment with this target: the vote, the batch ICP (0 after a vote alone), the whole call */
 int sfmhip_cloud_align_last_timing(sfmhip_cloud* target, double ms3[3]);
 
+/* ---- point-to-plane, trimmed and one-to-one ICP ----
+ * A second registration entry beside sfmhip_cloud_register: the same search, the same loop record and the same batch, with
+ * rejectors between the search and the sums and a second estimator.  The arithmetic is csrc/register_icp.h (compiled by g++
+ * and hipcc without contraction; the device equals the host build bit for bit).  PCL parity is UNPINNED.
+ *  1 refusals: whatever f-17 rule 1 refuses; trim outside (0, 1] or NaN; metric or one_to_one not 0 or 1; normal_stride not 3
+ *    or 4; metric 1 without normals or with eps not > 0; min_pairs below the unknowns (3 for metric 0; 6, with scale 7, for
+ *    metric 1).  Empty inputs as in f-17 rule 1.
+ *  2 the search: f-17 rules 2 - 3 (the nearest finite target point by (d2, index), the source's cell order, max_dist).
+ *  3 no plane (metric 1): a pair whose target normal has a non-finite component or is exactly (0, 0, 0) is dropped.  Normals
+ *    are used as given (not renormalised) and uploaded once per call.
+ *  4 one-to-one: among the surviving sources that chose target j only the one of least (d2, source index) survives.
+ *  5 trim: N survivors; K = ceil(trim N) in f64, at least 1 when N >= 1; tau = the K-th smallest d2; every survivor with
+ *    d2 <= tau is kept (ties at tau all stay: the kept count can exceed K).  N = 0 or trim = 1: tau = +inf.
+ *  6 a dropped pair reports idx -1; pairs, mse, plane_mse and trim_d2 describe the kept set under the returned transform.
+ *  7 metric 0: f-17 rules 4 - 6 on the kept pairs (the fixed-point stop: the kept set did not change).  With trim = 1 and
+ *    one_to_one = 0 the call returns sfmhip_cloud_register's bytes.
+ *  8 metric 1, the step: c = 0.5 (lo + hi) of the target's finite box, f64.  Per kept pair q (the moved source float), m, n
+ *    widened: r = (n0 (q0 - m0) + n1 (q1 - m1)) + n2 (q2 - m2); qt = q - c; the row a = (qt x n, n, with_scale ? (n0 qt0 + n1
+ *    qt1) + n2 qt2 : 0).  One pass of f64 sums in f-17 rule 4's order: N, a_i a_j (i <= j), a_i r, r r, (double)d2.  (a^T a) x
+ *    = -(a^T r) by Cholesky in one written order (csrc/register_icp.h, plane_solve); DEGENERATE when a pivot is not > 1e-12
+ *    times the largest diagonal entry or anything is non-finite (a target that is one plane is).  omega = x[0..2]: v = omega /
+ *    2, vv = (v0 v0 + v1 v1) + v2 v2, dR = I + (2 (1 / (1 + vv))) ([v]x + (v v^T - vv I)); g = 1 + x[6] (1 without scale),
+ *    finite and > 0 or DEGENERATE.  scale' = scale g; R' = dR R, each entry (a0 b0 + a1 b1) + a2 b2; t'_r = (g (dR (t - c))_r +
+ *    c_r) + x[3 + r].
+ *  9 metric 1, the loop: as f-17 rule 6 without the fixed-point stop: FEW; k > 0 and within eps: converged 2; k == max_iters:
+ *    converged 0; else the step.
+ * 10 the batch: results[b] and row b of idx are byte-equal to the single call from inits[b]; n_init in 1..1024. */
+typedef struct sfmhip_icp_opts {
+  int32_t max_iters;     /* 50 */
+  int32_t with_scale;    /* 0 rigid, 1 similarity */
+  int32_t min_pairs;     /* 3 for metric 0; at least 6 (7 with scale) for metric 1 */
+  int32_t metric;        /* 0 point-to-point, 1 point-to-plane */
+  int32_t one_to_one;    /* 1: a target point keeps only its best source */
+  int32_t normal_stride; /* 3 or 4 (what sfmhip_cloud_normals writes); default 4 */
+  double max_dist;       /* as f-17 */
+  double eps;            /* metric 0: as f-17, default 0.  metric 1: must be > 0 */
+  double trim;           /* (0, 1]; 1: off.  The fraction of the surviving pairs that is kept */
+} sfmhip_icp_opts;
+typedef struct sfmhip_icp_result {
+  sfmhip_transform T;
+  int32_t iterations, pairs, converged, flags; /* as sfmhip_register_result; pairs = the kept ones */
+  double mse;       /* mean (double)d2 over the kept pairs */
+  double plane_mse; /* mean r^2 over the kept pairs (metric 1; NaN for metric 0) */
+  double trim_d2;   /* the trim threshold tau of the last pair set (+inf with trim = 1) */
+} sfmhip_icp_result;
+void sfmhip_icp_default_opts(sfmhip_icp_opts* opts);
+/* target_normals: host, one row of normal_stride floats per target point; NULL allowed for metric 0.  opts: NULL for the
+ * defaults; init: NULL for the identity; idx: NULL or one entry per source point, the kept pairs under out->T */
+int sfmhip_cloud_register_icp(sfmhip_cloud* target, sfmhip_cloud* source, const float* target_normals, const sfmhip_icp_opts* opts,
+                              const sfmhip_transform* init, sfmhip_icp_result* out, int32_t* idx);
+/* results: n_init entries; idx: NULL or n_init rows of one entry per source point */
+int sfmhip_cloud_register_icp_batch(sfmhip_cloud* target, sfmhip_cloud* source, const float* target_normals, const sfmhip_icp_opts* opts,
+                                    const sfmhip_transform* inits, int n_init, sfmhip_icp_result* results, int32_t* idx);
+/* With sfmhip_set_timing on (zeros while it is off): host-clock ms of the last call of either entry with this target, summed
+ * over its iterations -- search, rejectors, sums, update + the record's read -- and the iterations of its longest problem. */
+int sfmhip_cloud_register_icp_last_timing(sfmhip_cloud* target, double ms4[4], int32_t* iterations);
+
 /* ---- the second half of create_mesh: Poisson surface reconstruction (reference src/Sfm.cpp:1365-1381) ----
  * pcl::Poisson at depth 7 on the cloud and its flipped normals, as a screened Poisson solve on the same device-resident
  * cloud.  The rules (PCL 1.8.1 parity is UNPINNED -- PCL is absent and its solver is an adaptive octree):

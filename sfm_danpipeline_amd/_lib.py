@@ -82,6 +82,7 @@ SYMBOLS = [
     "sfmhip_cloud_register_last_timing",
     "sfmhip_align_default_opts", "sfmhip_frame_from_ground", "sfmhip_cloud_register_batch", "sfmhip_cloud_register_batch_last_timing",
     "sfmhip_cloud_align_vote", "sfmhip_cloud_align", "sfmhip_cloud_align_last_timing",
+    "sfmhip_icp_default_opts", "sfmhip_cloud_register_icp", "sfmhip_cloud_register_icp_batch", "sfmhip_cloud_register_icp_last_timing",
     "sfmhip_terrain_default_opts", "sfmhip_terrain_opts_from_ground", "sfmhip_cloud_terrain", "sfmhip_cloud_terrain_raster",
     "sfmhip_cloud_terrain_normalize", "sfmhip_cloud_terrain_last_timing",
     "sfmhip_crowns_default_opts", "sfmhip_chm_crowns", "sfmhip_cloud_crowns", "sfmhip_cloud_crowns_raster",
@@ -263,6 +264,11 @@ def lib():
         L.sfmhip_cloud_align_vote.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
         L.sfmhip_cloud_align.argtypes = [vp, vp, vp, vp, vp, vp]
         L.sfmhip_cloud_align_last_timing.argtypes = [vp, vp]
+        L.sfmhip_icp_default_opts.argtypes = [vp]
+        L.sfmhip_icp_default_opts.restype = None
+        L.sfmhip_cloud_register_icp.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.sfmhip_cloud_register_icp_batch.argtypes = [vp, vp, vp, vp, vp, cint, vp, vp]
+        L.sfmhip_cloud_register_icp_last_timing.argtypes = [vp, vp, vp]
         L.sfmhip_terrain_default_opts.argtypes = [vp]
         L.sfmhip_terrain_default_opts.restype = None
         L.sfmhip_terrain_opts_from_ground.argtypes = [vp, vp]

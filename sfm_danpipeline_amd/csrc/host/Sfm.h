@@ -247,6 +247,12 @@ class StructFromMotion {
   // record.  max_dist: reference units, +inf keeps every pair.  Nothing calls it by default.
   double registerCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, const pcl::PointCloud<pcl::PointXYZ>& reference, double* scale_out = nullptr,
                        double max_dist = INFINITY, const sfmhip_transform* guess = nullptr, sfmhip_register_result* result = nullptr);
+  // (ours) the same through sfmhip_cloud_register_icp with the caller's options: the trimmed and one-to-one
+  // rejectors, and with opts.metric 1 the point-to-plane metric against `reference_normals` (opts.normal_stride floats per
+  // reference point; NULL: the reference's own k-NN normals, sfmhip_cloud_normals with k = 10, stride 4).  Returns
+  // result->T.scale, 0 when a flag is set.
+  double registerCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, const pcl::PointCloud<pcl::PointXYZ>& reference, const sfmhip_icp_opts& opts,
+                       const float* reference_normals = nullptr, const sfmhip_transform* guess = nullptr, sfmhip_icp_result* result = nullptr);
 
   // (ours) the starting guess registerCloud needs when `cloud` and `reference` stand in unrelated gauges (two
   // reconstructions of one plot): each cloud is levelled by its own ground plane (sfmhip_cloud_ground_plane with `ground`, NULL:

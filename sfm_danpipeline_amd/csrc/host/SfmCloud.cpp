@@ -158,6 +158,30 @@ double StructFromMotion::registerCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& clou
   return scale;
 }
 
+double StructFromMotion::registerCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, const pcl::PointCloud<pcl::PointXYZ>& reference,
+                                       const sfmhip_icp_opts& opts, const float* reference_normals, const sfmhip_transform* guess,
+                                       sfmhip_icp_result* result) {
+  sfmhip_cloud* ref = nullptr;
+  check(sfmhip_cloud_create(sfm_hip_context(), (int)reference.size(), reference.size() ? &reference.points[0].x : nullptr, &ref),
+        "sfmhip_cloud_create");
+  sfmhip_icp_opts o = opts;
+  std::vector<float> own;
+  int rc = SFMHIP_OK;
+  if (o.metric == 1 && !reference_normals) {  // the reference's own normals, towards the origin as create_mesh takes them
+    own.resize(4 * reference.size() + 4);
+    const float vp[3] = {0.0f, 0.0f, 0.0f};
+    rc = sfmhip_cloud_normals(ref, 10, vp, own.data());
+    reference_normals = own.data();
+    o.normal_stride = 4;
+  }
+  sfmhip_icp_result res;
+  if (rc == SFMHIP_OK) rc = sfmhip_cloud_register_icp(ref, device_cloud(*cloud), reference_normals, &o, guess, &res, nullptr);
+  sfmhip_cloud_destroy(ref);
+  check(rc, "sfmhip_cloud_register_icp");
+  if (result) *result = res;
+  return res.flags == 0 ? res.T.scale : 0.0;
+}
+
 int StructFromMotion::alignPlots(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, const pcl::PointCloud<pcl::PointXYZ>& reference,
                                  const sfmhip_align_opts& opts, sfmhip_align_result* result, const sfmhip_ground_opts* ground) {
   sfmhip_cloud* ref = nullptr;

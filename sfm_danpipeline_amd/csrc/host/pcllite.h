@@ -443,6 +443,9 @@ class StatisticalOutlierRemoval {
 // ---- pcl::IterativeClosestPoint, its similarity form and pcl::transformPointCloud with PCL's setters, forwarding to
 // sfmhip_cloud_register / sfmhip_cloud_transform (include/sfmhip.h, DESIGN.md f-17 rules 1-8).  The matrix is the 4 x 4 float
 // one PCL code reads the result from.  Not mirrored: reciprocal correspondences, RANSAC rejection, the Euclidean fitness epsilon.
+// The rejectors of DESIGN.md f-22 are setters here (setTrimFraction: CorrespondenceRejectorTrimmed's overlap ratio; setOneToOne:
+// CorrespondenceRejectorOneToOne), and pcl::IterativeClosestPointWithNormals is its point-to-plane metric; a call that uses
+// any of them goes through sfmhip_cloud_register_icp, every other call through sfmhip_cloud_register as before.
 }  // namespace pcl
 
 namespace Eigen {
@@ -514,6 +517,8 @@ class IterativeClosestPoint {
   void setMaximumIterations(int n) { max_iters_ = n; }
   void setTransformationEpsilon(double e) { eps_ = e; }
   void setEstimateScale(bool on) { with_scale_ = on; }  // (ours: TransformationEstimationSVDScale in place of ...SVD)
+  void setTrimFraction(double keep) { trim_ = keep; }    // (ours: the kept fraction of the surviving pairs, (0, 1]; 1: off)
+  void setOneToOne(bool on) { one_to_one_ = on; }        // (ours: a target point keeps only its best source)
   void align(PointCloud<PointSource>& output) { align(output, Eigen::Matrix4f::Identity()); }
   // the source under the final transformation; a guess must be a similarity with finite entries
   void align(PointCloud<PointSource>& output, const Eigen::Matrix4f& guess) {
@@ -524,7 +529,20 @@ class IterativeClosestPoint {
     o.max_iters = max_iters_, o.with_scale = with_scale_ ? 1 : 0, o.max_dist = max_dist_, o.eps = eps_;
     const sfmhip_transform init = detail::to_transform(guess);
     sfmhip_cloud *hs = detail::upload(src), *ht = detail::upload(tgt), *moved = nullptr;
-    int rc = sfmhip_cloud_register(ht, hs, &o, &init, &result_, nullptr);
+    int rc;
+    if (metric_ == 0 && trim_ == 1.0 && !one_to_one_) {
+      rc = sfmhip_cloud_register(ht, hs, &o, &init, &result_, nullptr);
+      icp_result_ = sfmhip_icp_result();
+    } else {  // f-22: the rejectors and the plane metric
+      sfmhip_icp_opts io;
+      sfmhip_icp_default_opts(&io);
+      io.max_iters = o.max_iters, io.with_scale = o.with_scale, io.max_dist = o.max_dist, io.eps = o.eps;
+      io.metric = metric_, io.one_to_one = one_to_one_ ? 1 : 0, io.trim = trim_, io.normal_stride = 3;
+      if (metric_ == 1) io.min_pairs = with_scale_ ? 7 : 6, io.eps = eps_ > 0.0 ? eps_ : 1e-9;  // (the metric needs an eps)
+      rc = sfmhip_cloud_register_icp(ht, hs, metric_ == 1 ? normals_.data() : nullptr, &io, &init, &icp_result_, nullptr);
+      result_.T = icp_result_.T, result_.iterations = icp_result_.iterations, result_.pairs = icp_result_.pairs;
+      result_.converged = icp_result_.converged, result_.flags = icp_result_.flags, result_.mse = icp_result_.mse;
+    }
     if (rc == SFMHIP_OK) rc = sfmhip_cloud_transform(hs, &result_.T, &moved);
     sfmhip_cloud_destroy(hs);
     sfmhip_cloud_destroy(ht);
@@ -536,14 +554,19 @@ class IterativeClosestPoint {
   double getFitnessScore() const { return result_.mse; }
   Eigen::Matrix4f getFinalTransformation() const { return detail::to_matrix(result_.T); }
   const sfmhip_register_result& result() const { return result_; }  // (ours: the f64 transform, the counts and the flags)
+  const sfmhip_icp_result& icpResult() const { return icp_result_; }  // (ours: plane_mse and trim_d2 too; zeros after an f-17 call)
 
  protected:
   typename PointCloud<PointSource>::Ptr source_;
   typename PointCloud<PointTarget>::Ptr target_;
   double max_dist_ = INFINITY, eps_ = 0.0;  // PCL: sqrt(DBL_MAX) and 0
   int max_iters_ = 10;                      // PCL's default
-  bool with_scale_ = false;
+  bool with_scale_ = false, one_to_one_ = false;
+  double trim_ = 1.0;
+  int metric_ = 0;               // 1: set by IterativeClosestPointWithNormals
+  std::vector<float> normals_;   // ... with the target's normals, 3 floats a point
   sfmhip_register_result result_ = sfmhip_register_result();
+  sfmhip_icp_result icp_result_ = sfmhip_icp_result();
 };
 
 // (ours) the similarity form under a name of its own
@@ -551,6 +574,24 @@ template <typename PointSource, typename PointTarget>
 class IterativeClosestPointWithScale : public IterativeClosestPoint<PointSource, PointTarget> {
  public:
   IterativeClosestPointWithScale() { this->with_scale_ = true; }
+};
+
+// pcl::IterativeClosestPointWithNormals: the point-to-plane metric (f-22 rule 8) against the normals the target's points carry
+// (a PointNormal target); a target row whose normal is zero or non-finite takes no part
+template <typename PointSource, typename PointTarget>
+class IterativeClosestPointWithNormals : public IterativeClosestPoint<PointSource, PointTarget> {
+ public:
+  IterativeClosestPointWithNormals() { this->metric_ = 1; }
+  void align(PointCloud<PointSource>& output) { align(output, Eigen::Matrix4f::Identity()); }
+  void align(PointCloud<PointSource>& output, const Eigen::Matrix4f& guess) {
+    const size_t n = this->target_ ? this->target_->size() : 0;
+    this->normals_.assign(3 * n + 3, 0.0f);
+    for (size_t i = 0; i < n; ++i) {
+      const PointTarget& p = this->target_->points[i];
+      this->normals_[3 * i] = p.normal_x, this->normals_[3 * i + 1] = p.normal_y, this->normals_[3 * i + 2] = p.normal_z;
+    }
+    IterativeClosestPoint<PointSource, PointTarget>::align(output, guess);
+  }
 };
 
 }  // namespace pcl

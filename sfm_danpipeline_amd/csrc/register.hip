@@ -23,7 +23,7 @@
 #include "cloud.h"
 #include "cloud_grid.h"
 #include "block_sum.h"
-#include "register.h"
+#include "register_icp.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -306,7 +306,353 @@ int launch_iteration(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, const in
   return SFMHIP_OK;
 }
 
+// ---------------------------------------------------------------- f-22: the rejectors and the point-to-plane step
+// The second entry runs reg_nearest as it is (into the raw row idx / d2, nothing tracked), then the rejectors of f-22 rules
+// 3 - 5 into a row of kept pairs, then either f-17's own sums and update on that row (metric 0) or icp_plane_sums /
+// icp_plane_update (metric 1).  The loop's record is f-17's DevLoop, so the search reads its transform and its stop flag from
+// where it always did; what the plane metric and the trim add is an IcpExtra per problem.  icp_survive: rule 3 and, with
+// one_to_one, an unsigned 64-bit atomicMin of (bits(d2) << 32 | i) into the target's slot; icp_unique: a source stays when its
+// slot names it (a loser keeps its target as -(j + 2), so icp_keep can clear the slot by a plain store: the slots are all
+// "empty" again after every iteration).  The trim's tau: a radix select over the float's bits, four digits of 8, a 256-bin
+// integer histogram per digit (LDS atomics, then one global atomicAdd per occupied bin: exact whatever the order) and one wave
+// that finds the digit.  icp_keep writes the kept row, raises "changed" and records tau.  The problem is grid dimension y
+// throughout.  No spins, no hand-offs between workgroups, no float atomics.
+struct Sel {  // the select's state of one problem
+  uint32_t prefix, k, n;
+  float tau;
+};
+struct Centre {
+  double c[3];
+};
+
+struct IcpState {  // on the TARGET handle, beside f-17's (which does not move)
+  static constexpr sfmgrid::Stage slot = sfmgrid::REGISTER_ICP;
+  Grow<int> cand, kept;
+  Grow<unsigned long long> slots;
+  Grow<uint32_t> hist;
+  Grow<Sel> sel;
+  Grow<sfmreg::IcpExtra> extra;
+  Grow<double> part;
+  Grow<float> normals;
+  double ms[4] = {0, 0, 0, 0};  // search, rejectors, sums, update of the last call
+  int iterations = 0;           // ... of its longest problem
+};
+
+__global__ __launch_bounds__(256) void icp_survive(const int* idx, const float* d2, const float* normals, int stride, int metric, int one_to_one,
+                                                   int n_src, int n_tgt, const DevLoop* rec, size_t row, int* cand, unsigned long long* slot) {
+  if (rec[blockIdx.y].L.stop) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_src) return;
+  idx += row * blockIdx.y, d2 += row * blockIdx.y, cand += row * blockIdx.y;
+  int j = idx[i];
+  if (j >= 0 && metric == sfmreg::METRIC_PLANE) {
+    const float* n = normals + (size_t)stride * j;
+    if (!sfmreg::has_plane(n[0], n[1], n[2])) j = -1;
+  }
+  cand[i] = j;
+  if (one_to_one && j >= 0) atomicMin(&slot[(size_t)n_tgt * blockIdx.y + j], (unsigned long long)sfmreg::slot_of(d2[i], i));
+}
+
+__global__ __launch_bounds__(256) void icp_unique(int n_src, int n_tgt, const DevLoop* rec, size_t row, int* cand, const unsigned long long* slot) {
+  if (rec[blockIdx.y].L.stop) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_src) return;
+  cand += row * blockIdx.y;
+  const int j = cand[i];
+  if (j >= 0 && sfmreg::slot_source(slot[(size_t)n_tgt * blockIdx.y + j]) != i) cand[i] = sfmreg::lost(j);
+}
+
+// digit `pass` (0: the top 8 bits) of the survivors whose higher digits equal the select's prefix
+__global__ __launch_bounds__(256) void icp_hist(const int* cand, const float* d2, int n_src, const DevLoop* rec, size_t row, const Sel* sel, int pass,
+                                                uint32_t* hist) {
+  __shared__ uint32_t bins[256];
+  if (rec[blockIdx.y].L.stop) return;  // (uniform over the workgroup)
+  cand += row * blockIdx.y, d2 += row * blockIdx.y, hist += ((size_t)blockIdx.y * 4 + pass) * 256;
+  bins[threadIdx.x] = 0;
+  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_src && cand[i] >= 0) {
+    const uint32_t b = sfmreg::d2_bits(d2[i]);
+    const int low = 32 - 8 * pass;  // the bits below the digits already fixed
+    const bool match = pass == 0 || (b >> low) == (sel[blockIdx.y].prefix >> low);
+    if (match) atomicAdd(&bins[(b >> (24 - 8 * pass)) & 255u], 1u);
+  }
+  __syncthreads();
+  if (bins[threadIdx.x]) atomicAdd(&hist[threadIdx.x], bins[threadIdx.x]);
+}
+
+// one wave per problem: the bin in which the k-th smallest lies; lane l holds bins 4 l .. 4 l + 3
+__global__ __launch_bounds__(64) void icp_pick(const uint32_t* hist, int pass, double trim, const DevLoop* rec, Sel* sel) {
+  if (rec[blockIdx.x].L.stop) return;
+  hist += ((size_t)blockIdx.x * 4 + pass) * 256;
+  sel += blockIdx.x;
+  const int l = threadIdx.x;
+  uint32_t c[4], sum = 0;
+  for (int q = 0; q < 4; ++q) c[q] = hist[4 * l + q], sum += c[q];
+  uint32_t incl = sum;
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t up = __shfl_up(incl, off);
+    if (l >= off) incl += up;
+  }
+  const uint32_t total = __shfl(incl, 63);
+  const uint32_t n = pass == 0 ? total : sel->n;
+  if (n == 0) {  // rule 5 without a survivor: nothing to trim
+    if (pass == 0 && l == 0) sel->prefix = 0, sel->k = 0, sel->n = 0, sel->tau = sfmreg::inf_f();
+    return;
+  }
+  const uint32_t k = pass == 0 ? sfmreg::trim_count(trim, n) : sel->k;
+  const uint32_t prefix = pass == 0 ? 0u : sel->prefix;
+  uint32_t cum = incl - sum;
+  if (cum < k && k <= incl) {  // (one lane: 1 <= k <= total)
+    int digit = 4 * l + 3;
+    bool found = false;
+    for (int q = 0; q < 4; ++q) {
+      if (found) continue;
+      if (k <= cum + c[q]) digit = 4 * l + q, found = true;
+      else cum += c[q];
+    }
+    const uint32_t p = prefix | ((uint32_t)digit << (24 - 8 * pass));
+    sel->prefix = p, sel->k = k - cum, sel->n = n;
+    if (pass == 3) sel->tau = sfmcloud::bits_f(p);
+  }
+}
+
+// rule 5's cut and rule 6's row: kept[i] is the pair of source i or -1; a slot that was written goes back to "empty"
+__global__ __launch_bounds__(256) void icp_keep(const int* cand, const float* d2, int n_src, int n_tgt, DevLoop* rec, size_t row, const Sel* sel,
+                                                int one_to_one, unsigned long long* slot, int* kept, sfmreg::IcpExtra* extra) {
+  rec += blockIdx.y;
+  if (rec->L.stop) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_src) return;
+  cand += row * blockIdx.y, d2 += row * blockIdx.y, kept += row * blockIdx.y;
+  const float tau = sel ? sel[blockIdx.y].tau : sfmreg::inf_f();
+  const int c = cand[i];
+  const int out = c >= 0 && d2[i] <= tau ? c : -1;
+  if (kept[i] != out) rec->changed = 1;
+  kept[i] = out;
+  if (one_to_one) {
+    const int j = c >= 0 ? c : c <= -2 ? sfmreg::lost_target(c) : -1;
+    if (j >= 0) slot[(size_t)n_tgt * blockIdx.y + j] = sfmreg::SLOT_EMPTY;
+  }
+  if (i == 0) extra[blockIdx.y].trim_d2 = (double)tau;
+}
+
+// rule 8's one pass: 256 source points per workgroup, NP sums through block_tree
+__global__ __launch_bounds__(SUM_BLOCK) void icp_plane_sums(const float* src, const float* tgt, const float* normals, int stride, const int* kept,
+                                                           const float* d2, int n_src, const DevLoop* rec, size_t row, Centre ctr, int with_scale,
+                                                           double* part) {
+  constexpr int NP = sfmreg::NP;
+  __shared__ double sh[NP][4];
+  rec += blockIdx.y;
+  if (rec->L.stop) return;  // (uniform over the workgroup)
+  kept += row * blockIdx.y, d2 += row * blockIdx.y, part += (size_t)gridDim.x * NP * blockIdx.y;
+  const int i = blockIdx.x * SUM_BLOCK + threadIdx.x;
+  float q[3] = {0.0f, 0.0f, 0.0f}, m[3] = {0.0f, 0.0f, 0.0f}, n[3] = {0.0f, 0.0f, 0.0f}, dd = 0.0f;
+  bool on = false;
+  if (i < n_src) {
+    const int j = kept[i];
+    on = j >= 0;
+    if (on) {
+      const Transform T = rec->L.T;
+      sfmreg::move(T, src[3 * (size_t)i], src[3 * (size_t)i + 1], src[3 * (size_t)i + 2], q);
+      for (int a = 0; a < 3; ++a) m[a] = tgt[3 * (size_t)j + a], n[a] = normals[(size_t)stride * j + a];
+      dd = d2[i];
+    }
+  }
+  double v[NP];
+  sfmreg::plane_terms(on, q, m, n, dd, ctr.c, with_scale, v);
+  // block_sum.h's block_tree, unrolled (NP sums stay in registers): the same butterfly, the same pairing
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    double x = v[k];
+    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off);
+    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < NP) {
+    const double w = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
+    part[(size_t)blockIdx.x * NP + threadIdx.x] = w;
+  }
+}
+
+// the partials in ascending block order, a lane per sum; then rule 9's step on lane 0
+__global__ __launch_bounds__(64) void icp_plane_update(const double* part, int n_blocks, sfmreg::IcpOpts o, Centre ctr, DevLoop* rec,
+                                                       sfmreg::IcpExtra* extra) {
+  constexpr int NP = sfmreg::NP;
+  __shared__ double s[NP];
+  const int k = threadIdx.x;
+  rec += blockIdx.x, part += (size_t)n_blocks * NP * blockIdx.x;
+  if (rec->L.stop) return;
+  if (k < NP) {
+    double a = 0.0;
+    for (int b = 0; b < n_blocks; ++b) a = a + part[(size_t)b * NP + k];
+    s[k] = a;
+  }
+  __syncthreads();
+  if (k == 0) {
+    double t[NP];
+    for (int q = 0; q < NP; ++q) t[q] = s[q];
+    sfmreg::plane_loop_step(rec->L, extra[blockIdx.x], o, ctr.c, t);
+    rec->changed = 0;
+  }
+}
+
+// one iteration of the second entry for n_init problems.  t (nullable): host-clock ms added to search / rejectors / sums /
+// update, a stream synchronisation between them
+int launch_icp_iteration(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, IcpState* z, const int* order, const sfmreg::IcpOpts& o, float md2,
+                         const Centre& ctr, int n_init, double* t) {
+  hipStream_t st = tgt->ctx->stream;
+  const int n = src->n, nb = (int)blocks(n, SUM_BLOCK), nt = tgt->n;
+  const size_t row = (size_t)n;
+  DevLoop* rec = s->rec.p;
+  const bool trim = o.trim < 1.0;
+  double t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+  if (t) t0 = sfm_now_ms();
+  launch_nearest(tgt, src, s, order, md2, false, false, n_init);
+  SFM_HIP_TRY(hipGetLastError());
+  if (t) {
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+    t1 = sfm_now_ms();
+  }
+  if (nb > 0) {
+    const dim3 grid(nb, n_init);
+    hipLaunchKernelGGL(icp_survive, grid, dim3(256), 0, st, s->idx.p, s->d2.p, z->normals.p, o.normal_stride, o.metric, o.one_to_one, n, nt, rec, row,
+                       z->cand.p, z->slots.p);
+    if (o.one_to_one) hipLaunchKernelGGL(icp_unique, grid, dim3(256), 0, st, n, nt, rec, row, z->cand.p, z->slots.p);
+    if (trim) {
+      SFM_HIP_TRY(hipMemsetAsync(z->hist.p, 0, sizeof(uint32_t) * 1024 * (size_t)n_init, st));
+      for (int pass = 0; pass < 4; ++pass) {
+        hipLaunchKernelGGL(icp_hist, grid, dim3(256), 0, st, z->cand.p, s->d2.p, n, rec, row, z->sel.p, pass, z->hist.p);
+        hipLaunchKernelGGL(icp_pick, dim3(n_init), dim3(64), 0, st, z->hist.p, pass, o.trim, rec, z->sel.p);
+      }
+    }
+    hipLaunchKernelGGL(icp_keep, grid, dim3(256), 0, st, z->cand.p, s->d2.p, n, nt, rec, row, trim ? z->sel.p : nullptr, o.one_to_one, z->slots.p,
+                       z->kept.p, z->extra.p);
+  }
+  SFM_HIP_TRY(hipGetLastError());
+  if (t) {
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+    t2 = sfm_now_ms();
+  }
+  if (o.metric == sfmreg::METRIC_POINT) {
+    if (nb > 0) hipLaunchKernelGGL(reg_sums1, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, z->kept.p, n, rec, row, s->part1.p);
+    hipLaunchKernelGGL(reg_means, dim3(n_init), dim3(64), 0, st, s->part1.p, nb, rec);
+    if (nb > 0)
+      hipLaunchKernelGGL(reg_sums2, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, z->kept.p, s->d2.p, n, rec, row, s->part2.p);
+  } else if (nb > 0) {
+    hipLaunchKernelGGL(icp_plane_sums, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, z->normals.p, o.normal_stride, z->kept.p,
+                       s->d2.p, n, rec, row, ctr, o.with_scale, z->part.p);
+  }
+  SFM_HIP_TRY(hipGetLastError());
+  if (t) {
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+    t3 = sfm_now_ms();
+  }
+  if (o.metric == sfmreg::METRIC_POINT) hipLaunchKernelGGL(reg_update, dim3(n_init), dim3(64), 0, st, s->part2.p, nb, sfmreg::point_opts(o), rec);
+  else hipLaunchKernelGGL(icp_plane_update, dim3(n_init), dim3(64), 0, st, z->part.p, nb, o, ctr, rec, z->extra.p);
+  SFM_HIP_TRY(hipGetLastError());
+  if (t) t[0] += t1 - t0, t[1] += t2 - t1, t[2] += t3 - t2, t[3] -= t3;  // (the caller adds the clock after the record's read)
+  return SFMHIP_OK;
+}
+
+// both entries: n_init starts in one lock-step loop (a single call: one start, the source walked in cell order)
+int run_icp(sfmhip_cloud* tgt, sfmhip_cloud* src, const float* normals, const sfmreg::IcpOpts& o, const Transform* inits, int n_init, bool single,
+            sfmhip_icp_result* out, int32_t* idx) {
+  RegState* s = nullptr;
+  SFM_TRY(prepare(tgt, src, &s, n_init));
+  IcpState* z = stage<IcpState>(tgt);
+  hipStream_t st = tgt->ctx->stream;
+  const bool timing = tgt->ctx->timing;
+  const int n = src->n;
+  const size_t n1 = (size_t)std::max(n, 1), nt1 = (size_t)std::max(tgt->n, 1), B = (size_t)n_init, nb = blocks(n1, SUM_BLOCK);
+  const bool plane = o.metric == sfmreg::METRIC_PLANE;
+  SFM_TRY(z->cand.need(B * n1));
+  SFM_TRY(z->kept.need(B * n1));
+  SFM_TRY(z->extra.need(B));
+  SFM_TRY(z->slots.need(o.one_to_one ? B * nt1 : 1));
+  SFM_TRY(z->hist.need(B * 1024));
+  SFM_TRY(z->sel.need(B));
+  SFM_TRY(z->part.need(plane ? B * nb * sfmreg::NP : 1));
+  SFM_TRY(z->normals.need(plane ? nt1 * (size_t)o.normal_stride : 1));
+  if (plane && tgt->n > 0)  // rule 3: once per call
+    SFM_HIP_TRY(hipMemcpyAsync(z->normals.p, normals, sizeof(float) * (size_t)tgt->n * o.normal_stride, hipMemcpyHostToDevice, st));
+  if (o.one_to_one) SFM_HIP_TRY(hipMemsetAsync(z->slots.p, 0xFF, sizeof(unsigned long long) * B * nt1, st));
+  Centre ctr;
+  sfmreg::box_centre(tgt->n_valid, tgt->lo, tgt->hi, ctr.c);
+  const float md2 = sfmreg::max_d2(o.max_dist);
+  for (double& m : z->ms) m = 0;
+  z->iterations = 0;
+  std::vector<DevLoop> h(B);
+  std::vector<sfmreg::IcpExtra> ex(B);
+  memset(h.data(), 0, sizeof(DevLoop) * B);
+  for (size_t b = 0; b < B; ++b) sfmreg::loop_init(h[b].L, inits[b]), ex[b].plane_mse = sfmreg::qnan_d(), ex[b].trim_d2 = sfmreg::inf_d();
+  DevLoop* rec = s->rec.p;
+  SFM_HIP_TRY(hipMemcpyAsync(rec, h.data(), sizeof(DevLoop) * B, hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemcpyAsync(z->extra.p, ex.data(), sizeof(sfmreg::IcpExtra) * B, hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemsetAsync(z->kept.p, 0xFE, sizeof(int) * B * n1, st));  // (no index: C_0 differs from it)
+  const int* order = nullptr;
+  if (single) {
+    const double ts = timing ? sfm_now_ms() : 0.0;
+    SFM_TRY(sort_source(tgt, src, s, &rec->L.T, &order));
+    if (timing) {
+      SFM_HIP_TRY(hipStreamSynchronize(st));
+      z->ms[0] = sfm_now_ms() - ts;  // (the source's cell order counts as search)
+    }
+  }
+  for (int round = 0;; ++round) {
+    SFM_TRY(launch_icp_iteration(tgt, src, s, z, order, o, md2, ctr, n_init, timing ? z->ms : nullptr));
+    SFM_HIP_TRY(hipMemcpyAsync(h.data(), rec, sizeof(DevLoop) * B, hipMemcpyDeviceToHost, st));  // the block of records, once
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+    if (timing) z->ms[3] += sfm_now_ms();
+    bool all = true;
+    for (size_t b = 0; b < B; ++b) {
+      if (h[b].L.k < 0 || h[b].L.k > o.max_iters) return SFMHIP_ERR_STATE;
+      all = all && h[b].L.stop;
+    }
+    if (all) break;
+    if (round >= o.max_iters) return SFMHIP_ERR_STATE;  // (a problem stops at k == max_iters at the latest)
+  }
+  SFM_HIP_TRY(hipMemcpyAsync(ex.data(), z->extra.p, sizeof(sfmreg::IcpExtra) * B, hipMemcpyDeviceToHost, st));
+  if (idx && n > 0) SFM_HIP_TRY(hipMemcpyAsync(idx, z->kept.p, sizeof(int) * B * (size_t)n, hipMemcpyDeviceToHost, st));
+  SFM_HIP_TRY(hipStreamSynchronize(st));
+  for (size_t b = 0; b < B; ++b) {
+    out[b] = mirror<sfmhip_icp_result>(sfmreg::icp_result(h[b].L.res, ex[b]));
+    z->iterations = std::max(z->iterations, (int)h[b].L.res.iterations);
+  }
+  return SFMHIP_OK;
+}
+
 }  // namespace
+
+extern "C" void sfmhip_icp_default_opts(sfmhip_icp_opts* o) {
+  if (o) *o = mirror<sfmhip_icp_opts>(sfmreg::default_icp_opts());
+}
+
+extern "C" int sfmhip_cloud_register_icp(sfmhip_cloud* tgt, sfmhip_cloud* src, const float* target_normals, const sfmhip_icp_opts* opts,
+                                         const sfmhip_transform* init, sfmhip_icp_result* out, int32_t* idx) {
+  if (!tgt || !src || !out || tgt->ctx != src->ctx) return SFMHIP_ERR_ARG;
+  const sfmreg::IcpOpts o = opts ? mirror<sfmreg::IcpOpts>(*opts) : sfmreg::default_icp_opts();
+  const Transform T0 = init ? mirror<Transform>(*init) : sfmreg::identity();
+  if (!sfmreg::valid_icp_batch(o, target_normals != nullptr, &T0, 1)) return SFMHIP_ERR_ARG;
+  return run_icp(tgt, src, target_normals, o, &T0, 1, true, out, idx);
+}
+
+extern "C" int sfmhip_cloud_register_icp_batch(sfmhip_cloud* tgt, sfmhip_cloud* src, const float* target_normals, const sfmhip_icp_opts* opts,
+                                               const sfmhip_transform* inits, int n_init, sfmhip_icp_result* out, int32_t* idx) {
+  if (!tgt || !src || !out || !inits || tgt->ctx != src->ctx) return SFMHIP_ERR_ARG;
+  const sfmreg::IcpOpts o = opts ? mirror<sfmreg::IcpOpts>(*opts) : sfmreg::default_icp_opts();
+  static_assert(sizeof(sfmhip_transform) == sizeof(Transform), "the C ABI mirrors register.h");
+  if (!sfmreg::valid_icp_batch(o, target_normals != nullptr, (const Transform*)inits, n_init)) return SFMHIP_ERR_ARG;
+  return run_icp(tgt, src, target_normals, o, (const Transform*)inits, n_init, false, out, idx);
+}
+
+extern "C" int sfmhip_cloud_register_icp_last_timing(sfmhip_cloud* tgt, double ms4[4], int32_t* iterations) {
+  if (!tgt || !ms4) return SFMHIP_ERR_ARG;
+  const IcpState* z = stage<IcpState>(tgt);
+  for (int i = 0; i < 4; ++i) ms4[i] = z->ms[i];
+  if (iterations) *iterations = z->iterations;
+  return SFMHIP_OK;
+}
 
 extern "C" void sfmhip_register_default_opts(sfmhip_register_opts* o) {
   if (o) *o = mirror<sfmhip_register_opts>(sfmreg::default_opts());

@@ -12,7 +12,12 @@ The coarse alignment needs no `init`: `icp_batch(target, source
 lock-step loop (each result is `icp`'s from that start, byte for byte), `align_vote(target, source, target_frame,
 source_frame, **opts)` lists candidate poses of two levelled clouds by a height-keyed vote, `align(...)` runs the batch from
 them and returns the winner, whose `.reg.T` is the `init` for `icp` on the full clouds.  `Frame.from_ground(result)` makes
-a frame of a ground-plane result; `scale_guess(stats)` is the ratio of the two clouds' heights."""
+a frame of a ground-plane result; `scale_guess(stats)` is the ratio of the two clouds' heights.
+
+The second entry adds rejectors and a second estimator: `icp_ex(target, source, normals, init, **opts)` takes
+every option of IcpOpts (metric, trim, one_to_one, ...) and returns an IcpResult; `icp_plane(...)` is the point-to-plane
+metric with the target's normals (computed by `Cloud.normals(k)` when not given); `icp_ex_batch` / `icp_plane_batch` run many
+starts in one lock-step loop, each result the single call's from that start, byte for byte."""
 import ctypes as C
 import math
 
@@ -256,3 +261,101 @@ def last_timing(target):
     ms, it = (C.c_double * 3)(), C.c_int32(0)
     _lib.check(_lib.lib().sfmhip_cloud_register_last_timing(target.h, ms, C.byref(it)), "sfmhip_cloud_register_last_timing")
     return dict(search=ms[0], sums=ms[1], update=ms[2], iterations=it.value)
+
+
+# ---------------------------------------------------------------- point-to-plane, trimmed and one-to-one ICP (f-22)
+POINT, PLANE = 0, 1                          # IcpOpts.metric
+PLANE_EPS = 1e-9                             # icp_plane's default eps (metric 1 needs one)
+
+
+class IcpOpts(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("with_scale", C.c_int32), ("min_pairs", C.c_int32), ("metric", C.c_int32),
+                ("one_to_one", C.c_int32), ("normal_stride", C.c_int32), ("max_dist", C.c_double), ("eps", C.c_double),
+                ("trim", C.c_double)]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("T", Transform), ("iterations", C.c_int32), ("pairs", C.c_int32), ("converged", C.c_int32), ("flags", C.c_int32),
+                ("mse", C.c_double), ("plane_mse", C.c_double), ("trim_d2", C.c_double)]
+    idx = None   # the kept pairs under T, with return_pairs=True
+
+
+def icp_default_opts(**kw):
+    """f-17's defaults, metric 0, no rejector (trim 1, one_to_one 0), normal_stride 4; keyword arguments override fields."""
+    o = IcpOpts()
+    _lib.lib().sfmhip_icp_default_opts(C.byref(o))
+    return set_opts(o, **kw)
+
+
+def plane_opts(kw):
+    """icp_plane's options: metric 1, eps 1e-9 and min_pairs 6 (7 with scale) unless given."""
+    kw = dict(kw)
+    kw.setdefault("eps", PLANE_EPS)
+    kw.setdefault("min_pairs", 7 if kw.get("with_scale") else 6)
+    kw["metric"] = PLANE
+    return kw
+
+
+def _normals(target, normals, o, k):
+    """The host array of the target's normals and its stride written into o (None for metric 0 without normals)."""
+    if normals is None:
+        if o.metric != PLANE:
+            return None
+        from .cloud import K_NORMALS
+        normals = target.normals(K_NORMALS if k is None else k)
+    normals = np.ascontiguousarray(normals, np.float32)
+    if normals.ndim != 2 or normals.shape[0] != target.n or normals.shape[1] not in (3, 4):
+        raise ValueError("normals: one row of 3 or 4 floats per target point")
+    o.normal_stride = normals.shape[1]
+    return normals
+
+
+def icp_ex(target, source, normals=None, init=None, return_pairs=False, opts=None, k=None, **kw):
+    """IcpResult of sfmhip_cloud_register_icp: options by keyword (every field of IcpOpts) or as an IcpOpts; `normals` [n_target,
+    3 or 4] float32, or None (metric 1 then computes them with target.normals(k))."""
+    o = set_opts(opts, **kw) if opts is not None else icp_default_opts(**kw)
+    nrm = _normals(target, normals, o, k)
+    res = IcpResult()
+    idx = np.empty(max(source.n, 1), np.int32) if return_pairs else None
+    _lib.check(_lib.lib().sfmhip_cloud_register_icp(target.h, source.h, None if nrm is None else nrm.ctypes.data, C.byref(o), _ref(init),
+                                                    C.byref(res), None if idx is None else idx.ctypes.data), "sfmhip_cloud_register_icp")
+    if return_pairs:
+        res.idx = idx[:source.n].copy()
+    return res
+
+
+def icp_ex_batch(target, source, inits, normals=None, return_pairs=False, opts=None, k=None, **kw):
+    """A list of IcpResult, one per Transform of `inits`: what `icp_ex` returns from that start (with return_pairs its idx row)."""
+    o = set_opts(opts, **kw) if opts is not None else icp_default_opts(**kw)
+    nrm = _normals(target, normals, o, k)
+    n = len(inits)
+    starts = (Transform * max(n, 1))(*inits)
+    res = (IcpResult * max(n, 1))()
+    idx = np.empty((max(n, 1), max(source.n, 1)), np.int32) if return_pairs else None
+    _lib.check(_lib.lib().sfmhip_cloud_register_icp_batch(target.h, source.h, None if nrm is None else nrm.ctypes.data, C.byref(o), starts, n,
+                                                          res, None if idx is None else idx.ctypes.data), "sfmhip_cloud_register_icp_batch")
+    out = []
+    for b in range(n):
+        r = IcpResult.from_buffer_copy(res[b])
+        if return_pairs:
+            r.idx = idx[b, :source.n].copy()
+        out.append(r)
+    return out
+
+
+def icp_plane(target, source, normals=None, init=None, return_pairs=False, k=None, **kw):
+    """Point-to-plane ICP (f-22 metric 1) against the target's normals; trim=, one_to_one= and f-17's options by keyword."""
+    return icp_ex(target, source, normals, init, return_pairs, k=k, **plane_opts(kw))
+
+
+def icp_plane_batch(target, source, inits, normals=None, return_pairs=False, k=None, **kw):
+    """icp_plane from every start of `inits` in one lock-step loop."""
+    return icp_ex_batch(target, source, inits, normals, return_pairs, k=k, **plane_opts(kw))
+
+
+def icp_last_timing(target):
+    """ms of the last icp_ex / icp_plane (or their batch) with this target, with Context.set_timing on: search, rejectors, sums,
+    update; and the iterations of its longest problem."""
+    ms, it = (C.c_double * 4)(), C.c_int32(0)
+    _lib.check(_lib.lib().sfmhip_cloud_register_icp_last_timing(target.h, ms, C.byref(it)), "sfmhip_cloud_register_icp_last_timing")
+    return dict(search=ms[0], rejectors=ms[1], sums=ms[2], update=ms[3], iterations=it.value)
