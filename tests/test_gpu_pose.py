@@ -1,8 +1,10 @@
 """GPU: the pose step of baseReconstruction (getCameraPose, reference src/Sfm.cpp:713-789) -- sfmhip_recover_pose bit for
 bit against the CPU build of the same header (tests/stub/pose_capi.cpp over csrc/pose.h), sfmhip_essential_pose against
 the oracle's findEssentialMat and that stub, the RANSAC it shares with sfmhip_score_essential, batch independence, and
-the host mirror's baseReconstruction on the temple sequence (BASELINE.json configs[0]).  PARITY UNPINNED: OpenCV is not
-in the image (include/sfmhip.h)."""
+the host mirror's baseReconstruction on the temple sequence (BASELINE.json configs[0]).  The scenes of
+tests/pose_scenes.py add what synth.two_view_scene's one pose never reaches: each of the four candidates winning, tied
+counts, a wave kept in the Jacobi loop by a NaN lane, E far from norm 1, thresholds off 50 and mask bytes other than 0
+and 1.  PARITY UNPINNED: OpenCV is not in the image (include/sfmhip.h)."""
 import ctypes as C
 import os
 import struct
@@ -12,6 +14,8 @@ import numpy as np
 import pytest
 
 from sfm_danpipeline_amd import build, pose, scoring, synth
+from tests import pose_scenes as S
+from tests import test_pose_cpu as CPU          # its stub wrappers (recover, decompose) and numpy restatement (np_recover)
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -28,6 +32,7 @@ def pc(tmp_path_factory):
     lib = C.CDLL(so)
     vp = C.c_void_p
     lib.pose_recover.argtypes = [C.c_int, vp, vp, vp] + [C.c_double] * 4 + [vp] * 6
+    lib.pose_decompose.argtypes = [vp] * 4
     lib.pose_check_rotation.argtypes = [vp]
     return lib
 
@@ -192,6 +197,248 @@ def test_batch_independence(ctx):
         for k in ("E", "R", "t"):
             assert np.array_equal(_bits(s[k][0]), _bits(r[k][p])), (p, k)
         assert np.array_equal(s["masks"][0], r["masks"][p]), p
+
+
+# ---------------------------------------------------------------- every candidate, ties, wave edges, degenerate E
+# (tests/pose_scenes.py; tests/test_pose_cpu.py asserts on the CPU what these scenes make the header do)
+def _same(a, b):
+    """bit for bit, except that a NaN must meet a NaN in the same entry (the host's and the device's NaNs differ in sign)"""
+    a, b = np.ascontiguousarray(a, np.float64).reshape(-1), np.ascontiguousarray(b, np.float64).reshape(-1)
+    na = np.isnan(a)
+    return a.shape == b.shape and np.array_equal(na, np.isnan(b)) and np.array_equal(a.view(np.uint64)[~na], b.view(np.uint64)[~na])
+
+
+def _assert_equals_stub(pc, got, i, a, b, E, mask=None, dist=50.0):
+    """pair i of a recover_pose result (R, t, n_good, masks) against the stub: R, t, n_good and the mask bit for bit.
+    Returns the stub's result."""
+    R, t, ng, out = got
+    s = CPU.recover(pc, np.reshape(a, (-1, 2)), np.reshape(b, (-1, 2)), E, S.F, S.PPX, S.PPY, dist=dist, mask=mask)
+    assert _same(R[i], s["R"]) and _same(t[i], s["t"]), (i, R[i], s["R"], t[i], s["t"])
+    assert int(ng[i]) == s["n_good"] and np.array_equal(out[i], s["mask"]), (i, int(ng[i]), s["n_good"])
+    return s
+
+
+def _choice(pc, E, R, t):
+    """the candidate whose (R, t) the result is, bit for bit, among the stub's decomposition of E"""
+    R1, R2, tt, _ = CPU.decompose(pc, E)
+    c = [k for k, (Rc, tc) in enumerate([(R1, tt), (R2, tt), (R1, -tt), (R2, -tt)])
+         if np.array_equal(_bits(R), _bits(Rc)) and np.array_equal(_bits(t), _bits(tc))]
+    assert len(c) == 1, c
+    return c[0]
+
+
+FAMILY_SIZES = [63, 64, 65, 255, 256, 257, 511, 512, 513, 1, 300, 0]    # around the wave (64) and the tile (256); one; none
+
+
+@pytest.fixture(scope="module")
+def family_batch():
+    """12 pairs: the four poses of one E for each of the three rotations, so that neighbours choose different candidates.
+    [(left, right, E of the rotation, true R, true unit t, mask)]"""
+    rng = np.random.default_rng(12)
+    out = []
+    for ri, R in enumerate(S.ROTATIONS):
+        E = S.essential(R, S.T)
+        for k, (Rk, tk) in enumerate(S.family(R)):
+            m = FAMILY_SIZES[4 * ri + k]
+            a, b = S.scene(Rk, tk, max(m, 1), 100 + 10 * ri + k, 0.3)
+            mask = (rng.random(m) < 0.85).astype(np.uint8)
+            mask[:1] = 1                                                  # (the one-match pair keeps its match)
+            out.append((a[:m], b[:m], E, Rk, tk / np.linalg.norm(tk), mask))
+    return out
+
+
+@pytest.mark.parametrize("sign", [1, -1])
+@pytest.mark.parametrize("with_mask", [False, True])
+def test_four_winners_in_one_batch(ctx, pc, family_batch, with_mask, sign):
+    """One call whose neighbouring pairs choose different candidates, at sizes around the wave and the tile: a count added
+    to a neighbour's slot of counts[4 * p + c], or a selection that disagrees with pose_candidates' decomposition, shows
+    as the wrong pose.  Against the stub bit for bit, against numpy's restatement away from its thresholds, and against
+    the same pairs run one per call."""
+    pairs = [(a, b) for a, b, *_ in family_batch]
+    Es = np.array([sign * E for _, _, E, *_ in family_batch])
+    masks = [mk for *_, mk in family_batch] if with_mask else None
+    got = pose.recover_pose(pairs, Es, S.F, (S.PPX, S.PPY), masks=masks, ctx=ctx)
+    assert pose.last_flags(ctx) == 0
+    R, t, ng, out = got
+    sels = []
+    for i, (a, b, _, Rtrue, ttrue, mk) in enumerate(family_batch):
+        mk = mk if with_mask else None
+        s = _assert_equals_stub(pc, got, i, a, b, Es[i], mask=mk)
+        sels.append(_choice(pc, Es[i], R[i], t[i]))
+        assert sels[i] == s["sel"] and s["flags"] == 0, i
+        m = len(a)
+        if m == 0:
+            assert sels[i] == 0 and int(ng[i]) == 0
+            continue
+        assert np.abs(R[i] - Rtrue).max() < 1e-2 and np.abs(t[i] - ttrue).max() < 1e-1, i
+        sel, Rn, tn, g, nmasks, near = CPU.np_recover(a, b, Es[i], S.F, S.PPX, S.PPY, mask=mk)
+        assert np.abs(R[i] - Rn).max() < 1e-9 and np.abs(t[i] - tn).max() < 1e-9, i     # (numpy chose the same pose)
+        assert near.sum() <= max(2, m // 200), (i, near.sum())
+        assert np.array_equal((out[i] != 0)[~near], nmasks[sel][~near]), i
+        assert abs(int(ng[i]) - int(g[sel])) <= near.sum() and int(ng[i]) == int((out[i] != 0).sum()), i
+        assert int(ng[i]) >= 0.7 * m
+    assert set(sels) == {0, 1, 2, 3}
+    assert all(x != y for x, y in zip(sels, sels[1:])), sels
+    assert sels[:4] == S.FAMILY_WINNERS
+    print("\nchosen candidates (E sign %+d, masks %s): %s" % (sign, with_mask, sels))
+    for i, (a, b) in enumerate(pairs):                                   # one pair per call: the same bytes
+        R1, t1, ng1, out1 = pose.recover_pose([(a, b)], Es[i:i + 1], S.F, (S.PPX, S.PPY), masks=[masks[i]] if with_mask else None, ctx=ctx)
+        assert np.array_equal(_bits(R1[0]), _bits(R[i])) and np.array_equal(_bits(t1[0]), _bits(t[i])), i
+        assert int(ng1[0]) == int(ng[i]) and np.array_equal(out1[0], out[i]), i
+
+
+def test_ties_and_empties(ctx, pc):
+    """Counts that tie above zero take the first candidate that reaches the maximum; an empty pair and an all-zero mask
+    sit between the mixtures, so their zero counts must not leak into a neighbour's four slots."""
+    mixes = [S.mixture(parts) for parts, _, _ in S.TIES]
+    blank = S.scene(*S.family()[0], 70, 9, 0.3)
+    pairs = [mixes[0], (np.zeros((0, 2)), np.zeros((0, 2))), mixes[1], blank, mixes[2], mixes[3]]
+    want = [S.TIES[0], None, S.TIES[1], None, S.TIES[2], S.TIES[3]]
+    masks = [np.zeros(70, np.uint8) if k == 3 else np.ones(len(a), np.uint8) for k, (a, _) in enumerate(pairs)]
+    Es = np.array([S.E0] * len(pairs))
+    got = pose.recover_pose(pairs, Es, S.F, (S.PPX, S.PPY), masks=masks, ctx=ctx)
+    assert pose.last_flags(ctx) == 0
+    R, t, ng, out = got
+    R1, R2, tt, _ = CPU.decompose(pc, S.E0)
+    for i, (a, b) in enumerate(pairs):
+        s = _assert_equals_stub(pc, got, i, a, b, S.E0, mask=masks[i])
+        counts, choice = (want[i][1], want[i][2]) if want[i] else ([0, 0, 0, 0], 0)
+        assert list(s["counts"]) == counts and _choice(pc, S.E0, R[i], t[i]) == choice, i
+        assert int(ng[i]) == counts[choice] and int((out[i] != 0).sum()) == counts[choice], i
+        assert np.array_equal(_bits(R[i]), _bits(R2 if choice & 1 else R1)), i
+        assert np.array_equal(_bits(t[i]), _bits(-tt if choice & 2 else tt)), i
+    assert not out[3].any() and len(out[1]) == 0
+
+
+def test_a_wave_that_runs_all_thirty_sweeps(ctx, pc):
+    """The test of dlt_null_vector's wave-uniform exit `if (!__any(changed)) break;` -- the one place where pose.h differs
+    between host and device.  A correspondence with a NaN never meets the Jacobi's convergence test (a comparison with a
+    NaN is false), so its lane rotates in every one of the 30 sweeps and keeps its whole wave in the loop, long after the
+    other 63 lanes converged.  The stub runs each correspondence alone and leaves at its own convergence: every other
+    lane's mask byte must equal the stub's, so the forced sweeps changed no converged lane."""
+    R, tv = S.family()[0]
+    a0, b0 = S.scene(R, tv, 128, 41, 0.0)                                # exact
+    a1, b1 = S.scene(R, tv, 128, 42, 0.3)                                # noisy
+    a, b = np.concatenate([a0, a1]), np.concatenate([b0, b1])
+    a[5, 0] = np.nan                                                     # wave 0
+    b[70, 1] = np.inf                                                    # wave 1
+    b[130] = a[130]                                                      # wave 2: left pixel == right pixel
+    c, d = S.scene(R, tv, 64, 43, 0.3)                                   # one wave of matches in a tile of 256 lanes
+    c[0] = np.nan
+    pairs = [(a, b), (c, d)]
+    for masks in (None, [np.ones(256, np.uint8), np.ones(64, np.uint8)]):
+        got = pose.recover_pose(pairs, np.array([S.E0, S.E0]), S.F, (S.PPX, S.PPY), masks=masks, ctx=ctx)
+        assert pose.last_flags(ctx) == 0
+        byte = 255 if masks is None else 1
+        for i, (x, y) in enumerate(pairs):
+            s = _assert_equals_stub(pc, got, i, x, y, S.E0, mask=None if masks is None else masks[i])
+            assert s["sel"] == S.FAMILY_WINNERS[0] and set(np.unique(got[3][i])) == {0, byte}
+        big, small = got[3]
+        assert big[5] == 0 and big[70] == 0 and small[0] == 0
+        assert int(got[2][0]) >= 250 and int(got[2][1]) == 63
+
+
+def _degenerate_batch():
+    """the flagged and unflagged E of pose_scenes.DEGENERATE, each beside an ordinary pair: [(name, left, right, E)]"""
+    fam = S.family()
+    out = []
+    for k, (name, (E, _)) in enumerate(S.DEGENERATE.items()):
+        a, b = S.scene(*fam[0], 60 + 37 * k, 200 + k, 0.3)
+        out.append((name, a, b, E))
+        j = k % 4
+        a, b = S.scene(*fam[j], 100 + 31 * k, 300 + k, 0.3)
+        out.append(("plain", a, b, S.E0))
+    return out
+
+
+def test_degenerate_and_scaled_essential_matrices_on_the_device(ctx, pc):
+    """E of norm 1e-200 .. 1e200, zero, rank 1 and NaN beside ordinary pairs: every pair equals the stub (a NaN meets a
+    NaN), the flag is raised by the batch that holds a flagged E and by no other."""
+    batch = _degenerate_batch()
+    pairs = [(a, b) for _, a, b, _ in batch]
+    Es = np.array([E for *_, E in batch])
+    with np.errstate(all="ignore"):
+        got = pose.recover_pose(pairs, Es, S.F, (S.PPX, S.PPY), ctx=ctx)
+        assert pose.last_flags(ctx) == 1
+        for i, (name, a, b, E) in enumerate(batch):
+            s = _assert_equals_stub(pc, got, i, a, b, E)
+            assert s["flags"] == (S.DEGENERATE[name][1] if name != "plain" else 0), name
+            if s["flags"] == 0:
+                assert int(got[2][i]) >= 0.9 * len(a), (name, int(got[2][i]))
+            else:
+                assert int(got[2][i]) == 0 and not got[3][i].any(), name
+    assert not np.isfinite(got[0][[n for n, *_ in batch].index("1e200")]).all()
+    # the flag does not stick
+    live = [i for i, (name, *_) in enumerate(batch) if name == "plain"]
+    got = pose.recover_pose([pairs[i] for i in live], Es[live], S.F, (S.PPX, S.PPY), ctx=ctx)
+    assert pose.last_flags(ctx) == 0
+    for k, i in enumerate(live):
+        _assert_equals_stub(pc, got, k, *pairs[i], Es[i])
+    # scaled, unflagged E alone: sfm_hypot's tiny-argument branch with real rotations
+    idx = [i for i, (name, *_) in enumerate(batch) if name in S.UNFLAGGED]
+    assert len(idx) == 5
+    got = pose.recover_pose([pairs[i] for i in idx], Es[idx], S.F, (S.PPX, S.PPY), ctx=ctx)
+    assert pose.last_flags(ctx) == 0
+    for k, i in enumerate(idx):
+        _assert_equals_stub(pc, got, k, *pairs[i], Es[i])
+        plain = CPU.recover(pc, *pairs[i], S.E0, S.F, S.PPX, S.PPY)   # the pose of the unscaled E (1e-6: test_pose_cpu.py)
+        assert max(np.abs(got[0][k] - plain["R"]).max(), np.abs(got[1][k] - plain["t"]).max()) < 1e-6, batch[i][0]
+        assert np.array_equal(got[3][k], plain["mask"]), batch[i][0]
+
+
+def test_thresholds_and_mask_bytes(ctx, pc):
+    """distance_thresh off 50 (a part, nothing, inf, NaN) and mask bytes that are not 0 / 1: the output byte is the input
+    byte wherever the candidate passes"""
+    a, b = S.scene(*S.family()[0], 300, 100, 0.3)
+    mb = S.mask_bytes(300)
+    ngs = []
+    for d in S.THRESHOLDS:
+        free = pose.recover_pose([(a, b)], S.E0[None], S.F, (S.PPX, S.PPY), distance_thresh=d, ctx=ctx)
+        assert pose.last_flags(ctx) == 0
+        _assert_equals_stub(pc, free, 0, a, b, S.E0, dist=d)
+        ngs.append(int(free[2][0]))
+        got = pose.recover_pose([(a, b)], S.E0[None], S.F, (S.PPX, S.PPY), masks=[mb], distance_thresh=d, ctx=ctx)
+        _assert_equals_stub(pc, got, 0, a, b, S.E0, mask=mb, dist=d)
+        if _choice(pc, S.E0, got[0][0], got[1][0]) == _choice(pc, S.E0, free[0][0], free[1][0]):
+            assert np.array_equal(got[3][0], np.where(free[3][0] != 0, mb, 0).astype(np.uint8)), d
+    assert ngs[0] == 300 and 0 < ngs[1] < 300 and ngs[2:5] == [0, 0, 0] and ngs[5] == 300 and ngs[6] == 0, ngs
+    got = pose.recover_pose([(a, b)], S.E0[None], S.F, (S.PPX, S.PPY), masks=[mb], ctx=ctx)
+    assert set(np.unique(got[3][0])) == set(S.MASK_BYTES.tolist()) and int(got[2][0]) == int((mb != 0).sum())
+
+
+def test_essential_pose_with_mixed_winners(ctx, pc, orc):
+    """findEssentialMat + recoverPose on the four poses of one E, with outliers: RANSAC's own E (its SVD's signs are its
+    own) must still lead each member to its true pose -- the first essential_pose runs that return anything but
+    candidate 2 -- beside pairs too small for a model."""
+    fam = S.family()
+    pairs = []
+    for k, (Rk, tk) in enumerate(fam):
+        pairs.append(S.scene(Rk, tk, 400, 700 + k, 0.3, outliers=0.2))
+        if k == 0:
+            pairs.append(tuple(x[:4] for x in S.scene(Rk, tk, 4, 710, 0.3)))
+        if k == 2:
+            pairs.append((np.zeros((0, 2)), np.zeros((0, 2))))
+    r = pose.essential_pose(pairs, S.K1, ctx=ctx)
+    assert pose.last_flags(ctx) == 0
+    member = [0, None, 1, 2, None, 3]
+    sels = []
+    for i, (a, b) in enumerate(pairs):
+        cnt, mask, E, it, fl = orc.find_essential_mat(a, b, S.K1)
+        assert fl == 0 and int(r["inliers"][i]) == cnt, i
+        if member[i] is None:
+            assert E is None or len(a) < 5
+            assert r["n_good"][i] == -1 and not r["E"][i].any() and not r["R"][i].any() and not r["t"][i].any(), i
+            assert not r["masks"][i].any()
+            continue
+        assert np.array_equal(_bits(r["E"][i]), _bits(E)), i
+        s = _assert_equals_stub(pc, (r["R"], r["t"], r["n_good"], r["masks"]), i, a, b, E, mask=mask)
+        assert not (r["masks"][i] & ~mask).any() and s["n_good"] > 0.7 * 400
+        Rk, tk = fam[member[i]]
+        assert np.abs(r["R"][i] - Rk).max() < 1e-2 and np.abs(r["t"][i] - tk / np.linalg.norm(tk)).max() < 1e-1, i
+        sels.append(_choice(pc, E, r["R"][i], r["t"][i]))
+    # each member has its own E here, so the four need not land on four candidates: the oracle's E give 0, 1, 1, 2
+    assert len(set(sels)) >= 3, sels
+    print("\nessential_pose chose candidates", sels)
 
 
 # ---------------------------------------------------------------- cfg1: the temple sequence through baseReconstruction

@@ -1,7 +1,9 @@
 """The pose step of baseReconstruction (csrc/pose.h: getCameraPose's recoverPose and CheckCoherentRotation, reference
 src/Sfm.cpp:713-799) on the CPU, through a g++ build of the header the device kernels compile: decomposeEssentialMat
 against numpy's SVD, recoverPose against an independent numpy restatement (numpy SVD, a per-point numpy DLT), the edge
-cases of the selection and the thresholds, the float-narrowed rotation check, and one shape under ASan / UBSan."""
+cases of the selection and the thresholds, the float-narrowed rotation check, and one shape under ASan / UBSan.  The
+last section runs the scenes of tests/pose_scenes.py (every candidate a winner, ties, degenerate and scaled E, mask
+bytes, thresholds): what it asserts here is what tests/test_gpu_pose.py relies on when it runs them on the device."""
 import ctypes as C
 import os
 import subprocess
@@ -10,6 +12,7 @@ import numpy as np
 import pytest
 
 from sfm_danpipeline_amd import synth
+from tests import pose_scenes as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STUB = os.path.join(ROOT, "tests", "stub", "pose_capi.cpp")
@@ -286,3 +289,102 @@ def test_recover_pose_under_asan_ubsan(pc, tmp_path):
     assert lines[:11] == ["sel", str(got["sel"]), "n_good", str(got["n_good"]), "counts", *map(str, got["counts"]), "flags", "0"]
     words = np.array([int(w, 16) for w in lines[11:23]], np.uint64)
     assert np.array_equal(words, np.concatenate([got["R"].ravel(), got["t"]]).view(np.uint64))
+
+
+# ---------------------------------------------------------------- every candidate, ties, degenerate E (tests/pose_scenes.py)
+def _family_run(pc, R, sign, m=300, noise=0.3, seed=100):
+    """recoverPose by the stub and by numpy on the four members of family(R) under sign * E: [(member's true R, true unit
+    t, stub result, np_recover result)]"""
+    E = sign * S.essential(R, S.T)
+    out = []
+    for k, (Rk, tk) in enumerate(S.family(R)):
+        a, b = S.scene(Rk, tk, m, seed + k, noise)
+        out.append((Rk, tk / np.linalg.norm(tk), recover(pc, a, b, E, S.F, S.PPX, S.PPY), np_recover(a, b, E, S.F, S.PPX, S.PPY)))
+    return E, out
+
+
+def test_every_candidate_wins_somewhere(pc):
+    """The four poses that share one E land on four different candidates, and the three rotations permute which: the choice
+    is the scene's true pose, numpy's restatement picks the same one and counts the same, candidate by candidate."""
+    m, chosen = 300, set()
+    for ri, R in enumerate(S.ROTATIONS):
+        for sign in (1, -1):
+            E, runs = _family_run(pc, R, sign, m=m, seed=100 + 10 * ri)
+            sels = [got["sel"] for _, _, got, _ in runs]
+            assert sorted(sels) == [0, 1, 2, 3], (ri, sign, sels)
+            if ri == 0:
+                assert sels == S.FAMILY_WINNERS, (sign, sels)
+            chosen |= set(sels)
+            R1, R2, tt, fl = decompose(pc, E)
+            assert fl == 0
+            cands = [(R1, tt), (R2, tt), (R1, -tt), (R2, -tt)]
+            nR1, nR2, nt = np_decompose(E)
+            ncands = [(nR1, nt), (nR2, nt), (nR1, -nt), (nR2, -nt)]
+            for k, (Rk, tk, got, (sel, Rn, tn, g, masks, near)) in enumerate(runs):
+                assert got["flags"] == 0
+                assert np.array_equal(got["R"], cands[got["sel"]][0]) and np.array_equal(got["t"], cands[got["sel"]][1])
+                assert np.abs(got["R"] - Rk).max() < 1e-2 and np.abs(got["t"] - tk).max() < 1e-1, (ri, sign, k)
+                assert np.abs(got["R"] - Rn).max() < 1e-9 and np.abs(got["t"] - tn).max() < 1e-9, (ri, sign, k)
+                assert near.sum() <= max(2, m // 200), near.sum()
+                mine = got["mask"] != 0
+                assert np.array_equal(mine[~near], masks[sel][~near])
+                assert abs(got["n_good"] - int(g[sel])) <= near.sum() and got["n_good"] == int(mine.sum()) > 0.9 * m
+                for c, (Rc, tc) in enumerate(cands):
+                    j = [i for i, (Rx, tx) in enumerate(ncands) if np.abs(Rx - Rc).max() < 1e-9 and np.abs(tx - tc).max() < 1e-9]
+                    assert len(j) == 1 and abs(int(got["counts"][c]) - int(g[j[0]])) <= near.sum(), (ri, sign, k, c, j)
+    assert chosen == {0, 1, 2, 3}
+
+
+@pytest.mark.parametrize("parts,counts,choice", S.TIES)
+def test_tied_counts_take_the_first_candidate(pc, parts, counts, choice):
+    a, b = S.mixture(parts)
+    assert len(a) == sum(n for _, n in parts)
+    got = recover(pc, a, b, S.E0, S.F, S.PPX, S.PPY)
+    assert list(got["counts"]) == counts and got["sel"] == choice and got["n_good"] == counts[choice] == max(counts)
+    R1, R2, t, _ = decompose(pc, S.E0)
+    assert np.array_equal(got["R"], R2 if choice & 1 else R1) and np.array_equal(got["t"], -t if choice & 2 else t)
+    assert int((got["mask"] != 0).sum()) == counts[choice]
+
+
+def test_degenerate_and_scaled_essential_matrices(pc):
+    """flags: 1 where a singular value is not above DBL_MIN (zero, rank 1, NaN, squares that underflow or overflow), else 0;
+    an unflagged scaled E gives the unscaled pose and count (the candidate's index may move with the scale: the SVD's signs)"""
+    fam = S.family()
+    a, b = S.scene(*fam[0], 300, 100, 0.3)
+    base = recover(pc, a, b, S.E0, S.F, S.PPX, S.PPY)
+    assert base["flags"] == 0 and base["n_good"] == 300
+    assert set(S.FLAGGED) == {"zero", "rank1", "nan", "1e-200", "1e200"} and set(S.UNFLAGGED) == {"1e-75", "1e-100", "1e-140", "1e60", "1e75"}
+    for name, (E, flags) in S.DEGENERATE.items():
+        got = recover(pc, a, b, E, S.F, S.PPX, S.PPY)
+        assert got["flags"] == flags == decompose(pc, E)[3], name
+        if not flags:
+            worst = max(np.abs(got["R"] - base["R"]).max(), np.abs(got["t"] - base["t"]).max())
+            assert worst < 1e-6 and got["n_good"] == base["n_good"], (name, worst)
+            assert np.array_equal(got["mask"], base["mask"]), name
+    assert not np.isfinite(recover(pc, a, b, S.DEGENERATE["1e200"][0], S.F, S.PPX, S.PPY)["R"]).all()
+    assert np.isnan(recover(pc, a, b, S.DEGENERATE["nan"][0], S.F, S.PPX, S.PPY)["R"]).all()
+
+
+def test_mask_bytes_pass_through(pc):
+    """bitwise_and(mask, mask1): the output is the input BYTE where the candidate passes, whatever it is, and 0 elsewhere"""
+    fam = S.family()
+    a, b = S.scene(*fam[0], 300, 100, 0.3, outliers=0.2)
+    mb = S.mask_bytes(300)
+    assert set(np.unique(mb)) == set(S.MASK_BYTES.tolist())
+    free = recover(pc, a, b, S.E0, S.F, S.PPX, S.PPY)
+    got = recover(pc, a, b, S.E0, S.F, S.PPX, S.PPY, mask=mb)
+    assert got["sel"] == free["sel"]
+    passes = free["mask"] != 0
+    assert 0 < passes.sum() < 300 and set(np.unique(mb[passes])) == set(S.MASK_BYTES.tolist())
+    assert np.array_equal(got["mask"], np.where(passes, mb, 0).astype(np.uint8))
+    assert got["n_good"] == int((passes & (mb != 0)).sum())
+    assert set(np.unique(free["mask"])) == {0, 255}
+
+
+def test_distance_thresholds(pc):
+    """depths are 4 .. 8 baselines: 6 cuts a part, 3 and below everything, inf nothing, and a NaN compares false"""
+    fam = S.family()
+    a, b = S.scene(*fam[0], 300, 100, 0.3)
+    ng = [recover(pc, a, b, S.E0, S.F, S.PPX, S.PPY, dist=d)["n_good"] for d in S.THRESHOLDS]
+    assert S.THRESHOLDS[:5] == [50.0, 6.0, 3.0, 0.0, -1.0] and np.isinf(S.THRESHOLDS[5]) and np.isnan(S.THRESHOLDS[6])
+    assert ng[0] == 300 and 0 < ng[1] < 300 and ng[2:5] == [0, 0, 0] and ng[5] == 300 and ng[6] == 0
