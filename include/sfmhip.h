@@ -456,6 +456,61 @@ int sfmhip_cloud_download(sfmhip_cloud* cloud, float* xyz /* 3 n */);
  * sort, voxel reduce -- and of its last outlier call -- neighbour means, threshold + compaction. */
 int sfmhip_cloud_filter_last_timing(sfmhip_cloud* cloud, double ms4[4]);
 
+/* ---- smoothing on the same cloud: PCL 1.8.1's MovingLeastSquares ----
+ * computeMLSPointNormal with no upsampling (NONE) and SIMPLE projection: every point is moved onto the plane, or the
+ * polynomial surface, fitted to its neighbours within search_radius.  The reference's create_mesh still carries the remains
+ * of this pass (src/Sfm.cpp:1347-1383) but does not call it.  The rules are PCL's as recalled (parity UNPINNED, PCL is not
+ * in the image).  This list is the contract; csrc/mls.h holds it as code.  A dagger marks what nothing here can check, + what
+ * is ours.
+ *   M1. neighbours of point i: the finite points with d2 < (float)(r * r), d2 = ((dx dx) + dy dy) + dz dz in float (the
+ *       radius search of sfmhip_cloud_radius_count), i itself and its duplicates included.  A non-finite point is nobody's
+ *       neighbour and is not output.
+ *   M2. + order: every sum over a point's neighbours runs sequentially from zero in ascending (cell key, input index).  The
+ *       key is that of the radius grid for r: origin = the box minimum of the finite points; cell = r (1 + 2^-10), doubled
+ *       while prod_a min(floor(extent_a / cell) + 1, 2^12) exceeds 2^22; a coordinate's cell = floor((v - origin) / cell) in
+ *       double, clamped to [0, D_a - 1]; key = (cz D_y + cy) D_x + cx.  The result is a function of the points and the
+ *       options alone.
+ *   M3. (dagger) fewer than 3 neighbours: the point is dropped.  Otherwise, in double: the nine sums xx xy xz yy yz zz x y z,
+ *       each divided by the count, cov = E[ab] - E[a]E[b]; pcl::eigen33 (scale by the largest |entry|, 1 when that is <=
+ *       DBL_MIN; the trigonometric roots, the quadratic when |c0| < DBL_EPSILON or the smallest root is <= 0; the largest
+ *       of the three row cross products of cov / scale - root0 I, normalised) gives the plane normal n and lambda0; d = -n.mean,
+ *       dist = p.n + d, q = p - dist n, curvature = |lambda0 / trace| (0 for a zero trace).  Dots are (a0 b0 + a1 b1) + a2 b2.
+ *   M4. + n not finite (all neighbours identical or exactly collinear): the point is output unmoved, its normal and curvature
+ *       are NaN (0x7FC00000), and it is counted in n_degenerate.
+ *   M5. (dagger) polynomial_order 0 (PCL's setPolynomialFit(false)) stops at M3.  Order 1 has 3 coefficients, order 2 has 6; with
+ *       fewer neighbours than coefficients M3's result stands (n_plane_only).  Otherwise per neighbour x: e = x - q, w =
+ *       exp(-(e.e) / g) with g = sqr_gauss_param, or r r in double when that is <= 0; v_axis = Eigen's unitOrthogonal of n
+ *       ((-ny, nx, 0) / sqrt(nx nx + ny ny) unless |nx| and |ny| are both <= 1e-12 |nz|, then (0, -nz, ny) / sqrt(ny ny +
+ *       nz nz)), u_axis = n x v_axis; u = e.u_axis, v = e.v_axis, f = e.n; terms t = u^a v^b for a = 0..order, b =
+ *       0..order - a, powers by repeated multiplication.  A = sum w (u^a v^b) over the distinct exponent pairs and b = sum
+ *       (w t) f by M2's order; Cholesky (LLT), forward then back substitution, each inner sum subtracted in ascending index;
+ *       q += c[0] n, normal = n - c[order + 1] u_axis - c[1] v_axis, normalised.  The curvature stays M3's.  + A pivot that is
+ *       <= 0 or not finite, or a coefficient that is not finite, keeps M3's result (n_fit_failed).
+ *   M6. + exp(x), x <= 0: k = floor(x / ln 2 + 1/2), r = (x - k ln2_hi) - k ln2_lo, the Taylor polynomial of degree 13 by
+ *       Horner, times 2^k through the exponent bits; 0 below -708.  Within 1 ulp of libm on [-50, 0].
+ *   M7. outputs are floats rounded once from the doubles; rows in input order of the surviving points; src_index[row] = the
+ *       input index (PCL's getCorrespondingIndices).  Normals are not flipped towards a viewpoint: the sign is eigen33's. */
+typedef struct sfmhip_mls_opts {
+  double search_radius;     /* r: finite and > 0 (the default 0 must be replaced) */
+  int32_t polynomial_order; /* 0, 1 or 2 */
+  int32_t compute_normals;  /* 0: out_normals4 is not written */
+  double sqr_gauss_param;   /* g; <= 0: r r */
+} sfmhip_mls_opts;
+typedef struct sfmhip_mls_stats {
+  int32_t n_out, n_dropped /* finite points with fewer than 3 neighbours */, n_plane_only, n_degenerate, n_fit_failed, max_neighbours;
+} sfmhip_mls_stats;
+/* radius 0 (must be set), order 2, normals on, gauss 0 */
+int sfmhip_mls_default_opts(sfmhip_mls_opts* opts);
+/* out_xyz: 3 n, out_normals4: n x (nx, ny, nz, curvature), src_index: n, stats: each may be NULL.  out_cloud: NULL, or it
+ * receives a new handle on the same context over the smoothed points, which never leave the device.  SFMHIP_ERR_ARG with
+ * nothing written for a NULL cloud, opts or n_out, a radius that is not finite and > 0, an order outside 0..2 or a non-finite
+ * sqr_gauss_param.  No point, or no finite point: SFMHIP_OK, *n_out = 0. */
+int sfmhip_cloud_mls(sfmhip_cloud* cloud, const sfmhip_mls_opts* opts, float* out_xyz, float* out_normals4, int32_t* src_index,
+                     int32_t* n_out, sfmhip_mls_stats* stats, sfmhip_cloud** out_cloud);
+/* With sfmhip_set_timing on (zeros while it is off): host-clock ms of the last call on this handle -- the radius grid (0 when
+ * it was there already), the fit, the compaction with its downloads. */
+int sfmhip_cloud_mls_last_timing(sfmhip_cloud* cloud, double ms3[3]);
+
 /* ---- colour region growing and the dendrometry bounds (reference src/Segmentation.cpp:3-66, src/DendrometryE.cpp:3-29) ----
  * pcl::RegionGrowingRGB over the index list of a PassThrough, on the same device-resident cloud.  The rules (DESIGN.md
  * f-8 has them in full; parity UNPINNED, PCL is not in the image; + marks what is our reading):

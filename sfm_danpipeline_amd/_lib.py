@@ -87,6 +87,7 @@ SYMBOLS = [
     "sfmhip_cloud_terrain_normalize", "sfmhip_cloud_terrain_last_timing",
     "sfmhip_crowns_default_opts", "sfmhip_chm_crowns", "sfmhip_cloud_crowns", "sfmhip_cloud_crowns_raster",
     "sfmhip_cloud_crowns_last_timing", "sfmhip_cloud_crowns_last_rounds",
+    "sfmhip_mls_default_opts", "sfmhip_cloud_mls", "sfmhip_cloud_mls_last_timing",
     "sfmhip_verify_default_opts", "sfmhip_matchplan_verify", "sfmhip_verify_lists", "sfmhip_verified_counts", "sfmhip_verified_download",
     "sfmhip_tracks_build_from_verified", "sfmhip_verified_last_timing", "sfmhip_verified_destroy",
 ]
@@ -179,6 +180,9 @@ def lib():
         L.sfmhip_cloud_size.argtypes = [vp, vp, vp]
         L.sfmhip_cloud_download.argtypes = [vp, vp]
         L.sfmhip_cloud_filter_last_timing.argtypes = [vp, vp]
+        L.sfmhip_mls_default_opts.argtypes = [vp]
+        L.sfmhip_cloud_mls.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+        L.sfmhip_cloud_mls_last_timing.argtypes = [vp, vp]
         L.sfmhip_segment_default_opts.argtypes = [vp]
         L.sfmhip_segment_default_opts.restype = None
         L.sfmhip_cloud_segment_rgb.argtypes = [vp, vp, vp, cint, vp, vp, vp, vp]

@@ -15,7 +15,7 @@ SO = os.path.join(HERE, "libsfmhip.so")
 # and want v_fma_f64 -- "fast-honor-pragmas", not "fast": the one function that must NOT contract, the trust-region decision
 # lm_decide (the same bits on the host and on the device), says so with a pragma, which plain "fast" ignores
 SOURCES = {"context.hip": "off", "match.hip": "off", "triangulate.hip": "off", "incremental.hip": "off",
-           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "cloud_filter.hip": "off", "register.hip": "off", "align.hip": "off", "segment.hip": "off", "poisson.hip": "off", "dendro.hip": "off", "ground.hip": "off", "trees.hip": "off", "terrain.hip": "off", "crowns.hip": "off", "tracks.hip": "off", "verify.hip": "off", "mvs.hip": "off", "undistort.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
+           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "cloud_filter.hip": "off", "mls.hip": "off", "register.hip": "off", "align.hip": "off", "segment.hip": "off", "poisson.hip": "off", "dendro.hip": "off", "ground.hip": "off", "trees.hip": "off", "terrain.hip": "off", "crowns.hip": "off", "tracks.hip": "off", "verify.hip": "off", "mvs.hip": "off", "undistort.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -146,6 +146,14 @@ def build_cloud_filter_demo(force=False):
     kept points and their normals as a binary PCD (needs the GPU)."""
     return _build_host_exe(os.path.join(HERE, "sfm_cloud_filter_selftest"),
                            ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "cloud_filter_selftest.cpp"), force)
+
+
+def build_smooth_demo(force=False):
+    """The smoothing pass in front of create_mesh in the host mirror (StructFromMotion::smoothCloud over pcl::MovingLeastSquares as
+    pcllite.h mirrors it, then create_mesh with a smoothing radius: MLS, normals and Poisson on one device cloud) on a PCD; writes
+    the smoothed points with their normals as a binary PCD and the meshes as binary PLYs (needs the GPU)."""
+    return _build_host_exe(os.path.join(HERE, "sfm_smooth_selftest"),
+                           ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "smooth_selftest.cpp"), force)
 
 
 def build_mesh_demo(force=False):

@@ -23,6 +23,15 @@ def _p(a):
     return a.ctypes.data
 
 
+class MlsOpts(C.Structure):                      # sfmhip_mls_opts
+    _fields_ = [("search_radius", C.c_double), ("polynomial_order", C.c_int32), ("compute_normals", C.c_int32),
+                ("sqr_gauss_param", C.c_double)]
+
+
+class MlsStats(C.Structure):                     # sfmhip_mls_stats
+    _fields_ = [(k, C.c_int32) for k in ("n_out", "n_dropped", "n_plane_only", "n_degenerate", "n_fit_failed", "max_neighbours")]
+
+
 class Cloud:
     """A cloud of n points (float32 [n, 3]) resident on the device of `ctx`."""
 
@@ -140,6 +149,28 @@ class Cloud:
                                                                C.byref(m), _p(md), C.byref(thr)), "sfmhip_cloud_statistical_outlier")
         kept = out[:m.value].copy()
         return (kept, md[:self.n].copy(), thr.value) if return_distances else kept
+
+    def mls(self, radius, order=2, normals=True, sqr_gauss=0.0, return_cloud=False):
+        """PCL's MovingLeastSquares without upsampling: every point moved onto the plane (order 0) or the
+        polynomial of order 1 or 2 fitted to its neighbours within `radius`.  A dict with `xyz` [m, 3], `normals` [m, 4] (nx,
+        ny, nz, curvature; None without `normals`), `src_index` [m] (the input index of each row: points with fewer than 3
+        neighbours and non-finite points are dropped), `stats` (a dict of sfmhip_mls_stats) and `cloud`: with return_cloud, the
+        smoothed points as a device cloud that was never on the host, else None."""
+        o = MlsOpts(float(radius), int(order), int(bool(normals)), float(sqr_gauss))
+        n1 = max(self.n, 1)
+        oxyz, onrm, src = np.empty((n1, 3), np.float32), np.empty((n1, 4), np.float32), np.empty(n1, np.int32)
+        m, st, h = C.c_int32(0), MlsStats(), C.c_void_p()
+        _lib.check(_lib.lib().sfmhip_cloud_mls(self.h, C.addressof(o), _p(oxyz), _p(onrm) if normals else None, _p(src), C.addressof(m),
+                                               C.addressof(st), C.byref(h) if return_cloud else None), "sfmhip_cloud_mls")
+        return {"xyz": oxyz[:m.value].copy(), "normals": onrm[:m.value].copy() if normals else None, "src_index": src[:m.value].copy(),
+                "stats": {k: getattr(st, k) for k, _ in MlsStats._fields_},
+                "cloud": Cloud.from_handle(h, self.ctx) if return_cloud else None}
+
+    def mls_last_timing(self):
+        """ms of the last mls call (radius grid, fit, compaction) with Context.set_timing on; zeros otherwise."""
+        ms = (C.c_double * 3)()
+        _lib.check(_lib.lib().sfmhip_cloud_mls_last_timing(self.h, ms), "sfmhip_cloud_mls_last_timing")
+        return list(ms)
 
     def filter_last_timing(self):
         """ms of the last voxel grid (key + sort, reduce) and outlier call (neighbour means, threshold + compaction) with

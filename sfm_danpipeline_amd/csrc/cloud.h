@@ -54,6 +54,48 @@ SFM_CLOUD_INLINE float radius2(double r) { return (float)(r * r); }
 // a neighbour of the radius search: d2 < r2 (strict)
 SFM_CLOUD_INLINE bool in_radius(float d2, float r2) { return d2 < r2; }
 
+// ---- the geometry of a uniform grid (cloud_grid.h's grid_build, the kernels that walk a grid, and the CPU stubs that
+// restate a walk's order): dimensions floor(extent / cell) + 1 per axis capped at AXIS_CAP, the cell doubled while the grid
+// holds more than CELL_CAP cells; a coordinate's cell by floor((v - o) / cell) in double, clamped to the grid; keys x-fastest
+constexpr long long AXIS_CAP = 1 << 12;  // cells per axis
+constexpr long long CELL_CAP = 1 << 22;  // cells in all
+struct GridGeom {
+  double o[3], cell;
+  int D[3];
+  long long ncell;
+};
+// the grid over the box [lo, hi] of `n_valid` finite points (no point: one cell) that starts from cells of `cell`
+SFM_CLOUD_INLINE void grid_geometry(const double lo[3], const double hi[3], int n_valid, double cell, GridGeom& g) {
+  for (;;) {
+    long long tot = 1;
+    for (int a = 0; a < 3; ++a) {
+      const double ext = n_valid ? hi[a] - lo[a] : 0.0;
+      const double d = floor(ext / cell) + 1.0;
+      g.D[a] = (int)((double)AXIS_CAP < d ? (double)AXIS_CAP : d);
+      tot *= g.D[a];
+    }
+    if (tot <= CELL_CAP) {
+      g.ncell = tot;
+      break;
+    }
+    cell *= 2;
+  }
+  for (int a = 0; a < 3; ++a) g.o[a] = lo[a];
+  g.cell = cell;
+}
+SFM_CLOUD_INLINE int cell_of(double v, double o, double cell, int D) {
+  double f = floor((v - o) / cell);
+  f = f < 0.0 ? 0.0 : f;
+  f = f > (double)(D - 1) ? (double)(D - 1) : f;
+  return (int)f;
+}
+// the radius grid's starting cell for radius r (the margin covers the float rounding of d2 and the double rounding of cell_of)
+SFM_CLOUD_INLINE double radius_cell(double r) { return r * (1.0 + 1.0 / 1024.0); }
+SFM_CLOUD_INLINE int cell_key(const GridGeom& g, float x, float y, float z) {
+  const int cx = cell_of(x, g.o[0], g.cell, g.D[0]), cy = cell_of(y, g.o[1], g.cell, g.D[1]), cz = cell_of(z, g.o[2], g.cell, g.D[2]);
+  return (cz * g.D[1] + cy) * g.D[0] + cx;
+}
+
 // PassThrough on one field (limits as float, inclusive): a non-finite point is always dropped; otherwise kept iff
 // the value lies inside [lo, hi] (negative: iff it lies outside)
 SFM_CLOUD_INLINE bool passthrough_keep(float x, float y, float z, int axis, float lo, float hi, bool negative) {

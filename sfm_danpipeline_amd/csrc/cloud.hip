@@ -251,22 +251,11 @@ int sfmgrid::grid_build(sfmhip_cloud* c, const GridSrc& src, Grid& g, double cel
   g.release();
   SFM_TRY(ensure_ibuf(c));
   hipStream_t st = c->ctx->stream;
-  for (;;) {
-    long long tot = 1;
-    for (int a = 0; a < 3; ++a) {
-      const double ext = src.n_valid ? src.hi[a] - src.lo[a] : 0.0;
-      const double d = std::floor(ext / cell) + 1.0;
-      g.D[a] = (int)std::min((double)AXIS_CAP, d);
-      tot *= g.D[a];
-    }
-    if (tot <= CELL_CAP) {
-      g.ncell = tot;
-      break;
-    }
-    cell *= 2;
-  }
-  for (int a = 0; a < 3; ++a) g.o[a] = src.lo[a];
-  g.cell = cell;
+  sfmcloud::GridGeom geom;
+  sfmcloud::grid_geometry(src.lo, src.hi, src.n_valid, cell, geom);  // (cloud.h: the CPU stubs restate a walk's order from it)
+  for (int a = 0; a < 3; ++a) g.o[a] = geom.o[a], g.D[a] = geom.D[a];
+  g.cell = geom.cell;
+  g.ncell = geom.ncell;
   SFM_TRY(sfm_dev_alloc(&g.start, (size_t)g.ncell));
   SFM_TRY(sfm_dev_alloc(&g.end, (size_t)g.ncell));
   SFM_TRY(sfm_dev_alloc(&g.keys, (size_t)std::max(src.n, 1)));
@@ -318,16 +307,12 @@ int sfmgrid::density_grid(sfmhip_cloud* c, const GridSrc& src, Grid& g, double o
   return SFMHIP_OK;
 }
 
-namespace {
-
-int radius_grid(sfmhip_cloud* c, double radius) {
+int sfmgrid::radius_grid(sfmhip_cloud* c, double radius) {
   if (c->rg.built && c->rg.param == radius) return SFMHIP_OK;
-  SFM_TRY(grid_build(c, whole_cloud(c), c->rg, radius * (1.0 + 1.0 / 1024.0), true));
+  SFM_TRY(grid_build(c, whole_cloud(c), c->rg, sfmcloud::radius_cell(radius), true));
   c->rg.param = radius;
   return SFMHIP_OK;
 }
-
-}  // namespace
 
 // the k-NN grid: about KNN_OCCUPANCY points per occupied cell
 int sfmgrid::knn_grid(sfmhip_cloud* c) {

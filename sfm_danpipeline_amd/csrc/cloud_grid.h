@@ -26,8 +26,8 @@
 namespace sfmgrid {
 
 constexpr int CHUNK = 64;                 // points per radius_count workgroup (one wave)
-constexpr long long AXIS_CAP = 1 << 12;   // cells per axis
-constexpr long long CELL_CAP = 1 << 22;   // cells in all
+using sfmcloud::AXIS_CAP;                 // cells per axis   (cloud.h: the grid geometry is shared with the CPU stubs)
+using sfmcloud::CELL_CAP;                 // cells in all
 
 struct GridDev {
   double o[3], cell;
@@ -115,7 +115,7 @@ struct Grow {
 };
 
 // the stages that keep state on the handle, and a stage's slot: the state and what deletes it
-enum Stage { SEGMENT, POISSON, DENDRO, GROUND, TREES, FILTER, REGISTER, ALIGN, TERRAIN, CROWNS, REGISTER_ICP, N_STAGES };
+enum Stage { SEGMENT, POISSON, DENDRO, GROUND, TREES, FILTER, REGISTER, ALIGN, TERRAIN, CROWNS, REGISTER_ICP, MLS, N_STAGES };
 struct StageSlot {
   void* p = nullptr;
   void (*free)(void*) = nullptr;
@@ -156,6 +156,9 @@ int density_grid(sfmhip_cloud* c, const GridSrc& src, Grid& g, double occupancy)
 // the handle's k-NN grid (about 16 points per occupied cell), built on first use, and the slack its ring searches give
 // the double rounding of a cell coordinate
 int knn_grid(sfmhip_cloud* c);
+// the handle's radius grid for `radius` (cells of cloud.h's radius_cell(radius), with the chunk list: one entry per run of at
+// most CHUNK points of one cell), kept until a call asks for another radius: radius_count, radius_outlier and mls.hip share it
+int radius_grid(sfmhip_cloud* c, double radius);
 double knn_abs_eps(const sfmhip_cloud* c);
 // both filters' compaction: the 0/1 flags in ibuf[0] -> the kept indices, in input order, on the host
 int compact(sfmhip_cloud* c, int32_t* idx_out, int32_t* n_out);
@@ -185,12 +188,7 @@ S* stage(sfmhip_cloud* c) {
 }
 
 #ifdef __HIPCC__
-__device__ __forceinline__ int cell_of(double v, double o, double cell, int D) {
-  double f = floor((v - o) / cell);
-  f = f < 0.0 ? 0.0 : f;
-  f = f > (double)(D - 1) ? (double)(D - 1) : f;
-  return (int)f;
-}
+using sfmcloud::cell_of;  // (cloud.h's: one body for grid_build's kernel, the walks and the CPU stubs)
 
 // distance from p to the nearest face of the block of cells [c - R, c + R] that has cells beyond it (+inf if none)
 __device__ __forceinline__ double block_bound(const GridDev& g, const float4& p, const int c[3], int R) {

@@ -240,6 +240,13 @@ class StructFromMotion {
   // reported on stderr with its residual.  mesh.cloud takes the vertices, mesh.polygons the triangles.  vizualizeMesh is
   // not built (GUI).
   void create_mesh(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PolygonMesh& mesh);
+  // (ours) the pass the reference's create_mesh still names (`cloud_smoothed`, src/Sfm.cpp:1347-1383) and does
+  // not run: pcl::MovingLeastSquares with search radius `radius` and the polynomial of `order` (0: the plane alone), normals
+  // computed; smoothed takes the surviving points in input order.
+  void smoothCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, double radius, int order, pcl::PointCloud<pcl::PointNormal>::Ptr& smoothed);
+  // create_mesh with that pass in front: sfmhip_cloud_mls at order 2 and radius smooth_radius, then the normals (k = 10, towards
+  // the sensor origin, times -1) and Poisson as above on the smoothed handle; the smoothed points never come to the host.
+  void create_mesh(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PolygonMesh& mesh, double smooth_radius);
   // (ours) the similarity ICP that brings `cloud` onto `reference`, a cloud of the same scene in metres (a
   // terrestrial scan, last year's reconstruction, a surveyed subset): sfmhip_cloud_register with the scale estimated, from
   // `guess` (NULL: the identity; a large motion needs one).  Returns the metres per cloud unit that Dendrometry takes as

@@ -60,6 +60,34 @@ void take(const pcl::PointCloud<pcl::PointXYZ>& in, const std::vector<int32_t>& 
   out = r;
 }
 
+// create_mesh's second half on a device cloud `h` whose normals (rows of 4 floats, flipped already) are `nrm`: pcl::Poisson
+// with the reference's setters, the mesh read back into `mesh`
+void poisson_mesh(sfmhip_cloud* h, const std::vector<float>& nrm, pcl::PolygonMesh& mesh) {
+  sfmhip_poisson_opts o;
+  sfmhip_poisson_default_opts(&o);  // setDepth(7), setPointWeight(4), setScale(1.1); rows of 4 floats
+  // the default cap of 4 * 2^depth steps ends conjugate gradients short of cg_rtol at depth 7 (DESIGN.md f-9: about
+  // 6 * 2^depth steps are needed); twice the default lets the solve converge
+  o.cg_max_iter = 8 << o.depth;
+  sfmhip_mesh* m = nullptr;
+  sfmhip_poisson_summary s;
+  check(sfmhip_cloud_poisson(h, nrm.data(), &o, &m, &s), "sfmhip_cloud_poisson");
+  if (s.cg_iterations >= o.cg_max_iter && s.cg_relative_residual > o.cg_rtol)
+    std::fprintf(stderr, "create_mesh: the Poisson solve stopped at its cap of %d steps with relative residual %.3e (cg_rtol %.1e)\n",
+                 (int)o.cg_max_iter, s.cg_relative_residual, o.cg_rtol);
+  std::vector<float> v(3 * (size_t)s.n_vertices + 3);
+  std::vector<int32_t> t(3 * (size_t)s.n_triangles + 3);
+  check(sfmhip_mesh_download(m, v.data(), t.data()), "sfmhip_mesh_download");
+  sfmhip_mesh_destroy(m);
+  mesh = pcl::PolygonMesh();
+  mesh.cloud.points.resize((size_t)s.n_vertices);
+  for (int i = 0; i < s.n_vertices; ++i) mesh.cloud.points[i] = pcl::PointXYZ(v[3 * i], v[3 * i + 1], v[3 * i + 2]);
+  mesh.cloud.width = (uint32_t)s.n_vertices;
+  mesh.cloud.height = 1;
+  mesh.polygons.resize((size_t)s.n_triangles);
+  for (int i = 0; i < s.n_triangles; ++i)
+    mesh.polygons[i].vertices = {(uint32_t)t[3 * i], (uint32_t)t[3 * i + 1], (uint32_t)t[3 * i + 2]};
+}
+
 }  // namespace
 
 void StructFromMotion::cloudPointFilter(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud,
@@ -114,29 +142,40 @@ void StructFromMotion::create_mesh(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, p
     const pcl::Normal& q = normals->points[i];
     nrm[4 * i] = q.normal_x, nrm[4 * i + 1] = q.normal_y, nrm[4 * i + 2] = q.normal_z, nrm[4 * i + 3] = q.curvature;
   }
-  sfmhip_poisson_opts o;
-  sfmhip_poisson_default_opts(&o);  // setDepth(7), setPointWeight(4), setScale(1.1); rows of 4 floats
-  // the default cap of 4 * 2^depth steps ends conjugate gradients short of cg_rtol at depth 7 (DESIGN.md f-9: about
-  // 6 * 2^depth steps are needed); twice the default lets the solve converge
-  o.cg_max_iter = 8 << o.depth;
-  sfmhip_mesh* m = nullptr;
-  sfmhip_poisson_summary s;
-  check(sfmhip_cloud_poisson(device_cloud(*cloud), nrm.data(), &o, &m, &s), "sfmhip_cloud_poisson");
-  if (s.cg_iterations >= o.cg_max_iter && s.cg_relative_residual > o.cg_rtol)
-    std::fprintf(stderr, "create_mesh: the Poisson solve stopped at its cap of %d steps with relative residual %.3e (cg_rtol %.1e)\n",
-                 (int)o.cg_max_iter, s.cg_relative_residual, o.cg_rtol);
-  std::vector<float> v(3 * (size_t)s.n_vertices + 3);
-  std::vector<int32_t> t(3 * (size_t)s.n_triangles + 3);
-  check(sfmhip_mesh_download(m, v.data(), t.data()), "sfmhip_mesh_download");
-  sfmhip_mesh_destroy(m);
-  mesh = pcl::PolygonMesh();
-  mesh.cloud.points.resize((size_t)s.n_vertices);
-  for (int i = 0; i < s.n_vertices; ++i) mesh.cloud.points[i] = pcl::PointXYZ(v[3 * i], v[3 * i + 1], v[3 * i + 2]);
-  mesh.cloud.width = (uint32_t)s.n_vertices;
-  mesh.cloud.height = 1;
-  mesh.polygons.resize((size_t)s.n_triangles);
-  for (int i = 0; i < s.n_triangles; ++i)
-    mesh.polygons[i].vertices = {(uint32_t)t[3 * i], (uint32_t)t[3 * i + 1], (uint32_t)t[3 * i + 2]};
+  poisson_mesh(device_cloud(*cloud), nrm, mesh);
+}
+
+void StructFromMotion::smoothCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, double radius, int order,
+                                   pcl::PointCloud<pcl::PointNormal>::Ptr& smoothed) {
+  pcl::MovingLeastSquares<pcl::PointXYZ, pcl::PointNormal> mls;
+  mls.setInputCloud(cloud);
+  mls.setSearchRadius(radius);
+  mls.setPolynomialFit(order > 0);
+  if (order > 0) mls.setPolynomialOrder(order);
+  mls.setComputeNormals(true);
+  if (!smoothed) smoothed.reset(new pcl::PointCloud<pcl::PointNormal>);
+  mls.process(*smoothed);
+}
+
+void StructFromMotion::create_mesh(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PolygonMesh& mesh, double smooth_radius) {
+  // the pass the reference's create_mesh left commented out (`ne.setInputCloud (cloud_smoothed)`): MovingLeastSquares at
+  // order 2, then the normals and Poisson on the smoothed cloud, which stays on the device from the smoothing to the mesh
+  sfmhip_mls_opts mo;
+  sfmhip_mls_default_opts(&mo);
+  mo.search_radius = smooth_radius;
+  mo.compute_normals = 0;
+  int32_t m = 0;
+  sfmhip_cloud* sm = nullptr;
+  check(sfmhip_cloud_mls(device_cloud(*cloud), &mo, nullptr, nullptr, nullptr, &m, nullptr, &sm), "sfmhip_cloud_mls");
+  std::vector<float> nrm(4 * (size_t)m + 4);
+  const float vp[3] = {cloud->sensor_origin_[0], cloud->sensor_origin_[1], cloud->sensor_origin_[2]};
+  const int rc = sfmhip_cloud_normals(sm, 10, vp, nrm.data());
+  if (rc != SFMHIP_OK) sfmhip_cloud_destroy(sm);
+  check(rc, "sfmhip_cloud_normals");
+  for (int32_t i = 0; i < m; ++i)
+    for (int a = 0; a < 3; ++a) nrm[4 * (size_t)i + a] = -nrm[4 * (size_t)i + a];  // create_mesh: every normal times -1
+  poisson_mesh(sm, nrm, mesh);
+  sfmhip_cloud_destroy(sm);
 }
 
 double StructFromMotion::registerCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, const pcl::PointCloud<pcl::PointXYZ>& reference,

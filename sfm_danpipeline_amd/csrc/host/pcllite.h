@@ -440,6 +440,64 @@ class StatisticalOutlierRemoval {
   bool negative_ = false;
 };
 
+// pcl::MovingLeastSquares without upsampling (NONE, SIMPLE projection) over sfmhip_cloud_mls (include/sfmhip.h rules M1-M7,
+// DESIGN.md f-23).  PCL 1.8.1's defaults: no polynomial fit (order 0 in the library's terms), order 2 once it is on, normals
+// off, the Gaussian's parameter r * r unless set.  setSearchMethod is accepted and ignored: the search is the library's grid.
+template <typename PointInT, typename PointOutT>
+class MovingLeastSquares {
+ public:
+  void setInputCloud(const typename PointCloud<PointInT>::Ptr& cloud) { input_ = cloud; }
+  template <typename Tree>
+  void setSearchMethod(const Tree&) {}
+  void setSearchRadius(double radius) { radius_ = radius; }
+  void setPolynomialFit(bool fit) { fit_ = fit; }
+  void setPolynomialOrder(int order) { order_ = order; }
+  void setSqrGaussParam(double g) { gauss_ = g; }
+  void setComputeNormals(bool compute) { normals_ = compute; }
+  // the smoothed points in input order; points with fewer than 3 neighbours and non-finite points are left out
+  void process(PointCloud<PointOutT>& output) {
+    const PointCloud<PointInT> in = input_ ? *input_ : PointCloud<PointInT>();
+    const size_t n = in.size();
+    sfmhip_mls_opts o;
+    sfmhip_mls_default_opts(&o);
+    o.search_radius = radius_;
+    o.polynomial_order = fit_ ? order_ : 0;
+    o.compute_normals = normals_ ? 1 : 0;
+    o.sqr_gauss_param = gauss_;
+    std::vector<float> xyz(3 * n + 3), n4(4 * n + 4, 0.0f);
+    std::vector<int32_t> src(n + 1);
+    int32_t m = 0;
+    sfmhip_cloud* h = detail::upload(in);
+    const int rc = sfmhip_cloud_mls(h, &o, xyz.data(), n4.data(), src.data(), &m, nullptr, nullptr);
+    sfmhip_cloud_destroy(h);
+    detail::filter_check(rc, "sfmhip_cloud_mls");
+    PointCloud<PointOutT> out;
+    out.points.resize((size_t)m);
+    out.width = (uint32_t)m;
+    out.height = 1;
+    out.is_dense = true;
+    for (int a = 0; a < 4; ++a) out.sensor_origin_[a] = in.sensor_origin_[a];
+    for (int32_t r = 0; r < m; ++r) {
+      PointOutT p = PointOutT();
+      p.x = xyz[3 * r], p.y = xyz[3 * r + 1], p.z = xyz[3 * r + 2];
+      p.normal_x = n4[4 * r], p.normal_y = n4[4 * r + 1], p.normal_z = n4[4 * r + 2], p.curvature = n4[4 * r + 3];
+      out.points[r] = p;
+    }
+    indices_.reset(new PointIndices);
+    indices_->indices.assign(src.begin(), src.begin() + m);
+    output = out;
+  }
+  // the input index of every output row (of the last process())
+  std::shared_ptr<PointIndices> getCorrespondingIndices() const { return indices_; }
+
+ private:
+  typename PointCloud<PointInT>::Ptr input_;
+  double radius_ = 0.0, gauss_ = 0.0;
+  bool fit_ = false, normals_ = false;
+  int order_ = 2;
+  std::shared_ptr<PointIndices> indices_{new PointIndices};
+};
+
 // ---- pcl::IterativeClosestPoint, its similarity form and pcl::transformPointCloud with PCL's setters, forwarding to
 // sfmhip_cloud_register / sfmhip_cloud_transform (include/sfmhip.h, DESIGN.md f-17 rules 1-8).  The matrix is the 4 x 4 float
 // one PCL code reads the result from.  Not mirrored: reciprocal correspondences, RANSAC rejection, the Euclidean fitness epsilon.
