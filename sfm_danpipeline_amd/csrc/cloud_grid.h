@@ -115,7 +115,7 @@ struct Grow {
 };
 
 // the stages that keep state on the handle, and a stage's slot: the state and what deletes it
-enum Stage { SEGMENT, POISSON, DENDRO, GROUND, TREES, FILTER, REGISTER, ALIGN, TERRAIN, CROWNS, REGISTER_ICP, MLS, N_STAGES };
+enum Stage { SEGMENT, POISSON, DENDRO, GROUND, TREES, FILTER, REGISTER, ALIGN, TERRAIN, CROWNS, MLS, N_STAGES };
 struct StageSlot {
   void* p = nullptr;
   void (*free)(void*) = nullptr;

@@ -2,9 +2,9 @@
 // similarity ICP) as code that hipcc and a plain g++ both compile: moving a point, the pair test, the terms of the two
 // fixed-order sums, the Umeyama / Horn estimate over pose.h's svd3 and the loop's stop decision.  The device code
 // (register.hip) and the CPU test stub (tests/stub/register_capi.cpp) share these bodies, so the device result is checked
-// bit for bit against a CPU build.  Compile with -ffp-contract=off.  The host form of the whole call (run_host, with a plain
-// uniform grid of its own for the search: a pair is the least (d2, index), which no search structure changes) is below the
-// shared part.
+// bit for bit against a CPU build.  Compile with -ffp-contract=off.  Below the shared part: the host's search (a plain
+// uniform grid of its own: a pair is the least (d2, index), which no search structure changes) and the fixed-order sum.  The
+// host form of the whole call (run_host, run_host_batch) is an adapter of register_icp.h's one loop, included at the end.
 // PARITY UNPINNED: PCL is not in the image; what is marked + in DESIGN.md f-17 is a reading of PCL 1.8.1 from memory.
 #pragma once
 #include <cstdint>
@@ -196,11 +196,12 @@ namespace sfmreg {
 struct HostGrid {
   int n = 0, nv = 0, D[3] = {1, 1, 1};
   const float* xyz = nullptr;
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // the box of the nv finite points (f-22 rule 8 takes its centre from here)
   double o[3] = {0, 0, 0}, cell = 1;
   std::vector<int> start, order;
   void build(int n_, const float* xyz_) {
     n = n_, xyz = xyz_, nv = 0;
-    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0;
     for (int i = 0; i < n; ++i) {
       if (!sfmcloud::finite3(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2])) continue;
       for (int a = 0; a < 3; ++a) {
@@ -311,81 +312,6 @@ inline void sum_host(int n_src, Terms terms, double out[Q]) {
   }
 }
 
-// one step of rule 6 on the host: C_k under L.T into idx / d2 (prev: scratch for C_{k-1}), the two sums, the decision
-inline bool iterate_host(const HostGrid& g, const float* tgt, int n_src, const float* src, const Opts& o, float md2, Loop& L,
-                         std::vector<int32_t>& idx, std::vector<int32_t>& prev, std::vector<float>& d2) {
-  prev = idx;
-  nearest_host(g, n_src, src, L.T, md2, false, idx.data(), d2.data());
-  bool changed = false;
-  for (int i = 0; i < n_src; ++i) changed = changed || idx[i] != prev[i];
-  double s1[N1], s2[N2], mu_p[3], mu_m[3];
-  auto pm = [&](int i, float p[3], float m[3]) {
-    const bool paired = idx[i] >= 0;
-    for (int a = 0; a < 3; ++a) p[a] = src[3 * i + a], m[a] = paired ? tgt[3 * (size_t)idx[i] + a] : 0.0f;
-    return paired;
-  };
-  sum_host<N1>(n_src, [&](int i, double* v) {
-    float p[3], m[3];
-    const bool paired = pm(i, p, m);
-    terms1(paired, p, m, v);
-  }, s1);
-  means(s1, mu_p, mu_m);
-  sum_host<N2>(n_src, [&](int i, double* v) {
-    float p[3], m[3];
-    const bool paired = pm(i, p, m);
-    terms2(paired, p, m, d2[i], mu_p, mu_m, v);
-  }, s2);
-  return loop_step(L, o, changed, s1, s2);
-}
-
-// the whole of rule 6; idx (n_src, or NULL) receives the pairs under res.T.  false: rule 1 refuses
-inline bool run_host(int n_tgt, const float* tgt, int n_src, const float* src, const Opts& o, const Transform* init, Result& res, int32_t* idx_out) {
-  const Transform T0 = init ? *init : identity();
-  if (!valid_opts(o) || !valid_transform(T0)) return false;
-  HostGrid g;
-  g.build(n_tgt, tgt);
-  const float md2 = max_d2(o.max_dist);
-  std::vector<int32_t> idx((size_t)std::max(n_src, 1), -2), prev;
-  std::vector<float> d2((size_t)std::max(n_src, 1));
-  Loop L;
-  loop_init(L, T0);
-  while (!iterate_host(g, tgt, n_src, src, o, md2, L, idx, prev, d2)) {
-  }
-  res = L.res;
-  if (idx_out)
-    for (int i = 0; i < n_src; ++i) idx_out[i] = idx[i];
-  return true;
-}
-
-// f-18's batch: n_init starts in one lock-step loop over one grid, a record per problem; a problem that has stopped is left
-// alone.  results[b] and row b of idx_out (n_init x n_src, or NULL) are run_host's from inits[b].  false: refused, nothing
-// written.  `longest` (nullable): the iterations of the problem that ran longest.
-inline bool run_host_batch(int n_tgt, const float* tgt, int n_src, const float* src, const Opts& o, const Transform* inits, int n_init,
-                           Result* results, int32_t* idx_out, int* longest = nullptr) {
-  if (!valid_batch(o, inits, n_init)) return false;
-  HostGrid g;
-  g.build(n_tgt, tgt);
-  const float md2 = max_d2(o.max_dist);
-  const size_t n1 = (size_t)std::max(n_src, 1);
-  std::vector<std::vector<int32_t>> idx((size_t)n_init, std::vector<int32_t>(n1, -2));
-  std::vector<int32_t> prev;
-  std::vector<float> d2(n1);  // (a problem's d2 is read only inside its own step)
-  std::vector<Loop> L((size_t)n_init);
-  for (int b = 0; b < n_init; ++b) loop_init(L[b], inits[b]);
-  for (int round = 0, open = n_init; open > 0 && round <= o.max_iters; ++round)
-    for (int b = 0; b < n_init; ++b)
-      if (!L[b].stop && iterate_host(g, tgt, n_src, src, o, md2, L[b], idx[b], prev, d2)) --open;
-  int most = 0;
-  for (int b = 0; b < n_init; ++b) {
-    results[b] = L[b].res;
-    most = std::max(most, (int)L[b].res.iterations);
-    if (idx_out)
-      for (int i = 0; i < n_src; ++i) idx_out[(size_t)b * n_src + i] = idx[b][i];
-  }
-  if (longest) *longest = most;
-  return true;
-}
-
 // rule 8 on the host: the image of every point (a non-finite point stays)
 inline void transform_host(int n, const float* xyz, const Transform& T, float* out) {
   for (int i = 0; i < n; ++i) {
@@ -397,4 +323,8 @@ inline void transform_host(int n, const float* xyz, const Transform& T, float* o
 }
 
 }  // namespace sfmreg
+
+// the whole call (run_host, run_host_batch) is register_icp.h's one loop with metric 0 and no rejector: that header is built
+// on the rules above and this one ends by including it, so either of the two can be included alone
+#include "register_icp.h"
 #endif

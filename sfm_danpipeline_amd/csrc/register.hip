@@ -1,24 +1,39 @@
-// register.hip -- two clouds meet: the nearest target point of every source point, rigid and similarity
-// ICP around it, and the two calls that keep the result on the device (transform, concat).  The rules are register.h's,
-// which the CPU test stub compiles too.
+// register.hip -- two clouds meet: the nearest target point of every source point, ONE ICP loop
+// around it behind the four looping entries (sfmhip_cloud_register, its batch, sfmhip_cloud_register_icp, its batch), and the two
+// calls that keep the result on the device (transform, concat).  The rules are register.h's and register_icp.h's, which the CPU
+// test stubs compile too.
 //
-// reg_nearest: a lane per source point; a source of at least SORT_MIN points is walked in the order of the target cells of its
-// images under the call's first transform (reg_keys + the handle's cell_sort, once per call), so that the lanes of a wave
-// walk the same rows; results do not depend on the order.  The point is moved by the current transform (read from the loop's
-// record on the device), its cell in the TARGET's k-NN grid is cell_of clamped to the grid, and the rings grow as in cloud_knn with one
-// best slot.  block_bound stays a lower bound for a point outside the grid's box: it only counts faces that have cells
-// beyond them, the clamped cell is the border cell on every axis on which the point is outside, so the face the point is
-// beyond is never counted, and the distance to every counted face is taken from the point's own coordinate.  The slack
-// adds the point's magnitude, since a source point can lie far from the box the grid's knn_abs_eps was sized for.
-// reg_sums1 / reg_sums2: 256 source points per workgroup through block_tree; reg_means and reg_update (one wave each)
-// fold the partials in ascending order, a lane per sum; reg_update's lane 0 then takes rule 6's decision (loop_step) and
-// writes the next transform.  The host reads the loop's record once per iteration; no n-sized array crosses the bus
-// inside the loop.  No atomics, no spins, no hand-offs between workgroups: the "pairs changed" flag is a plain store of 1.
+// The loop (run_loop) and its iteration (launch_iteration): the search, the rejectors, the sums, the update.  A call is a
+// batch of n_init problems, the problem being grid dimension y: problem b owns record b, row b of idx / d2 / kept and slab b of
+// the partials; a workgroup whose problem has stopped reads the stop flag and returns, so a stopped problem's row stays the
+// pairs under its result.  The host reads the block of records once per iteration and leaves when all have stopped; no
+// n-sized array crosses the bus inside the loop.  f-17's entries are the loop with metric 0 and no rejector (f-22 rule 7); what
+// the entries keep to themselves is their rule 1, the struct they hand back and which of the state's three timing records the
+// call fills.
 //
-// The batch (f-18, sfmhip_cloud_register_batch): the same kernels with the problem as grid dimension y.  Problem b owns record
-// b, row b of idx / d2 and slab b of the partials; a workgroup whose problem has stopped reads the stop flag and returns, so
-// a stopped problem's row stays the pairs under its result.  A single call is a batch of one whose record never reads
-// "stopped" at a launch.  The host reads the block of records once per iteration and leaves when all have stopped.
+// reg_nearest: a lane per source point; in a single call a source of at least SORT_MIN points is walked in the order of the
+// target cells of its images under the call's first transform (reg_keys + the handle's cell_sort, once per call), so that the
+// lanes of a wave walk the same rows; results do not depend on the order.  The point is moved by the current transform (read
+// from the loop's record on the device), its cell in the TARGET's k-NN grid is cell_of clamped to the grid, and the rings grow
+// as in cloud_knn with one best slot.  block_bound stays a lower bound for a point outside the grid's box: it only counts faces
+// that have cells beyond them, the clamped cell is the border cell on every axis on which the point is outside, so the face the
+// point is beyond is never counted, and the distance to every counted face is taken from the point's own coordinate.  The
+// slack adds the point's magnitude, since a source point can lie far from the box the grid's knn_abs_eps was sized for.
+//
+// The rejectors (f-22 rules 3 - 5) run only when one is active: the plane metric (a target row without a plane), one_to_one or
+// trim < 1.  Then the search tracks nothing, the rejectors write a row of kept pairs and raise "changed" themselves, and the sums
+// read that row.  Without one the stage is skipped, launches and timing bracket alike: the search tracks "changed" on the idx
+// row, the sums read idx, and idx is what the caller gets.  icp_survive: rule 3 and, with one_to_one, an unsigned 64-bit atomicMin
+// of (bits(d2) << 32 | i) into the target's slot; icp_unique: a source stays when its slot names it (a loser keeps its target as
+// -(j + 2), so icp_keep can clear the slot by a plain store: the slots are all "empty" again after every iteration).  The trim's
+// tau: a radix select over the float's bits, four digits of 8, a 256-bin integer histogram per digit (LDS atomics, then one
+// global atomicAdd per occupied bin: exact whatever the order) and one wave that finds the digit.  icp_keep writes the kept row,
+// raises "changed" and records tau.
+//
+// The sums: 256 source points per workgroup through block_tree (reg_sums1 / reg_sums2, metric 0) or its unrolled form
+// (icp_plane_sums, metric 1); reg_means, reg_update and icp_plane_update (one wave each) fold the partials in ascending block order,
+// a lane per sum (fold_partials); lane 0 then takes the step's decision (loop_step / plane_loop_step) and writes the next
+// transform.  No spins, no hand-offs between workgroups, no float atomics: the "pairs changed" flag is a plain store of 1.
 #include "common.h"
 #include "cloud.h"
 #include "cloud_grid.h"
@@ -48,17 +63,54 @@ struct DevLoop {  // the loop's record on the device
   double s1[N1], mu_p[3], mu_m[3];
 };
 
-struct RegState {  // on the TARGET handle, freed with it
+struct Sel {  // the trim's select of one problem
+  uint32_t prefix, k, n;
+  float tau;
+};
+struct Centre {
+  double c[3];
+};
+struct Timing {  // host-clock ms of a call's stages (search, rejectors, sums, update) and the iterations of its longest problem
+  double ms[4] = {0, 0, 0, 0};
+  int iterations = 0;
+};
+
+struct RegState {  // the one state of the loop, on the TARGET handle, freed with it
   static constexpr sfmgrid::Stage slot = sfmgrid::REGISTER;
   Grow<int> idx, kin, kout, vin, order;
   Grow<float> d2;
   Grow<double> part1, part2;
   Grow<DevLoop> rec;
-  double ms[3] = {0, 0, 0};  // search, sums, update of the last register call
-  int iterations = 0;
-  double batch_ms[3] = {0, 0, 0};  // the same of the last batch call
-  int batch_iterations = 0;        // ... of its longest problem
+  // f-22's, each sized only by a call that asks for its feature: the rejectors' rows, one_to_one's slots, the trim's select, the
+  // plane metric's partials and normals
+  Grow<int> cand, kept;
+  Grow<sfmreg::IcpExtra> extra;
+  Grow<unsigned long long> slots;
+  Grow<uint32_t> hist;
+  Grow<Sel> sel;
+  Grow<double> part;
+  Grow<float> normals;
+  Timing single, batch, icp;  // of the last sfmhip_cloud_register, of the last _batch, of the last _icp / _icp_batch
 };
+
+// lane k < Q: sum k of the n_blocks partials in ascending block order into s[k]; every lane may read s afterwards
+template <int Q>
+__device__ __forceinline__ void fold_partials(const double* part, int n_blocks, double* s) {
+  const int k = threadIdx.x;
+  if (k < Q) {
+    double a = 0.0;
+    for (int b = 0; b < n_blocks; ++b) a = a + part[(size_t)b * Q + k];
+    s[k] = a;
+  }
+  __syncthreads();
+}
+// lane k < Q stores its workgroup's partial of sum k from the four wave sums the block's tree left in sh, by the tree's own
+// pairing: what block_tree hands every lane as v[k], read where it lies (picking v[k] by the lane would index the register array)
+template <int Q>
+__device__ __forceinline__ void store_partial(const double (*sh)[4], double* part) {
+  const int k = threadIdx.x;
+  if (k < Q) part[(size_t)blockIdx.x * Q + k] = (sh[k][0] + sh[k][1]) + (sh[k][2] + sh[k][3]);
+}
 
 __device__ __forceinline__ void scan_best(const GridDev& g, int row, int xa, int xb, const float4& q, float& bd, int& bi) {
   int s, e;
@@ -161,25 +213,15 @@ __global__ __launch_bounds__(SUM_BLOCK) void reg_sums1(const float* src, const f
   double v[N1];
   sfmreg::terms1(paired, p, m, v);
   sfmsum::block_tree<N1>(v, sh);
-  if (threadIdx.x < N1) {
-    double w = v[0];
-    for (int k = 1; k < N1; ++k) w = threadIdx.x == k ? v[k] : w;
-    part[(size_t)blockIdx.x * N1 + threadIdx.x] = w;
-  }
+  store_partial<N1>(sh, part);
 }
 
 // the partials of pass 1 in ascending block order, a lane per sum; then the means
 __global__ __launch_bounds__(64) void reg_means(const double* part, int n_blocks, DevLoop* rec) {
-  const int k = threadIdx.x;
   rec += blockIdx.x, part += (size_t)n_blocks * N1 * blockIdx.x;
   if (rec->L.stop) return;
-  if (k < N1) {
-    double s = 0.0;
-    for (int b = 0; b < n_blocks; ++b) s = s + part[(size_t)b * N1 + k];
-    rec->s1[k] = s;
-  }
-  __syncthreads();
-  if (k == 0) sfmreg::means(rec->s1, rec->mu_p, rec->mu_m);
+  fold_partials<N1>(part, n_blocks, rec->s1);
+  if (threadIdx.x == 0) sfmreg::means(rec->s1, rec->mu_p, rec->mu_m);
 }
 
 __global__ __launch_bounds__(SUM_BLOCK) void reg_sums2(const float* src, const float* tgt, const int* idx, const float* d2, int n_src,
@@ -196,26 +238,16 @@ __global__ __launch_bounds__(SUM_BLOCK) void reg_sums2(const float* src, const f
   double v[N2];
   sfmreg::terms2(paired, p, m, paired ? d2[i] : 0.0f, mu_p, mu_m, v);
   sfmsum::block_tree<N2>(v, sh);
-  if (threadIdx.x < N2) {
-    double w = v[0];
-    for (int k = 1; k < N2; ++k) w = threadIdx.x == k ? v[k] : w;
-    part[(size_t)blockIdx.x * N2 + threadIdx.x] = w;
-  }
+  store_partial<N2>(sh, part);
 }
 
 // pass 2's partials folded as pass 1's, then rule 6's step on lane 0: the stop decision or the next transform
 __global__ __launch_bounds__(64) void reg_update(const double* part, int n_blocks, Opts o, DevLoop* rec) {
   __shared__ double s2[N2];
-  const int k = threadIdx.x;
   rec += blockIdx.x, part += (size_t)n_blocks * N2 * blockIdx.x;
   if (rec->L.stop) return;
-  if (k < N2) {
-    double s = 0.0;
-    for (int b = 0; b < n_blocks; ++b) s = s + part[(size_t)b * N2 + k];
-    s2[k] = s;
-  }
-  __syncthreads();
-  if (k == 0) {
+  fold_partials<N2>(part, n_blocks, s2);
+  if (threadIdx.x == 0) {
     double t2[N2];
     for (int q = 0; q < N2; ++q) t2[q] = s2[q];
     sfmreg::loop_step(rec->L, o, rec->changed != 0, rec->s1, t2);
@@ -276,68 +308,7 @@ void launch_nearest(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, const int
                      order, s->rec.p, (size_t)src->n, md2, exact ? 1 : 0, s->idx.p, s->d2.p, track ? 1 : 0);
 }
 
-// one iteration of rule 6 for n_init problems: the search, the two sums, the step.  t (nullable): host-clock ms added to
-// search / sums / update, a stream synchronisation between them; else the launches only
-int launch_iteration(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, const int* order, const Opts& o, float md2, int n_init, double* t) {
-  hipStream_t st = tgt->ctx->stream;
-  const int n = src->n, nb = (int)blocks(n, SUM_BLOCK);
-  const size_t row = (size_t)n;
-  DevLoop* rec = s->rec.p;
-  double t0 = 0, t1 = 0, t2 = 0;
-  if (t) t0 = sfm_now_ms();
-  launch_nearest(tgt, src, s, order, md2, false, true, n_init);
-  SFM_HIP_TRY(hipGetLastError());
-  if (t) {
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-    t1 = sfm_now_ms();
-  }
-  if (nb > 0) hipLaunchKernelGGL(reg_sums1, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, s->idx.p, n, rec, row, s->part1.p);
-  hipLaunchKernelGGL(reg_means, dim3(n_init), dim3(64), 0, st, s->part1.p, nb, rec);
-  if (nb > 0)
-    hipLaunchKernelGGL(reg_sums2, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, s->idx.p, s->d2.p, n, rec, row, s->part2.p);
-  SFM_HIP_TRY(hipGetLastError());
-  if (t) {
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-    t2 = sfm_now_ms();
-  }
-  hipLaunchKernelGGL(reg_update, dim3(n_init), dim3(64), 0, st, s->part2.p, nb, o, rec);
-  SFM_HIP_TRY(hipGetLastError());
-  if (t) t[0] += t1 - t0, t[1] += t2 - t1, t[2] -= t2;  // (the caller adds the clock after the record's read)
-  return SFMHIP_OK;
-}
-
 // ---------------------------------------------------------------- f-22: the rejectors and the point-to-plane step
-// The second entry runs reg_nearest as it is (into the raw row idx / d2, nothing tracked), then the rejectors of f-22 rules
-// 3 - 5 into a row of kept pairs, then either f-17's own sums and update on that row (metric 0) or icp_plane_sums /
-// icp_plane_update (metric 1).  The loop's record is f-17's DevLoop, so the search reads its transform and its stop flag from
-// where it always did; what the plane metric and the trim add is an IcpExtra per problem.  icp_survive: rule 3 and, with
-// one_to_one, an unsigned 64-bit atomicMin of (bits(d2) << 32 | i) into the target's slot; icp_unique: a source stays when its
-// slot names it (a loser keeps its target as -(j + 2), so icp_keep can clear the slot by a plain store: the slots are all
-// "empty" again after every iteration).  The trim's tau: a radix select over the float's bits, four digits of 8, a 256-bin
-// integer histogram per digit (LDS atomics, then one global atomicAdd per occupied bin: exact whatever the order) and one wave
-// that finds the digit.  icp_keep writes the kept row, raises "changed" and records tau.  The problem is grid dimension y
-// throughout.  No spins, no hand-offs between workgroups, no float atomics.
-struct Sel {  // the select's state of one problem
-  uint32_t prefix, k, n;
-  float tau;
-};
-struct Centre {
-  double c[3];
-};
-
-struct IcpState {  // on the TARGET handle, beside f-17's (which does not move)
-  static constexpr sfmgrid::Stage slot = sfmgrid::REGISTER_ICP;
-  Grow<int> cand, kept;
-  Grow<unsigned long long> slots;
-  Grow<uint32_t> hist;
-  Grow<Sel> sel;
-  Grow<sfmreg::IcpExtra> extra;
-  Grow<double> part;
-  Grow<float> normals;
-  double ms[4] = {0, 0, 0, 0};  // search, rejectors, sums, update of the last call
-  int iterations = 0;           // ... of its longest problem
-};
-
 __global__ __launch_bounds__(256) void icp_survive(const int* idx, const float* d2, const float* normals, int stride, int metric, int one_to_one,
                                                    int n_src, int n_tgt, const DevLoop* rec, size_t row, int* cand, unsigned long long* slot) {
   if (rec[blockIdx.y].L.stop) return;
@@ -469,10 +440,7 @@ __global__ __launch_bounds__(SUM_BLOCK) void icp_plane_sums(const float* src, co
     if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = x;
   }
   __syncthreads();
-  if (threadIdx.x < NP) {
-    const double w = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
-    part[(size_t)blockIdx.x * NP + threadIdx.x] = w;
-  }
+  store_partial<NP>(sh, part);
 }
 
 // the partials in ascending block order, a lane per sum; then rule 9's step on lane 0
@@ -480,16 +448,10 @@ __global__ __launch_bounds__(64) void icp_plane_update(const double* part, int n
                                                        sfmreg::IcpExtra* extra) {
   constexpr int NP = sfmreg::NP;
   __shared__ double s[NP];
-  const int k = threadIdx.x;
   rec += blockIdx.x, part += (size_t)n_blocks * NP * blockIdx.x;
   if (rec->L.stop) return;
-  if (k < NP) {
-    double a = 0.0;
-    for (int b = 0; b < n_blocks; ++b) a = a + part[(size_t)b * NP + k];
-    s[k] = a;
-  }
-  __syncthreads();
-  if (k == 0) {
+  fold_partials<NP>(part, n_blocks, s);
+  if (threadIdx.x == 0) {
     double t[NP];
     for (int q = 0; q < NP; ++q) t[q] = s[q];
     sfmreg::plane_loop_step(rec->L, extra[blockIdx.x], o, ctr.c, t);
@@ -497,51 +459,54 @@ __global__ __launch_bounds__(64) void icp_plane_update(const double* part, int n
   }
 }
 
-// one iteration of the second entry for n_init problems.  t (nullable): host-clock ms added to search / rejectors / sums /
-// update, a stream synchronisation between them
-int launch_icp_iteration(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, IcpState* z, const int* order, const sfmreg::IcpOpts& o, float md2,
-                         const Centre& ctr, int n_init, double* t) {
+// one iteration for n_init problems: the search, the rejectors when one is active (else skipped, and the search tracks the idx
+// row itself), the sums and the update of the metric.  t (nullable): host-clock ms added to search / rejectors / sums / update, a
+// stream synchronisation after every stage that ran; else the launches only
+int launch_iteration(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, const int* order, const sfmreg::IcpOpts& o, float md2, const Centre& ctr,
+                     bool reject, int n_init, double* t) {
   hipStream_t st = tgt->ctx->stream;
   const int n = src->n, nb = (int)blocks(n, SUM_BLOCK), nt = tgt->n;
   const size_t row = (size_t)n;
   DevLoop* rec = s->rec.p;
+  const int* pairs = reject ? s->kept.p : s->idx.p;  // the row the sums read
   const bool trim = o.trim < 1.0;
   double t0 = 0, t1 = 0, t2 = 0, t3 = 0;
   if (t) t0 = sfm_now_ms();
-  launch_nearest(tgt, src, s, order, md2, false, false, n_init);
+  launch_nearest(tgt, src, s, order, md2, false, !reject, n_init);
   SFM_HIP_TRY(hipGetLastError());
   if (t) {
     SFM_HIP_TRY(hipStreamSynchronize(st));
-    t1 = sfm_now_ms();
+    t2 = t1 = sfm_now_ms();
   }
-  if (nb > 0) {
-    const dim3 grid(nb, n_init);
-    hipLaunchKernelGGL(icp_survive, grid, dim3(256), 0, st, s->idx.p, s->d2.p, z->normals.p, o.normal_stride, o.metric, o.one_to_one, n, nt, rec, row,
-                       z->cand.p, z->slots.p);
-    if (o.one_to_one) hipLaunchKernelGGL(icp_unique, grid, dim3(256), 0, st, n, nt, rec, row, z->cand.p, z->slots.p);
-    if (trim) {
-      SFM_HIP_TRY(hipMemsetAsync(z->hist.p, 0, sizeof(uint32_t) * 1024 * (size_t)n_init, st));
-      for (int pass = 0; pass < 4; ++pass) {
-        hipLaunchKernelGGL(icp_hist, grid, dim3(256), 0, st, z->cand.p, s->d2.p, n, rec, row, z->sel.p, pass, z->hist.p);
-        hipLaunchKernelGGL(icp_pick, dim3(n_init), dim3(64), 0, st, z->hist.p, pass, o.trim, rec, z->sel.p);
+  if (reject) {
+    if (nb > 0) {
+      const dim3 grid(nb, n_init);
+      hipLaunchKernelGGL(icp_survive, grid, dim3(256), 0, st, s->idx.p, s->d2.p, s->normals.p, o.normal_stride, o.metric, o.one_to_one, n, nt, rec,
+                         row, s->cand.p, s->slots.p);
+      if (o.one_to_one) hipLaunchKernelGGL(icp_unique, grid, dim3(256), 0, st, n, nt, rec, row, s->cand.p, s->slots.p);
+      if (trim) {
+        SFM_HIP_TRY(hipMemsetAsync(s->hist.p, 0, sizeof(uint32_t) * 1024 * (size_t)n_init, st));
+        for (int pass = 0; pass < 4; ++pass) {
+          hipLaunchKernelGGL(icp_hist, grid, dim3(256), 0, st, s->cand.p, s->d2.p, n, rec, row, s->sel.p, pass, s->hist.p);
+          hipLaunchKernelGGL(icp_pick, dim3(n_init), dim3(64), 0, st, s->hist.p, pass, o.trim, rec, s->sel.p);
+        }
       }
+      hipLaunchKernelGGL(icp_keep, grid, dim3(256), 0, st, s->cand.p, s->d2.p, n, nt, rec, row, trim ? s->sel.p : nullptr, o.one_to_one, s->slots.p,
+                         s->kept.p, s->extra.p);
     }
-    hipLaunchKernelGGL(icp_keep, grid, dim3(256), 0, st, z->cand.p, s->d2.p, n, nt, rec, row, trim ? z->sel.p : nullptr, o.one_to_one, z->slots.p,
-                       z->kept.p, z->extra.p);
-  }
-  SFM_HIP_TRY(hipGetLastError());
-  if (t) {
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-    t2 = sfm_now_ms();
+    SFM_HIP_TRY(hipGetLastError());
+    if (t) {
+      SFM_HIP_TRY(hipStreamSynchronize(st));
+      t2 = sfm_now_ms();
+    }
   }
   if (o.metric == sfmreg::METRIC_POINT) {
-    if (nb > 0) hipLaunchKernelGGL(reg_sums1, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, z->kept.p, n, rec, row, s->part1.p);
+    if (nb > 0) hipLaunchKernelGGL(reg_sums1, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, pairs, n, rec, row, s->part1.p);
     hipLaunchKernelGGL(reg_means, dim3(n_init), dim3(64), 0, st, s->part1.p, nb, rec);
-    if (nb > 0)
-      hipLaunchKernelGGL(reg_sums2, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, z->kept.p, s->d2.p, n, rec, row, s->part2.p);
+    if (nb > 0) hipLaunchKernelGGL(reg_sums2, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, pairs, s->d2.p, n, rec, row, s->part2.p);
   } else if (nb > 0) {
-    hipLaunchKernelGGL(icp_plane_sums, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, z->normals.p, o.normal_stride, z->kept.p,
-                       s->d2.p, n, rec, row, ctr, o.with_scale, z->part.p);
+    hipLaunchKernelGGL(icp_plane_sums, dim3(nb, n_init), dim3(SUM_BLOCK), 0, st, src->xyz, tgt->xyz, s->normals.p, o.normal_stride, pairs, s->d2.p, n,
+                       rec, row, ctr, o.with_scale, s->part.p);
   }
   SFM_HIP_TRY(hipGetLastError());
   if (t) {
@@ -549,61 +514,77 @@ int launch_icp_iteration(sfmhip_cloud* tgt, sfmhip_cloud* src, RegState* s, IcpS
     t3 = sfm_now_ms();
   }
   if (o.metric == sfmreg::METRIC_POINT) hipLaunchKernelGGL(reg_update, dim3(n_init), dim3(64), 0, st, s->part2.p, nb, sfmreg::point_opts(o), rec);
-  else hipLaunchKernelGGL(icp_plane_update, dim3(n_init), dim3(64), 0, st, z->part.p, nb, o, ctr, rec, z->extra.p);
+  else hipLaunchKernelGGL(icp_plane_update, dim3(n_init), dim3(64), 0, st, s->part.p, nb, o, ctr, rec, s->extra.p);
   SFM_HIP_TRY(hipGetLastError());
   if (t) t[0] += t1 - t0, t[1] += t2 - t1, t[2] += t3 - t2, t[3] -= t3;  // (the caller adds the clock after the record's read)
   return SFMHIP_OK;
 }
 
-// both entries: n_init starts in one lock-step loop (a single call: one start, the source walked in cell order)
-int run_icp(sfmhip_cloud* tgt, sfmhip_cloud* src, const float* normals, const sfmreg::IcpOpts& o, const Transform* inits, int n_init, bool single,
-            sfmhip_icp_result* out, int32_t* idx) {
+struct Sink {  // where a call's outcome goes
+  Timing RegState::*clock;           // which of the state's timing records the call fills
+  int32_t* idx;                      // n_init rows of the pairs under the results (nullable)
+  std::vector<sfmreg::IcpResult> res;  // one per start
+};
+
+// the one loop: n_init starts in lock step (cell_order: the source walked in the order of the target's cells under the first
+// start -- the single calls; a batch would need a sort per start, and results do not depend on it).  The entries have applied
+// their rule 1
+int run_loop(sfmhip_cloud* tgt, sfmhip_cloud* src, const float* normals, const sfmreg::IcpOpts& o, const Transform* inits, int n_init,
+             bool cell_order, Sink& sink) {
   RegState* s = nullptr;
   SFM_TRY(prepare(tgt, src, &s, n_init));
-  IcpState* z = stage<IcpState>(tgt);
   hipStream_t st = tgt->ctx->stream;
   const bool timing = tgt->ctx->timing;
   const int n = src->n;
   const size_t n1 = (size_t)std::max(n, 1), nt1 = (size_t)std::max(tgt->n, 1), B = (size_t)n_init, nb = blocks(n1, SUM_BLOCK);
-  const bool plane = o.metric == sfmreg::METRIC_PLANE;
-  SFM_TRY(z->cand.need(B * n1));
-  SFM_TRY(z->kept.need(B * n1));
-  SFM_TRY(z->extra.need(B));
-  SFM_TRY(z->slots.need(o.one_to_one ? B * nt1 : 1));
-  SFM_TRY(z->hist.need(B * 1024));
-  SFM_TRY(z->sel.need(B));
-  SFM_TRY(z->part.need(plane ? B * nb * sfmreg::NP : 1));
-  SFM_TRY(z->normals.need(plane ? nt1 * (size_t)o.normal_stride : 1));
-  if (plane && tgt->n > 0)  // rule 3: once per call
-    SFM_HIP_TRY(hipMemcpyAsync(z->normals.p, normals, sizeof(float) * (size_t)tgt->n * o.normal_stride, hipMemcpyHostToDevice, st));
-  if (o.one_to_one) SFM_HIP_TRY(hipMemsetAsync(z->slots.p, 0xFF, sizeof(unsigned long long) * B * nt1, st));
+  const bool plane = o.metric == sfmreg::METRIC_PLANE, trim = o.trim < 1.0, reject = plane || trim || o.one_to_one != 0;
+  if (reject) {
+    SFM_TRY(s->cand.need(B * n1));
+    SFM_TRY(s->kept.need(B * n1));
+    SFM_TRY(s->extra.need(B));
+  }
+  if (o.one_to_one) {
+    SFM_TRY(s->slots.need(B * nt1));
+    SFM_HIP_TRY(hipMemsetAsync(s->slots.p, 0xFF, sizeof(unsigned long long) * B * nt1, st));
+  }
+  if (trim) {
+    SFM_TRY(s->hist.need(B * 1024));
+    SFM_TRY(s->sel.need(B));
+  }
+  if (plane) {
+    SFM_TRY(s->part.need(B * nb * sfmreg::NP));
+    SFM_TRY(s->normals.need(nt1 * (size_t)o.normal_stride));
+    if (tgt->n > 0)  // rule 3: once per call
+      SFM_HIP_TRY(hipMemcpyAsync(s->normals.p, normals, sizeof(float) * (size_t)tgt->n * o.normal_stride, hipMemcpyHostToDevice, st));
+  }
   Centre ctr;
   sfmreg::box_centre(tgt->n_valid, tgt->lo, tgt->hi, ctr.c);
   const float md2 = sfmreg::max_d2(o.max_dist);
-  for (double& m : z->ms) m = 0;
-  z->iterations = 0;
+  Timing& clock = s->*sink.clock;
+  clock = Timing();
   std::vector<DevLoop> h(B);
   std::vector<sfmreg::IcpExtra> ex(B);
   memset(h.data(), 0, sizeof(DevLoop) * B);
   for (size_t b = 0; b < B; ++b) sfmreg::loop_init(h[b].L, inits[b]), ex[b].plane_mse = sfmreg::qnan_d(), ex[b].trim_d2 = sfmreg::inf_d();
   DevLoop* rec = s->rec.p;
+  int* pairs = reject ? s->kept.p : s->idx.p;  // the row under the results
   SFM_HIP_TRY(hipMemcpyAsync(rec, h.data(), sizeof(DevLoop) * B, hipMemcpyHostToDevice, st));
-  SFM_HIP_TRY(hipMemcpyAsync(z->extra.p, ex.data(), sizeof(sfmreg::IcpExtra) * B, hipMemcpyHostToDevice, st));
-  SFM_HIP_TRY(hipMemsetAsync(z->kept.p, 0xFE, sizeof(int) * B * n1, st));  // (no index: C_0 differs from it)
+  if (reject) SFM_HIP_TRY(hipMemcpyAsync(s->extra.p, ex.data(), sizeof(sfmreg::IcpExtra) * B, hipMemcpyHostToDevice, st));
+  SFM_HIP_TRY(hipMemsetAsync(pairs, 0xFE, sizeof(int) * B * n1, st));  // (no index: C_0 differs from it)
   const int* order = nullptr;
-  if (single) {
+  if (cell_order) {
     const double ts = timing ? sfm_now_ms() : 0.0;
     SFM_TRY(sort_source(tgt, src, s, &rec->L.T, &order));
     if (timing) {
       SFM_HIP_TRY(hipStreamSynchronize(st));
-      z->ms[0] = sfm_now_ms() - ts;  // (the source's cell order counts as search)
+      clock.ms[0] = sfm_now_ms() - ts;  // (the source's cell order counts as search)
     }
   }
   for (int round = 0;; ++round) {
-    SFM_TRY(launch_icp_iteration(tgt, src, s, z, order, o, md2, ctr, n_init, timing ? z->ms : nullptr));
+    SFM_TRY(launch_iteration(tgt, src, s, order, o, md2, ctr, reject, n_init, timing ? clock.ms : nullptr));
     SFM_HIP_TRY(hipMemcpyAsync(h.data(), rec, sizeof(DevLoop) * B, hipMemcpyDeviceToHost, st));  // the block of records, once
     SFM_HIP_TRY(hipStreamSynchronize(st));
-    if (timing) z->ms[3] += sfm_now_ms();
+    if (timing) clock.ms[3] += sfm_now_ms();
     bool all = true;
     for (size_t b = 0; b < B; ++b) {
       if (h[b].L.k < 0 || h[b].L.k > o.max_iters) return SFMHIP_ERR_STATE;
@@ -612,13 +593,24 @@ int run_icp(sfmhip_cloud* tgt, sfmhip_cloud* src, const float* normals, const sf
     if (all) break;
     if (round >= o.max_iters) return SFMHIP_ERR_STATE;  // (a problem stops at k == max_iters at the latest)
   }
-  SFM_HIP_TRY(hipMemcpyAsync(ex.data(), z->extra.p, sizeof(sfmreg::IcpExtra) * B, hipMemcpyDeviceToHost, st));
-  if (idx && n > 0) SFM_HIP_TRY(hipMemcpyAsync(idx, z->kept.p, sizeof(int) * B * (size_t)n, hipMemcpyDeviceToHost, st));
+  if (reject) SFM_HIP_TRY(hipMemcpyAsync(ex.data(), s->extra.p, sizeof(sfmreg::IcpExtra) * B, hipMemcpyDeviceToHost, st));
+  if (sink.idx && n > 0)  // (n > 0: the rows are n apart on the device too)
+    SFM_HIP_TRY(hipMemcpyAsync(sink.idx, pairs, sizeof(int) * B * (size_t)n, hipMemcpyDeviceToHost, st));
   SFM_HIP_TRY(hipStreamSynchronize(st));
+  sink.res.resize(B);
   for (size_t b = 0; b < B; ++b) {
-    out[b] = mirror<sfmhip_icp_result>(sfmreg::icp_result(h[b].L.res, ex[b]));
-    z->iterations = std::max(z->iterations, (int)h[b].L.res.iterations);
+    sink.res[b] = sfmreg::icp_result(h[b].L.res, ex[b]);
+    clock.iterations = std::max(clock.iterations, (int)h[b].L.res.iterations);
   }
+  return SFMHIP_OK;
+}
+
+int report(sfmhip_cloud* tgt, Timing RegState::*clock, bool rejectors, double* ms, int32_t* iterations) {
+  if (!tgt || !ms) return SFMHIP_ERR_ARG;
+  const Timing& t = stage<RegState>(tgt)->*clock;
+  for (int i = 0; i < 4; ++i)
+    if (rejectors || i != 1) *ms++ = t.ms[i];  // (f-17's calls report three stages: they run no rejector)
+  if (iterations) *iterations = t.iterations;
   return SFMHIP_OK;
 }
 
@@ -634,7 +626,10 @@ extern "C" int sfmhip_cloud_register_icp(sfmhip_cloud* tgt, sfmhip_cloud* src, c
   const sfmreg::IcpOpts o = opts ? mirror<sfmreg::IcpOpts>(*opts) : sfmreg::default_icp_opts();
   const Transform T0 = init ? mirror<Transform>(*init) : sfmreg::identity();
   if (!sfmreg::valid_icp_batch(o, target_normals != nullptr, &T0, 1)) return SFMHIP_ERR_ARG;
-  return run_icp(tgt, src, target_normals, o, &T0, 1, true, out, idx);
+  Sink sink{&RegState::icp, idx};
+  SFM_TRY(run_loop(tgt, src, target_normals, o, &T0, 1, true, sink));
+  *out = mirror<sfmhip_icp_result>(sink.res[0]);
+  return SFMHIP_OK;
 }
 
 extern "C" int sfmhip_cloud_register_icp_batch(sfmhip_cloud* tgt, sfmhip_cloud* src, const float* target_normals, const sfmhip_icp_opts* opts,
@@ -643,15 +638,14 @@ extern "C" int sfmhip_cloud_register_icp_batch(sfmhip_cloud* tgt, sfmhip_cloud* 
   const sfmreg::IcpOpts o = opts ? mirror<sfmreg::IcpOpts>(*opts) : sfmreg::default_icp_opts();
   static_assert(sizeof(sfmhip_transform) == sizeof(Transform), "the C ABI mirrors register.h");
   if (!sfmreg::valid_icp_batch(o, target_normals != nullptr, (const Transform*)inits, n_init)) return SFMHIP_ERR_ARG;
-  return run_icp(tgt, src, target_normals, o, (const Transform*)inits, n_init, false, out, idx);
+  Sink sink{&RegState::icp, idx};
+  SFM_TRY(run_loop(tgt, src, target_normals, o, (const Transform*)inits, n_init, false, sink));
+  for (int b = 0; b < n_init; ++b) out[b] = mirror<sfmhip_icp_result>(sink.res[b]);
+  return SFMHIP_OK;
 }
 
 extern "C" int sfmhip_cloud_register_icp_last_timing(sfmhip_cloud* tgt, double ms4[4], int32_t* iterations) {
-  if (!tgt || !ms4) return SFMHIP_ERR_ARG;
-  const IcpState* z = stage<IcpState>(tgt);
-  for (int i = 0; i < 4; ++i) ms4[i] = z->ms[i];
-  if (iterations) *iterations = z->iterations;
-  return SFMHIP_OK;
+  return report(tgt, &RegState::icp, true, ms4, iterations);
 }
 
 extern "C" void sfmhip_register_default_opts(sfmhip_register_opts* o) {
@@ -679,47 +673,16 @@ extern "C" int sfmhip_cloud_nearest(sfmhip_cloud* tgt, sfmhip_cloud* src, const 
   return SFMHIP_OK;
 }
 
+// f-17's and f-18's entries: the loop with metric 0 and no rejector (sfmreg::icp_opts), its result narrowed to theirs
 extern "C" int sfmhip_cloud_register(sfmhip_cloud* tgt, sfmhip_cloud* src, const sfmhip_register_opts* opts, const sfmhip_transform* init,
                                      sfmhip_register_result* out, int32_t* idx) {
   if (!tgt || !src || !out || tgt->ctx != src->ctx) return SFMHIP_ERR_ARG;
   const Opts o = opts ? mirror<Opts>(*opts) : sfmreg::default_opts();
   const Transform T0 = init ? mirror<Transform>(*init) : sfmreg::identity();
   if (!sfmreg::valid_opts(o) || !sfmreg::valid_transform(T0)) return SFMHIP_ERR_ARG;
-  RegState* s = nullptr;
-  SFM_TRY(prepare(tgt, src, &s));
-  hipStream_t st = tgt->ctx->stream;
-  const bool timing = tgt->ctx->timing;
-  const int n = src->n;
-  const float md2 = sfmreg::max_d2(o.max_dist);
-  s->ms[0] = s->ms[1] = s->ms[2] = 0;
-  s->iterations = 0;
-  DevLoop h;
-  memset(&h, 0, sizeof h);
-  sfmreg::loop_init(h.L, T0);
-  DevLoop* rec = s->rec.p;
-  SFM_HIP_TRY(hipMemcpyAsync(rec, &h, sizeof h, hipMemcpyHostToDevice, st));
-  SFM_HIP_TRY(hipMemsetAsync(s->idx.p, 0xFE, sizeof(int) * (size_t)std::max(n, 1), st));  // (no index: C_0 differs from it)
-  const int* order = nullptr;
-  const double ts = timing ? sfm_now_ms() : 0.0;
-  SFM_TRY(sort_source(tgt, src, s, &rec->L.T, &order));
-  if (timing) {
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-    s->ms[0] = sfm_now_ms() - ts;  // (the source's cell order counts as search)
-  }
-  for (;;) {
-    SFM_TRY(launch_iteration(tgt, src, s, order, o, md2, 1, timing ? s->ms : nullptr));
-    SFM_HIP_TRY(hipMemcpyAsync(&h.L, &rec->L, sizeof h.L, hipMemcpyDeviceToHost, st));  // the one small record of the iteration
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-    if (timing) s->ms[2] += sfm_now_ms();
-    if (h.L.stop) break;
-    if (h.L.k < 0 || h.L.k > o.max_iters) return SFMHIP_ERR_STATE;
-  }
-  s->iterations = h.L.res.iterations;
-  *out = mirror<sfmhip_register_result>(h.L.res);
-  if (idx && n > 0) {
-    SFM_HIP_TRY(hipMemcpyAsync(idx, s->idx.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-  }
+  Sink sink{&RegState::single, idx};
+  SFM_TRY(run_loop(tgt, src, nullptr, sfmreg::icp_opts(o), &T0, 1, true, sink));
+  *out = mirror<sfmhip_register_result>(sfmreg::point_result(sink.res[0]));
   return SFMHIP_OK;
 }
 
@@ -727,44 +690,11 @@ extern "C" int sfmhip_cloud_register_batch(sfmhip_cloud* tgt, sfmhip_cloud* src,
                                            int n_init, sfmhip_register_result* out, int32_t* idx) {
   if (!tgt || !src || !out || !inits || tgt->ctx != src->ctx) return SFMHIP_ERR_ARG;
   const Opts o = opts ? mirror<Opts>(*opts) : sfmreg::default_opts();
-  static_assert(sizeof(sfmhip_transform) == sizeof(Transform) && sizeof(sfmhip_register_result) == sizeof(Result), "the C ABI mirrors register.h");
+  static_assert(sizeof(sfmhip_transform) == sizeof(Transform), "the C ABI mirrors register.h");
   if (!sfmreg::valid_batch(o, (const Transform*)inits, n_init)) return SFMHIP_ERR_ARG;
-  RegState* s = nullptr;
-  SFM_TRY(prepare(tgt, src, &s, n_init));
-  hipStream_t st = tgt->ctx->stream;
-  const bool timing = tgt->ctx->timing;
-  const int n = src->n;
-  const float md2 = sfmreg::max_d2(o.max_dist);
-  s->batch_ms[0] = s->batch_ms[1] = s->batch_ms[2] = 0;
-  s->batch_iterations = 0;
-  std::vector<DevLoop> h((size_t)n_init);
-  memset(h.data(), 0, sizeof(DevLoop) * h.size());
-  for (int b = 0; b < n_init; ++b) sfmreg::loop_init(h[b].L, mirror<Transform>(inits[b]));
-  DevLoop* rec = s->rec.p;
-  SFM_HIP_TRY(hipMemcpyAsync(rec, h.data(), sizeof(DevLoop) * h.size(), hipMemcpyHostToDevice, st));
-  SFM_HIP_TRY(hipMemsetAsync(s->idx.p, 0xFE, sizeof(int) * (size_t)n_init * std::max(n, 1), st));  // (no index: C_0 differs from it)
-  // (no cell order per problem: each start would need a sort of its own, and results do not depend on it)
-  for (int round = 0;; ++round) {
-    SFM_TRY(launch_iteration(tgt, src, s, nullptr, o, md2, n_init, timing ? s->batch_ms : nullptr));
-    SFM_HIP_TRY(hipMemcpyAsync(h.data(), rec, sizeof(DevLoop) * h.size(), hipMemcpyDeviceToHost, st));  // the block of records, once
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-    if (timing) s->batch_ms[2] += sfm_now_ms();
-    bool all = true;
-    for (int b = 0; b < n_init; ++b) {
-      if (h[b].L.k < 0 || h[b].L.k > o.max_iters) return SFMHIP_ERR_STATE;
-      all = all && h[b].L.stop;
-    }
-    if (all) break;
-    if (round >= o.max_iters) return SFMHIP_ERR_STATE;  // (a problem stops at k == max_iters at the latest)
-  }
-  if (idx && n > 0) {  // (n > 0: the rows are n apart on the device too)
-    SFM_HIP_TRY(hipMemcpyAsync(idx, s->idx.p, sizeof(int) * (size_t)n_init * n, hipMemcpyDeviceToHost, st));
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-  }
-  for (int b = 0; b < n_init; ++b) {
-    out[b] = mirror<sfmhip_register_result>(h[b].L.res);
-    s->batch_iterations = std::max(s->batch_iterations, (int)h[b].L.res.iterations);
-  }
+  Sink sink{&RegState::batch, idx};
+  SFM_TRY(run_loop(tgt, src, nullptr, sfmreg::icp_opts(o), (const Transform*)inits, n_init, false, sink));
+  for (int b = 0; b < n_init; ++b) out[b] = mirror<sfmhip_register_result>(sfmreg::point_result(sink.res[b]));
   return SFMHIP_OK;
 }
 
@@ -809,17 +739,9 @@ extern "C" int sfmhip_cloud_concat(sfmhip_cloud* a, sfmhip_cloud* b, sfmhip_clou
 }
 
 extern "C" int sfmhip_cloud_register_last_timing(sfmhip_cloud* tgt, double ms3[3], int32_t* iterations) {
-  if (!tgt || !ms3) return SFMHIP_ERR_ARG;
-  const RegState* s = stage<RegState>(tgt);
-  for (int i = 0; i < 3; ++i) ms3[i] = s->ms[i];
-  if (iterations) *iterations = s->iterations;
-  return SFMHIP_OK;
+  return report(tgt, &RegState::single, false, ms3, iterations);
 }
 
 extern "C" int sfmhip_cloud_register_batch_last_timing(sfmhip_cloud* tgt, double ms3[3], int32_t* iterations) {
-  if (!tgt || !ms3) return SFMHIP_ERR_ARG;
-  const RegState* s = stage<RegState>(tgt);
-  for (int i = 0; i < 3; ++i) ms3[i] = s->batch_ms[i];
-  if (iterations) *iterations = s->batch_iterations;
-  return SFMHIP_OK;
+  return report(tgt, &RegState::batch, false, ms3, iterations);
 }

@@ -2,8 +2,10 @@
 // code that hipcc and a plain g++ both compile, on top of register.h: the options' refusals, the no-plane test, the one-to-one
 // slot, the trim count, the row and the sums of the point-to-plane step, its Cholesky solve, the Cayley increment and the loop's
 // decision.  The device code (register.hip) and the CPU test stub (tests/stub/register_icp_capi.cpp) share these bodies, so the
-// device result is checked bit for bit against a CPU build.  Compile with -ffp-contract=off.  The host form of the whole call
-// (run_host_icp) is below the shared part.  Every product below is bracketed as written: that bracketing is the contract.
+// device result is checked bit for bit against a CPU build.  Compile with -ffp-contract=off.  Below the shared part is the host
+// form of the whole call: ONE loop (iterate_host, loop_host) behind f-17's run_host, f-18's run_host_batch and f-22's run_host_icp
+// and run_host_icp_batch, which differ in their rule 1 and in the struct they hand back.  Every product below is bracketed as
+// written: that bracketing is the contract.
 #pragma once
 #include "register.h"
 
@@ -54,6 +56,13 @@ SFM_REG_INLINE Opts point_opts(const IcpOpts& o) {
   p.max_iters = o.max_iters, p.with_scale = o.with_scale, p.min_pairs = o.min_pairs, p.reserved = 0;
   p.max_dist = o.max_dist, p.eps = o.eps;
   return p;
+}
+// ... and its inverse: f-17's call as the loop sees it (rule 7: metric 0, no rejector)
+SFM_REG_INLINE IcpOpts icp_opts(const Opts& p) {
+  IcpOpts o = default_icp_opts();
+  o.max_iters = p.max_iters, o.with_scale = p.with_scale, o.min_pairs = p.min_pairs;
+  o.max_dist = p.max_dist, o.eps = p.eps;
+  return o;
 }
 
 // rule 3: a target normal that gives a plane
@@ -227,6 +236,14 @@ SFM_REG_INLINE IcpResult icp_result(const Result& r, const IcpExtra& ex) {
   o.mse = r.mse, o.plane_mse = ex.plane_mse, o.trim_d2 = ex.trim_d2;
   return o;
 }
+// f-17's result of the loop's
+SFM_REG_INLINE Result point_result(const IcpResult& r) {
+  Result o;
+  o.T = r.T;
+  o.iterations = r.iterations, o.pairs = r.pairs, o.converged = r.converged, o.flags = r.flags;
+  o.mse = r.mse;
+  return o;
+}
 
 }  // namespace sfmreg
 
@@ -265,95 +282,105 @@ inline float reject_host(int n_tgt, int n_src, const IcpOpts& o, const float* no
   return tau;
 }
 
-// one step of the loop on the host: the search under L.T, the rejectors, the sums, the decision
-inline bool iterate_host_icp(const HostGrid& g, int n_tgt, const float* tgt, const float* normals, int n_src, const float* src, const IcpOpts& o,
-                             float md2, const double c[3], Loop& L, IcpExtra& ex, std::vector<int32_t>& idx, std::vector<int32_t>& prev,
-                             std::vector<float>& d2) {
+// one step of the loop on the host, for every entry: the search under L.T, the rejectors (without an active one idx stays rule
+// 2's), then metric 0's two sums and f-17's decision or the plane's one sum and rule 9's.  prev: scratch for C_{k-1}
+inline bool iterate_host(const HostGrid& g, const float* tgt, const float* normals, int n_src, const float* src, const IcpOpts& o, float md2,
+                         const double c[3], Loop& L, IcpExtra& ex, std::vector<int32_t>& idx, std::vector<int32_t>& prev, std::vector<float>& d2) {
   prev = idx;
   nearest_host(g, n_src, src, L.T, md2, false, idx.data(), d2.data());
-  ex.trim_d2 = (double)reject_host(n_tgt, n_src, o, normals, idx, d2);
-  if (o.metric == METRIC_POINT) {
-    bool changed = false;
-    for (int i = 0; i < n_src; ++i) changed = changed || idx[i] != prev[i];
-    double s1[N1], s2[N2], mu_p[3], mu_m[3];
-    auto pm = [&](int i, float p[3], float m[3]) {
-      const bool paired = idx[i] >= 0;
-      for (int a = 0; a < 3; ++a) p[a] = src[3 * i + a], m[a] = paired ? tgt[3 * (size_t)idx[i] + a] : 0.0f;
-      return paired;
-    };
-    sum_host<N1>(n_src, [&](int i, double* v) {
-      float p[3], m[3];
-      const bool paired = pm(i, p, m);
-      terms1(paired, p, m, v);
-    }, s1);
-    means(s1, mu_p, mu_m);
-    sum_host<N2>(n_src, [&](int i, double* v) {
-      float p[3], m[3];
-      const bool paired = pm(i, p, m);
-      terms2(paired, p, m, d2[i], mu_p, mu_m, v);
-    }, s2);
-    ex.plane_mse = qnan_d();
-    return loop_step(L, point_opts(o), changed, s1, s2);
+  ex.trim_d2 = (double)reject_host(g.n, n_src, o, normals, idx, d2);
+  if (o.metric == METRIC_PLANE) {
+    double s[NP];
+    const Transform T = L.T;
+    sum_host<NP>(n_src, [&](int i, double* v) {
+      const bool kept = idx[i] >= 0;
+      float q[3] = {0, 0, 0}, m[3] = {0, 0, 0}, n[3] = {0, 0, 0};
+      if (kept) {
+        move(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], q);
+        for (int a = 0; a < 3; ++a) m[a] = tgt[3 * (size_t)idx[i] + a], n[a] = normals[(size_t)o.normal_stride * idx[i] + a];
+      }
+      plane_terms(kept, q, m, n, kept ? d2[i] : 0.0f, c, o.with_scale, v);
+    }, s);
+    return plane_loop_step(L, ex, o, c, s);
   }
-  double s[NP];
-  const Transform T = L.T;
-  sum_host<NP>(n_src, [&](int i, double* v) {
-    const bool kept = idx[i] >= 0;
-    float q[3] = {0, 0, 0}, m[3] = {0, 0, 0}, n[3] = {0, 0, 0};
-    if (kept) {
-      move(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], q);
-      for (int a = 0; a < 3; ++a) m[a] = tgt[3 * (size_t)idx[i] + a], n[a] = normals[(size_t)o.normal_stride * idx[i] + a];
-    }
-    plane_terms(kept, q, m, n, kept ? d2[i] : 0.0f, c, o.with_scale, v);
-  }, s);
-  return plane_loop_step(L, ex, o, c, s);
+  bool changed = false;
+  for (int i = 0; i < n_src; ++i) changed = changed || idx[i] != prev[i];
+  double s1[N1], s2[N2], mu_p[3], mu_m[3];
+  auto pm = [&](int i, float p[3], float m[3]) {
+    const bool paired = idx[i] >= 0;
+    for (int a = 0; a < 3; ++a) p[a] = src[3 * i + a], m[a] = paired ? tgt[3 * (size_t)idx[i] + a] : 0.0f;
+    return paired;
+  };
+  sum_host<N1>(n_src, [&](int i, double* v) {
+    float p[3], m[3];
+    const bool paired = pm(i, p, m);
+    terms1(paired, p, m, v);
+  }, s1);
+  means(s1, mu_p, mu_m);
+  sum_host<N2>(n_src, [&](int i, double* v) {
+    float p[3], m[3];
+    const bool paired = pm(i, p, m);
+    terms2(paired, p, m, d2[i], mu_p, mu_m, v);
+  }, s2);
+  ex.plane_mse = qnan_d();
+  return loop_step(L, point_opts(o), changed, s1, s2);
 }
 
-inline void host_centre(const HostGrid& g, int n_tgt, const float* tgt, double c[3]) {
-  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-  int nv = 0;
-  for (int i = 0; i < n_tgt; ++i) {
-    if (!sfmcloud::finite3(tgt[3 * i], tgt[3 * i + 1], tgt[3 * i + 2])) continue;
-    for (int a = 0; a < 3; ++a) {
-      const double v = tgt[3 * i + a];
-      lo[a] = nv ? std::min(lo[a], v) : v, hi[a] = nv ? std::max(hi[a], v) : v;
-    }
-    ++nv;
-  }
-  (void)g;
-  box_centre(nv, lo, hi, c);
-}
-
-// the batch (a single call is a batch of one): results[b] and row b of idx_out (n_init x n_src, or NULL).  false: refused
-inline bool run_host_icp_batch(int n_tgt, const float* tgt, const float* normals, int n_src, const float* src, const IcpOpts& o,
-                               const Transform* inits, int n_init, IcpResult* results, int32_t* idx_out) {
-  if (!valid_icp_batch(o, normals != nullptr, inits, n_init)) return false;
+// the one loop: n_init starts in lock step over one grid, a record per problem; a problem that has stopped is left alone.
+// results[b] and row b of idx_out (n_init x n_src, or NULL) are what a single call from inits[b] gives.  Refuses nothing: every
+// entry below applies its own rule 1 first
+inline void loop_host(int n_tgt, const float* tgt, const float* normals, int n_src, const float* src, const IcpOpts& o, const Transform* inits,
+                      int n_init, IcpResult* results, int32_t* idx_out) {
   HostGrid g;
   g.build(n_tgt, tgt);
   double c[3];
-  host_centre(g, n_tgt, tgt, c);
+  box_centre(g.nv, g.lo, g.hi, c);
   const float md2 = max_d2(o.max_dist);
   const size_t n1 = (size_t)std::max(n_src, 1);
   std::vector<std::vector<int32_t>> idx((size_t)n_init, std::vector<int32_t>(n1, -2));
   std::vector<int32_t> prev;
-  std::vector<float> d2(n1);
+  std::vector<float> d2(n1);  // (a problem's d2 is read only inside its own step)
   std::vector<Loop> L((size_t)n_init);
   std::vector<IcpExtra> ex((size_t)n_init);
   for (int b = 0; b < n_init; ++b) loop_init(L[b], inits[b]), ex[b].plane_mse = qnan_d(), ex[b].trim_d2 = inf_d();
   for (int round = 0, open = n_init; open > 0 && round <= o.max_iters; ++round)
     for (int b = 0; b < n_init; ++b)
-      if (!L[b].stop && iterate_host_icp(g, n_tgt, tgt, normals, n_src, src, o, md2, c, L[b], ex[b], idx[b], prev, d2)) --open;
+      if (!L[b].stop && iterate_host(g, tgt, normals, n_src, src, o, md2, c, L[b], ex[b], idx[b], prev, d2)) --open;
   for (int b = 0; b < n_init; ++b) {
     results[b] = icp_result(L[b].res, ex[b]);
     if (idx_out)
       for (int i = 0; i < n_src; ++i) idx_out[(size_t)b * n_src + i] = idx[b][i];
   }
+}
+
+// f-22's two entries (a single call is a batch of one).  false: refused, nothing written
+inline bool run_host_icp_batch(int n_tgt, const float* tgt, const float* normals, int n_src, const float* src, const IcpOpts& o,
+                               const Transform* inits, int n_init, IcpResult* results, int32_t* idx_out) {
+  if (!valid_icp_batch(o, normals != nullptr, inits, n_init)) return false;
+  loop_host(n_tgt, tgt, normals, n_src, src, o, inits, n_init, results, idx_out);
   return true;
 }
 inline bool run_host_icp(int n_tgt, const float* tgt, const float* normals, int n_src, const float* src, const IcpOpts& o, const Transform* init,
                          IcpResult& res, int32_t* idx_out) {
   const Transform T0 = init ? *init : identity();
   return run_host_icp_batch(n_tgt, tgt, normals, n_src, src, o, &T0, 1, &res, idx_out);
+}
+
+// f-17's and f-18's entries: the loop with metric 0 and no rejector (f-22 rule 7).  results[b] and row b of idx_out are run_host's
+// from inits[b]; `longest` (nullable): the iterations of the problem that ran longest.  false: refused, nothing written
+inline bool run_host_batch(int n_tgt, const float* tgt, int n_src, const float* src, const Opts& o, const Transform* inits, int n_init,
+                           Result* results, int32_t* idx_out, int* longest = nullptr) {
+  if (!valid_batch(o, inits, n_init)) return false;
+  std::vector<IcpResult> r((size_t)n_init);
+  loop_host(n_tgt, tgt, nullptr, n_src, src, icp_opts(o), inits, n_init, r.data(), idx_out);
+  int most = 0;
+  for (int b = 0; b < n_init; ++b) results[b] = point_result(r[b]), most = std::max(most, (int)r[b].iterations);
+  if (longest) *longest = most;
+  return true;
+}
+inline bool run_host(int n_tgt, const float* tgt, int n_src, const float* src, const Opts& o, const Transform* init, Result& res, int32_t* idx_out) {
+  const Transform T0 = init ? *init : identity();
+  return run_host_batch(n_tgt, tgt, n_src, src, o, &T0, 1, &res, idx_out);
 }
 
 }  // namespace sfmreg

@@ -1,8 +1,9 @@
 """GPU: the second registration entry (csrc/register.hip, DESIGN.md f-22: point-to-plane, trimmed and one-to-one ICP) against the
 g++ build of the same header (tests/stub/register_icp_capi.cpp), byte for byte: the result struct and idx.  Source sizes on both
 sides of a sum block and of the cell-order threshold, targets of 1, 3 and 8 500 points, both metrics with every rejector, metric
-0 without rejectors against sfmhip_cloud_register on the device, batches with a start that stops at once and one that runs to
-the limit, a target handle reused around the family's other calls, the timing call, and the host mirror's self-test."""
+0 without rejectors against sfmhip_cloud_register on the device (single calls and batches), the four looping entries against the
+bytes frozen from the commit before they shared one loop (tests/golden/register_parent.npz), batches with a start that stops at
+once and one that runs to the limit, a target handle reused around the family's other calls, the timing call, and the host mirror's self-test."""
 import math
 import subprocess
 
@@ -14,7 +15,8 @@ from sfm_danpipeline_amd.cloud import Cloud
 from sfm_danpipeline_amd.register import FEW, Transform
 from tests.test_align_cpu import GOOD, LEVEL
 from tests.test_register_cpu import icp_scene, motion, moved_back, planted_plot, result_bytes
-from tests.test_register_icp_cpu import ig, plane_kw, plot_normals, stems_scene, stub_icp, stub_icp_batch, yaw_motion  # noqa: F401
+from tests.test_register_icp_cpu import (batch_inits, frozen_cases, frozen_hash, frozen_mismatch, ig, plane_kw, plot_normals, stems_scene,  # noqa: F401
+                                         stub_icp, stub_icp_batch, yaw_motion)
 
 pytestmark = pytest.mark.gpu
 
@@ -103,6 +105,52 @@ def test_metric_0_without_rejectors_equals_register_on_the_device(ctx, ig, scene
             old = register.icp(tc, bc, return_pairs=True, max_iters=2, **kw)
             new = register.icp_ex(tc, bc, return_pairs=True, max_iters=2, **kw)
             assert result_bytes(new)[:len(result_bytes(old))] == result_bytes(old) and np.array_equal(new.idx, old.idx)
+
+
+def test_icp_batch_without_rejectors_equals_register_batch_on_the_device(ctx):
+    """The batch form of the equality above: both are the one loop, the second narrowed to f-17's result."""
+    tgt, nrm, src, M = stems_scene()
+    with Cloud(tgt, ctx=ctx) as tc, Cloud(src, ctx=ctx) as sc:
+        for n_init in (1, 2, 5):
+            inits = batch_inits()[:n_init]                        # the second starts at t = (300, 0, 0): FEW at k = 0
+            for kw in (dict(max_dist=1.0), dict(max_dist=1.0, with_scale=1, max_iters=3), dict(max_dist=1.0, eps=1e-3)):
+                old = register.icp_batch(tc, sc, inits, return_pairs=True, **kw)
+                new = register.icp_ex_batch(tc, sc, inits, return_pairs=True, **kw)
+                assert len(old) == len(new) == n_init
+                for b in range(n_init):
+                    assert result_bytes(new[b])[:len(result_bytes(old[b]))] == result_bytes(old[b]), (n_init, kw, b, show(new[b]))
+                    assert np.array_equal(new[b].idx, old[b].idx), (n_init, kw, b)
+                    assert math.isnan(new[b].plane_mse) and new[b].trim_d2 == math.inf
+                if n_init > 1:
+                    assert old[1].flags == FEW and old[1].iterations == 0 and (old[1].idx == -1).all()
+
+
+# ---------------------------------------------------------------- the frozen record
+def device_run(tc, sc, entry, nrm, starts, kw):
+    """One frozen case on the device: (the result structs' bytes, idx)."""
+    if entry == "f17":
+        res = register.icp(tc, sc, starts, return_pairs=True, **kw)
+    elif entry == "icp":
+        res = register.icp_ex(tc, sc, nrm, starts, return_pairs=True, **kw)
+    else:
+        rows = (register.icp_batch(tc, sc, starts, return_pairs=True, **kw) if entry == "f17_batch" else
+                register.icp_ex_batch(tc, sc, starts, nrm, return_pairs=True, **kw))
+        return b"".join(result_bytes(r) for r in rows), np.stack([r.idx for r in rows])
+    return result_bytes(res), res.idx
+
+
+def test_device_equals_the_frozen_record(ctx):
+    """The device against the parent's bytes: one f-17 single call, the f-17 batch, every rejector combination at metric 0 and 1 and
+    the two f-22 batches; each at most 6 iterations on a few thousand points."""
+    chosen = [c for c in frozen_cases() if c[0] in ("f17 | icp_scene | no init | max_iters=2", "f17_batch | stems | short")
+              or (c[1] == "icp" and c[0].endswith("| short")) or c[1] == "icp_batch"]
+    assert len(chosen) == 11 and all(c[6].get("max_iters", 50) <= 6 for c in chosen)
+    bad = []
+    for name, entry, tgt, src, nrm, starts, kw in chosen:
+        with Cloud(np.ascontiguousarray(tgt, np.float32), ctx=ctx) as tc, Cloud(np.ascontiguousarray(src, np.float32), ctx=ctx) as sc:
+            res, idx = device_run(tc, sc, entry, nrm, starts, kw)
+        bad.append(frozen_mismatch(name, frozen_hash(tgt, src, nrm, starts, kw), res, idx))
+    assert not any(bad), [b for b in bad if b]
 
 
 # ---------------------------------------------------------------- batches

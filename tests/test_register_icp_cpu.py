@@ -5,6 +5,7 @@ search, numpy.linalg.solve), the ground-and-stems scene that motivates the featu
 rows without a plane, the degenerate single plane, the floors of min_pairs, the refusals, a planted scale and the Cayley
 increment.  No GPU."""
 import ctypes as C
+import hashlib
 import math
 import os
 import subprocess
@@ -14,12 +15,15 @@ import pytest
 from scipy.spatial import cKDTree
 
 from sfm_danpipeline_amd.register import DEGENERATE, FEW, IcpOpts, IcpResult, Transform, set_opts
+from tests.test_align_cpu import al, stub_batch  # noqa: F401
 from tests.test_register_cpu import (icp_scene, motion, moved_back, np_estimate, partial_scene, planted_plot, result_bytes, rg,  # noqa: F401
                                      stub_run)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STUB = os.path.join(ROOT, "tests", "stub", "register_icp_capi.cpp")
 INF32 = np.float32(np.inf)
+FROZEN = os.path.join(ROOT, "tests", "golden", "register_parent.npz")   # tests/golden/make_register_parent.py writes it
+FROZEN_IDX_MAX = 4096                                            # the record keeps idx for sources of at most this many points
 # the worst entry of (scale R | t) of the stub minus the numpy transcription's over reference_cases() was 1.78e-15 (the plane
 # metric on icp_scene after 4 steps; DESIGN.md f-22 records it): the test asserts at 4 times that, rounded up to one digit
 T_REF_MAX = 8e-15
@@ -324,6 +328,11 @@ def test_metric_0_without_rejectors_is_f17_byte_for_byte(ig, rg):
         assert math.isnan(got.plane_mse) and got.trim_d2 == math.inf, name
         init = motion(3.0, 0.2, 1.0)
         assert result_bytes(stub_icp(ig, tgt, src, None, init, **kw)[0])[:C.sizeof(want)] == result_bytes(stub_run(rg, tgt, src, init, **kw)[0]), name
+        # and both sides against the parent's bytes: after the two became one loop, equality alone compares a function with its adapter
+        for iname, start in (("no init", None), ("init", init)):
+            sha = frozen_hash(tgt, src, None, start, kw)
+            for res, idx in (stub_run(rg, tgt, src, start, **kw), stub_icp(ig, tgt, src, None, start, **kw)):
+                assert frozen_mismatch(f"f17 | {name} | {iname} | default", sha, result_bytes(res)[:C.sizeof(want)], idx) is None, (name, iname)
 
 
 # ---------------------------------------------------------------- 2. against the numpy transcription
@@ -588,7 +597,91 @@ def test_cayley_increment_stays_orthonormal(ig):
     assert np.abs(R @ R.T - np.eye(3)).max() <= 1e-14 and abs(np.linalg.det(R) - 1) <= 1e-14
 
 
-# ---------------------------------------------------------------- 8. the host build under the sanitizers
+# ---------------------------------------------------------------- 8. the frozen record: nothing moved
+def batch_inits():
+    """The five starts of test_batch_rows_equal_the_single_runs; the second stops at k = 0 with FEW."""
+    return [Transform.make(), Transform.make(t=[300.0, 0, 0]), motion(1.0, 0.05), stems_scene()[3], yaw_motion(2.0, (0.2, -0.1, 0.0))]
+
+
+def frozen_cases():
+    """(name, entry, target, source, normals, starts, options) of every case of tests/golden/register_parent.npz.  entry: "f17"
+    (run_host), "f17_batch" (run_host_batch), "icp" (run_host_icp) or "icp_batch"; starts: None, a Transform or a list of them.  The
+    cases whose name ends in "short" stop after at most 4 iterations: the ones the device is run on."""
+    for name, tgt, src, kw in f17_scenes():
+        for iname, init in (("no init", None), ("init", motion(3.0, 0.2, 1.0))):
+            for ename, extra in (("default", dict()), ("max_iters=0", dict(max_iters=0)), ("max_iters=2", dict(max_iters=2))):
+                yield f"f17 | {name} | {iname} | {ename}", "f17", tgt, src, None, init, dict(kw, **extra)
+    for name, tgt, src, nrm, kw in reference_cases():
+        yield f"icp | {name}", "icp", tgt, src, nrm, None, kw
+        yield f"icp | {name} | short", "icp", tgt, src, nrm, None, dict(kw, max_iters=4)
+    tgt, nrm, src, M = stems_scene()
+    yield "icp_batch | stems plane trim one-to-one", "icp_batch", tgt, src, nrm, batch_inits(), plane_kw(max_dist=1.0, trim=0.8, one_to_one=1, max_iters=6)
+    yield "icp_batch | stems point trim", "icp_batch", tgt, src, nrm, batch_inits(), dict(max_dist=1.0, trim=0.8, max_iters=4)
+    yield "f17_batch | stems", "f17_batch", tgt, src, None, batch_inits(), dict(max_dist=1.0)
+    yield "f17_batch | stems | short", "f17_batch", tgt, src, None, batch_inits(), dict(max_dist=1.0, max_iters=4)
+
+
+def frozen_hash(tgt, src, nrm, starts, kw):
+    """SHA-256 over a case's input arrays, its starts and its options."""
+    h = hashlib.sha256()
+    for a in (f32(tgt), f32(src)) + (() if nrm is None else (np.ascontiguousarray(nrm, np.float32),)):
+        h.update(repr(a.shape).encode() + a.tobytes())
+    for T in [] if starts is None else starts if isinstance(starts, list) else [starts]:
+        h.update(result_bytes(T))
+    h.update(repr(sorted(kw.items())).encode())
+    return h.hexdigest()
+
+
+def frozen_stub_run(rg, ig, al, entry, tgt, src, nrm, starts, kw):
+    """One case through the g++ stubs: (the result structs' bytes, idx)."""
+    if entry == "f17":
+        res, idx = stub_run(rg, tgt, src, starts, **kw)
+        return result_bytes(res), idx
+    if entry == "icp":
+        res, idx = stub_icp(ig, tgt, src, nrm, starts, **kw)
+        return result_bytes(res), idx
+    res, idx = stub_batch(al, tgt, src, starts, **kw)[:2] if entry == "f17_batch" else stub_icp_batch(ig, tgt, src, starts, nrm, **kw)
+    return b"".join(result_bytes(r) for r in res), idx
+
+
+_FROZEN = {}
+
+
+def frozen():
+    """The record: a dict of name -> (input hash, result bytes, idx or None)."""
+    if not _FROZEN:
+        with np.load(FROZEN) as z:
+            for name in z["names"].tolist():
+                _FROZEN[name] = (str(z[name + " | sha"]), z[name + " | res"].tobytes(), z[name + " | idx"] if name + " | idx" in z else None)
+    return _FROZEN
+
+
+def frozen_mismatch(name, sha, res, idx):
+    """What of (input hash, result bytes, idx) differs from the record's case `name`: a message, or None."""
+    if name not in frozen():
+        return f"{name}: not in the record (run tests/golden/make_register_parent.py on the parent commit)"
+    wsha, wres, widx = frozen()[name]
+    if sha != wsha:
+        return f"{name}: the INPUT differs from the frozen one (sha {sha[:12]} against {wsha[:12]}): the scene or its options changed"
+    if res != wres:
+        return f"{name}: the result bytes differ from the parent's"
+    if widx is not None and not np.array_equal(idx, widx):
+        return f"{name}: idx differs from the parent's"
+    return None
+
+
+def test_every_frozen_case_equals_the_parents_bytes(rg, ig, al):
+    cases = list(frozen_cases())
+    assert sorted(frozen()) == sorted(c[0] for c in cases)
+    bad = []
+    for name, entry, tgt, src, nrm, starts, kw in cases:
+        res, idx = frozen_stub_run(rg, ig, al, entry, tgt, src, nrm, starts, kw)
+        bad.append(frozen_mismatch(name, frozen_hash(tgt, src, nrm, starts, kw), res, idx))
+        assert frozen()[name][2] is not None or len(src) > FROZEN_IDX_MAX, name
+    assert not any(bad), [b for b in bad if b]
+
+
+# ---------------------------------------------------------------- 9. the host build under the sanitizers
 def test_register_icp_under_asan_ubsan(tmp_path):
     """AddressSanitizer + UBSan over the stub's own driver, a stand-alone program run as a child process (host code only)."""
     exe = str(tmp_path / "register_icp_asan")
