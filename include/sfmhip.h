@@ -1260,6 +1260,67 @@ int sfmhip_poisson_extract(sfmhip_ctx* ctx, int n, const double* chi, double iso
  * the whole call. */
 int sfmhip_cloud_poisson_last_timing(sfmhip_cloud* cloud, double* ms4);
 
+/* ---- finishing a mesh against the cloud it was made from (the reference has no mesh post-processing) ----
+ * A Poisson surface is closed: over every hole in the data it invents a sheet.  The call trims what no point supports, drops
+ * small components, and gives every vertex a colour, a normal and its nearest point.  The mesh stays a host object: the call
+ * uploads the input mesh and downloads the output.  The rules (arithmetic: csrc/mesh.h, -ffp-contract=off, the device equal
+ * to the g++ build bit for bit):
+ *   M1. inputs: a vertex with a non-finite coordinate is never supported, whatever min_support says.  A triangle with a
+ *       repeated index, or with an unsupported vertex, does not survive.  A cloud without a finite point or a mesh without a
+ *       vertex: status OK and an empty output, every input vertex counted unsupported and every triangle trimmed.
+ *   M2. support of vertex v over the finite cloud points p: d2 = the family's float dist2 (((dx dx) + dy dy) + dz dz); a
+ *       point counts iff d2 < (float)(r * r), r squared in f64 -- sfmhip_cloud_radius_count's test, strict.  support = the
+ *       count, not capped.  nearest / nearest_d2 = the least (d2, index) among the counted points (d2, then index); with none
+ *       -1 and +inf.  Colour weights in f64: w = (1 - d2 / r2)^2 with r2 = (double)(float)(r * r); sw, sr, sg, sb summed in
+ *       one order, that of the handle's radius grid for r (cells of r (1 + 1/1024), doubled while the grid exceeds 2^22
+ *       cells, as sfmhip_cloud_radius_count and sfmhip_cloud_mls share it): ascending (cell id, input index), cell ids
+ *       x-fastest.  A channel is (int)(s / sw + 0.5) clamped to 0..255; support 0 gives colour 0.  A vertex outside the
+ *       cloud's box is looked up from the border cell it is clamped into: the block of cells around that cell still holds
+ *       every point within r, and the distance test decides.
+ *   M3. trim: a vertex is supported iff it is finite and support >= min_support; a triangle survives iff it has no repeated
+ *       index and its three vertices are supported.
+ *   M4. components: the vertices of the surviving triangles joined (a-b, b-c); a component's id is its least vertex index,
+ *       its size its number of surviving triangles.  Components with size < min_component_triangles are dropped; with
+ *       keep_largest = k > 0 only the first k by (size descending, id ascending) stay.  Integer atomics only, none whose
+ *       order matters.
+ *   M5. compaction: surviving triangles keep input order; the vertices at least one of them uses keep input order and are
+ *       renumbered; vertex_src / triangle_src map output rows to input rows.
+ *   M6. normals: per output vertex the f64 sum, over its output triangles ascending by output triangle index, of
+ *       cross(b - a, c - a) of the widened floats (area-weighted, oriented as the triangles are), normalised in f64 and
+ *       cast to float; a zero or non-finite length writes 0x7FC00000 three times.
+ *   M7. area = sum of |cross| / 2 and volume = sum of a . (b x c) / 6 over the output triangles in f64: consecutive blocks
+ *       of 256 triangles by the 256-slot tree of f-9, the block partials added in ascending order.  volume is a plain
+ *       signed sum: a volume only for a closed mesh (no closedness test).
+ * support_radius has no default: 0, negative or non-finite is SFMHIP_ERR_ARG, as a negative count is.  min_support 0 trims
+ * nothing finite (the search still runs: counts, nearest, colours).  sfmhip_mesh_create wraps caller arrays (nv = 0 and
+ * nt = 0 are accepted; a triangle index outside [0, nv) is SFMHIP_ERR_ARG).  A mesh that did not come out of
+ * sfmhip_cloud_mesh_finish has no attributes: sfmhip_mesh_attributes on it is SFMHIP_ERR_STATE when any array is asked for;
+ * rgb is filled only when the finishing call was given colours.  sfmhip_mesh_counts, sfmhip_mesh_download and
+ * sfmhip_mesh_destroy serve every mesh.  The handle keeps the call's device blocks: a repeat call allocates nothing. */
+typedef struct {
+  double  support_radius;          /* cloud units; > 0 and finite, else SFMHIP_ERR_ARG: there is no default */
+  int32_t min_support;             /* >= 0; 0: no trimming (the search still runs: counts, nearest, colours) */
+  int32_t min_component_triangles; /* >= 0; components with fewer surviving triangles are dropped; 0: off */
+  int32_t keep_largest;            /* >= 0; k > 0: only the k largest components survive; 0: off */
+  int32_t reserved;
+} sfmhip_mesh_finish_opts;
+typedef struct {
+  int32_t n_vertices_in, n_triangles_in, n_vertices, n_triangles;
+  int32_t n_unsupported_vertices, n_trimmed_triangles; /* by M3 */
+  int32_t n_components, n_components_kept;             /* after M3 / after M4 */
+  double  area, volume;                                /* M7, of the output */
+} sfmhip_mesh_finish_summary;
+void sfmhip_mesh_finish_default_opts(sfmhip_mesh_finish_opts* opts); /* radius 0 (must be set), min_support 1, rest 0 */
+int sfmhip_mesh_create(const float* vertices, int nv, const int32_t* triangles, int nt, sfmhip_mesh** out);
+int sfmhip_cloud_mesh_finish(sfmhip_cloud* cloud, const uint32_t* rgb /* n, 0x00RRGGBB, or NULL */, const sfmhip_mesh* in,
+                             const sfmhip_mesh_finish_opts* opts, sfmhip_mesh** out, sfmhip_mesh_finish_summary* summary);
+/* each array may be NULL: normals 3 nv, rgb nv, support nv, nearest nv, nearest_d2 nv, vertex_src nv, triangle_src nt */
+int sfmhip_mesh_attributes(const sfmhip_mesh* mesh, float* normals, uint32_t* rgb, int32_t* support, int32_t* nearest,
+                           float* nearest_d2, int32_t* vertex_src, int32_t* triangle_src);
+/* host-clock ms of the last sfmhip_cloud_mesh_finish call on this handle (timing on): search, trim + components, compaction +
+ * normals + sums + download, the whole call; the call less the three stages is the upload of the mesh and the colours. */
+int sfmhip_cloud_mesh_last_timing(sfmhip_cloud* cloud, double ms4[4]);
+
 /* ---- adjustBundle solver core (reference src/BundleAdjustment.cpp:46-175) ---- */
 typedef struct {
   int max_iterations;           /* 500   src/BundleAdjustment.cpp:118 */

@@ -88,6 +88,8 @@ SYMBOLS = [
     "sfmhip_crowns_default_opts", "sfmhip_chm_crowns", "sfmhip_cloud_crowns", "sfmhip_cloud_crowns_raster",
     "sfmhip_cloud_crowns_last_timing", "sfmhip_cloud_crowns_last_rounds",
     "sfmhip_mls_default_opts", "sfmhip_cloud_mls", "sfmhip_cloud_mls_last_timing",
+    "sfmhip_mesh_finish_default_opts", "sfmhip_mesh_create", "sfmhip_cloud_mesh_finish", "sfmhip_mesh_attributes",
+    "sfmhip_cloud_mesh_last_timing",
     "sfmhip_verify_default_opts", "sfmhip_matchplan_verify", "sfmhip_verify_lists", "sfmhip_verified_counts", "sfmhip_verified_download",
     "sfmhip_tracks_build_from_verified", "sfmhip_verified_last_timing", "sfmhip_verified_destroy",
 ]
@@ -216,6 +218,12 @@ def lib():
         L.sfmhip_poisson_solve.argtypes = [vp, cint, vp, vp, f64, f64, cint, vp, vp, vp]
         L.sfmhip_poisson_extract.argtypes = [vp, cint, vp, f64, vp, f64, C.POINTER(vp)]
         L.sfmhip_cloud_poisson_last_timing.argtypes = [vp, vp]
+        L.sfmhip_mesh_finish_default_opts.argtypes = [vp]
+        L.sfmhip_mesh_finish_default_opts.restype = None
+        L.sfmhip_mesh_create.argtypes = [vp, cint, vp, cint, C.POINTER(vp)]
+        L.sfmhip_cloud_mesh_finish.argtypes = [vp, vp, vp, vp, C.POINTER(vp), vp]
+        L.sfmhip_mesh_attributes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+        L.sfmhip_cloud_mesh_last_timing.argtypes = [vp, vp]
         L.sfmhip_mvs_default_opts.argtypes = [vp]
         L.sfmhip_mvs_default_opts.restype = None
         L.sfmhip_mvs_create.argtypes = [vp, cint, cint, cint, vp, vp, vp, vp, cint, C.POINTER(vp)]

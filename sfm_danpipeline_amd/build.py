@@ -15,7 +15,7 @@ SO = os.path.join(HERE, "libsfmhip.so")
 # and want v_fma_f64 -- "fast-honor-pragmas", not "fast": the one function that must NOT contract, the trust-region decision
 # lm_decide (the same bits on the host and on the device), says so with a pragma, which plain "fast" ignores
 SOURCES = {"context.hip": "off", "match.hip": "off", "triangulate.hip": "off", "incremental.hip": "off",
-           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "cloud_filter.hip": "off", "mls.hip": "off", "register.hip": "off", "align.hip": "off", "segment.hip": "off", "poisson.hip": "off", "dendro.hip": "off", "ground.hip": "off", "trees.hip": "off", "terrain.hip": "off", "crowns.hip": "off", "tracks.hip": "off", "verify.hip": "off", "mvs.hip": "off", "undistort.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
+           "score.hip": "off", "pose.hip": "off", "pnp.hip": "off", "cloud.hip": "off", "cloud_filter.hip": "off", "mls.hip": "off", "register.hip": "off", "align.hip": "off", "segment.hip": "off", "poisson.hip": "off", "mesh.hip": "off", "dendro.hip": "off", "ground.hip": "off", "trees.hip": "off", "terrain.hip": "off", "crowns.hip": "off", "tracks.hip": "off", "verify.hip": "off", "mvs.hip": "off", "undistort.hip": "off", "sift.hip": "off", "ba.hip": "fast-honor-pragmas", "probe.hip": "off"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -161,6 +161,14 @@ def build_mesh_demo(force=False):
     writes the mesh as a binary PLY (needs the GPU)."""
     return _build_host_exe(os.path.join(HERE, "sfm_mesh_selftest"),
                            ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "mesh_selftest.cpp"), force)
+
+
+def build_mesh_finish_demo(force=False):
+    """create_mesh on a coloured cloud in the host mirror: the normals, Poisson at depth 7, then StructFromMotion::finishMesh (the
+    trim of unsupported surface, per-vertex colours and normals) on a PCD; writes the finished mesh as a binary PLY with normals
+    and colours (needs the GPU)."""
+    return _build_host_exe(os.path.join(HERE, "sfm_mesh_finish_selftest"),
+                           ("Sfm.cpp", "SfmIO.cpp", "SfmCloud.cpp", "BundleAdjustment.cpp", "mesh_finish_selftest.cpp"), force)
 
 
 def build_dense_demo(force=False):

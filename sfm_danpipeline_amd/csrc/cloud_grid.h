@@ -1,7 +1,7 @@
 // cloud_grid.h -- the device-resident cloud (sfmhip_cloud), its uniform grids and everything the cloud family shares:
 // cloud.hip (map3D's step 10), cloud_filter.hip (the voxel grid and the statistical outlier removal), register.hip (two clouds:
 // nearest points and ICP, whose queries are not the grid's own points), align.hip (two levelled clouds: the pose vote), segment.hip (the colour
-// region growing after it), poisson.hip (create_mesh), dendro.hip (the dendrometry after the segmentation), ground.hip (the
+// region growing after it), poisson.hip (create_mesh), mesh.hip (the finishing of its mesh: queries that are the mesh's vertices), dendro.hip (the dendrometry after the segmentation), ground.hip (the
 // ground plane that gives it its vertical), trees.hip (the trees of a plot), terrain.hip (the terrain under them), crowns.hip (the crowns
 // on its canopy raster) and, for blocks(), mvs.hip.
 // The handle plumbing is here once: a stage keeps its state in its slot of the handle's table (stage<S>(): made on first use,
@@ -115,7 +115,7 @@ struct Grow {
 };
 
 // the stages that keep state on the handle, and a stage's slot: the state and what deletes it
-enum Stage { SEGMENT, POISSON, DENDRO, GROUND, TREES, FILTER, REGISTER, ALIGN, TERRAIN, CROWNS, MLS, N_STAGES };
+enum Stage { SEGMENT, POISSON, DENDRO, GROUND, TREES, FILTER, REGISTER, ALIGN, TERRAIN, CROWNS, MLS, MESH, N_STAGES };
 struct StageSlot {
   void* p = nullptr;
   void (*free)(void*) = nullptr;

@@ -247,6 +247,15 @@ class StructFromMotion {
   // create_mesh with that pass in front: sfmhip_cloud_mls at order 2 and radius smooth_radius, then the normals (k = 10, towards
   // the sensor origin, times -1) and Poisson as above on the smoothed handle; the smoothed points never come to the host.
   void create_mesh(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, pcl::PolygonMesh& mesh, double smooth_radius);
+  // (ours) the finishing of a mesh against the coloured cloud it was made from: sfmhip_cloud_mesh_finish (the
+  // trim of the surface no point within opts.support_radius supports, the component filters, per-vertex colours and normals).
+  // mesh is replaced by the finished mesh, mesh.colours and mesh.normals filled.  Returns the call's summary.
+  sfmhip_mesh_finish_summary finishMesh(const pcl::PointCloud<pcl::PointXYZRGB>& cloud, pcl::PolygonMesh& mesh, const sfmhip_mesh_finish_opts& opts);
+  // create_mesh on a coloured cloud (its sensor origin as the two-argument form takes it), then finishMesh with
+  // support_radius = 1.5 cells of the Poisson cube -- the half-width of the splat's kernel: a vertex is supported where some
+  // sample's splat reaches its neighbourhood -- min_support = 1 and the component filters off.  Nobody has measured that these
+  // are good values on real plots.  summary (may be NULL) receives finishMesh's.
+  void create_mesh(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloud, pcl::PolygonMesh& mesh, sfmhip_mesh_finish_summary* summary = nullptr);
   // (ours) the similarity ICP that brings `cloud` onto `reference`, a cloud of the same scene in metres (a
   // terrestrial scan, last year's reconstruction, a surveyed subset): sfmhip_cloud_register with the scale estimated, from
   // `guess` (NULL: the identity; a large motion needs one).  Returns the metres per cloud unit that Dendrometry takes as

@@ -1,5 +1,5 @@
 // SfmCloud.cpp -- map3D's step 10 on the dense cloud (reference src/Sfm.cpp:94-102, bodies :1323-1383) in the host
-// mirror: cloudPointFilter, removePoints and create_mesh (normals, then Poisson) over sfmhip_cloud_* (cloud.hip, poisson.hip).  Kept out
+// mirror: cloudPointFilter, removePoints, create_mesh (normals, then Poisson) and finishMesh over sfmhip_cloud_* (cloud.hip, poisson.hip, mesh.hip).  Kept out
 // of Sfm.cpp / SfmIO.cpp, which the oracle's sanitizer builds link against a CPU stub of the C ABI.
 #include <cstdio>
 #include <cstdlib>
@@ -62,7 +62,7 @@ void take(const pcl::PointCloud<pcl::PointXYZ>& in, const std::vector<int32_t>& 
 
 // create_mesh's second half on a device cloud `h` whose normals (rows of 4 floats, flipped already) are `nrm`: pcl::Poisson
 // with the reference's setters, the mesh read back into `mesh`
-void poisson_mesh(sfmhip_cloud* h, const std::vector<float>& nrm, pcl::PolygonMesh& mesh) {
+void poisson_mesh(sfmhip_cloud* h, const std::vector<float>& nrm, pcl::PolygonMesh& mesh, double* cell = nullptr) {
   sfmhip_poisson_opts o;
   sfmhip_poisson_default_opts(&o);  // setDepth(7), setPointWeight(4), setScale(1.1); rows of 4 floats
   // the default cap of 4 * 2^depth steps ends conjugate gradients short of cg_rtol at depth 7 (about
@@ -78,6 +78,7 @@ void poisson_mesh(sfmhip_cloud* h, const std::vector<float>& nrm, pcl::PolygonMe
   std::vector<int32_t> t(3 * (size_t)s.n_triangles + 3);
   check(sfmhip_mesh_download(m, v.data(), t.data()), "sfmhip_mesh_download");
   sfmhip_mesh_destroy(m);
+  if (cell) *cell = s.cell;
   mesh = pcl::PolygonMesh();
   mesh.cloud.points.resize((size_t)s.n_vertices);
   for (int i = 0; i < s.n_vertices; ++i) mesh.cloud.points[i] = pcl::PointXYZ(v[3 * i], v[3 * i + 1], v[3 * i + 2]);
@@ -176,6 +177,91 @@ void StructFromMotion::create_mesh(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, p
     for (int a = 0; a < 3; ++a) nrm[4 * (size_t)i + a] = -nrm[4 * (size_t)i + a];  // create_mesh: every normal times -1
   poisson_mesh(sm, nrm, mesh);
   sfmhip_cloud_destroy(sm);
+}
+
+namespace {
+
+// the positions of a coloured cloud as the PointXYZ cloud the device cache is keyed by, and its colours
+void split_colours(const pcl::PointCloud<pcl::PointXYZRGB>& in, pcl::PointCloud<pcl::PointXYZ>& xyz, std::vector<uint32_t>& rgb) {
+  xyz.points.resize(in.size());
+  rgb.resize(in.size() + 1);
+  for (size_t i = 0; i < in.size(); ++i) {
+    xyz.points[i] = pcl::PointXYZ(in.points[i].x, in.points[i].y, in.points[i].z);
+    rgb[i] = in.points[i].rgba & 0x00FFFFFFu;
+  }
+  xyz.width = (uint32_t)in.size();
+  xyz.height = 1;
+  xyz.is_dense = in.is_dense;
+  for (int a = 0; a < 4; ++a) xyz.sensor_origin_[a] = in.sensor_origin_[a];
+}
+
+sfmhip_mesh_finish_summary finish_mesh(sfmhip_cloud* h, const std::vector<uint32_t>& rgb, pcl::PolygonMesh& mesh, const sfmhip_mesh_finish_opts& opts) {
+  const size_t nv = mesh.cloud.size(), nt = mesh.polygons.size();
+  std::vector<float> v(3 * nv + 3);
+  std::vector<int32_t> t(3 * nt + 3);
+  for (size_t i = 0; i < nv; ++i) v[3 * i] = mesh.cloud.points[i].x, v[3 * i + 1] = mesh.cloud.points[i].y, v[3 * i + 2] = mesh.cloud.points[i].z;
+  for (size_t i = 0; i < nt; ++i) {
+    if (mesh.polygons[i].vertices.size() != 3) {
+      std::fprintf(stderr, "[sfm] finishMesh: polygon %zu is not a triangle\n", i);
+      std::abort();
+    }
+    for (int k = 0; k < 3; ++k) t[3 * i + k] = (int32_t)mesh.polygons[i].vertices[k];
+  }
+  sfmhip_mesh *in = nullptr, *out = nullptr;
+  check(sfmhip_mesh_create(v.data(), (int)nv, t.data(), (int)nt, &in), "sfmhip_mesh_create");
+  sfmhip_mesh_finish_summary s;
+  const int rc = sfmhip_cloud_mesh_finish(h, rgb.data(), in, &opts, &out, &s);
+  sfmhip_mesh_destroy(in);
+  check(rc, "sfmhip_cloud_mesh_finish");
+  std::vector<float> ov(3 * (size_t)s.n_vertices + 3), on(3 * (size_t)s.n_vertices + 3);
+  std::vector<int32_t> ot(3 * (size_t)s.n_triangles + 3);
+  std::vector<uint32_t> oc((size_t)s.n_vertices + 1);
+  check(sfmhip_mesh_download(out, ov.data(), ot.data()), "sfmhip_mesh_download");
+  check(sfmhip_mesh_attributes(out, on.data(), oc.data(), nullptr, nullptr, nullptr, nullptr, nullptr), "sfmhip_mesh_attributes");
+  sfmhip_mesh_destroy(out);
+  mesh = pcl::PolygonMesh();
+  mesh.cloud.points.resize((size_t)s.n_vertices);
+  mesh.colours.assign(oc.begin(), oc.begin() + s.n_vertices);
+  mesh.normals.resize((size_t)s.n_vertices);
+  for (int i = 0; i < s.n_vertices; ++i) {
+    mesh.cloud.points[i] = pcl::PointXYZ(ov[3 * i], ov[3 * i + 1], ov[3 * i + 2]);
+    mesh.normals[i].normal_x = on[3 * i], mesh.normals[i].normal_y = on[3 * i + 1], mesh.normals[i].normal_z = on[3 * i + 2];
+  }
+  mesh.cloud.width = (uint32_t)s.n_vertices;
+  mesh.cloud.height = 1;
+  mesh.polygons.resize((size_t)s.n_triangles);
+  for (int i = 0; i < s.n_triangles; ++i) mesh.polygons[i].vertices = {(uint32_t)ot[3 * i], (uint32_t)ot[3 * i + 1], (uint32_t)ot[3 * i + 2]};
+  return s;
+}
+
+}  // namespace
+
+sfmhip_mesh_finish_summary StructFromMotion::finishMesh(const pcl::PointCloud<pcl::PointXYZRGB>& cloud, pcl::PolygonMesh& mesh,
+                                                        const sfmhip_mesh_finish_opts& opts) {
+  pcl::PointCloud<pcl::PointXYZ> xyz;
+  std::vector<uint32_t> rgb;
+  split_colours(cloud, xyz, rgb);
+  return finish_mesh(device_cloud(xyz), rgb, mesh, opts);
+}
+
+void StructFromMotion::create_mesh(pcl::PointCloud<pcl::PointXYZRGB>::Ptr& cloud, pcl::PolygonMesh& mesh, sfmhip_mesh_finish_summary* summary) {
+  pcl::PointCloud<pcl::PointXYZ>::Ptr xyz(new pcl::PointCloud<pcl::PointXYZ>);
+  std::vector<uint32_t> rgb;
+  split_colours(*cloud, *xyz, rgb);
+  pcl::PointCloud<pcl::Normal>::Ptr normals(new pcl::PointCloud<pcl::Normal>);
+  computeNormals(xyz, normals);  // (flipped already)
+  std::vector<float> nrm(4 * xyz->size() + 4);
+  for (size_t i = 0; i < xyz->size(); ++i) {
+    const pcl::Normal& q = normals->points[i];
+    nrm[4 * i] = q.normal_x, nrm[4 * i + 1] = q.normal_y, nrm[4 * i + 2] = q.normal_z, nrm[4 * i + 3] = q.curvature;
+  }
+  double cell = 0.0;
+  poisson_mesh(device_cloud(*xyz), nrm, mesh, &cell);
+  sfmhip_mesh_finish_opts o;
+  sfmhip_mesh_finish_default_opts(&o);  // min_support 1, the component filters off
+  o.support_radius = cell > 0.0 ? 1.5 * cell : 1.0;  // (no sample: no cube, an empty mesh)
+  const sfmhip_mesh_finish_summary s = finish_mesh(device_cloud(*xyz), rgb, mesh, o);
+  if (summary) *summary = s;
 }
 
 double StructFromMotion::registerCloud(pcl::PointCloud<pcl::PointXYZ>::Ptr& cloud, const pcl::PointCloud<pcl::PointXYZ>& reference,

@@ -75,10 +75,13 @@ struct Vertices {
 };
 
 // pcl::PolygonMesh keeps its vertices as a PCLPointCloud2 blob; the stand-in keeps them as the PointXYZ cloud that
-// pcl::fromPCLPointCloud2 would read out of it.  polygons: triangles (Poisson's outputPolygons is off)
+// pcl::fromPCLPointCloud2 would read out of it.  polygons: triangles (Poisson's outputPolygons is off).  colours (0x00RRGGBB) and
+// normals: one per vertex after StructFromMotion::finishMesh (in PCL further fields of the blob), empty in every other mesh
 struct PolygonMesh {
   PointCloud<PointXYZ> cloud;
   std::vector<Vertices> polygons;
+  std::vector<uint32_t> colours;
+  std::vector<Normal> normals;
 };
 
 namespace io {

@@ -16,6 +16,7 @@
 // Extraction: crossed edges per grid point and triangles per cube are counted, scanned (common.h) and written in place.
 #include "common.h"
 #include "cloud_grid.h"
+#include "mesh_object.h"  // (sfmhip_mesh)
 #include "poisson.h"
 #include <algorithm>
 #include <cmath>
@@ -24,11 +25,6 @@
 using namespace sfmpoisson;
 using sfmgrid::blocks;
 using sfmsum::block_tree;  // (block_sum.h: the chunk tree over the 256 threads of a workgroup)
-
-struct sfmhip_mesh {
-  std::vector<float> verts;
-  std::vector<int32_t> tris;
-};
 
 namespace {
 
